@@ -25,6 +25,11 @@ and the hash-range shard r of the block map; every tick the N camera frames are 
 and each rank integrates all of them into the blocks it owns (owner-computes, weak scaling).
 
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, runs the pre-roll and warm-up, times the `--steps` steps, writes `--dump-outputs` if given and prints the
+line (headline, `ms_per_step`, the k_fuse roofline of the timed launches).  `--full` adds what takes runs or frames of its own:
+the latency frames with the per-kernel rooflines, the CPU baseline, the sub-streams of the default c3 line (c1, c2, output-copy
+variants, host input, the C++ class), the profiled RCCL ticks at N > 1, and bench_detail.json.
 """
 import argparse
 import ctypes
@@ -74,14 +79,20 @@ def parse_args():
                     help="hand the next frame over with khr_ingest_ahead while the current one is fused (N = 1).  Off by default: measured in "
                          "round 4, it does not shorten the step (the host and the main stream meet at the seed count every frame) and "
                          "the early conversion competes with k_fuse for the memory path")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs or frames of its own: latency frames + per-kernel rooflines, CPU baseline, "
+                         "the sub-streams of the default c3 line, profiled RCCL ticks (N > 1), bench_detail.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the path holds after its last timed step as DIR/<name>.npy "
+                         "(float32 / float64; a fixed, seeded sample of the map's blocks and of the last output's mesh)")
     ap.add_argument("--latency-frames", type=int, default=8,
-                    help="frames after the timed region that are run with a device synchronisation after each: per-frame latency "
+                    help="(--full) frames after the timed region that are run with a device synchronisation after each: per-frame latency "
                          "(the reference's active_window/all scope) beside the pipelined throughput; 0 = skip")
     ap.add_argument("--exact", action="store_true", help="(default) khr_config.exact_arithmetic = 1: values bit-identical to the CPU restatement")
     ap.add_argument("--fast", action="store_true", help="khr_config.exact_arithmetic = 0: decisions exact, distance / weight within ~1e-6 relative")
     ap.add_argument("--buffer-frames", type=int, default=100, help="frame_data_buffer.max_buffer_size (frames kept in HBM per camera)")
     ap.add_argument("--cpu-baseline-frames", type=int, default=-1,
-                    help="frames of the same stream timed on the CPU oracle (rank 0, N=1); -1 = auto, 0 = skip")
+                    help="(--full) frames of the same stream timed on the CPU oracle (rank 0, N=1); -1 = auto, 0 = skip")
     ap.add_argument("--output-copy", choices=["none", "device", "host"], default="device",
                     help="what happens to an output's map clone (VolumetricMap::cloneUpdated, active_window.cpp:229, inside the reference's "
                          "active_window/all timer scope): device (default line) = device-side snapshot of the updated blocks at every output "
@@ -92,7 +103,7 @@ def parse_args():
                          "voxel: what a TSDF / places consumer reads; colour and labels travel with the mesh vertices), all = the six "
                          "layers of khr_download_updated (25 B per voxel)")
     ap.add_argument("--no-extra-streams", action="store_true",
-                    help="default c3 run only: do not append the c1 / c2 streams and the output-copy variants (each a short sub-run of this script)")
+                    help="default c3 run with --full only: do not append the c1 / c2 streams and the output-copy variants (each a short sub-run of this script)")
     ap.add_argument("--no-roofline-timers", action="store_true")
     ap.add_argument("--all-timers", action="store_true", help="HIP-event timers on every kernel group (slower host path)")
     ap.add_argument("--frame-times", action="store_true", help="debug: synchronise and print per-frame wall times")
@@ -110,6 +121,8 @@ def parse_args():
                          "path), torch = khronos_amd/distributed.py over torch.distributed (the protocol test harness)")
     ap.add_argument("--halo-cap", type=int, default=None, help="halo records all-gathered per rank and tick (N > 1); default 8192 (c5: 65536)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     preset = {"c3": dict(width=1280, height=720, voxel_size=0.02, output_every=4, no_motion=False, no_objects=False, no_tracking=False, preroll=max(0, 75 - a.warmup)),
               "c2": dict(width=640, height=480, voxel_size=0.05, output_every=1, no_motion=True, no_objects=True, no_tracking=False, preroll=0),
               "c1": dict(width=640, height=480, voxel_size=0.05, output_every=0, no_motion=True, no_objects=True, no_tracking=True, preroll=0),
@@ -133,6 +146,66 @@ from khronos_amd.configs import OBJECT_YAML  # noqa: E402  (`active_window:` YAM
 
 
 from khronos_amd.bench_line import compact_line  # noqa: E402  (torch-free: tests/test_cpu_bench_line.py imports it without this script)
+
+DUMP_SEED = 1234             # --dump-outputs: the samples below are drawn with this seed, so two builds dump the same blocks / vertices
+DUMP_BLOCKS = 128            # map blocks downloaded whole (~200 KB each as float32 / float64)
+DUMP_SNAPSHOT_BLOCKS = 32    # blocks of the last output's snapshot (distance + weight)
+DUMP_MESH_VERTICES = 1 << 16
+
+
+def _u64_halves(a):
+    """uint64 values as exact float64 pairs (high 32 bits, low 32 bits)"""
+    a = np.asarray(a, np.uint64)
+    return np.stack([(a >> np.uint64(32)).astype(np.float64), (a & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1)
+
+
+def _sample(rng, n, k):
+    return np.sort(rng.choice(n, size=min(n, k), replace=False)) if n else np.zeros(0, np.int64)
+
+
+def dump_outputs(path, ctx, snap, slot, shape, dyn_counts):
+    """--dump-outputs: what the path holds after its last timed step, as DIR/<name>.npy in float32 / float64 (about 35 MB at c3).
+    The whole map as per-layer digests (khr_map_digest) and its sorted block indices, a seeded sample of its blocks, the last
+    output's snapshot (indices + sampled blocks) and mesh (vertices sorted, then sampled), the last frame's dynamic image and the
+    dynamic cluster count of every timed step.  Orders that the device does not fix (hash slots, vertex order) are sorted away."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    out = {"map_digest": _u64_halves(ctx.map_digest()), "dynamic_clusters_per_step": np.asarray(dyn_counts, np.float64)}
+    idx = ctx.block_indices()
+    idx = idx[np.lexsort((idx[:, 2], idx[:, 1], idx[:, 0]))]
+    out["block_indices"] = idx.astype(np.float64)
+    pick = _sample(rng, len(idx), DUMP_BLOCKS)
+    blocks = [ctx.download_block(idx[k], likelihoods=False) for k in pick]
+    out["sample_block_indices"] = idx[pick].astype(np.float64)
+    for name, dt in (("distance", np.float32), ("weight", np.float32), ("color", np.float32), ("flags", np.float32),
+                     ("sem_label", np.float64), ("last_observed", np.float64), ("last_occupied", np.float64)):
+        out["sample_" + name] = np.stack([b[name] for b in blocks]).astype(dt) if blocks else np.zeros((0, ctx.nvox), dt)
+    if snap is not None:
+        n = snap.num_blocks()
+        s_idx = np.zeros((max(n, 1), 3), np.int32)
+        s_dist = np.empty((max(n, 1), ctx.nvox), np.float32)
+        s_wgt = np.empty((max(n, 1), ctx.nvox), np.float32)
+        n = snap.download_into([s_idx.ctypes.data, s_dist.ctypes.data, s_wgt.ctypes.data, 0, 0, 0, 0], max(n, 1))
+        order = np.lexsort((s_idx[:n, 2], s_idx[:n, 1], s_idx[:n, 0]))
+        sp = order[_sample(rng, n, DUMP_SNAPSHOT_BLOCKS)]
+        out["snapshot_block_indices"] = s_idx[:n][order].astype(np.float64)
+        out["snapshot_sample_distance"] = s_dist[sp]
+        out["snapshot_sample_weight"] = s_wgt[sp]
+    mesh = ctx.download_mesh()
+    p, c = mesh["points"], mesh["colors"]
+    order = np.lexsort((mesh["stamps"], mesh["first_seen"], c[:, 3], c[:, 2], c[:, 1], c[:, 0], mesh["labels"], p[:, 2], p[:, 1], p[:, 0]))
+    mp = order[_sample(rng, len(p), DUMP_MESH_VERTICES)]
+    out["mesh_num_vertices"] = np.asarray([len(p)], np.float64)
+    out["mesh_sample_points"] = p[mp].astype(np.float32)
+    out["mesh_sample_colors"] = c[mp].astype(np.float32)
+    out["mesh_sample_labels"] = mesh["labels"][mp].astype(np.float64)
+    if slot is not None:
+        out["dynamic_image"] = ctx.download_frame(slot, shape, range_image=False, dynamic_image=True)[2].astype(np.float32)
+    total = 0
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    print("bench.py: %d outputs (%.1f MB) written to %s" % (len(out), total / 1e6, path), file=sys.stderr)
 
 
 def main():
@@ -176,13 +249,13 @@ def main():
     K = args.num_labels
     # stream layout: [pre-roll | warm-up | timed steps | latency frames]; only world == 1 runs pre-roll / latency frames
     pre = args.preroll if world == 1 else 0
-    lat = args.latency_frames if (world == 1 and not args.frame_times) else 0
+    lat = args.latency_frames if (args.full and world == 1 and not args.frame_times) else 0
     w0 = pre                      # first warm-up frame
     t0i = pre + args.warmup       # first timed frame
     t1i = t0i + args.steps        # first latency frame
-    # N > 1: a few more ticks behind the timed region with HIP events around every collective (kdist_profile): the line says
-    # what each exchange of the tick costs without those events sitting inside the timed steps
-    prof_ticks = 8 if (world > 1 and not emu) else 0
+    # N > 1 with --full: a few more ticks behind the timed region with HIP events around every collective (kdist_profile): the line
+    # says what each exchange of the tick costs without those events sitting inside the timed steps
+    prof_ticks = 8 if (args.full and world > 1 and not emu) else 0
     n_total = t1i + lat + prof_ticks
     trunc = 3.0 * vs
     cfg = default_config(
@@ -441,6 +514,7 @@ def main():
                 handed.pop(0)
             slot, n_dyn = ctx.process_frame(sensor, frame_desc[i], not host_input, flags)
             dyn_log[i] = n_dyn
+            last_slot[0] = slot
             _t1 = time.perf_counter()
             host_t[0] += _t1 - _t0
             if args.output_copy == "host":
@@ -485,6 +559,7 @@ def main():
 
     copy_stats = [0, 0]       # outputs whose map clone was taken, bytes brought to the host (--output-copy)
     dyn_log = {}              # frame index -> dynamic clusters the motion detector found (frames with seeds run the clustering chain)
+    last_slot = [None]        # frame slot of the last frame fused (--dump-outputs reads its dynamic image)
     handed = []               # indices of the frames handed over with khr_ingest_ahead[_host], oldest first
     lookahead = (args.lookahead or args.input == "host") and world == 1 and not emu  # (host frames: the copy of frame i + 1 beside frame i)
     held_snapshot = [None]
@@ -652,6 +727,9 @@ def main():
     gc.enable()
     ctx.timing_enable(False)
     st1 = ctx.stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, held_snapshot[0], last_slot[0] if (world == 1 and not args.no_motion) else None, (H, W),
+                     [dyn_log.get(i, 0) for i in range(t0i, t1i)])
     obj_timed = [obj_stats[k] - obj_before[k] for k in range(3)]
     copy_timed = [copy_stats[k] - copy_before[k] for k in range(2)]
     # per-frame latency: the same steps with a device synchronisation after each (the reference's active_window/all scope
@@ -697,16 +775,18 @@ def main():
     rccl_info = None
     if fusion_cxx is not None and not emu:
         counted = fusion_cxx.profile_get()  # the timed steps: calls and bytes (no events)
-        fusion_cxx.profile(True)
-        p0 = t1i + lat
-        for i in range(p0, p0 + prof_ticks):  # every rank runs them: the calls are collective
-            step(i)
-        if pipe is not None:
-            pipe.finish_frame()
-            pipe.join()
-        sync_all()
-        timed_c = fusion_cxx.profile_get()
-        fusion_cxx.profile(False)
+        timed_c = {}
+        if prof_ticks:  # (--full)
+            fusion_cxx.profile(True)
+            p0 = t1i + lat
+            for i in range(p0, p0 + prof_ticks):  # every rank runs them: the calls are collective
+                step(i)
+            if pipe is not None:
+                pipe.finish_frame()
+                pipe.join()
+            sync_all()
+            timed_c = fusion_cxx.profile_get()
+            fusion_cxx.profile(False)
         rccl_info = {
             "rccl_ranks": world, "library": os.environ.get("KDIST_RCCL_LIB", "librccl.so.1"),
             "frames_exchange": "torch.distributed all_gather_into_tensor on a side stream, one tick ahead (%d B per rank and tick)" % (11 * W * H)
@@ -887,7 +967,7 @@ def main():
 
     # ---- CPU baseline: the oracle on a bounded sample of the same stream (rank 0, N = 1 only) ----
     nb = args.cpu_baseline_frames
-    if rank == 0 and world == 1 and nb != 0:
+    if args.full and rank == 0 and world == 1 and nb != 0:
         from oracle import pyoracle as po
         cores = os.cpu_count() or 1
         if nb < 0:
@@ -996,11 +1076,11 @@ def main():
     ctx.close()
     # ---- the other streams north_star asks for, and what an output's map clone costs: short sub-runs of this script,
     #      appended to the default c3 line so that one driver invocation carries all of them ----
-    if (rank == 0 and world == 1 and not emu and not args.no_extra_streams and args.config == "c3" and preset_matches
+    if (args.full and rank == 0 and world == 1 and not emu and not args.no_extra_streams and args.config == "c3" and preset_matches
             and args.output_copy == "device" and not args.fast):
         import subprocess
         extra = {}
-        common_args = ["--steps", str(args.steps), "--warmup", str(args.warmup), "--no-extra-streams", "--latency-frames", "0"]
+        common_args = ["--steps", str(args.steps), "--warmup", str(args.warmup), "--full", "--no-extra-streams", "--latency-frames", "0"]
         runs = {"c1": ["--config", "c1"], "c2": ["--config", "c2"],
                 "c3_output_copy_none": ["--config", "c3", "--output-copy", "none", "--cpu-baseline-frames", "0"],
                 "c3_output_copy_host": ["--config", "c3", "--output-copy", "host", "--cpu-baseline-frames", "0"],
@@ -1045,15 +1125,20 @@ def main():
         # The driver parses the LAST stdout line: a compact record (< 6 KB).  Everything else -- sub-streams, per-kernel rooflines,
         # stage tables, notes -- goes to bench_detail.json next to this script and to stderr.
         detail_path = os.environ.get("KHR_BENCH_DETAIL", os.path.join(ROOT, "bench_detail.json"))
-        if not args.no_extra_streams or os.environ.get("KHR_BENCH_DETAIL"):
+        detail_written = False
+        if (args.full and not args.no_extra_streams) or os.environ.get("KHR_BENCH_DETAIL"):
             try:
                 with open(detail_path, "w") as f:
                     json.dump(out, f, indent=1)
+                detail_written = True
             except OSError as e:
                 print("bench_detail.json not written: %s" % e, file=sys.stderr)
         print(json.dumps(out), file=sys.stderr)
         sys.stderr.flush()
-        print(json.dumps(compact_line(out)))
+        line = compact_line(out)
+        if not detail_written:
+            line["detail"] = "stderr carries the full record (--full also writes bench_detail.json next to bench.py)"
+        print(json.dumps(line))
     if dist is not None:
         dist.destroy_process_group()
 

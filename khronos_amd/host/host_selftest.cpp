@@ -8,6 +8,7 @@
 #include <thread>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -390,7 +391,9 @@ int main(int argc, char** argv) {
     const auto st = rec.stats();
     CHECK(st.at("active_window/all").count == 2 && st.at("active_window/all").min == 0.25 && st.at("active_window/all").max == 0.75);
     CHECK(st.at("active_window/all").sum == 1.0 && st.count("active_window/update_map") == 1);
-    const std::string path = "/tmp/khr_selftest_stats.csv";
+    // (in $TMPDIR when set: the file must not be shared between users or runs of the test suite)
+    const char* tmpdir = std::getenv("TMPDIR");
+    const std::string path = std::string(tmpdir && *tmpdir ? tmpdir : "/tmp") + "/khr_selftest_stats.csv";
     CHECK(rec.logStats(path));
     std::ifstream f(path);
     std::string header, row;

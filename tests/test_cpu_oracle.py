@@ -43,11 +43,15 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_create_fails_loudly_without_gpu_or_bad_config():
-    import torch
+    import subprocess
     lib = capi.load_library()
     cfg = capi.default_config()
     h = ctypes.c_void_p()
-    if not torch.cuda.is_available():
+    # torch is asked in a child process: its own HIP runtime must not be loaded into the test process beside the library's
+    # (tests/common.py), or the GPU tests that run after this one in the same process see host memory misclassified
+    has_gpu = subprocess.run([sys.executable, "-c", "import sys, torch; sys.exit(0 if torch.cuda.is_available() else 1)"],
+                             timeout=300).returncode == 0
+    if not has_gpu:
         rc = lib.khr_create(ctypes.byref(cfg), ctypes.byref(h))
         assert rc == capi.KHR_EDEVICE and b"no CPU fallback" in lib.khr_last_error()
     bad = capi.default_config(neighbor_connectivity=7)
