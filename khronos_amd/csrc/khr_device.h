@@ -49,7 +49,7 @@ enum Counter : int {
   C_N_MESH,
   C_N_BAND,          // in-band records of the last integrate
   C_N_TSDF,          // non-culled work list length of the last integrate
-  C_BAND_OVERFLOW,
+  C_BAND_OVERFLOW,   // (unused; khr_stats.band_overflow is always 0)
   C_TSDF_CURSOR,     // (unused)
   C_MESH_OVERFLOW,
   C_N_PROC,          // tracking pass: blocks that need the full pass (pair 0: C_N_PROC, C_N_EF_A)
@@ -61,7 +61,6 @@ enum Counter : int {
   C_N_ITEMS1,
   C_N_ITEMS2,
   C_N_ITEMS3,
-  C_BAND_CURSOR,     // k_tsdf: record chunks drawn from the pool in the last integrate (BandPool::cursor)
   C_COUNT = 32
 };
 enum Stat64 : int { S_UPD = 0 /* unused */, S_BAND /* unused */, S_MESH_VERTS, S_PRUNED, S_CUM_UPD, S_CUM_BAND, S_CUM_VISITED, S_CUM_CALLS, S_COUNT = 8 };
@@ -360,7 +359,7 @@ __device__ inline void publishSeedCount(const DevMap& m, volatile uint32_t* host
   __threadfence_system();
 }
 
-constexpr int kFuseStatSlots = 2048;  // upper bound of k_fuse's grid: one {n_upd, n_band} statistics slot per workgroup
+constexpr int kUpdateStatSlots = 2048;  // upper bound of k_fuse's grid: one {n_upd, n_band} statistics slot per workgroup
 
 // per-call counter reset (one workgroup, any size).  k_fuse leaves its statistics as per-workgroup partial sums in
 // wg_stats; they are folded into the cumulative totals here, so that a benchmark can read N_upd / N_band sums once,
@@ -369,7 +368,7 @@ __device__ inline void beginIntegrate(DevMap m, int nvox, uint32_t* wg_stats) {
   unsigned long long u = 0, b = 0;
   uint2* __restrict__ st = reinterpret_cast<uint2*>(wg_stats);
 #pragma unroll 4
-  for (int i = threadIdx.x; i < kFuseStatSlots; i += blockDim.x) {
+  for (int i = threadIdx.x; i < kUpdateStatSlots; i += blockDim.x) {
     const uint2 v = st[i];
     u += v.x;
     b += v.y;
@@ -394,7 +393,6 @@ __device__ inline void beginIntegrate(DevMap m, int nvox, uint32_t* wg_stats) {
     m.counters[C_N_ITEMS1] = 0u;
     m.counters[C_N_ITEMS2] = 0u;
     m.counters[C_N_ITEMS3] = 0u;
-    m.counters[C_BAND_CURSOR] = 0u;
   }
 }
 

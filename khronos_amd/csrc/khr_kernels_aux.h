@@ -1033,12 +1033,11 @@ struct MeshBuffers {
   uint64_t* stamps;    // last_observed of the source voxel (first_seen == stamps, ASSUMPTIONS.md A.5)
 };
 
-// copy the meshes of blocks that are not regenerated from the old to the new vertex buffer.  Called by k_mesh_move and -- beside
-// the emit pass, which writes the OTHER blocks' vertices into the same buffer -- by the trailing workgroups of
-// k_marching_cubes<.., true> (one launch instead of two back to back).  Vertex-parallel (round 5): a wave takes 256 consecutive
-// vertices of the NEW buffer, finds the slot of its first and last one by bisection of the (monotone) offset array -- a slot's
-// vertices are contiguous, empty slots share their successor's offset, so the last slot with offset <= i owns vertex i -- and each
-// lane copies its vertices from the slot's old place (old_offset: k_mesh_prepare's snapshot of mesh_desc[].offset, so that the
+// copy the meshes of blocks that are not regenerated from the old to the new vertex buffer.  Called -- beside the emit pass,
+// which writes the OTHER blocks' vertices into the same buffer -- by the trailing workgroups of k_marching_cubes<.., true>.
+// Vertex-parallel (round 5): a wave takes 256 consecutive vertices of the NEW buffer, finds the slot of its first and last
+// one by bisection of the (monotone) offset array -- a slot's vertices are contiguous, empty slots share their successor's
+// offset, so the last slot with offset <= i owns vertex i -- and each lane copies its vertices from the slot's old place (old_offset: k_mesh_prepare's snapshot of mesh_desc[].offset, so that the
 // descriptor can be moved by whoever copies the slot's first vertex).  The per-slot form it replaces (one workgroup walks a
 // slot's vertices, slots dealt round robin) took 50 - 80 us of the 100 - 130 us emit launch for ~40 MB of traffic: a workgroup
 // with two large kept meshes ran ~25 dependent load -> store rounds (profiles/r05_mc_emit.txt).
@@ -1620,14 +1619,6 @@ __global__ __launch_bounds__(256) void k_mesh_carry_counts(DevMap m, uint32_t* _
   const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= m.counters[C_MAX_SLOT]) return;
   new_count[s] = (m.blk_flags[s] & BLK_LIVE) ? m.mesh_desc[s].count : 0u;
-}
-
-// copy the meshes of blocks that are not regenerated from the old to the new vertex buffer.
-// `regen` marks slots that pass 2 rewrites.
-__global__ __launch_bounds__(256) void k_mesh_move(DevMap m, const uint8_t* __restrict__ regen,
-                                                  const uint32_t* __restrict__ new_offset, const uint32_t* __restrict__ old_offset,
-                                                  MeshBuffers src, MeshBuffers dst, uint32_t max_vertices) {
-  meshMoveBlocks(m, regen, new_offset, old_offset, src, dst, max_vertices, blockIdx.x, gridDim.x);
 }
 
 __global__ __launch_bounds__(256) void k_mark_regen(const uint32_t* __restrict__ work, const uint32_t* n_work,

@@ -84,9 +84,9 @@ __device__ inline float divExact(float a, float b, float y) {
 
 typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));  // two adjacent pixels, 4-byte aligned
 
-// what changes from frame to frame: images, camera, stamp, per-frame switches.  A single-frame launch carries it inside
-// its kernel arguments (FuseArgs derives from it); k_fuse2<.., MULTI> reads an array of these from device memory and
-// walks an item through all of them in order (object extraction: a track's buffered frames in one launch).
+// what changes from frame to frame: images, camera, stamp, per-frame switches.  k_fuse carries it inside its kernel
+// arguments (FuseArgs derives from it); k_fuse2 reads an array of these from device memory and walks an item through all
+// of them in order (object extraction: a track's buffered frames in one launch; a rig tick: its cameras).
 struct FuseFrame {
   const float* range;
   const int32_t* dyn;
@@ -121,11 +121,8 @@ struct FuseArgs : FuseFrame {
   int interp, range_mode, use_dropoff, const_weight, with_tracking;
   int K, sem_mode;
   int KS;  // floats per likelihood row (likStride(K): rows of K > 4 labels fill whole 128-byte lines)
-  unsigned long long* dbg_buf;  // DBG & 64: per-wave timeline {start, end, band cycles, items, rounds, records, max item cycles, hw id}
-  int dbg;  // ablation switches of the DBG instantiation (env KHR_FUSE_DBG): 1 no band phase, 2 no voxel stores,
-            // 4 no distance / weight loads, 8 range gathers from a fixed address, 16 geometry only
-  int band_mode;  // 1 = likelihood rows moved as whole cache lines by 8 lanes each (fuseBandRows, default where the rows are
-                  // padded), 0 = lane <-> record (fuseBandRecord; env KHR_FUSE_BAND=0)
+  int band_mode;  // 1 = likelihood rows moved as whole cache lines by 8 lanes each (fuseBandRows, where the rows are padded),
+                  // 0 = lane <-> record (fuseBandRecord; frames up to 640 x 480, fillFuseMap)
   int blend_pre;  // khr_config.color_blend_weight: 0 = the colour blend uses the voxel weight AFTER the update (panoptic-lineage order,
                   // ASSUMPTIONS.md A.3), 1 = the weight before it.  The record's blend-weight field carries the one chosen.
   // speculative launch (khr_process_frame): the kernel is queued BEFORE the host has seen the motion detector's seed count
@@ -133,20 +130,20 @@ struct FuseArgs : FuseFrame {
   // without seeds -- most of them -- no longer idle the main stream for the seed count's trip to the host and back.
   const uint32_t* gate;
   void* sink;  // k_fuse: one 256-byte line per wave for the stores that must be issued but have nothing to write
-  // k_fuse2<.., MULTI>: the frames an item is walked through, in order
+  // k_fuse2: the frames an item is walked through, in order
   const FuseFrame* frames;
   int n_frames;
-  // tick form of MULTI (khr_tick_integrate): one byte per wave item [slot * items-per-block + item], bit k = the item is on
+  // tick form of k_fuse2 (khr_tick_integrate): one byte per wave item [slot * items-per-block + item], bit k = the item is on
   // camera k's TSDF list (k_tick_cull); the kernel clears the byte it has consumed.  nullptr: every frame, every item.
   uint8_t* item_mask;
-  // object-extraction form of MULTI (khr_integrate_shared_batch): bit f of words [item * frame_words ..] = frame f may update a voxel of
+  // object-extraction form of k_fuse2 (khr_integrate_shared_batch): bit f of words [item * frame_words ..] = frame f may update a voxel of
   // the item (k_multi_cull); nullptr: every frame
   const uint32_t* frame_bits;
   int frame_words;
   int frame_bit0;  // index of a.frames[0] in the bit rows (a launch may walk a chunk of the batch)
 };
 
-constexpr int kFuseCap = 256;        // in-band records a wave collects before it works them off (one 4-z chunk of a patch)
+constexpr int kRecCap = 256;        // in-band records a wave collects before it works them off (one 4-z chunk of a patch)
 
 // colour / label / likelihood update of one in-band voxel (the body of updateVoxel for |sdf| < truncation)
 // `a` points into the kernel-argument segment: the fields only this phase needs (image / layer pointers, label
@@ -154,10 +151,8 @@ constexpr int kFuseCap = 256;        // in-band records a wave collects before i
 typedef const FuseArgs __attribute__((address_space(4))) * FuseArgsK;
 typedef const FuseFrame __attribute__((address_space(4))) * FuseFrameK;  // a frame's arguments, through the scalar cache
 constexpr int kLikVec = 5;  // float4 likelihood vectors a lane holds at once (K = 20 in one round trip)
-template <int VPS, bool DBG = false>  // isa:band: lane<->record update (fuseBandRecord)
-__device__ inline void fuseBandRecord(FuseArgsK ka, FuseFrameK kf, size_t slot, uint32_t lin_mode, float w, float w_new, float u, float v,
-                                      unsigned long long* tacc = nullptr) {
-  (void)tacc;
+template <int VPS>  // isa:band: lane<->record update (fuseBandRecord)
+__device__ inline void fuseBandRecord(FuseArgsK ka, FuseFrameK kf, size_t slot, uint32_t lin_mode, float w, float w_new, float u, float v) {
   constexpr int NV = VPS * VPS * VPS;
   const FuseArgs __attribute__((address_space(4)))& a = *ka;
   const FuseFrame __attribute__((address_space(4)))& f = *kf;
@@ -176,34 +171,26 @@ __device__ inline void fuseBandRecord(FuseArgsK ka, FuseFrameK kf, size_t slot, 
   interpPixels(u, v, f.W, f.H, px4, &du, &dv);
   const int best = interpWeights(du, dv, use_nearest, w4);
   const uint32_t best_o = static_cast<uint32_t>(px4[best]) * 4u;
-  // development ablations of the band update (DBG instantiations only; env KHR_FUSE_DBG): 1024 no image gathers, 2048 no
-  // likelihood loads, 4096 no likelihood stores, 8192 no colour / flag / label stores, 16384 no colour / flag loads
-  const int bdbg = DBG ? a.dbg : 0;
   // ---- every load of the record is issued here, before the first store: a memory round trip costs 1.5 - 2 us under
   //      this kernel's load and vmcnt retires in order, so each load placed behind a store waits for that store too ----
   uint32_t c4[4] = {0u, 0u, 0u, 0u}, co = 0u;
   if (has_color) {
     const char* const rgba_b = reinterpret_cast<const char*>(f.rgba);
-    if (!(bdbg & 1024)) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) c4[k] = *reinterpret_cast<const uint32_t*>(rgba_b + static_cast<uint32_t>(px4[k]) * 4u);
-    }
-    if (!(bdbg & 16384)) co = *reinterpret_cast<const uint32_t*>(color_b + lin * 4u);
+    for (int k = 0; k < 4; ++k) c4[k] = *reinterpret_cast<const uint32_t*>(rgba_b + static_cast<uint32_t>(px4[k]) * 4u);
+    co = *reinterpret_cast<const uint32_t*>(color_b + lin * 4u);
   }
   int label = -1;
   uint8_t fl = 0;
   float4 l4[kLikVec];
   if (do_sem) {
-    if (bdbg & 1024) label = static_cast<int>(lin % 19u);
-    else
-      label = (a.sem_mode == 1) ? ((*reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(f.obj) + best_o) == f.object_id) ? 1 : 0)
-                                : *reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(f.label) + best_o);
-    if (!(bdbg & 16384)) fl = *reinterpret_cast<const uint8_t*>(vfl_b + lin);
+    label = (a.sem_mode == 1) ? ((*reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(f.obj) + best_o) == f.object_id) ? 1 : 0)
+                              : *reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(f.label) + best_o);
+    fl = *reinterpret_cast<const uint8_t*>(vfl_b + lin);
     if (vec) {  // a voxel without VOX_SEM_VALID holds no likelihoods yet: what is loaded is replaced by zeros below
 #pragma unroll
       for (int j = 0; j < kLikVec; ++j)
-        l4[j] = (j < K / 4 && !(bdbg & 2048)) ? *reinterpret_cast<const float4*>(lik_b + lik_o + static_cast<uint32_t>(j) * 16u)
-                                              : make_float4(0.f, 0.f, 0.f, 0.f);
+        l4[j] = j < K / 4 ? *reinterpret_cast<const float4*>(lik_b + lik_o + static_cast<uint32_t>(j) * 16u) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   }
   if (has_color) {
@@ -224,7 +211,7 @@ __device__ inline void fuseBandRecord(FuseArgsK ka, FuseFrameK kf, size_t slot, 
       const float cv = static_cast<float>((co >> (8 * ch)) & 0xffu);
       out |= static_cast<uint32_t>(toU8(divExact(cv * w_new + cn * w, tot, ytot))) << (8 * ch);
     }
-    if (!(bdbg & 8192)) *reinterpret_cast<uint32_t*>(color_b + lin * 4u) = out;
+    *reinterpret_cast<uint32_t*>(color_b + lin * 4u) = out;
   }
   if (!do_sem || label < 0 || label >= K) return;
   const bool empty = !(fl & VOX_SEM_VALID);
@@ -253,7 +240,7 @@ __device__ inline void fuseBandRecord(FuseArgsK ka, FuseFrameK kf, size_t slot, 
             bestk = k;
           }
         }
-        if (!(bdbg & 4096)) *reinterpret_cast<float4*>(lik_b + lik_o + static_cast<uint32_t>(j0 + j) * 16u) = make_float4(l[0], l[1], l[2], l[3]);
+        *reinterpret_cast<float4*>(lik_b + lik_o + static_cast<uint32_t>(j0 + j) * 16u) = make_float4(l[0], l[1], l[2], l[3]);
       }
     }
   } else {
@@ -276,7 +263,6 @@ __device__ inline void fuseBandRecord(FuseArgsK ka, FuseFrameK kf, size_t slot, 
       }
     }
   }
-  if (bdbg & 8192) return;
   if (empty) *reinterpret_cast<uint8_t*>(vfl_b + lin) = fl | VOX_SEM_VALID;
   *reinterpret_cast<uint32_t*>(lab_b + lin * 4u) = static_cast<uint32_t>(bestk);
 }
@@ -312,7 +298,7 @@ __device__ __forceinline__ uint32_t rowDown(uint32_t v) {
 // store, kRowPasses row stores -- lanes or passes without a record of their own work on the chunk's LAST record again (same
 // loads, same results, same stores: duplicates of a store the record's own lanes issue anyway), records that are not updated
 // write their row back unchanged.  Only the two stores that end a chunk (label, first-time flag) are conditional.
-template <int VPS, int CAP = kFuseCap>  // isa:band: whole-line likelihood rows (fuseBandRows)
+template <int VPS, int CAP = kRecCap>  // isa:band: whole-line likelihood rows (fuseBandRows)
 __device__ __forceinline__ void fuseBandRows(FuseArgsK ka, FuseFrameK kf, size_t slot, uint32_t* rec, uint32_t cnt, int lane) {
   constexpr int NV = VPS * VPS * VPS;
   const FuseArgs __attribute__((address_space(4)))& a = *ka;
@@ -508,17 +494,17 @@ struct FuseItem {
 typedef uint32_t u4v __attribute__((ext_vector_type(4)));
 typedef const u4v __attribute__((address_space(4))) * DescK;
 
-template <int VPS, int ZSPLIT, bool DEFCFG, bool EXACT, int WPW, bool DBG = false>
+template <int VPS, int ZSPLIT, bool DEFCFG, bool EXACT, int WPW>
 __global__ __launch_bounds__(64 * WPW) void k_fuse(FuseArgs a, FuseList list) {  // isa:kernel setup
   constexpr int NV = VPS * VPS * VPS;
   constexpr int SL = VPS * VPS;        // voxels per z slice
   constexpr int PATCHES = SL / 64;     // 64-voxel x-y patches per slice
   constexpr int ZR = VPS / ZSPLIT;     // z steps per wave item
   static_assert(SL % 64 == 0 && VPS % ZSPLIT == 0 && (ZR == 2 || ZR == 4), "bad block shape");
-  static_assert(64 * ZR <= kFuseCap, "record list must hold one item");
+  static_assert(64 * ZR <= kRecCap, "record list must hold one item");
   // per-wave record list, one LDS base per wave: field f of record r at s_rec[wave][f][r] (0 voxel | mode, 1 measurement
   // weight, 2 voxel weight after the update, 3 u, 4 v), so the five stores of a record differ by immediate offsets
-  __shared__ uint32_t s_rec[WPW][5][kFuseCap];
+  __shared__ uint32_t s_rec[WPW][5][kRecCap];
   __shared__ uint32_t s_stat[WPW][2];
   __shared__ uint32_t s_q;  // the workgroup's item queue: next index into its share of the descriptor list
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
@@ -535,9 +521,6 @@ __global__ __launch_bounds__(64 * WPW) void k_fuse(FuseArgs a, FuseList list) { 
   const uint32_t W4 = static_cast<uint32_t>(a.W) * 4u;
   const uint32_t n_items = list.counts[0] + list.counts[1] + list.counts[2] + list.counts[3];
   uint32_t n_upd = 0, n_band = 0;
-  const int dbg = DBG ? a.dbg : 0;
-  // (timeline probe: the constant 100 MHz counter is common to all XCDs, s_memtime is not)
-  const unsigned long long t_entry = (DBG && (dbg & 64)) ? __builtin_amdgcn_s_memrealtime() : 0ull;
   if (a.gate != nullptr && *a.gate != 0u) return;  // speculative launch, and the frame has motion seeds (workgroup-uniform)
   if (threadIdx.x == 0) s_q = 0u;
   __syncthreads();
@@ -550,7 +533,7 @@ __global__ __launch_bounds__(64 * WPW) void k_fuse(FuseArgs a, FuseList list) { 
   // (b % 8) * (grid / 8) + b / 8: list positions that are neighbours -- the items of one block, blocks that are neighbours
   // in the visible list -- land on workgroups of the SAME XCD and share its L2 for the image rows and voxel lines they
   // have in common.  (grid is a multiple of 8.)
-  const uint32_t first = (dbg & 512) ? blockIdx.x : (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  const uint32_t first = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
   auto pull = [&]() -> uint32_t {
     uint32_t j = 0u;
     if (lane == 0) j = atomicAdd(&s_q, 1u);
@@ -639,12 +622,8 @@ __global__ __launch_bounds__(64 * WPW) void k_fuse(FuseArgs a, FuseList list) { 
     }
   };
 
-  unsigned long long t_band = 0, t_item_max = 0;
-  uint32_t c_items = 0, c_rounds = 0, c_recs = 0;
-
   // ---- phase 2 of an item: measurement, decisions, read-modify-write, in-band records; then its band rounds ----
   auto phase2 = [&](FuseItem<VPS, ZR>& cur) {
-    const unsigned long long ti0 = (DBG && (dbg & 64)) ? __builtin_amdgcn_s_memtime() : 0ull;
     const size_t slot = cur.slot;  // isa:p2 setup (bases)
     char* const dist_b = reinterpret_cast<char*>(a.dist + slot * NV);
     char* const wgt_b = reinterpret_cast<char*>(a.weight + slot * NV);
@@ -759,10 +738,10 @@ __global__ __launch_bounds__(64 * WPW) void k_fuse(FuseArgs a, FuseList list) { 
                                                               __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m_band), 0u));
           uint32_t* const rec = &s_rec[wave][0][pos];
           rec[0] = lin | (use_nearest ? 0x10000u : 0u);
-          rec[kFuseCap] = __float_as_uint(w);
-          rec[2 * kFuseCap] = __float_as_uint(a.blend_pre ? w_old : w_new);
-          rec[3 * kFuseCap] = __float_as_uint(uc);
-          rec[4 * kFuseCap] = __float_as_uint(vc);
+          rec[kRecCap] = __float_as_uint(w);
+          rec[2 * kRecCap] = __float_as_uint(a.blend_pre ? w_old : w_new);
+          rec[3 * kRecCap] = __float_as_uint(uc);
+          rec[4 * kRecCap] = __float_as_uint(vc);
         }
         cnt += static_cast<uint32_t>(__popcll(m_band));
       }
@@ -807,10 +786,7 @@ __global__ __launch_bounds__(64 * WPW) void k_fuse(FuseArgs a, FuseList list) { 
     const uint32_t item_band = cnt;  // isa:band phase driver
     // ---- the item's in-band voxels, densely.  A cold block: the hint keeps the register allocator
     //      from favouring its values over the voxel loop's ----
-    if (DBG && (dbg & 1)) cnt = 0u;
     if (__builtin_expect(cnt > 0u, 0)) {
-      const unsigned long long tb0 = (DBG && (dbg & 64)) ? __builtin_amdgcn_s_memtime() : 0ull;
-      if (DBG) { c_rounds += (cnt + 63u) / 64u; c_recs += cnt; }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       // explicit kernel arguments start at offset 0 of the kernarg segment; the empty asm keeps the loads of the band
@@ -823,8 +799,8 @@ __global__ __launch_bounds__(64 * WPW) void k_fuse(FuseArgs a, FuseList list) { 
       } else {
         for (uint32_t r = static_cast<uint32_t>(lane); r < cnt; r += 64u) {
           const uint32_t* const rec = &s_rec[wave][0][r];
-          fuseBandRecord<VPS, DBG>(ka, kf, slot, rec[0], __uint_as_float(rec[kFuseCap]), __uint_as_float(rec[2 * kFuseCap]),
-                              __uint_as_float(rec[3 * kFuseCap]), __uint_as_float(rec[4 * kFuseCap]));
+          fuseBandRecord<VPS>(ka, kf, slot, rec[0], __uint_as_float(rec[kRecCap]), __uint_as_float(rec[2 * kRecCap]),
+                              __uint_as_float(rec[3 * kRecCap]), __uint_as_float(rec[4 * kRecCap]));
         }
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -833,7 +809,6 @@ __global__ __launch_bounds__(64 * WPW) void k_fuse(FuseArgs a, FuseList list) { 
       // a band load" into the item loop and protects the register's next use there with a vmcnt that drains the pipeline of
       // EVERY item (seen in the ISA: vmcnt(8) in the middle of the next prefetch)
       __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
-      if (DBG && (dbg & 64)) t_band += __builtin_amdgcn_s_memtime() - tb0;
     }
     // the item's record: {touched, wrote a negative distance, in-band count (next frame's cost class)}; a uniform store of
     // all lanes (one request), folded into the block flags by k_fuse_fold  // isa:item epilogue (item record)
@@ -841,16 +816,10 @@ __global__ __launch_bounds__(64 * WPW) void k_fuse(FuseArgs a, FuseList list) { 
       const uint32_t recw = min(item_band, static_cast<uint32_t>(kItemBandMask)) | (touched ? kItemTouched : 0u) | (wrote_neg ? kItemNeg : 0u);
       a.blk_band[slot * kBandSlots + (cur.sbi & (kBandSlots - 1))] = static_cast<uint16_t>(recw);
     }
-    if (DBG && (dbg & 64)) {
-      const unsigned long long dt = __builtin_amdgcn_s_memtime() - ti0;
-      t_item_max = dt > t_item_max ? dt : t_item_max;
-      ++c_items;
-    }
   };
 
   // ---- the item loop: two item states, alternating roles (no register copies between iterations) ----
   uint32_t item = pull();  // isa:item loop control / prefetch bookkeeping
-  const unsigned long long tw0 = (DBG && (dbg & 64)) ? __builtin_amdgcn_s_memtime() : 0ull;
   if (item < n_items) {
     FuseItem<VPS, ZR> sa, sb;
     uint4 d_cur = descOf(item);
@@ -877,17 +846,6 @@ __global__ __launch_bounds__(64 * WPW) void k_fuse(FuseArgs a, FuseList list) { 
         d_next = d_nn;
       }
     }
-  }
-  if (DBG && (dbg & 64) && lane == 0) {
-    unsigned long long* o = a.dbg_buf + (static_cast<size_t>(blockIdx.x) * WPW + wave) * 8;
-    o[0] = tw0;
-    o[1] = __builtin_amdgcn_s_memtime();
-    o[2] = t_band;
-    o[3] = c_items;
-    o[4] = c_rounds;
-    o[5] = c_recs;
-    o[6] = t_item_max;
-    o[7] = (t_entry & 0xffffffffull) | ((__builtin_amdgcn_s_memrealtime() & 0xffffffffull) << 32);  // entry | exit, 10 ns ticks
   }
   // statistics: one read-modify-write per workgroup on its own slot (folded by beginIntegrate / khr_get_stats)  // isa:kernel epilogue
   if (lane == 0) {
@@ -932,11 +890,11 @@ __global__ __launch_bounds__(256) void k_fuse_fold(uint32_t* __restrict__ blk_fl
 // other waves, not by the wave's own schedule.
 // ====================================================================================================================
 // isa:k_fuse2 (not part of this breakdown)
-// MULTI: an item is walked through a.n_frames frames (a.frames[], device memory, read through the scalar cache) in order before
+// An item is walked through a.n_frames frames (a.frames[], device memory, read through the scalar cache) in order before
 // the wave takes its next item -- the updates of a voxel by consecutive frames are order dependent, those of different items
 // are not.  One launch then replaces one launch per frame (MeshObjectExtractor re-integrates every buffered frame of a track,
 // mesh_object_extractor.cpp:239-243: 27 launches of ~18 us for a few hundred blocks each).
-template <int VPS, int ZSPLIT, bool DEFCFG, bool EXACT, int WPW, int MINW, bool MULTI = false>
+template <int VPS, int ZSPLIT, bool DEFCFG, bool EXACT, int WPW, int MINW>
 __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList list) {
   constexpr int NV = VPS * VPS * VPS;
   constexpr int SL = VPS * VPS;
@@ -1004,23 +962,21 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList l
     char* const lobs_b = reinterpret_cast<char*>(a.last_obs + slot * NV);
     bool touched = false, wrote_neg = false;
     uint32_t cnt = 0;
-    const int n_frames = MULTI ? a.n_frames : 1;
-    // MULTI: distance / weight of the item's voxels live in registers across the frames (one load before the first frame,
-    // one store -- with the stamp of the last frame that updated the voxel -- after the last) instead of a store + reload
-    // round trip per frame; the per-voxel sequence of updates is unchanged
+    const int n_frames = a.n_frames;
+    // distance / weight of the item's voxels live in registers across the frames (one load before the first frame, one
+    // store -- with the stamp of the last frame that updated the voxel -- after the last) instead of a store + reload round
+    // trip per frame; the per-voxel sequence of updates is unchanged
     float dreg[ZR], wreg[ZR];
     int lidx[ZR];
-    if (MULTI) {
 #pragma unroll
-      for (int k = 0; k < ZR; ++k) {
-        const uint32_t lin = static_cast<uint32_t>(lin_xy + (z0 + k) * SL);
-        dreg[k] = *reinterpret_cast<const float*>(dist_b + lin * 4u);
-        wreg[k] = *reinterpret_cast<const float*>(wgt_b + lin * 4u);
-        lidx[k] = -1;
-      }
+    for (int k = 0; k < ZR; ++k) {
+      const uint32_t lin = static_cast<uint32_t>(lin_xy + (z0 + k) * SL);
+      dreg[k] = *reinterpret_cast<const float*>(dist_b + lin * 4u);
+      wreg[k] = *reinterpret_cast<const float*>(wgt_b + lin * 4u);
+      lidx[k] = -1;
     }
     uint32_t frame_mask = ~0u;
-    if (MULTI && a.item_mask != nullptr) {  // which cameras listed the item (their culling is conservative: the others cannot touch it)
+    if (a.item_mask != nullptr) {  // which cameras listed the item (their culling is conservative: the others cannot touch it)
       const size_t mi = slot * static_cast<size_t>(PATCHES * ZSPLIT) + static_cast<size_t>(sbi);
       const uint32_t word = *(const uint32_t __attribute__((address_space(4)))*)(a.item_mask + (mi & ~static_cast<size_t>(3)));
       frame_mask = (word >> (8u * static_cast<uint32_t>(mi & 3))) & 0xffu;
@@ -1031,8 +987,8 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList l
     }
     uint32_t fbits = ~0u;
     for (int fi = 0; fi < n_frames; ++fi) {
-    if (MULTI && ((frame_mask >> fi) & 1u) == 0u) continue;
-    if (MULTI && a.frame_bits != nullptr) {  // (the item's word of 32 frames through the scalar cache: written by the launch before this one)
+    if (((frame_mask >> fi) & 1u) == 0u) continue;
+    if (a.frame_bits != nullptr) {  // (the item's word of 32 frames through the scalar cache: written by the launch before this one)
       const int gf = fi + a.frame_bit0;
       if ((gf & 31) == 0 || fi == 0) {
         const size_t wi = (slot * static_cast<size_t>(PATCHES * ZSPLIT) + static_cast<size_t>(sbi)) * static_cast<size_t>(a.frame_words) + static_cast<size_t>(gf >> 5);
@@ -1043,15 +999,14 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList l
         continue;
       }
     }
-    // the frame's arguments: the kernel's own (single frame), or entry fi of a.frames read through the scalar cache
-    FuseFrame Fm;
-    if (MULTI) {
+    // the frame's arguments: entry fi of a.frames, read through the scalar cache
+    FuseFrame F;
+    {
       const uint32_t __attribute__((address_space(4)))* const w = (const uint32_t __attribute__((address_space(4)))*)(a.frames + fi);
-      uint32_t* const d = reinterpret_cast<uint32_t*>(&Fm);
+      uint32_t* const d = reinterpret_cast<uint32_t*>(&F);
 #pragma unroll
       for (int i = 0; i < static_cast<int>(sizeof(FuseFrame) / 4); ++i) d[i] = w[i];
     }
-    const FuseFrame& F = MULTI ? Fm : static_cast<const FuseFrame&>(a);
     const float Wm1 = static_cast<float>(F.W - 1), Hm1 = static_cast<float>(F.H - 1);
     const float fxfy = F.fx * F.fy;
     const char* const range_b = reinterpret_cast<const char*>(F.range);
@@ -1065,7 +1020,6 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList l
 #pragma unroll
     for (int k = 0; k < ZR; ++k) {
       const int iz = z0 + k;
-      const uint32_t lin = static_cast<uint32_t>(lin_xy + iz * SL);
       const float pz = oz + (static_cast<float>(iz) + 0.5f) * a.vs;
       float pc[3];
 #pragma unroll
@@ -1083,15 +1037,8 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList l
       const uint32_t o0 = v0 * W4 + u0 * 4u, o1 = v1 * W4 + u0 * 4u;
       ra[k] = *reinterpret_cast<const f2u*>(range_b + o0);
       rb[k] = *reinterpret_cast<const f2u*>(range_b + o1);
-      dd[k] = 0.f;
-      ww[k] = 0.f;
-      if (MULTI) {
-        dd[k] = dreg[k];
-        ww[k] = wreg[k];
-      } else if (ok) {
-        dd[k] = *reinterpret_cast<const float*>(dist_b + lin * 4u);
-        ww[k] = *reinterpret_cast<const float*>(wgt_b + lin * 4u);
-      }
+      dd[k] = dreg[k];
+      ww[k] = wreg[k];
       uu[k] = uc;
       vv[k] = vc;
       zz[k] = voxel_range;
@@ -1180,21 +1127,12 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList l
         d_new = __builtin_fmaf(d_old, w_old, sdf_c * w) * __builtin_amdgcn_rcpf(tot);
       }
       const float w_new = fminf(tot, a.max_weight);
-      if (MULTI) {
-        if (ok) {
-          dreg[k] = d_new;
-          wreg[k] = w_new;
-          lidx[k] = fi;
-        }
-      } else if (ok) {
-        *reinterpret_cast<float*>(dist_b + lin * 4u) = d_new;
-        *reinterpret_cast<float*>(wgt_b + lin * 4u) = w_new;
-        if (a.with_tracking) *reinterpret_cast<uint64_t*>(lobs_b + lin * 8u) = F.stamp;
+      if (ok) {
+        dreg[k] = d_new;
+        wreg[k] = w_new;
+        lidx[k] = fi;
       }
       const unsigned long long m_ok = __builtin_amdgcn_ballot_w64(ok), m_band = __builtin_amdgcn_ballot_w64(in_band);
-      // (this kernel stores stamps per voxel: the voxels it has written no longer carry their group's lazy stamp, DevMap::obs)
-      if (!MULTI && a.with_tracking && m_ok != 0ull && lane == 0)
-        atomicAnd(reinterpret_cast<unsigned long long*>(a.obs + slot * static_cast<size_t>(NV / 64) + (lin >> 6)), ~m_ok);
       n_upd += static_cast<uint32_t>(__popcll(m_ok));
       touched = touched || (m_ok != 0ull);
       wrote_neg = wrote_neg || (__builtin_amdgcn_ballot_w64(ok && d_new < 0.f) != 0ull);
@@ -1219,7 +1157,7 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList l
       __builtin_amdgcn_wave_barrier();
       FuseArgsK ka = (FuseArgsK)__builtin_amdgcn_kernarg_segment_ptr();
       asm volatile("" : "+s"(ka));
-      const FuseFrameK kf = MULTI ? (FuseFrameK)(a.frames + fi) : (FuseFrameK)ka;
+      const FuseFrameK kf = (FuseFrameK)(a.frames + fi);
       if (ka->band_mode != 0 && fuseBandRowsOk(ka->KS, ka->sem_mode, kf->do_sem, kf->has_color)) {
         fuseBandRows<VPS, CAP>(ka, kf, slot, &s_rec[wave][0][0], cnt, lane);
       } else {
@@ -1233,18 +1171,16 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList l
       __builtin_amdgcn_wave_barrier();
     }
     }  // frames
-    if (MULTI) {
 #pragma unroll
-      for (int k = 0; k < ZR; ++k) {
-        const uint32_t lin = static_cast<uint32_t>(lin_xy + (z0 + k) * SL);
-        const unsigned long long m_upd = __builtin_amdgcn_ballot_w64(lidx[k] >= 0);
-        if (a.with_tracking && m_upd != 0ull && lane == 0)  // (per-voxel stamps from here on: DevMap::obs)
-          atomicAnd(reinterpret_cast<unsigned long long*>(a.obs + slot * static_cast<size_t>(NV / 64) + (lin >> 6)), ~m_upd);
-        if (lidx[k] < 0) continue;
-        *reinterpret_cast<float*>(dist_b + lin * 4u) = dreg[k];
-        *reinterpret_cast<float*>(wgt_b + lin * 4u) = wreg[k];
-        if (a.with_tracking) *reinterpret_cast<uint64_t*>(lobs_b + lin * 8u) = a.frames[lidx[k]].stamp;
-      }
+    for (int k = 0; k < ZR; ++k) {
+      const uint32_t lin = static_cast<uint32_t>(lin_xy + (z0 + k) * SL);
+      const unsigned long long m_upd = __builtin_amdgcn_ballot_w64(lidx[k] >= 0);
+      if (a.with_tracking && m_upd != 0ull && lane == 0)  // (per-voxel stamps from here on: DevMap::obs)
+        atomicAnd(reinterpret_cast<unsigned long long*>(a.obs + slot * static_cast<size_t>(NV / 64) + (lin >> 6)), ~m_upd);
+      if (lidx[k] < 0) continue;
+      *reinterpret_cast<float*>(dist_b + lin * 4u) = dreg[k];
+      *reinterpret_cast<float*>(wgt_b + lin * 4u) = wreg[k];
+      if (a.with_tracking) *reinterpret_cast<uint64_t*>(lobs_b + lin * 8u) = a.frames[lidx[k]].stamp;
     }
     if (lane == 0) {
       if (touched) atomicOr(&a.blk_flags[slot], BLK_UPDATED | BLK_MESH_UPDATED | BLK_TRACKING_UPDATED | (wrote_neg ? BLK_HAS_NEG : 0u));
@@ -1315,7 +1251,7 @@ __global__ __launch_bounds__(256) void k_multi_cull(const uint32_t* __restrict__
           zmin = fminf(zmin, pcs[k][2]);
           zmax = fmaxf(zmax, pcs[k][2]);
         }
-        // (voxel_range = z in the default range mode -- the only one MULTI runs in --, and z is affine in the voxel position: extremes at corners)
+        // (voxel_range = z in the default range mode -- the only one k_fuse2 runs in --, and z is affine in the voxel position: extremes at corners)
         if (zmax <= -margin) keep = false;              // every voxel behind the camera
         if (zmin > F.max_range + margin) keep = false;  // every voxel beyond max range
         if (zmax < F.min_range - margin) keep = false;
@@ -1354,7 +1290,7 @@ __global__ __launch_bounds__(256) void k_multi_cull(const uint32_t* __restrict__
 }
 
 // k_multi_order: the items of an object mini-map that at least one frame can touch, in four classes by the number of frames that can
-// (>= 3/4, >= 1/2, >= 1/4 of the batch, fewer), heaviest class first.  k_fuse2<.., MULTI> deals list position p to workgroup p mod
+// (>= 3/4, >= 1/2, >= 1/4 of the batch, fewer), heaviest class first.  k_fuse2 deals list position p to workgroup p mod
 // grid, and a workgroup's waves take its positions in order: every workgroup starts on its long items and fills up with the short
 // ones (the launch is as long as its slowest wave -- before: two items of 28 frames each, a dependent round trip or two per frame,
 // while most items see half the frames or none).  One thread per item, one returning atomic per class and workgroup.

@@ -32,7 +32,6 @@
 #include "khr_kernels_aux.h"
 #include "khr_kernels_fusion.h"
 #include "khr_kernels_fuse.h"
-#include "khr_kernels_fuse5.h"
 #include "khr_kernels_objects.h"
 
 using namespace khr;
@@ -144,17 +143,8 @@ struct khr_ctx {
   unsigned long long* d_digest = nullptr;  // khr_map_digest accumulators
   uint32_t* d_wg_stats = nullptr;
   bool defer_fold = false, fold_pending = false;  // k_fuse's item records: folded by the next k_tracking_select instead of k_fuse_fold
-  // k_fuse3 / k_band3 (round 5): chunked record lists of the in-band voxels (BandPool), sized from a bound on a frame's in-band
-  // volume on first use (grow-only)
-  uint32_t* d_band_rec = nullptr;
-  uint32_t* d_band_n = nullptr;
-  uint32_t band_chunks = 0;
-  int n_cus = 256, fuse5_grid = 0, band5_grid = 0, fuse5_zs = 0;
   int stream_priority = 0;  // +1 the active window's streams (highest), -1 an object mini-map's (lowest), 0 default (env KHR_STREAM_PRIORITY=0)
-  hipStream_t band_stream = nullptr;  // khr_process_frame: the band kernel beside the tracking pass
-  hipEvent_t ev_band_fork = nullptr, ev_band_join = nullptr;
-  bool band_fork = false, band_join_pending = false;  // per context (= per device): the persistent grids of k_tsdf / the band kernel
-  unsigned char* d_fuse_sink = nullptr;  // k_fuse: one 256-byte sink line per wave (kFuseStatSlots workgroups x 16 waves)
+  unsigned char* d_fuse_sink = nullptr;  // k_fuse: one 256-byte sink line per wave (kUpdateStatSlots workgroups x 16 waves)
   uint32_t* d_pix_scratch = nullptr;  // khr_pixel_iou: mask image + counters (allocated on first use)
   size_t pix_words = 0;
   uint8_t* d_inst = nullptr;          // khr_forward_instances: per-id accumulators
@@ -246,7 +236,6 @@ struct khr_ctx {
   hipEvent_t ev_ingest = nullptr;                // khr_process_frame: this frame's main-stream ingest is queued
   hipEvent_t ev_up = nullptr;                    // the last upload out of h_up has been consumed
   hipStream_t ingest_stream = nullptr;           // khr_process_frame: ingest on the auxiliary stream (set around khr_upload_frame)
-  bool early_ingest = true;                      // env KHR_NO_EARLY_INGEST=1 turns it off
   // frames handed over with khr_ingest_ahead[_host], oldest first, waiting for their khr_process_frame calls.  Up to kMaxAhead: a
   // frontend that hands frame i + 1 over BEFORE it calls khr_process_frame for frame i keeps the copy engine busy across the
   // host's wait inside that call (round 5: with one entry the host-to-device copy of a 720p frame, ~205 us, started only after
@@ -592,30 +581,14 @@ int dispatchVps(khr_ctx* c, F&& f) {
   return fail(KHR_EINVAL, "voxels_per_side must be 8 or 16");
 }
 
-int kAheadObjects = 1;  // env KHR_AHEAD_OBJECTS=0: khr_ingest_ahead converts the frame only (A/B)
-int kMcFork = 1;        // env KHR_MC_FORK=0: marching cubes on the main stream behind the tracking pass (A/B)
-int kSnapFork = 1;      // env KHR_SNAP_FORK=0: the output's snapshot on the main stream in front of marching cubes (A/B)
-int kFuseGrid = 0;      // 0 = resident workgroups of the instantiation (occupancy query) x CUs; env KHR_FUSE_GRID
-int kFuseZsplit = 0;    // 0 = by world size (wave items per x-y patch of a block: 2 / 4 / 8); env KHR_FUSE_ZSPLIT
-int kFuseExact = -1;    // -1 = !khr_config.relaxed_arithmetic; env KHR_FUSE_EXACT=0/1 overrides (A/B switch)
-int kFuseWavesPerCu = 16;  // env KHR_FUSE_WAVES: resident waves per CU the persistent grid is sized for
-constexpr int kFuseWpwDefault = 12;
-int kFuseDbg = 0;       // env KHR_FUSE_DBG: ablation switches (development; selects the DBG instantiation)
-int kFuseVer = 1;       // env KHR_FUSE_V: 1 = k_fuse (default: per-wave software pipeline, band phase inside), 2 = k_fuse2 (one item per wave),
-                        // 5 = k_tsdf + k_band5 (round 6, khr_kernels_fuse5.h: lean voxel kernel + balanced band kernel, the vehicle of the
-                        // speed-of-light decomposition; parity-green; 44 + 31 us against k_fuse's 72 and, with its band kernel on a second
-                        // stream beside the tracking pass, SLOWER per frame -- a cross-stream dependency costs ~20 us each way,
-                        // profiles/r06_fuse_sol.txt -- so it is the option, not the default)
-int kFuse3Waves = 0;    // env KHR_FUSE5_WAVES: resident waves per CU of k_tsdf's persistent grid (0 = what the occupancy query allows)
-int kBand3Waves = 0;    // env KHR_BAND5_WAVES: the same for k_band5
-int kFuse5Mode = 0;   // env KHR_FUSE5_MODE: 1 / 2 = the ALU-only / memory-only instantiations of k_tsdf (speed-of-light decomposition; development)
-int kTickUnion = 1;     // env KHR_TICK_UNION: khr_tick_integrate updates with ONE launch for all cameras of the tick (tickUnion)
-int kMultiChunk = 7;    // env KHR_MULTI_CHUNK: frames per launch of the object extractor's multi-frame update (0 = all buffered frames in one launch)
-int kFuseMulti = 1;     // env KHR_FUSE_MULTI: khr_integrate_shared_batch integrates all frames of a batch in one launch (k_fuse2 MULTI)
+constexpr int kUpdateWavesPerCu = 16;  // resident waves per CU the update kernel's persistent grid is sized for
+constexpr int kUpdateWpw = 12;         // waves per workgroup of k_fuse
+constexpr int kMultiChunk = 7;         // frames per launch of the object extractor's multi-frame update (integrateUpdateMulti)
 constexpr int kMaxMultiFrames = 1024;
-int kFuseSpec = 1;      // env KHR_FUSE_SPECULATIVE: khr_process_frame queues k_fuse before the seed count has reached the host (gated on the device)
-int kFuseBand = 1;      // env KHR_FUSE_BAND: 1 = likelihood rows as whole cache lines, 8 lanes per row (fuseBandRows; default, lane <-> record for small frames), 2 = rows always, 0 = lane <-> record
 constexpr int kStreamGrid = 4096;
+
+// exact (bit-for-bit) arithmetic in the update kernels unless the configuration asks for the relaxed form
+inline bool exactArithmetic(const khr_ctx* c) { return c->cfg.relaxed_arithmetic == 0; }
 
 }  // namespace
 
@@ -849,10 +822,6 @@ int khr_create(const khr_config* cfg, khr_ctx** out) {
   c->cfg = *cfg;
   c->device = cfg->device;
   {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) c->n_cus = prop.multiProcessorCount;
-  }
-  {
     static const bool prio_off = std::getenv("KHR_STREAM_PRIORITY") && std::atoi(std::getenv("KHR_STREAM_PRIORITY")) == 0;
     static const int prio_window = std::getenv("KHR_WINDOW_PRIORITY") ? std::atoi(std::getenv("KHR_WINDOW_PRIORITY")) : 0;
     c->stream_priority = prio_off ? 0 : (cfg->voxels_per_side == 8 ? -1 : prio_window);
@@ -916,24 +885,6 @@ int khr_create(const khr_config* cfg, khr_ctx** out) {
   p.rank = cfg->rank;
   p.world = cfg->world_size;
   p.dbg = std::getenv("KHR_DEBUG") ? std::atoi(std::getenv("KHR_DEBUG")) : 0;
-  if (std::getenv("KHR_AHEAD_OBJECTS")) kAheadObjects = std::atoi(std::getenv("KHR_AHEAD_OBJECTS"));
-  if (std::getenv("KHR_MC_FORK")) kMcFork = std::atoi(std::getenv("KHR_MC_FORK"));
-  if (std::getenv("KHR_SNAP_FORK")) kSnapFork = std::atoi(std::getenv("KHR_SNAP_FORK"));
-  if (std::getenv("KHR_FUSE_GRID")) kFuseGrid = std::max(8, std::min(kFuseStatSlots, std::atoi(std::getenv("KHR_FUSE_GRID"))));
-  if (std::getenv("KHR_FUSE_ZSPLIT")) kFuseZsplit = std::atoi(std::getenv("KHR_FUSE_ZSPLIT"));
-  if (std::getenv("KHR_FUSE_EXACT")) kFuseExact = std::atoi(std::getenv("KHR_FUSE_EXACT")) ? 1 : 0;
-  if (std::getenv("KHR_FUSE_WAVES")) kFuseWavesPerCu = std::max(4, std::atoi(std::getenv("KHR_FUSE_WAVES")));
-  if (std::getenv("KHR_FUSE_DBG")) kFuseDbg = std::atoi(std::getenv("KHR_FUSE_DBG"));
-  if (std::getenv("KHR_FUSE_BAND")) kFuseBand = std::atoi(std::getenv("KHR_FUSE_BAND"));
-  if (std::getenv("KHR_FUSE_SPECULATIVE")) kFuseSpec = std::atoi(std::getenv("KHR_FUSE_SPECULATIVE"));
-  if (std::getenv("KHR_TICK_UNION")) kTickUnion = std::atoi(std::getenv("KHR_TICK_UNION"));
-  if (std::getenv("KHR_MULTI_CHUNK")) kMultiChunk = std::atoi(std::getenv("KHR_MULTI_CHUNK"));
-  if (std::getenv("KHR_FUSE_MULTI")) kFuseMulti = std::atoi(std::getenv("KHR_FUSE_MULTI"));
-  if (std::getenv("KHR_FUSE_V")) kFuseVer = std::atoi(std::getenv("KHR_FUSE_V"));
-  if (std::getenv("KHR_FUSE5_WAVES")) kFuse3Waves = std::atoi(std::getenv("KHR_FUSE5_WAVES"));
-  if (std::getenv("KHR_BAND5_WAVES")) kBand3Waves = std::atoi(std::getenv("KHR_BAND5_WAVES"));
-  if (std::getenv("KHR_FUSE5_MODE")) kFuse5Mode = std::atoi(std::getenv("KHR_FUSE5_MODE"));
-  if (std::getenv("KHR_NO_EARLY_INGEST")) c->early_ingest = false;
 
   DevMap& m = c->m;
   const size_t cap = cfg->max_blocks, nv = p.nvox;
@@ -974,16 +925,14 @@ int khr_create(const khr_config* cfg, khr_ctx** out) {
   A(devAlloc(c, &c->d_trk_proc, cap));
   A(devAlloc(c, &c->d_dbg, 4096 * 4 * 12));
   A(devAlloc(c, &c->d_digest, kDigestWords));
-  A(devAlloc(c, &c->d_wg_stats, 2 * kFuseStatSlots));
-  A(devAlloc(c, &c->d_fuse_sink, static_cast<size_t>(kFuseStatSlots) * 16 * 256, false));
+  A(devAlloc(c, &c->d_wg_stats, 2 * kUpdateStatSlots));
+  A(devAlloc(c, &c->d_fuse_sink, static_cast<size_t>(kUpdateStatSlots) * 16 * 256, false));
   A(devAlloc(c, &c->d_fetch_done, 4));
   {
-    int zs = kFuseZsplit;
     // shards of a >= 4-rank map and small frames (up to 640 x 480 pixels) see few blocks per launch: 8 z ranges per patch
-    // instead of 4 halve the longest dependent chain (an item's band rounds) and double the items the waves can share
-    if (zs == 0) zs = (cfg->world_size >= 4 || cfg->max_frame_pixels <= 640u * 480u) ? 8 : 4;
-    if (zs != 4 && zs != 8) zs = 4;  // a wave item is a 64-voxel patch x 4 (or 2) z steps
-    if (cfg->voxels_per_side == 8) zs = 4;
+    // instead of 4 halve the longest dependent chain (an item's band rounds) and double the items the waves can share.
+    // A wave item is a 64-voxel patch x 4 (or 2) z steps; 8^3 blocks always take 4.
+    const int zs = (cfg->voxels_per_side != 8 && (cfg->world_size >= 4 || cfg->max_frame_pixels <= 640u * 480u)) ? 8 : 4;
     c->fuse_zsplit = zs;
     c->wpb = static_cast<uint32_t>((cfg->voxels_per_side * cfg->voxels_per_side / 64) * zs);
     c->item_cap = static_cast<uint32_t>(cap) * c->wpb;
@@ -1151,10 +1100,6 @@ void khr_destroy(khr_ctx* c) {
   if (c->ev_md_walk_up) hipEventDestroy(c->ev_md_walk_up);
   if (c->d_mh2_keys) { hipFree(c->d_mh2_keys); hipFree(c->d_mh2_offs); }
   if (c->d_pix_scratch) hipFree(c->d_pix_scratch);
-  if (c->d_band_rec) { hipFree(c->d_band_rec); hipFree(c->d_band_n); }
-  if (c->band_stream) { hipStreamSynchronize(c->band_stream); hipStreamDestroy(c->band_stream); }
-  if (c->ev_band_fork) hipEventDestroy(c->ev_band_fork);
-  if (c->ev_band_join) hipEventDestroy(c->ev_band_join);
   if (c->h2d_stream) { hipStreamSynchronize(c->h2d_stream); hipStreamDestroy(c->h2d_stream); }
   if (c->ev_h2d) hipEventDestroy(c->ev_h2d);
   for (int i = 0; i < 2; ++i) {
@@ -1578,7 +1523,6 @@ struct UpdateLists {
 // resident workgroups of a k_fuse instantiation x CUs, rounded down to whole XCD rounds (the grid is persistent: static
 // striding over the work items, so workgroups beyond residency would only add a tail)
 static int fuseGrid(khr_ctx* c, const void* kernel, int group, int block) {
-  if (kFuseGrid > 0) return std::max(8 * group, kFuseGrid / (8 * group) * (8 * group));
   static std::map<std::pair<int, const void*>, int> cache;  // (per device: the grid depends on its CU count)
   static std::mutex cache_mu;  // contexts of different threads (active window + extraction workers) launch concurrently
   std::lock_guard<std::mutex> lock(cache_mu);
@@ -1587,11 +1531,11 @@ static int fuseGrid(khr_ctx* c, const void* kernel, int group, int block) {
   if (it != cache.end()) return it->second;
   int per_cu = 0, cus = 256;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-  per_cu = std::min(per_cu, std::max(1, kFuseWavesPerCu / (block / 64)));
+  per_cu = std::min(per_cu, std::max(1, kUpdateWavesPerCu / (block / 64)));
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
   per_cu = std::min(per_cu, 8);
-  int grid = std::min(kFuseStatSlots, per_cu * cus);
+  int grid = std::min(kUpdateStatSlots, per_cu * cus);
   grid = std::max(8 * group, grid / (8 * group) * (8 * group));
   cache[key] = grid;
   return grid;
@@ -1611,8 +1555,7 @@ static int fuse2Grid(khr_ctx* c, const void* kern, int wpw) {
   hipDeviceProp_t prop;
   int cus = 256;
   if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-  int grid = std::min(kFuseStatSlots, per_cu * cus) / 8 * 8;
-  if (kFuseGrid > 0) grid = std::max(8, kFuseGrid / 8 * 8);
+  const int grid = std::min(kUpdateStatSlots, per_cu * cus) / 8 * 8;
   cache[key] = grid;
   return grid;
 }
@@ -1642,28 +1585,25 @@ static void fillFuseMap(khr_ctx* c, FuseArgs* a) {
   a->interp = c->p.interp; a->range_mode = c->p.range_mode; a->use_dropoff = c->p.use_dropoff; a->const_weight = c->p.const_weight;
   a->with_tracking = c->p.with_tracking;
   a->K = c->p.K; a->KS = c->p.KS; a->sem_mode = c->p.sem_mode;
-  a->dbg = kFuseDbg;
-  a->dbg_buf = c->d_dbg;
   // whole-line rows pay where the memory path is busy; small frames (up to 640 x 480: 3 - 5 k items, fewer than two per wave) are one
   // dependent chain per wave, and there the shorter lane <-> record form wins (c1: 17.8 - 18.3 against 20.3 us).  Decided HERE, not
   // from the item count inside the kernel: one more value alive in k_fuse's band dispatch tipped the register allocator into
   // spilling vector registers inside the item loop (scratch traffic is vector memory: every wait became vmcnt(0), 72 -> 95 us;
   // tests/test_cpu_host.py::test_update_kernel_keeps_its_registers guards the build against that)
-  a->band_mode = (kFuseBand == 1 && c->cfg.max_frame_pixels <= 640u * 480u) ? 0 : kFuseBand;
+  a->band_mode = c->cfg.max_frame_pixels <= 640u * 480u ? 0 : 1;
   a->sink = c->d_fuse_sink;
   a->blend_pre = c->cfg.color_blend_weight != 0;
 }
 
-// All frames of a batch in ONE launch (k_fuse2<.., MULTI>): every wave item is walked through the frames in order.  Only for
+// All frames of a batch in ONE launch (k_fuse2): every wave item is walked through the frames in order.  Only for
 // `allocate = false` integrations of 8^3-voxel maps with the default integrator switches (the object extractor's mini-map);
 // returns 1 when the batch was not taken (the caller then integrates frame by frame).
 static int integrateUpdateMulti(khr_ctx* c, khr_ctx* src, const int* src_slots, const int* object_ids, int n_frames, int use_mask) {
-  if (!kFuseMulti || c->cfg.voxels_per_side != 8 || n_frames < 2 || n_frames > kMaxMultiFrames) return 1;
+  if (c->cfg.voxels_per_side != 8 || n_frames < 2 || n_frames > kMaxMultiFrames) return 1;
   FuseArgs a{};
   fillFuseMap(c, &a);
   const bool defcfg = a.range_mode == 0 && a.interp == 2 && a.use_dropoff && !a.const_weight;
   if (!defcfg) return 1;
-  const bool exact = kFuseExact >= 0 ? kFuseExact != 0 : c->cfg.relaxed_arithmetic == 0;
   // per-frame arguments: pinned staging -> device array (reused only after the previous batch's copy has been consumed)
   if (!c->h_frames) {
     if (hipHostMalloc(reinterpret_cast<void**>(&c->h_frames), sizeof(FuseFrame) * kMaxMultiFrames, hipHostMallocDefault) != hipSuccess ||
@@ -1688,12 +1628,11 @@ static int integrateUpdateMulti(khr_ctx* c, khr_ctx* src, const int* src_slots, 
                        reinterpret_cast<uint32_t*>(c->d_frames), n_words);
   }
   HIP_TRY(hipEventRecord(c->ev_frames, c->stream));
-  static_cast<FuseFrame&>(a) = c->h_frames[0];  // (W, H etc. for code that looks at the kernel's own frame; unused by MULTI)
+  static_cast<FuseFrame&>(a) = c->h_frames[0];  // (the head frame; k_fuse2 itself reads a.frames)
   a.frames = c->d_frames;
   a.n_frames = n_frames;
   // which frames can touch which item (k_multi_cull): one bit per (item, frame), read by the update kernel through the scalar cache
-  static const bool no_multi_cull = std::getenv("KHR_MULTI_NO_CULL") != nullptr;
-  if (!no_multi_cull && c->item_cap > 0) {
+  if (c->item_cap > 0) {
     const int n_words = (n_frames + 31) / 32;
     const size_t need = static_cast<size_t>(c->item_cap) * static_cast<size_t>(n_words);
     if (need > c->frame_bits_words) {  // (grown in steps of four words per item = 128 frames: a worker thread's hipMalloc waits for the device)
@@ -1752,99 +1691,24 @@ static int integrateUpdateMulti(khr_ctx* c, khr_ctx* src, const int* src_slots, 
         per_cu_of[key] = {per_cu, cus};
       }
     }
-    int grid = std::min(kFuseStatSlots, per_cu * cus) / 8 * 8;
+    int grid = std::min(kUpdateStatSlots, per_cu * cus) / 8 * 8;
     if (c->explicit_blocks > 0) {
       const uint64_t items = c->explicit_blocks * c->wpb;
       grid = std::max(8, static_cast<int>(std::min<uint64_t>(static_cast<uint64_t>(grid), (items + WPW - 1) / WPW) + 7) / 8 * 8);
     }
-    // the buffered frames in chunks of kMultiChunk per launch (0 = all in one): the next chunk's workgroups cannot start before the
+    // the buffered frames in chunks of kMultiChunk per launch: the next chunk's workgroups cannot start before the
     // current chunk has drained, so the window's update kernel -- whose workgroup needs a whole CU's vector registers -- gets its CUs
     // within one chunk instead of within the whole extraction (an item's distance / weight pass through HBM at the chunk boundaries)
-    const int chunk = kMultiChunk > 0 ? kMultiChunk : n_frames;
-    for (int k0 = 0; k0 < n_frames; k0 += chunk) {
+    for (int k0 = 0; k0 < n_frames; k0 += kMultiChunk) {
       a.frames = c->d_frames + k0;
-      a.n_frames = std::min(chunk, n_frames - k0);
+      a.n_frames = std::min(kMultiChunk, n_frames - k0);
       a.frame_bit0 = k0;
       KHR_LAUNCH_TIMED(0, kern, dim3(grid), dim3(64 * WPW), a, list);
     }
   };
-  if (exact) go(&k_fuse2<8, 4, true, true, WPW, 4, true>);
-  else go(&k_fuse2<8, 4, true, false, WPW, 4, true>);
+  if (exactArithmetic(c)) go(&k_fuse2<8, 4, true, true, WPW, 4>);
+  else go(&k_fuse2<8, 4, true, false, WPW, 4>);
   HIP_TRY(hipGetLastError());
-  return KHR_OK;
-}
-
-// k_tsdf + band kernel (khr_kernels_fuse5.h, round 6): the update of a 16^3-voxel map with the reference's default integrator switches
-// and whole-line likelihood rows.  Returns 1 when the call is not one it takes (the caller falls back to k_fuse).
-static int ensureBandPool(khr_ctx* c, const FrameSlot& s, int grid) {
-  // record pool: one static chunk per workgroup + a bound on the in-band volume of a frame -- the voxels within the truncation
-  // distance of the surface along the view rays fill at most (solid angle) x max_range^2 x 2 truncation / voxel^3; x 1.5 for the
-  // lattice and the drop-off at the band's edge
-  const khr_sensor& sen = s.sensor;
-  const double omega = (static_cast<double>(sen.width) / sen.fx) * (static_cast<double>(sen.height) / sen.fy);
-  const double vol = omega * static_cast<double>(sen.max_range) * sen.max_range * 2.0 * c->p.trunc;
-  const double recs = 1.5 * vol / (static_cast<double>(c->p.vs) * c->p.vs * c->p.vs);
-  const uint64_t want64 = static_cast<uint64_t>(std::max(grid, kFuseStatSlots)) + static_cast<uint64_t>(recs / kBandChunk) + 64u;
-  if (want64 > (1u << 17)) return 1;  // (2.7 GB of records: not a frame this path is meant for)
-  const uint32_t want = static_cast<uint32_t>(want64);
-  if (want > c->band_chunks) {
-    // grow-only; happens on the first frames of a context (hipMalloc / hipFree wait for the device)
-    if (c->d_band_rec) { hipStreamSynchronize(c->stream); hipFree(c->d_band_rec); hipFree(c->d_band_n); c->d_band_rec = nullptr; c->d_band_n = nullptr; c->band_chunks = 0; }
-    const uint32_t n = want + want / 4;
-    if (hipMalloc(reinterpret_cast<void**>(&c->d_band_rec), static_cast<size_t>(n) * kBandFields * kBandChunk * 4u) != hipSuccess) { c->d_band_rec = nullptr; return 1; }
-    if (hipMalloc(reinterpret_cast<void**>(&c->d_band_n), static_cast<size_t>(n) * 4u) != hipSuccess) { hipFree(c->d_band_rec); c->d_band_rec = nullptr; c->d_band_n = nullptr; return 1; }
-    hipMemsetAsync(c->d_band_n, 0, static_cast<size_t>(n) * 4u, c->stream);
-    c->band_chunks = n;
-  }
-  return KHR_OK;
-}
-
-static int integrateUpdate5(khr_ctx* c, const FrameSlot& s, const FuseArgs& a, const FuseList& list, bool exact, int zs) {
-  constexpr int WPW = 8, OCC = 5;  // 8-wave workgroups, compiled for 5 waves per SIMD (<= 96 VGPRs: no scratch)
-  constexpr int BW = 4;
-  auto gridOf = [&](const void* kern, int wpw, int want_waves) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * wpw, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-    if (want_waves > 0) per_cu = std::max(1, std::min(per_cu, want_waves / wpw));
-    return std::max(8, std::min(kFuseStatSlots, per_cu * c->n_cus) / 8 * 8);
-  };
-  auto pick = [&](auto run) {
-    if (zs == 8) {  // (items of 64 x 2 voxels: small frames, shards of a rig)
-      if (exact) run(&k_tsdf<8, true, 8, 6, 0>);
-      else run(&k_tsdf<8, false, 8, 6, 0>);
-    } else if (kFuse5Mode == 1) run(&k_tsdf<4, true, WPW, OCC, 1>);
-    else if (kFuse5Mode == 2) run(&k_tsdf<4, true, WPW, OCC, 2>);
-    else if (kFuse5Mode == 3) run(&k_tsdf<4, true, WPW, OCC, 3>);
-    else if (exact) run(&k_tsdf<4, true, WPW, OCC, 0>);
-    else run(&k_tsdf<4, false, WPW, OCC, 0>);
-  };
-  if (c->fuse5_grid == 0 || c->fuse5_zs != zs) {
-    c->fuse5_zs = zs;
-    pick([&](auto kern) { c->fuse5_grid = gridOf(reinterpret_cast<const void*>(kern), zs == 8 ? 8 : WPW, kFuse3Waves); });
-    c->band5_grid = gridOf(reinterpret_cast<const void*>(&k_band5<BW, 5>), BW, kBand3Waves);
-    if (std::getenv("KHR_VERBOSE")) std::fprintf(stderr, "[khr] k_tsdf: %d workgroups of %d waves; band: %d of %d\n", c->fuse5_grid, WPW, c->band5_grid, BW);
-  }
-  if (int rc = ensureBandPool(c, s, c->fuse5_grid)) return rc;
-  BandPool bp{c->d_band_rec, c->d_band_n, &c->m.counters[C_BAND_CURSOR], &c->m.counters[C_BAND_OVERFLOW], c->band_chunks, static_cast<uint32_t>(c->fuse5_grid)};
-  const int grid = c->fuse5_grid;
-  pick([&](auto kern) { KHR_LAUNCH_TIMED(0, kern, dim3(grid), dim3(64 * (zs == 8 ? 8 : WPW)), a, list, bp); });
-  if (kFuse5Mode == 1) return KHR_OK;
-  // khr_process_frame (band_fork): the band kernel only touches colour / label / likelihoods and the record pool -- nothing the tracking
-  // pass reads or writes -- so it runs on its own stream beside that pass; the caller joins it before anything else reads those layers
-  hipStream_t band_stream = c->stream;
-  if (c->band_fork) {
-    if (!c->band_stream) HIP_TRY(createStream(c, &c->band_stream));
-    if (!c->ev_band_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_band_fork, hipEventDisableTiming));
-    if (!c->ev_band_join) HIP_TRY(hipEventCreateWithFlags(&c->ev_band_join, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c->ev_band_fork, c->stream));
-    HIP_TRY(hipStreamWaitEvent(c->band_stream, c->ev_band_fork, 0));
-    band_stream = c->band_stream;
-  }
-  KHR_LAUNCH_TIMED_ON(7, band_stream, (&k_band5<BW, 5>), dim3(c->band5_grid), dim3(64 * BW), a, bp);
-  if (c->band_fork) {
-    HIP_TRY(hipEventRecord(c->ev_band_join, c->band_stream));
-    c->band_join_pending = true;
-  }
   return KHR_OK;
 }
 
@@ -1857,7 +1721,7 @@ static int integrateUpdate(khr_ctx* c, FrameSlot& s, const DevFrame& f, int allo
   fillFuseMap(c, &a);
   fillFuseFrame(c, s, f, use_mask, object_id, &a);
   const bool defcfg = a.range_mode == 0 && a.interp == 2 && a.use_dropoff && !a.const_weight;
-  const bool exact = kFuseExact >= 0 ? kFuseExact != 0 : c->cfg.relaxed_arithmetic == 0;
+  const bool exact = exactArithmetic(c);
   int rc = dispatchVps(c, [&](auto vps) {
     constexpr int V = decltype(vps)::value;
     auto launch = [&](auto zsplit) {
@@ -1867,7 +1731,7 @@ static int integrateUpdate(khr_ctx* c, FrameSlot& s, const DevFrame& f, int allo
         int grid = fuseGrid(c, reinterpret_cast<const void*>(kern), G, 64 * wpw);
         // a small explicitly allocated map (object extraction): one workgroup per wpw items is enough; the rest of the
         // persistent grid would only be launched to find an empty queue (and takes CUs from the window's own kernels)
-        if (!allocate_blocks && c->explicit_blocks > 0 && kFuseGrid == 0) {
+        if (!allocate_blocks && c->explicit_blocks > 0) {
           const uint64_t items = c->explicit_blocks * c->wpb;
           const int want = static_cast<int>(std::min<uint64_t>(static_cast<uint64_t>(grid), (items + wpw - 1) / wpw));
           grid = std::max(8, (want + 7) / 8 * 8);
@@ -1883,22 +1747,8 @@ static int integrateUpdate(khr_ctx* c, FrameSlot& s, const DevFrame& f, int allo
       };
       // non-default switches are test configurations: they always run the bit-exact arithmetic
       a.gate = gate;
-      constexpr int WD = kFuseWpwDefault;
-      if (kFuseVer >= 5 && V == 16 && defcfg && fuseBandRowsOk(a.KS, a.sem_mode, a.do_sem, a.has_color) && c->m.capacity <= (1u << 20) &&
-          integrateUpdate5(c, s, a, list, exact, ZS) == KHR_OK) {
-        // k_tsdf + k_band5 took the call
-        if (c->defer_fold) c->fold_pending = true;
-        else hipLaunchKernelGGL(k_fuse_fold, dim3((c->m.capacity + 255) / 256), dim3(256), 0, c->stream, m.blk_flags, m.blk_band,
-                                &m.counters[C_MAX_SLOT], gate);
-      } else if (kFuseVer == 2 && V == 16 && defcfg && exact) {
-        // k_fuse2, single frame (A/B switch KHR_FUSE_V=2): 16 waves per workgroup, compiled for 4 waves per SIMD
-        constexpr int Z2 = (V == 16 ? ZS : 4);
-        auto kern = &k_fuse2<16, Z2, true, true, 16, 4>;
-        const int grid = fuse2Grid(c, reinterpret_cast<const void*>(kern), 16);
-        KHR_LAUNCH_TIMED(0, kern, dim3(grid), dim3(64 * 16), a, list);
-      } else if (defcfg && !exact && kFuseDbg && V == 16) {
-        go(&k_fuse<V, ZS, true, false, WD, (V == 16)>, WD);
-      } else if (defcfg && !exact) {
+      constexpr int WD = kUpdateWpw;
+      if (defcfg && !exact) {
         go(&k_fuse<V, ZS, true, false, WD>, WD);
       } else if (defcfg) {
         go(&k_fuse<V, ZS, true, true, WD>, WD);
@@ -2344,18 +2194,16 @@ int khr_tick_seed_counts(khr_ctx* c, uint32_t* n_seed_pixels, int n_frames) {
   return KHR_OK;
 }
 
-// The cameras of a tick in ONE update launch (k_fuse2<.., MULTI> over the union of their item lists, a camera mask per item)
+// The cameras of a tick in ONE update launch (k_fuse2 over the union of their item lists, a camera mask per item)
 // instead of one launch per camera: taken for the block shapes and switches k_fuse2 is instantiated for.
 static bool tickUnion(const khr_ctx* c) {
-  if (!kFuseMulti || kTickUnion == 0) return false;
   const DevParams& p = c->p;
   const bool defcfg = p.range_mode == 0 && p.interp == 2 && p.use_dropoff && !p.const_weight;
   if (!defcfg) return false;
-  const bool exact = kFuseExact >= 0 ? kFuseExact != 0 : c->cfg.relaxed_arithmetic == 0;
-  return c->cfg.voxels_per_side == 8 || (c->cfg.voxels_per_side == 16 && exact);
+  return c->cfg.voxels_per_side == 8 || (c->cfg.voxels_per_side == 16 && exactArithmetic(c));
 }
 
-static int tickFuseUnion(khr_ctx* c, const int* slots, const DevFrame* frames, int nb, int use_mask, int object_id) {
+static int tickUpdateUnion(khr_ctx* c, const int* slots, const DevFrame* frames, int nb, int use_mask, int object_id) {
   FuseArgs a{};
   fillFuseMap(c, &a);
   FuseFrameSet set{};
@@ -2366,18 +2214,17 @@ static int tickFuseUnion(khr_ctx* c, const int* slots, const DevFrame* frames, i
   a.n_frames = nb;
   a.item_mask = reinterpret_cast<uint8_t*>(c->d_tick_mask);
   FuseList list{c->d_tick_work4, c->d_tick_work4 + c->item_cap, c->item_cap, &c->d_tick_counts[2 * kMaxTick]};
-  const bool exact = kFuseExact >= 0 ? kFuseExact != 0 : c->cfg.relaxed_arithmetic == 0;
   auto go = [&](auto kern, int wpw) {
     const int grid = fuse2Grid(c, reinterpret_cast<const void*>(kern), wpw);
     KHR_LAUNCH_TIMED(0, kern, dim3(grid), dim3(64 * wpw), a, list);
   };
   if (c->cfg.voxels_per_side == 8) {
-    if (exact) go(&k_fuse2<8, 4, true, true, 8, 4, true>, 8);
-    else go(&k_fuse2<8, 4, true, false, 8, 4, true>, 8);
+    if (exactArithmetic(c)) go(&k_fuse2<8, 4, true, true, 8, 4>, 8);
+    else go(&k_fuse2<8, 4, true, false, 8, 4>, 8);
   } else if (c->fuse_zsplit == 8) {
-    go(&k_fuse2<16, 8, true, true, 16, 4, true>, 16);
+    go(&k_fuse2<16, 8, true, true, 16, 4>, 16);
   } else {
-    go(&k_fuse2<16, 4, true, true, 16, 4, true>, 16);
+    go(&k_fuse2<16, 4, true, true, 16, 4>, 16);
   }
   c->tick_mask_dirty = false;
   HIP_TRY(hipGetLastError());
@@ -2432,7 +2279,7 @@ int khr_tick_integrate(khr_ctx* c, const int* slots, int n_frames, int use_mask,
         cubes += S * S * S;
       }
       const size_t box = static_cast<size_t>(hi[0] - lo[0] + 1) * static_cast<size_t>(hi[1] - lo[1] + 1) * static_cast<size_t>(hi[2] - lo[2] + 1);
-      if (kTickUnion && nb > 1 && box <= cubes && box < (1ull << 31)) {
+      if (nb > 1 && box <= cubes && box < (1ull << 31)) {
         hipLaunchKernelGGL(k_tick_alloc, dim3(static_cast<unsigned>((box + kTickAllocThreads - 1) / kTickAllocThreads)), dim3(kTickAllocThreads), 0, c->stream, m, c->p, tf, nb, make_int3(lo[0], lo[1], lo[2]),
                            make_int3(hi[0] - lo[0] + 1, hi[1] - lo[1] + 1, hi[2] - lo[2] + 1), c->d_tick_work, cap, c->d_new,
                            c->d_tick_counts, c->motion_ignore_epoch);
@@ -2460,7 +2307,7 @@ int khr_tick_integrate(khr_ctx* c, const int* slots, int n_frames, int use_mask,
       HIP_TRY(hipGetLastError());
     }
     if ((phases & 2) && one_launch) {
-      rc = tickFuseUnion(c, slots + base, t.f, nb, use_mask, object_id);
+      rc = tickUpdateUnion(c, slots + base, t.f, nb, use_mask, object_id);
       if (rc) return rc;
     }
     for (int k = 0; k < nb && (phases & 2) && !one_launch; ++k) {
@@ -3828,15 +3675,6 @@ int khr_generate_mesh(khr_ctx* c, int only_mesh_updated, int clear_flag) {
     // no host round trip: the capacity check happens on the device (C_MESH_OVERFLOW), totals are read lazily
     // emit pass + the copy of the kept blocks' vertices in ONE launch (the trailing kMoveWgs workgroups copy)
     constexpr uint32_t kMoveWgs = 1024;
-    static const bool split_move = std::getenv("KHR_MC_SPLIT_MOVE") != nullptr;  // A/B: the copy of the kept meshes as a launch of its own
-    if (split_move) {
-      KHR_LAUNCH_TIMED(9, (k_marching_cubes<V, true>), dim3(kStreamGrid), dim3(256), m, c->p, c->d_work, c->d_mesh_nwork, c->d_mesh_count,
-                       c->d_mesh_offset, dst, clear_flag, maxv, rmh, static_cast<uint32_t>(kStreamGrid), static_cast<const uint8_t*>(c->d_regen), src,
-                       static_cast<const uint32_t*>(c->d_mesh_old_off));
-      hipLaunchKernelGGL(k_mesh_move, dim3(kMoveWgs), dim3(256), 0, c->stream, m, static_cast<const uint8_t*>(c->d_regen),
-                         static_cast<const uint32_t*>(c->d_mesh_offset), static_cast<const uint32_t*>(c->d_mesh_old_off), src, dst, maxv);
-      return KHR_OK;
-    }
     KHR_LAUNCH_TIMED(9, (k_marching_cubes<V, true>), dim3(kStreamGrid + kMoveWgs), dim3(256), m, c->p, c->d_work,
                      c->d_mesh_nwork, c->d_mesh_count, c->d_mesh_offset, dst, clear_flag, maxv, rmh, static_cast<uint32_t>(kStreamGrid),
                      static_cast<const uint8_t*>(c->d_regen), src, static_cast<const uint32_t*>(c->d_mesh_old_off));
@@ -4248,7 +4086,7 @@ static int ingestAhead(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fr
   // the same conditions as the early ingest inside khr_process_frame, plus a ring with slots to spare: the slot of the frame
   // being processed and the one before it may still be read
   const int next = peekSlot(c);
-  if (!c->early_ingest || !c->cfg.with_tracking || c->slots.size() < 3 + c->ahead_q.size() || next < 0 || next == c->last_frame_slot) return KHR_ENOTFOUND;
+  if (!c->cfg.with_tracking || c->slots.size() < 3 + c->ahead_q.size() || next < 0 || next == c->last_frame_slot) return KHR_ENOTFOUND;
   HIP_TRY(hipSetDevice(c->device));
   // the buffers are read asynchronously: they have to be what the entry point says they are
   if (!pointerIs(frame->depth, on_device) || !pointerIs(frame->color, on_device) || !pointerIs(frame->label, on_device))
@@ -4291,7 +4129,7 @@ static int ingestAhead(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fr
   // khr_process_frame call would otherwise launch its own request over this one, which then ran twice.
   // Not for host frames: their planes are still travelling, and the auxiliary stream -- in order -- would hold the CURRENT frame's
   // detector kernels, queued later by its khr_process_frame call, behind that wait.
-  if (on_device && c->obj_configured && kAheadObjects && c->obj_pending_slot < 0 && c->ahead_q.empty()) {
+  if (on_device && c->obj_configured && c->obj_pending_slot < 0 && c->ahead_q.empty()) {
     const int rco = objectsLaunch(c, slot);
     if (rco) {
       if (c->obj_pending_slot == slot) c->obj_pending_slot = -1;
@@ -4347,11 +4185,6 @@ int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fra
     bool ok = false;
     ~Leave() {
       c->defer_fold = false;
-      c->band_fork = false;
-      if (c->band_join_pending) {  // an error between the update launch and the join: the main stream still has to see the band kernel
-        hipStreamWaitEvent(c->stream, c->ev_band_join, 0);
-        c->band_join_pending = false;
-      }
       if (!ok && c->fold_pending) {  // an error between the update launch and the tracking pass: fold now, nobody else will
         hipLaunchKernelGGL(k_fuse_fold, dim3((c->m.capacity + 255) / 256), dim3(256), 0, c->stream, c->m.blk_flags, c->m.blk_band,
                            &c->m.counters[C_MAX_SLOT], static_cast<const uint32_t*>(nullptr));
@@ -4369,7 +4202,7 @@ int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fra
   // ingest runs on the second stream behind them.  Their copy REWRITES the slot's raw planes and nothing orders the copy stream
   // behind the slot's last readers: with a ring of two the slot is that of the frame before last, whose tail may still be queued
   //  -- three slots, as the look-ahead requires, or the ingest (and with it the copy) stays ordered on the main stream
-  const bool early = ahead || (c->early_ingest && (flags & KHR_PF_INPUT_READY) && (on_device || pinned_in) && motion && c->cfg.with_tracking &&
+  const bool early = ahead || ((flags & KHR_PF_INPUT_READY) && (on_device || pinned_in) && motion && c->cfg.with_tracking &&
                                c->slots.size() >= (pinned_in ? 3u : 2u) && peekSlot(c) != c->last_frame_slot);
   int slot;
   int ahead_ev = 0;
@@ -4432,17 +4265,12 @@ int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fra
   //      the culling pass and the update kernel, for the seed count's trip to the host and the launch's trip back.)
   bool speculated = false;
   size_t spec_timer = static_cast<size_t>(-1), spec_end = 0;
-  // the band kernel of the update beside the tracking pass (k_tsdf + k_band5 only; joined below, before the output stage)
-  static const bool no_band_fork = std::getenv("KHR_NO_BAND_FORK") != nullptr;
-  const bool band_fork = !no_band_fork && (flags & KHR_PF_TRACKING) && c->cfg.with_tracking;
   // the update kernel's item records are folded into the block flags by the tracking pass's first kernel when it follows directly
   c->defer_fold = (flags & KHR_PF_TRACKING) && c->cfg.with_tracking;  // (reset below, before the tracking pass)
   // (not behind a seed frame: the frame is expected to have seeds, its clustering chain is queued ahead of the count instead)
-  if (motion && kFuseSpec && c->cfg.with_tracking && !(c->md_seed_run && std::getenv("KHR_MD_NO_PRELAUNCH") == nullptr)) {
+  if (motion && c->cfg.with_tracking && !(c->md_seed_run && std::getenv("KHR_MD_NO_PRELAUNCH") == nullptr)) {
     const size_t n_pending = c->pending.size();
-    c->band_fork = band_fork;
     rc = integrateUpdate(c, s, f, 1, 0, -1, nullptr, &c->m.counters[C_N_SEEDS]);
-    c->band_fork = false;
     if (rc) return rc;
     if (c->pending.size() > n_pending) spec_timer = n_pending;  // (first of the launch's timer samples)
     spec_end = c->pending.size();
@@ -4464,9 +4292,7 @@ int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fra
   if (speculated && have_seeds && spec_timer != static_cast<size_t>(-1))  // the gated launches did nothing: not samples
     for (size_t i = spec_timer; i < spec_end && i < c->pending.size(); ++i) c->pending[i].which = -1;
   if (!speculated || have_seeds) {
-    c->band_fork = band_fork;
     rc = integrateUpdate(c, s, f, 1, motion ? 1 : 0, -1);
-    c->band_fork = false;
     if (rc) return rc;
   }
   if (c->md_summary_pending >= 0) {  // the dynamic clusters' summaries, behind the update kernels
@@ -4478,7 +4304,7 @@ int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fra
   // Output frames: marching cubes read distance / weight / colour / label / stamps, which the tracking pass does not touch
   // (it writes voxel flags, last_occupied, free bits and -- atomically -- block flags): the mesh kernels are forked onto
   // their own stream behind k_tracking_select (which has folded the update's block flags) and joined before archival.
-  const bool mc_fork = kMcFork && (flags & KHR_PF_OUTPUT) && (flags & KHR_PF_TRACKING) && c->cfg.with_tracking;
+  const bool mc_fork = (flags & KHR_PF_OUTPUT) && (flags & KHR_PF_TRACKING) && c->cfg.with_tracking;
   if (mc_fork) {
     if (!c->mc_stream) HIP_TRY(createStream(c, &c->mc_stream));
     if (!c->ev_mc_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_mc_fork, hipEventDisableTiming));
@@ -4487,16 +4313,10 @@ int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fra
   }
   rc = (flags & KHR_PF_TRACKING) ? khr_update_tracking(c, frame->timestamp_ns) : KHR_OK;
   c->fork_after_select = false;
-  if (c->band_join_pending) {  // from here on the main stream may read colour / labels / likelihoods again
-    c->band_join_pending = false;
-    if (mc_fork) HIP_TRY(hipStreamWaitEvent(c->mc_stream, c->ev_band_join, 0));
-    HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_band_join, 0));
-  }
   if (rc) return rc;
   // output frames: which blocks the archival below will drop is decided now (the tracking pass has set the block flags it looks at);
   // their list goes to the host at once, the archival itself has to wait for the mesh kernels and the snapshot
-  static const bool no_early_list = std::getenv("KHR_NO_EARLY_REMOVED") != nullptr;
-  const bool early_list = !no_early_list && (flags & KHR_PF_OUTPUT) && c->cfg.with_tracking;
+  const bool early_list = (flags & KHR_PF_OUTPUT) && c->cfg.with_tracking;
   if (mc_fork) {
     HIP_TRY(hipStreamWaitEvent(c->mc_stream, c->ev_mc_fork, 0));
     hipStream_t main_stream = c->stream;
@@ -4522,7 +4342,7 @@ int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fra
       HIP_TRY(hipEventRecord(c->ev_snap_fork, c->stream));
       HIP_TRY(hipStreamWaitEvent(c->snap_stream, c->ev_snap_fork, 0));
       const int64_t snap_cap = c->cfg.max_snapshot_blocks ? c->cfg.max_snapshot_blocks : 8192;  // (100 KB per block)
-      c->snap_stream_override = kSnapFork ? c->snap_stream : nullptr;
+      c->snap_stream_override = c->snap_stream;
       rc = khr_snapshot_updated(c, KHR_SNAP_ALL, snap_cap, &c->pending_snapshot);
       c->snap_stream_override = nullptr;
       if (rc) return rc;
@@ -4657,10 +4477,10 @@ int khr_get_stats(khr_ctx* c, khr_stats* out) {
   s.n_new_blocks = c->h_counters[C_N_NEW];
   s.n_visited_voxels = static_cast<uint64_t>(c->h_counters[C_N_VISIBLE]) * c->p.nvox;
   // k_fuse's per-workgroup partial sums since the last per-call reset (beginIntegrate folds them into the totals)
-  std::vector<uint32_t> wgs(2 * kFuseStatSlots);
+  std::vector<uint32_t> wgs(2 * kUpdateStatSlots);
   HIP_TRY(hipMemcpy(wgs.data(), c->d_wg_stats, sizeof(uint32_t) * wgs.size(), hipMemcpyDeviceToHost));
   uint64_t cur_upd = 0, cur_band = 0;
-  for (int i = 0; i < kFuseStatSlots; ++i) {
+  for (int i = 0; i < kUpdateStatSlots; ++i) {
     cur_upd += wgs[2 * i];
     cur_band += wgs[2 * i + 1];
   }
@@ -4682,7 +4502,7 @@ int khr_get_stats(khr_ctx* c, khr_stats* out) {
   s.n_md_host_walks = c->n_md_host_walks;
   s.n_md_prelaunched = c->n_md_prelaunched;
   s.n_md_prelaunch_repeats = c->n_md_prelaunch_repeats;
-  s.band_overflow = c->h_counters[C_BAND_OVERFLOW];  // k_tsdf: in-band records dropped for lack of record chunks (the pool is sized so that this stays 0)
+  s.band_overflow = 0;  // (no update kernel keeps a global record list)
   s.n_tracking_processed_blocks = c->h_counters[c->ef_cur ? C_N_PROC2 : C_N_PROC];
   s.cum_updated_voxels = st[S_CUM_UPD] + cur_upd;
   s.cum_band_voxels = st[S_CUM_BAND] + cur_band;

@@ -50,10 +50,12 @@ def test_alloc_candidate_camera_offset_equals_oracle_and_differs_from_block_cent
 
 
 def test_alloc_candidate_on_the_tick_path():
-    """the rig tick allocates with ONE launch for all cameras (k_tick_alloc): the same per-block question per camera"""
+    """the rig tick allocates with ONE launch for all cameras (k_tick_alloc): the same per-block question per camera.  Its update is
+    the multi-frame k_fuse2, which also carries the colour-blend switch in its record lists: one run with color_blend_weight = 1"""
     from common import DeviceArray
-    for mode in (0, 1):
-        cfg, ctx, ora, s, sen, osen = make_pair(width=160, height=120, num_frame_slots=8, alloc_candidate=mode, max_blocks=8192)
+    for mode, blend in ((0, 0), (1, 0), (0, 1)):
+        cfg, ctx, ora, s, sen, osen = make_pair(width=160, height=120, num_frame_slots=8, alloc_candidate=mode, max_blocks=8192,
+                                                color_blend_weight=blend)
         for tick in range(4):
             frs = [s.render(tick, yaw_offset=2.1 * k + 0.1 * tick) for k in range(3)]  # three cameras of a rig
             stamp = frs[0]["stamp"]
@@ -68,7 +70,7 @@ def test_alloc_candidate_on_the_tick_path():
             for f in frs:
                 ora.integrate(osen, stamp, f["pose"], f["depth"], f["rgb"], f["label"])
             gi, oi = ctx.block_indices(), ora.block_indices()
-            assert gi.shape == oi.shape and (gi == oi).all(), (mode, tick)
+            assert gi.shape == oi.shape and (gi == oi).all(), (mode, blend, tick)
         compare_maps(ctx, ora, max_blocks=40, exact=True)
         ctx.close()
         ora.close()
@@ -109,16 +111,12 @@ def test_mesh_switches_change_the_mesh():
         assert np.array_equal(x["points"], y["points"])
 
 
-def test_switches_in_the_update_kernel_variants(monkeypatch):
-    """k_tsdf + k_band5 (KHR_FUSE_V = 5, khr_kernels_fuse5.h) carry the blend switch in their record lists; they, the default k_fuse
-    (KHR_FUSE_V = 1) and k_fuse2 must all equal the oracle"""
-    for ver in ("5", "1", "2"):
-        monkeypatch.setenv("KHR_FUSE_V", ver)
-        for blend in (0, 1):
-            _run(6, color_blend_weight=blend, exact_arithmetic=1)
-        _run(4, exact_arithmetic=0)
-    monkeypatch.delenv("KHR_FUSE_V")
-    _run(2, exact_arithmetic=1)  # (leaves the process-wide switch at the default for the tests that follow)
+def test_switches_in_the_update_kernel_variants():
+    """k_fuse carries the blend switch in its record lists: both settings in exact arithmetic and the relaxed form must equal the
+    oracle (the multi-frame k_fuse2 of the rig tick: test_alloc_candidate_on_the_tick_path)"""
+    for blend in (0, 1):
+        _run(6, color_blend_weight=blend, exact_arithmetic=1)
+    _run(4, exact_arithmetic=0)
 
 
 def test_packed_likelihood_rows_equal_the_padded_pool():

@@ -1,5 +1,5 @@
 #!/bin/bash
-# PMC passes on k_fuse for one or more env settings: tools/pmc_fuse.sh "<passes>" base KHR_FUSE_BAND=0 ...
+# PMC passes on k_fuse for one or more env settings: tools/pmc_fuse.sh "<passes>" base KHR_STREAM_PRIORITY=0 ...
 # (one counter group per run; --kernel-trace only, as gpurun requires)
 P="$1"; shift
 R=$PWD; export TMPDIR=/tmp
