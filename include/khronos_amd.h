@@ -494,6 +494,16 @@ int64_t khr_block_indices(khr_ctx* ctx, int32_t* out, int64_t cap, int only_upda
 int khr_download_block(khr_ctx* ctx, int32_t bx, int32_t by, int32_t bz, float* distance, float* weight,
                        uint8_t* color_rgba, uint64_t* last_observed, uint64_t* last_occupied,
                        uint8_t* voxel_flags, uint32_t* sem_label, float* likelihoods, uint8_t* block_flags);
+/* One z-plane of the live map, read on the device (ActiveWindowVisualizer's map slices, active_window_visualizer.cpp:345-520):
+ * the vps*vps voxels at global voxel z `voxel_z` of every live block on that layer, blocks sorted by (bx, by), voxels x-outer /
+ * y-inner (output voxel = rank * vps^2 + x * vps + y).  block_xy: 2 per block; positions: the voxel centres, 3 floats per voxel;
+ * last_observed: 0 without tracking; voxel_flags: KHR_VOX_* bits.  Any output may be NULL (not copied).  *n_voxels = count; if it
+ * exceeds cap nothing is written and KHR_ENOMEM is returned.  One host wait per call once the context's slice staging has grown
+ * to the layer.  Sharded contexts: this rank's blocks. */
+int khr_map_slice(khr_ctx* ctx, int64_t voxel_z, int64_t cap, int32_t* block_xy, float* positions, float* distance, float* weight,
+                  uint64_t* last_observed, uint8_t* voxel_flags, int64_t* n_voxels);
+/* getVoxelKey((0, 0, height)).z as a global voxel index (ASSUMPTIONS.md A.10); needs no context and no device */
+int khr_slice_voxel_z(float height, float voxel_size, int32_t voxels_per_side, int64_t* voxel_z);
 /* Order-independent 64-bit digests of the WHOLE map (every live block, every voxel), one word per layer, on the values
  * khr_download_block hands out:  digest[layer] = sum_b sum_i mix(mix(key(b) * G + layer * L + i) ^ value_bits) mod 2^64
  * (mix = splitmix64 finaliser, key = 3 x 21-bit packed block index; csrc/khr_kernels_aux.h: digestTerm).  Sums commute, so

@@ -93,6 +93,7 @@ EXPORTS = [
     "khr_rv_create", "khr_rv_destroy", "khr_rv_clear", "khr_rv_add_rays", "khr_rv_num_rays", "khr_rv_num_pairs", "khr_rv_check",
     "khr_snapshot_updated", "khr_take_snapshot", "khr_snapshot_num_blocks", "khr_snapshot_download", "khr_snapshot_download_extra", "khr_snapshot_download_begin", "khr_snapshot_download_end", "khr_snapshot_poll", "khr_fetch_mesh_launch", "khr_reserve_mesh_staging", "khr_reserve_snapshots", "khr_mirror_dynamic", "khr_snapshot_release",
     "khr_rv_check_stamps", "khr_get_config", "khr_cluster_voxels_launch", "khr_cluster_voxels_fetch", "khr_reset_map", "khr_depend_on", "khr_retain_slot", "khr_release_slot",
+    "khr_map_slice", "khr_slice_voxel_z",
 ]
 
 _lib = None
@@ -178,6 +179,8 @@ def load_library():
     lib.khr_block_indices.argtypes = [vp, vp, i64, i32]
     lib.khr_block_indices.restype = i64
     lib.khr_download_block.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 9
+    lib.khr_map_slice.argtypes = [vp, i64, i64] + [vp] * 7
+    lib.khr_slice_voxel_z.argtypes = [C.c_float, C.c_float, C.c_int32, vp]
     lib.khr_mesh_halo_requests.argtypes = [vp, vp, i64, i32, i32]
     lib.khr_mesh_halo_export.argtypes = [vp, vp, i64, vp, i64, i32]
     lib.khr_mesh_halo_import.argtypes = [vp, vp, i64, i32]
@@ -247,6 +250,20 @@ def default_config(**overrides):
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def slice_voxel_z(height, voxel_size, voxels_per_side):
+    """getVoxelKey((0, 0, height)).z as a global voxel index (ASSUMPTIONS.md A.10): block floor, then voxel floor inside the
+    block, in float32; a voxel index of -1 / vps that rounding produces stays as it is and names the edge voxel of the
+    neighbouring layer.  Same rule as khr_slice_voxel_z (C) and hydra::sliceVoxelZ (C++); needs no library."""
+    f32 = np.float32
+    h, vs = f32(height), f32(voxel_size)
+    if not (np.isfinite(h) and vs > 0 and voxels_per_side >= 1):
+        raise ValueError("bad slice arguments (%r, %r, %r)" % (height, voxel_size, voxels_per_side))
+    bs = vs * f32(voxels_per_side)
+    bz = int(np.floor(h * (f32(1) / bs)))
+    v = int(np.floor((h - f32(bz) * bs) * (f32(1) / vs)))
+    return bz * int(voxels_per_side) + v
 
 
 class FusionContext:
@@ -642,6 +659,36 @@ class FusionContext:
             _ptr(b["likelihoods"]), _ptr(bf)))
         b["block_flags"] = int(bf[0])
         return b
+
+    SLICE_FIELDS = ("block_xy", "positions", "distance", "weight", "last_observed", "flags")
+
+    def map_slice_into(self, voxel_z, cap, out):
+        """khr_map_slice into caller arrays (`out`: SLICE_FIELDS -> contiguous array or None); returns (return code, voxel count)
+        without raising, so that callers can see KHR_ENOMEM and the true count."""
+        n = C.c_int64(0)
+        rc = self.lib.khr_map_slice(self.h, int(voxel_z), int(cap), *[_ptr(out.get(k)) for k in self.SLICE_FIELDS], C.byref(n))
+        return rc, n.value
+
+    def map_slice(self, voxel_z):
+        """One z-plane of the live map (khr_map_slice): dict with voxel_z, block_xy (blocks, 2) int32 sorted by (bx, by),
+        positions (n, 3) float32 voxel centres, distance, weight, last_observed (uint64), flags (uint8); voxels of a block
+        x-outer / y-inner."""
+        vps = self.cfg.voxels_per_side
+        cap = getattr(self, "_slice_hint", 0)
+        while True:
+            out = {"block_xy": np.zeros((cap // (vps * vps), 2), np.int32), "positions": np.zeros((cap, 3), np.float32),
+                   "distance": np.zeros(cap, np.float32), "weight": np.zeros(cap, np.float32),
+                   "last_observed": np.zeros(cap, np.uint64), "flags": np.zeros(cap, np.uint8)}
+            rc, n = self.map_slice_into(voxel_z, cap, out)
+            if rc == KHR_ENOMEM and n > cap:
+                cap = n
+                continue
+            self._chk(rc)
+            break
+        self._slice_hint = n
+        res = {k: v[: n // (vps * vps)] if k == "block_xy" else v[:n] for k, v in out.items()}
+        res["voxel_z"] = int(voxel_z)
+        return res
 
     def mesh_halo_words(self):
         v = self.cfg.voxels_per_side

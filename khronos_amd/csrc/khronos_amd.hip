@@ -33,6 +33,7 @@
 #include "khr_kernels_fusion.h"
 #include "khr_kernels_fuse.h"
 #include "khr_kernels_objects.h"
+#include "khr_kernels_slice.h"
 
 using namespace khr;
 
@@ -360,6 +361,13 @@ struct khr_ctx {
   bool host_index_valid = false;
   std::map<std::array<int32_t, 3>, uint32_t> host_index;
   std::vector<uint32_t> host_flags;
+  // map slices (khr_map_slice): sort keys (nextpow2(capacity) words) + count, created at the first slice; the SoA staging and its
+  // page-locked mirror (same layout, count word in front) grow on demand; slice_hint = blocks the next call copies up front
+  uint64_t* d_slice_keys = nullptr;
+  uint32_t* d_slice_count = nullptr;
+  uint8_t* d_slice_stage = nullptr;
+  uint8_t* h_slice_stage = nullptr;
+  uint32_t slice_cap = 0, slice_hint = 0;
   // timing
   uint32_t timing = 0;  // bit i = timer i enabled
   std::vector<TimingRec> pending;
@@ -1107,6 +1115,9 @@ void khr_destroy(khr_ctx* c) {
     if (c->ev_ahead_h2d[i]) hipEventDestroy(c->ev_ahead_h2d[i]);
   }
   if (c->d_inst) hipFree(c->d_inst);
+  if (c->d_slice_keys) { hipFree(c->d_slice_keys); hipFree(c->d_slice_count); }
+  if (c->d_slice_stage) hipFree(c->d_slice_stage);
+  if (c->h_slice_stage) hipHostFree(c->h_slice_stage);
   if (c->pending_snapshot) khr_snapshot_release(c->pending_snapshot);
   if (c->snap_stream) {
     hipStreamSynchronize(c->snap_stream);
@@ -4604,6 +4615,162 @@ int khr_download_block(khr_ctx* c, int32_t bx, int32_t by, int32_t bz, float* di
       if (!(f[i] & VOX_SEM_VALID))
         for (int k = 0; k < c->p.K; ++k) likelihoods[static_cast<size_t>(k) * nv + i] = 0.f;
   }
+  return KHR_OK;
+}
+
+// ---- one z-plane of the live map (khr_map_slice; ActiveWindowVisualizer's map slices, active_window_visualizer.cpp:345-520) ----
+// getVoxelKey((0, 0, height)).z as a global voxel index: ASSUMPTIONS.md A.10 (hydra::sliceVoxelZ and capi.slice_voxel_z are
+// the same rule)
+int khr_slice_voxel_z(float height, float voxel_size, int32_t voxels_per_side, int64_t* voxel_z) {
+  if (!voxel_z || !(voxel_size > 0.f) || voxels_per_side < 1 || !std::isfinite(height)) return fail(KHR_EINVAL, "bad argument");
+  const float bs = voxel_size * static_cast<float>(voxels_per_side), bs_inv = 1.f / bs, vs_inv = 1.f / voxel_size;
+  const float fb = std::floor(height * bs_inv);
+  if (!(std::fabs(fb) < 1e15f)) return fail(KHR_EINVAL, "slice height %g is out of range", static_cast<double>(height));
+  const int64_t bz = static_cast<int64_t>(fb);
+  const float origin = static_cast<float>(bz) * bs;
+  const int64_t v = static_cast<int64_t>(std::floor((height - origin) * vs_inv));
+  *voxel_z = bz * voxels_per_side + v;
+  return KHR_OK;
+}
+
+// byte offsets of the fields inside the slice staging of `cap` blocks (device staging and page-locked mirror alike)
+struct SliceLayout {
+  size_t xy, pos, dist, weight, obs, flags, bytes;
+  SliceLayout(size_t cap, size_t np) {
+    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+    xy = 256;  // (the mirror's first word takes the count)
+    pos = xy + al(cap * 8);
+    dist = pos + al(cap * np * 12);
+    weight = dist + al(cap * np * 4);
+    obs = weight + al(cap * np * 4);
+    flags = obs + al(cap * np * 8);
+    bytes = flags + al(cap * np);
+  }
+};
+
+static int sliceGrow(khr_ctx* c, uint32_t need) {
+  const uint32_t cap = std::min<uint32_t>(std::max<uint32_t>(need + need / 2, 64u), c->m.capacity);
+  const SliceLayout L(cap, static_cast<size_t>(c->p.vps) * c->p.vps);
+  if (c->d_slice_stage) HIP_TRY(hipFree(c->d_slice_stage));
+  if (c->h_slice_stage) HIP_TRY(hipHostFree(c->h_slice_stage));
+  c->d_slice_stage = c->h_slice_stage = nullptr;
+  c->slice_cap = 0;
+  if (hipMalloc(reinterpret_cast<void**>(&c->d_slice_stage), L.bytes) != hipSuccess) return fail(KHR_ENOMEM, "slice staging of %zu bytes", L.bytes);
+  if (hipHostMalloc(reinterpret_cast<void**>(&c->h_slice_stage), L.bytes, hipHostMallocDefault) != hipSuccess) {
+    hipFree(c->d_slice_stage);
+    c->d_slice_stage = nullptr;
+    return fail(KHR_ENOMEM, "page-locked slice staging of %zu bytes", L.bytes);
+  }
+  c->slice_cap = cap;
+  return KHR_OK;
+}
+
+int khr_map_slice(khr_ctx* c, int64_t voxel_z, int64_t cap, int32_t* block_xy, float* positions, float* distance, float* weight,
+                  uint64_t* last_observed, uint8_t* voxel_flags, int64_t* n_voxels) {
+  if (!c || !n_voxels || cap < 0) return fail(KHR_EINVAL, "bad argument");
+  *n_voxels = 0;
+  HIP_TRY(hipSetDevice(c->device));
+  if (c->m.capacity >= (1u << kSliceSlotBits)) return fail(KHR_EINVAL, "map slices need max_blocks < %u", 1u << kSliceSlotBits);
+  const int64_t vps = c->p.vps, np = vps * vps;
+  const int64_t bz = (voxel_z >= 0 ? voxel_z : voxel_z - (vps - 1)) / vps, lz = voxel_z - bz * vps;  // floor division
+  if (bz < -(1 << 20) || bz >= (1 << 20)) return KHR_OK;  // (beyond the block index range: no block lies there)
+  const uint32_t sort_len = slicePadded(c->m.capacity);
+  if (!c->d_slice_keys) {
+    if (hipMalloc(reinterpret_cast<void**>(&c->d_slice_keys), sizeof(uint64_t) * sort_len) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&c->d_slice_count), sizeof(uint32_t)) != hipSuccess) {
+      if (c->d_slice_keys) hipFree(c->d_slice_keys);
+      c->d_slice_keys = nullptr;
+      return fail(KHR_ENOMEM, "slice sort keys (%u words)", sort_len);
+    }
+  }
+  if (!c->d_slice_stage) {
+    const int rc = sliceGrow(c, 64u);
+    if (rc) return rc;
+  }
+  const bool want[6] = {block_xy != nullptr, positions != nullptr, distance != nullptr, weight != nullptr, last_observed != nullptr,
+                        voxel_flags != nullptr};
+  auto outFor = [&]() {
+    const SliceLayout L(c->slice_cap, static_cast<size_t>(np));
+    uint8_t* d = c->d_slice_stage;
+    SliceOut o{};
+    o.block_xy = want[0] ? reinterpret_cast<int32_t*>(d + L.xy) : nullptr;
+    o.pos = want[1] ? reinterpret_cast<float*>(d + L.pos) : nullptr;
+    o.dist = want[2] ? reinterpret_cast<float*>(d + L.dist) : nullptr;
+    o.weight = want[3] ? reinterpret_cast<float*>(d + L.weight) : nullptr;
+    o.last_obs = want[4] ? reinterpret_cast<uint64_t*>(d + L.obs) : nullptr;
+    o.vflags = want[5] ? d + L.flags : nullptr;
+    o.cap_blocks = c->slice_cap;
+    return o;
+  };
+  const int gather_grid = static_cast<int>(std::min<uint32_t>(c->m.capacity, 2048u));
+  auto gather = [&]() {
+    return dispatchVps(c, [&](auto vps_c) {
+      constexpr int V = decltype(vps_c)::value;
+      hipLaunchKernelGGL((k_slice_gather<V>), dim3(gather_grid), dim3(V * V), 0, c->stream, c->m, c->p, c->d_slice_keys,
+                         c->d_slice_count, static_cast<int>(bz), static_cast<int>(lz), outFor());
+      HIP_TRY(hipGetLastError());
+      return KHR_OK;
+    });
+  };
+  // per-block bytes of each field and its offset: copies of the blocks [b0, b1) into the mirror
+  auto copies = [&](uint32_t b0, uint32_t b1) {
+    const SliceLayout L(c->slice_cap, static_cast<size_t>(np));
+    const size_t off[6] = {L.xy, L.pos, L.dist, L.weight, L.obs, L.flags};
+    const size_t per[6] = {8, static_cast<size_t>(np) * 12, static_cast<size_t>(np) * 4, static_cast<size_t>(np) * 4,
+                           static_cast<size_t>(np) * 8, static_cast<size_t>(np)};
+    for (int f = 0; f < 6; ++f)
+      if (want[f] && b1 > b0)
+        HIP_TRY(hipMemcpyAsync(c->h_slice_stage + off[f] + b0 * per[f], c->d_slice_stage + off[f] + b0 * per[f], (b1 - b0) * per[f],
+                               hipMemcpyDeviceToHost, c->stream));
+    return KHR_OK;
+  };
+  // select -> sort -> gather, all on the device; then the count and the hinted number of blocks of every requested field in one batch
+  HIP_TRY(hipMemsetAsync(c->d_slice_count, 0, sizeof(uint32_t), c->stream));
+  hipLaunchKernelGGL(k_slice_select, dim3(std::min(gridFor(c->m.capacity), 1024)), dim3(256), 0, c->stream, c->m, static_cast<int>(bz),
+                     c->d_slice_count, c->d_slice_keys);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_slice_sort_tile, dim3(std::max(1u, sort_len / kSliceSortTile)), dim3(kSliceSortThreads), 0, c->stream,
+                     c->d_slice_keys, c->d_slice_count, 0u);
+  HIP_TRY(hipGetLastError());
+  for (uint32_t k = 2 * kSliceSortTile; k <= sort_len; k <<= 1) {  // multi-pass: stages beyond the count's length exit on the device
+    for (uint32_t j = k / 2; j >= kSliceSortTile; j >>= 1) {
+      hipLaunchKernelGGL(k_slice_sort_step, dim3(std::min(gridFor(sort_len / 2), 1024)), dim3(256), 0, c->stream, c->d_slice_keys,
+                         c->d_slice_count, k, j);
+      HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_slice_sort_tile, dim3(sort_len / kSliceSortTile), dim3(kSliceSortThreads), 0, c->stream, c->d_slice_keys,
+                       c->d_slice_count, k);
+    HIP_TRY(hipGetLastError());
+  }
+  int rc = gather();
+  if (rc) return rc;
+  uint32_t n_copied = std::min(c->slice_cap, c->slice_hint);
+  HIP_TRY(hipMemcpyAsync(c->h_slice_stage, c->d_slice_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if ((rc = copies(0, n_copied))) return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const uint32_t n = *reinterpret_cast<const uint32_t*>(c->h_slice_stage);
+  if (n > c->slice_cap) {  // (the staging was too small and the gather wrote nothing: grow, gather again)
+    if ((rc = sliceGrow(c, n))) return rc;
+    if ((rc = gather())) return rc;
+    n_copied = 0;
+  }
+  if (n > n_copied) {  // (more blocks than the hint: the rest)
+    if ((rc = copies(n_copied, n))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  c->slice_hint = n + n / 4 + 16;
+  *n_voxels = static_cast<int64_t>(n) * np;
+  if (*n_voxels > cap)
+    return fail(KHR_ENOMEM, "the slice holds %lld voxels, cap %lld", static_cast<long long>(*n_voxels), static_cast<long long>(cap));
+  const SliceLayout L(c->slice_cap, static_cast<size_t>(np));
+  const uint8_t* h = c->h_slice_stage;
+  const size_t nv = static_cast<size_t>(*n_voxels);
+  if (block_xy) std::memcpy(block_xy, h + L.xy, static_cast<size_t>(n) * 8);
+  if (positions) std::memcpy(positions, h + L.pos, nv * 12);
+  if (distance) std::memcpy(distance, h + L.dist, nv * 4);
+  if (weight) std::memcpy(weight, h + L.weight, nv * 4);
+  if (last_observed) std::memcpy(last_observed, h + L.obs, nv * 8);
+  if (voxel_flags) std::memcpy(voxel_flags, h + L.flags, nv);
   return KHR_OK;
 }
 

@@ -2,6 +2,7 @@
 // thread drives the reference (spinOnce per InputPacket, finishMapping at shutdown), and prints a JSON
 // summary that tests/test_gpu_host.py compares with the step-wise C-ABI path and the oracle.
 // usage: aw_demo <config.yaml> <width> <height> <frames> [object_label]
+//        aw_demo --slices | --bench | --rayver ... (below)
 //   object_label >= 0: the stand-in detector / tracker below; otherwise the plugins named in the config
 #include <execinfo.h>
 #include <csignal>
@@ -255,6 +256,131 @@ static int benchDemo(int argc, char** argv) {
   return 0;
 }
 
+// The visualizer's three map slices restated over a cloneBlock loop (the path INTEGRATION.md section 3 used to give sinks): every
+// allocated block on the layer, in allocatedBlockIndices' sorted order, copied whole, its plane read x-outer / y-inner.
+static hydra::MapSlice sliceByBlockCopies(const VolumetricMap& map, float height) {
+  hydra::MapSlice s;
+  const int vps = map.config.voxels_per_side;
+  s.voxel_z = hydra::sliceVoxelZ(height, map.config.voxel_size, vps);
+  s.voxels_per_side = vps;
+  const int64_t bz = (s.voxel_z >= 0 ? s.voxel_z : s.voxel_z - (vps - 1)) / vps, lz = s.voxel_z - bz * vps;
+  const float bs = map.blockSize(), vs = map.config.voxel_size;
+  for (const auto& idx : map.allocatedBlockIndices()) {
+    if (idx[2] != bz) continue;
+    const hydra::BlockCopy b = map.cloneBlock(idx);
+    s.block_xy.insert(s.block_xy.end(), {idx[0], idx[1]});
+    for (int x = 0; x < vps; ++x)
+      for (int y = 0; y < vps; ++y) {
+        const size_t lin = static_cast<size_t>(x + vps * (y + vps * lz));
+        s.positions.insert(s.positions.end(), {static_cast<float>(idx[0]) * bs + (static_cast<float>(x) + 0.5f) * vs,
+                                               static_cast<float>(idx[1]) * bs + (static_cast<float>(y) + 0.5f) * vs,
+                                               static_cast<float>(idx[2]) * bs + (static_cast<float>(lz) + 0.5f) * vs});
+        s.distance.push_back(b.distance[lin]);
+        s.weight.push_back(b.weight[lin]);
+        s.last_observed.push_back(b.last_observed[lin]);
+        s.flags.push_back(b.flags[lin]);
+      }
+  }
+  return s;
+}
+
+template <typename T>
+static bool sameBits(const std::vector<T>& a, const std::vector<T>& b) {
+  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
+}
+
+// aw_demo --slices <config.yaml> <width> <height> <frames> [slice_height] [relative] [show_unknown]: a Khronos sink builds the
+// visualizer's three slices every frame twice, through VolumetricMap::slice (khr_map_slice) and through a cloneBlock loop, checks
+// that they agree and times both (the device is drained before each, so neither pays for the frame's own kernels).  One JSON line:
+// per-frame means after kWarm frames -- device_slice_ms (VolumetricMap::slice + the three classifications), device_fetch_ms (the
+// slice call alone), block_copy_ms (the cloneBlock loop + the same classifications).
+static int slicesDemo(int argc, char** argv) {
+  if (argc < 6) {
+    std::fprintf(stderr, "usage: aw_demo --slices <config.yaml> <width> <height> <frames> [slice_height] [relative] [show_unknown]\n");
+    return 2;
+  }
+  std::ifstream in(argv[2]);
+  std::stringstream ss;
+  ss << in.rdbuf();
+  const int W = std::atoi(argv[3]), H = std::atoi(argv[4]), N = std::atoi(argv[5]);
+  hydra::SliceConfig sc;
+  if (argc > 6) sc.slice_height = static_cast<float>(std::atof(argv[6]));
+  if (argc > 7) sc.slice_height_is_relative = std::atoi(argv[7]) != 0;
+  if (argc > 8) sc.show_unknown_voxels = std::atoi(argv[8]) != 0;
+  constexpr int kWarm = 3;  // frames before the averages (the slice staging grows on the first calls)
+  ActiveWindow::Config cfg = ActiveWindow::Config::fromYamlString(ss.str());
+  cfg.max_frame_pixels = static_cast<uint32_t>(W) * H;
+  auto out_queue = std::make_shared<ActiveWindow::OutputQueue>();
+  ActiveWindow aw(cfg, out_queue);
+  int frames = 0, agree = 0, timed = 0;
+  double ms_dev = 0, ms_fetch = 0, ms_copy = 0, blocks = 0;
+  size_t blocks_max = 0, points = 0;
+  std::string first_mismatch;
+  using clk = std::chrono::steady_clock;
+  aw.addKhronosSink([&](const FrameData& data, const VolumetricMap& map, const Tracks&) {
+    const float h = sc.height(data.input.world_T_body);
+    const uint64_t stamp = data.input.timestamp_ns;
+    const float trunc = map.config.truncation_distance;
+    khr_sync(map.ctx());
+    const auto t0 = clk::now();
+    const hydra::MapSlice a = map.slice(h);
+    const auto t_fetch = clk::now();
+    const hydra::SlicePoints ea = hydra::everFreeSlice(a, sc.show_unknown_voxels), ta = hydra::trackingSlice(a, stamp, sc.show_unknown_voxels),
+                             da = hydra::tsdfSlice(a, trunc);
+    const auto t1 = clk::now();
+    const hydra::MapSlice b = sliceByBlockCopies(map, h);
+    const hydra::SlicePoints eb = hydra::everFreeSlice(b, sc.show_unknown_voxels), tb = hydra::trackingSlice(b, stamp, sc.show_unknown_voxels),
+                             db = hydra::tsdfSlice(b, trunc);
+    const auto t2 = clk::now();
+    const bool same_slice = a.voxel_z == b.voxel_z && a.block_xy == b.block_xy && sameBits(a.positions, b.positions) &&
+                            sameBits(a.distance, b.distance) && sameBits(a.weight, b.weight) && a.last_observed == b.last_observed &&
+                            a.flags == b.flags;
+    const bool ok = same_slice && ea == eb && ta == tb && da == db;
+    if (ok) ++agree;
+    else if (first_mismatch.empty())
+      first_mismatch = "frame " + std::to_string(frames) + (same_slice ? ": classifications differ" : ": slices differ") + " (" +
+                       std::to_string(a.numBlocks()) + " / " + std::to_string(b.numBlocks()) + " blocks)";
+    if (frames >= kWarm) {
+      ms_dev += std::chrono::duration<double, std::milli>(t1 - t0).count();
+      ms_fetch += std::chrono::duration<double, std::milli>(t_fetch - t0).count();
+      ms_copy += std::chrono::duration<double, std::milli>(t2 - t1).count();
+      blocks += static_cast<double>(a.numBlocks());
+      ++timed;
+    }
+    blocks_max = std::max(blocks_max, a.numBlocks());
+    points += ea.voxel.size() + ta.voxel.size() + da.voxel.size();
+    ++frames;
+  });
+  void* scene = synth_create(1234, 12, 1);
+  const size_t n = static_cast<size_t>(W) * H;
+  std::vector<float> depth(n);
+  std::vector<uint8_t> rgb(n * 3);
+  std::vector<int32_t> label(n);
+  for (int i = 0; i < N; ++i) {
+    hydra::InputPacket pkt;
+    pkt.timestamp_ns = static_cast<uint64_t>(std::llround((1.0 + 0.1 * i) * 1e9));
+    circlePose(0.1 * i, pkt.world_T_body);
+    pkt.sensor = {W, H, W / 2.f, W / 2.f, W / 2.f, H / 2.f, 0.1f, 5.f};
+    synth_render(scene, W, H, pkt.sensor.fx, pkt.sensor.fy, pkt.sensor.cx, pkt.sensor.cy, pkt.world_T_body, 0.1 * i, 5.f, 0.f,
+                 1234u + 7919u * i, depth.data(), rgb.data(), label.data(), 0);
+    pkt.depth = depth.data();
+    pkt.color = rgb.data();
+    pkt.labels = label.data();
+    aw.step(pkt);
+    hydra::ActiveWindowOutput::Ptr popped;
+    while (out_queue->pop(&popped)) {}
+  }
+  aw.finishMapping();
+  synth_destroy(scene);
+  const double d = timed ? static_cast<double>(timed) : 1.0;
+  std::printf("{\"what\": \"ActiveWindowVisualizer map slices (ever-free, tracking, TSDF) per frame, %dx%d, voxel %.4g m\", \"frames\": %d, "
+              "\"agree_frames\": %d, \"first_mismatch\": \"%s\", \"timed_frames\": %d, \"device_slice_ms\": %.4f, \"device_fetch_ms\": %.4f, \"block_copy_ms\": %.4f, "
+              "\"blocks_on_layer_mean\": %.1f, \"blocks_on_layer_max\": %zu, \"points\": %zu, \"slice_height\": %.4g, \"relative\": %d}\n",
+              W, H, static_cast<double>(cfg.volumetric_map.voxel_size), frames, agree, first_mismatch.c_str(), timed, ms_dev / d, ms_fetch / d, ms_copy / d,
+              blocks / d, blocks_max, points, static_cast<double>(sc.slice_height), int(sc.slice_height_is_relative));
+  return agree == frames ? 0 : 3;
+}
+
 static void onSegv(int sig) {  // a crash must not look like an empty result: print where it happened
   void* bt[48];
   const int n = backtrace(bt, 48);
@@ -270,6 +396,14 @@ int main(int argc, char** argv) {
   if (argc >= 3 && std::string(argv[1]) == "--rayver") {
     try {
       return rayverDemo(argv[2]);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "aw_demo: %s\n", e.what());
+      return 1;
+    }
+  }
+  if (argc >= 2 && std::string(argv[1]) == "--slices") {
+    try {
+      return slicesDemo(argc, argv);
     } catch (const std::exception& e) {
       std::fprintf(stderr, "aw_demo: %s\n", e.what());
       return 1;

@@ -138,6 +138,107 @@ struct BlockCopy {
   uint8_t block_flags = 0;
 };
 
+// ---- map slices (ActiveWindowVisualizer::visualize{EverFree,Tracking,Tsdf}Slice, active_window_visualizer.cpp:345-520) ----
+// getVoxelKey((0, 0, height)).z as a global voxel index (ASSUMPTIONS.md A.10): the block floor, then the voxel floor inside the
+// block (A.1), in float.  A local index of -1 / vps that rounding produces is kept: bz * vps + v then names the edge voxel of the
+// neighbouring layer, the voxel the height lies in to within that rounding.  Same rule as khr_slice_voxel_z and
+// khronos_amd.capi.slice_voxel_z.
+inline int64_t sliceVoxelZ(float height, float voxel_size, int voxels_per_side) {
+  const float bs = voxel_size * static_cast<float>(voxels_per_side), bs_inv = 1.f / bs, vs_inv = 1.f / voxel_size;
+  const int64_t bz = static_cast<int64_t>(std::floor(height * bs_inv));
+  const float origin = static_cast<float>(bz) * bs;
+  const int64_t v = static_cast<int64_t>(std::floor((height - origin) * vs_inv));
+  return bz * voxels_per_side + v;
+}
+
+// The visualizer's slice height: slice_height, plus world_T_body.z when slice_height_is_relative (:114, :364-367; config keys :71-73)
+struct SliceConfig {
+  float slice_height = -0.5f;  // (khronos_ros/config/mapper/uHumans2.yaml)
+  bool slice_height_is_relative = true;
+  bool show_unknown_voxels = false;
+  float height(const double* world_T_body) const {
+    float h = slice_height;
+    if (slice_height_is_relative) h += static_cast<float>(world_T_body[11]);
+    return h;
+  }
+};
+
+// One z-plane of the live map (VolumetricMap::slice): every live block on the layer, sorted by (bx, by), its vps x vps voxels at
+// the plane x-outer / y-inner (voxel i of block k is entry k * vps^2 + x * vps + y).
+struct MapSlice {
+  int64_t voxel_z = 0;
+  int voxels_per_side = 0;
+  std::vector<int32_t> block_xy;     // 2 per block
+  std::vector<float> positions;      // voxel centres, 3 per voxel
+  std::vector<float> distance, weight;
+  std::vector<uint64_t> last_observed;
+  std::vector<uint8_t> flags;        // KHR_VOX_* bits
+  size_t size() const { return distance.size(); }
+  size_t numBlocks() const { return block_xy.size() / 2; }
+};
+
+// What the visualizer draws for a slice, as scalars (the colormaps are Hydra's): the slice voxels it keeps, in its order, with
+// their class and value.
+enum class SliceClass : uint8_t {
+  kUnknown = 0,   // gray
+  kFree = 1,      // ever-free slice: green
+  kOccupied = 2,  // ever-free slice: red
+  kTooOld = 3,    // tracking slice: age above max_age (black)
+  kValue = 4,     // tracking slice: age; TSDF slice: 0.5 + 0.5 * distance / truncation (colormap input)
+};
+struct SlicePoints {
+  std::vector<uint32_t> voxel;  // entry of the MapSlice (its position: MapSlice::positions[3 * voxel])
+  std::vector<SliceClass> cls;
+  std::vector<float> value;     // kValue only (0 otherwise)
+  void add(uint32_t v, SliceClass c, float x = 0.f) {
+    voxel.push_back(v);
+    cls.push_back(c);
+    value.push_back(x);
+  }
+  bool operator==(const SlicePoints& o) const {
+    return voxel == o.voxel && cls == o.cls && value.size() == o.value.size() &&
+           (value.empty() || std::memcmp(value.data(), o.value.data(), value.size() * sizeof(float)) == 0);
+  }
+};
+// visualizeEverFreeSlice (:382-397): unknown iff last_observed == 0 (drawn only with show_unknown_voxels), else free / occupied by
+// the ever-free bit
+inline SlicePoints everFreeSlice(const MapSlice& s, bool show_unknown_voxels) {
+  SlicePoints r;
+  for (size_t i = 0; i < s.size(); ++i) {
+    const bool unknown = s.last_observed[i] == 0u;
+    if (unknown && !show_unknown_voxels) continue;
+    r.add(static_cast<uint32_t>(i), unknown ? SliceClass::kUnknown : ((s.flags[i] & KHR_VOX_EVER_FREE) ? SliceClass::kFree : SliceClass::kOccupied));
+  }
+  return r;
+}
+// visualizeTrackingSlice (:443-459): age = stamp_s - toSeconds(last_observed) in double, then float (:453); above max_age = 3 its own class
+inline SlicePoints trackingSlice(const MapSlice& s, TimeStamp stamp_ns, bool show_unknown_voxels) {
+  SlicePoints r;
+  const double stamp_s = toSeconds(stamp_ns);
+  constexpr float max_age = 3;
+  for (size_t i = 0; i < s.size(); ++i) {
+    const bool unknown = s.last_observed[i] == 0u;
+    if (unknown && !show_unknown_voxels) continue;
+    if (unknown) {
+      r.add(static_cast<uint32_t>(i), SliceClass::kUnknown);
+      continue;
+    }
+    const float age = static_cast<float>(stamp_s - toSeconds(s.last_observed[i]));
+    if (age > max_age) r.add(static_cast<uint32_t>(i), SliceClass::kTooOld);
+    else r.add(static_cast<uint32_t>(i), SliceClass::kValue, age);
+  }
+  return r;
+}
+// visualizeTsdfSlice (:500-512): every voxel; unknown iff weight < 1e-6, else value = 0.5 + 0.5 * d / truncation in double (:508-511)
+inline SlicePoints tsdfSlice(const MapSlice& s, float truncation_distance) {
+  SlicePoints r;
+  for (size_t i = 0; i < s.size(); ++i) {
+    if (s.weight[i] < 1e-6) r.add(static_cast<uint32_t>(i), SliceClass::kUnknown);
+    else r.add(static_cast<uint32_t>(i), SliceClass::kValue, static_cast<float>(0.5 + 0.5 * s.distance[i] / truncation_distance));
+  }
+  return r;
+}
+
 // hydra::VolumetricMap role: here a handle on the HBM-resident map of a fusion context.
 class VolumetricMap {
  public:
@@ -174,9 +275,33 @@ class VolumetricMap {
                        &b.block_flags);
     return b;
   }
+  // one z-plane of the live map, gathered and ordered on the device (khr_map_slice): for sinks that read planes (the
+  // visualizer's slices); cloneBlock is for whole blocks
+  MapSlice slice(float height) const {
+    MapSlice s;
+    s.voxel_z = sliceVoxelZ(height, config.voxel_size, config.voxels_per_side);
+    s.voxels_per_side = config.voxels_per_side;
+    const size_t np = static_cast<size_t>(config.voxels_per_side) * config.voxels_per_side;
+    int64_t n = 0;
+    for (size_t cap = slice_hint_;; cap = static_cast<size_t>(n)) {
+      s.block_xy.resize(2 * (cap / np)); s.positions.resize(3 * cap); s.distance.resize(cap); s.weight.resize(cap);
+      s.last_observed.resize(cap); s.flags.resize(cap);
+      const int rc = khr_map_slice(ctx_, s.voxel_z, static_cast<int64_t>(cap), s.block_xy.data(), s.positions.data(), s.distance.data(),
+                                   s.weight.data(), s.last_observed.data(), s.flags.data(), &n);
+      if (rc == KHR_ENOMEM && static_cast<size_t>(n) > cap) continue;
+      if (rc != KHR_OK) throw std::runtime_error(std::string("khr_map_slice: ") + khr_last_error());
+      break;
+    }
+    const size_t nv = static_cast<size_t>(n);
+    slice_hint_ = nv;
+    s.block_xy.resize(2 * (nv / np)); s.positions.resize(3 * nv); s.distance.resize(nv); s.weight.resize(nv);
+    s.last_observed.resize(nv); s.flags.resize(nv);
+    return s;
+  }
 
  private:
   khr_ctx* ctx_ = nullptr;
+  mutable size_t slice_hint_ = 0;  // voxels of the last slice: the first guess of the next call's buffers
 };
 
 struct Mesh {
