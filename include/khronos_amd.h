@@ -514,6 +514,67 @@ int khr_slice_voxel_z(float height, float voxel_size, int32_t voxels_per_side, i
  * label, 7 likelihoods, 8 block flags (KHR_BLK_* bits), 9 sum of mix(key), 10 block count, 11 reserved (0). */
 #define KHR_DIGEST_WORDS 12
 int khr_map_digest(khr_ctx* ctx, uint64_t* out);
+/* ---- map checkpoints: save and restore the live map ------------------------------------------------------------------------
+ * The reference has no counterpart in its tree: the role is that of the map save / load of the un-vendored hydra::VolumetricMap
+ * (ASSUMPTIONS.md A.11).  A checkpoint is ONE contiguous, self-describing byte stream of public values, independent of pool slots:
+ *   [0, 256)  header: khr_checkpoint_header, zero-padded to KHR_CKPT_HEADER_BYTES
+ *   sections, each starting on a 64-byte boundary at the offset the header gives (0 = the configuration has no such layer), blocks
+ *   in the lexicographic (x, y, z) order of khr_block_indices, voxels in linear order:
+ *     KHR_CKPT_INDICES 3 x int32 per block | _DISTANCE f32 | _WEIGHT f32 | _COLOR rgba8 | _LAST_OBSERVED u64 (with_tracking) |
+ *     _LAST_OCCUPIED u64 (with_tracking) | _VOXEL_FLAGS u8 (KHR_VOX_* bits) | _SEM_LABEL u32 (with_semantics) |
+ *     _BLOCK_FLAGS u8 per block (KHR_BLK_* bits) | _LIKELIHOODS num_labels f32 per voxel, voxel-major, rows never padded
+ *     (with_semantics; zeros for a voxel without KHR_VOX_SEM_VALID)
+ * -- exactly the values khr_download_block hands out.  No internal word is stored (lazy stamps are resolved by the save, every
+ * derived word is rebuilt by the load), so a stream loads into a context with another max_blocks, packed_likelihood_rows, rank or
+ * world_size.  NOT part of a checkpoint: the mesh layer, the frame ring, the detectors' state and every host-side track; a
+ * restored map has all its blocks' meshes to generate (khr_generate_mesh with only_mesh_updated = 0).
+ * The transfers run in chunks of blocks through two device staging areas of 32 MiB each, whatever the size of the map: the copy of
+ * one chunk overlaps the pack / unpack kernels of the next.  Pageable and page-locked host buffers both work (page-locked ones are
+ * copied to and from directly; pageable ones through a page-locked mirror of the staging). */
+#define KHR_CKPT_MAGIC 0x4d52484bu /* "KHRM" */
+#define KHR_CKPT_VERSION 1u
+#define KHR_CKPT_HEADER_BYTES 256
+#define KHR_CKPT_INDICES 0
+#define KHR_CKPT_DISTANCE 1
+#define KHR_CKPT_WEIGHT 2
+#define KHR_CKPT_COLOR 3
+#define KHR_CKPT_LAST_OBSERVED 4
+#define KHR_CKPT_LAST_OCCUPIED 5
+#define KHR_CKPT_VOXEL_FLAGS 6
+#define KHR_CKPT_SEM_LABEL 7
+#define KHR_CKPT_BLOCK_FLAGS 8
+#define KHR_CKPT_LIKELIHOODS 9
+#define KHR_CKPT_SECTIONS 10
+typedef struct khr_checkpoint_header {
+  uint32_t magic;   /* KHR_CKPT_MAGIC */
+  uint32_t version; /* KHR_CKPT_VERSION */
+  float voxel_size;
+  int32_t voxels_per_side;
+  float truncation_distance;
+  int32_t with_semantics;
+  int32_t with_tracking;
+  int32_t num_labels;    /* 0 without semantics */
+  int32_t semantic_mode; /* 0 without semantics */
+  uint32_t header_bytes; /* KHR_CKPT_HEADER_BYTES */
+  uint64_t num_blocks;
+  uint64_t total_bytes;                /* length of the stream */
+  uint64_t offset[KHR_CKPT_SECTIONS]; /* byte offset of each section from the start of the stream, 0 = absent */
+} khr_checkpoint_header;
+/* bytes and block count of a checkpoint of the live map (either pointer may be NULL); sharded contexts: this rank's blocks */
+int khr_checkpoint_size(khr_ctx* ctx, uint64_t* n_bytes, int64_t* n_blocks);
+/* write the stream into `buffer` (host memory, cap_bytes long); *n_bytes (may be NULL) = its length.  KHR_ENOMEM, and nothing
+ * written, when the buffer is too small (*n_bytes still receives the length needed).  Waits for the transfer. */
+int khr_checkpoint_save(khr_ctx* ctx, void* buffer, uint64_t cap_bytes, uint64_t* n_bytes);
+/* restore a stream into an EMPTY map (a fresh context, or one after khr_reset_map; KHR_ESTATE otherwise, map untouched).  A sharded
+ * context keeps the blocks it owns and skips the rest; *n_kept (may be NULL) = blocks kept.  Errors, each named in khr_last_error:
+ * KHR_EINVAL before any device work for a bad magic, an unknown version, a buffer shorter than the header claims or a header field
+ * that differs from the context's configuration (the text names the field); KHR_ENOMEM for more kept blocks than max_blocks;
+ * KHR_EINVAL for a block index that occurs twice (found when the second one meets the first in the hash table).  Every failure
+ * leaves the map empty and usable.  A successful load zeroes the cumulative khr_stats counters, like khr_reset_map. */
+int khr_checkpoint_load(khr_ctx* ctx, const void* buffer, uint64_t n_bytes, int64_t* n_kept);
+/* parse and validate the header of a stream (magic, version, field ranges, canonical section offsets, length); needs no context and
+ * no device */
+int khr_checkpoint_inspect(const void* buffer, uint64_t n_bytes, khr_checkpoint_header* out);
 /* replaces: VolumetricMap::cloneUpdated (active_window.cpp:229) in ONE packed transfer: every block flagged
  * KHR_BLK_UPDATED, in sorted block order, gathered on the device and copied per field (any pointer may be
  * NULL; arrays hold cap_blocks * nvox elements, indices 3 * cap_blocks).  Returns the number of blocks. */

@@ -64,6 +64,17 @@ class KhrObjectDetectorConfig(C.Structure):
                 ("object_labels", C.POINTER(C.c_int32)), ("n_object_labels", C.c_int32)]
 
 
+CKPT_SECTIONS = ("indices", "distance", "weight", "color", "last_observed", "last_occupied", "flags", "sem_label", "block_flags",
+                 "likelihoods")
+
+
+class KhrCheckpointHeader(C.Structure):
+    _fields_ = [("magic", C.c_uint32), ("version", C.c_uint32), ("voxel_size", C.c_float), ("voxels_per_side", C.c_int32),
+                ("truncation_distance", C.c_float), ("with_semantics", C.c_int32), ("with_tracking", C.c_int32),
+                ("num_labels", C.c_int32), ("semantic_mode", C.c_int32), ("header_bytes", C.c_uint32),
+                ("num_blocks", C.c_uint64), ("total_bytes", C.c_uint64), ("offset", C.c_uint64 * len(CKPT_SECTIONS))]
+
+
 class KhrStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "n_allocated_blocks", "n_visible_blocks", "n_new_blocks", "n_visited_voxels", "n_updated_voxels",
@@ -94,6 +105,7 @@ EXPORTS = [
     "khr_snapshot_updated", "khr_take_snapshot", "khr_snapshot_num_blocks", "khr_snapshot_download", "khr_snapshot_download_extra", "khr_snapshot_download_begin", "khr_snapshot_download_end", "khr_snapshot_poll", "khr_fetch_mesh_launch", "khr_reserve_mesh_staging", "khr_reserve_snapshots", "khr_mirror_dynamic", "khr_snapshot_release",
     "khr_rv_check_stamps", "khr_get_config", "khr_cluster_voxels_launch", "khr_cluster_voxels_fetch", "khr_reset_map", "khr_depend_on", "khr_retain_slot", "khr_release_slot",
     "khr_map_slice", "khr_slice_voxel_z",
+    "khr_checkpoint_size", "khr_checkpoint_save", "khr_checkpoint_load", "khr_checkpoint_inspect",
 ]
 
 _lib = None
@@ -181,6 +193,10 @@ def load_library():
     lib.khr_download_block.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 9
     lib.khr_map_slice.argtypes = [vp, i64, i64] + [vp] * 7
     lib.khr_slice_voxel_z.argtypes = [C.c_float, C.c_float, C.c_int32, vp]
+    lib.khr_checkpoint_size.argtypes = [vp, C.POINTER(u64), C.POINTER(i64)]
+    lib.khr_checkpoint_save.argtypes = [vp, vp, u64, C.POINTER(u64)]
+    lib.khr_checkpoint_load.argtypes = [vp, vp, u64, C.POINTER(i64)]
+    lib.khr_checkpoint_inspect.argtypes = [vp, u64, C.POINTER(KhrCheckpointHeader)]
     lib.khr_mesh_halo_requests.argtypes = [vp, vp, i64, i32, i32]
     lib.khr_mesh_halo_export.argtypes = [vp, vp, i64, vp, i64, i32]
     lib.khr_mesh_halo_import.argtypes = [vp, vp, i64, i32]
@@ -264,6 +280,31 @@ def slice_voxel_z(height, voxel_size, voxels_per_side):
     bz = int(np.floor(h * (f32(1) / bs)))
     v = int(np.floor((h - f32(bz) * bs) * (f32(1) / vs)))
     return bz * int(voxels_per_side) + v
+
+
+def _byte_view(buf, writable=False):
+    """a flat uint8 numpy view of a bytes-like object or array (no copy where the object allows it)"""
+    if isinstance(buf, np.ndarray):
+        a = buf.reshape(-1).view(np.uint8) if buf.flags.c_contiguous else np.ascontiguousarray(buf).reshape(-1).view(np.uint8)
+    else:
+        a = np.frombuffer(buf, np.uint8)
+    if writable and not a.flags.writeable:
+        raise ValueError("the buffer is read-only")
+    return a
+
+
+def checkpoint_inspect(buf):
+    """khr_checkpoint_inspect: parse and validate the header of a map checkpoint; needs no context and no device.  Returns
+    (return code, header dict or None); the error text is khr_last_error's."""
+    a = _byte_view(buf)
+    h = KhrCheckpointHeader()
+    lib = load_library()
+    rc = lib.khr_checkpoint_inspect(C.c_void_p(a.ctypes.data if a.size else None), a.size, C.byref(h))
+    if rc != 0:
+        return rc, None
+    out = {n: getattr(h, n) for n, _ in KhrCheckpointHeader._fields_ if n != "offset"}
+    out["offset"] = {n: int(h.offset[i]) for i, n in enumerate(CKPT_SECTIONS)}
+    return rc, out
 
 
 class FusionContext:
@@ -659,6 +700,48 @@ class FusionContext:
             _ptr(b["likelihoods"]), _ptr(bf)))
         b["block_flags"] = int(bf[0])
         return b
+
+    # ---- map checkpoints (khr_checkpoint_*; the format: include/khronos_amd.h, numpy codec: khronos_amd/checkpoint.py) ----
+    def checkpoint_size(self):
+        """(bytes, blocks) of a checkpoint of the live map"""
+        nb, nk = C.c_uint64(0), C.c_int64(0)
+        self._chk(self.lib.khr_checkpoint_size(self.h, C.byref(nb), C.byref(nk)))
+        return nb.value, nk.value
+
+    def save_map_into(self, out):
+        """khr_checkpoint_save into a writable buffer; returns (return code, stream length) without raising"""
+        a = _byte_view(out, writable=True)
+        n = C.c_uint64(0)
+        rc = self.lib.khr_checkpoint_save(self.h, C.c_void_p(a.ctypes.data if a.size else None), a.size, C.byref(n))
+        return rc, n.value
+
+    def save_map(self, out=None):
+        """The live map as one checkpoint stream: `bytes`, or -- with `out`, a writable buffer -- the number of bytes written."""
+        if out is not None:
+            rc, n = self.save_map_into(out)
+            self._chk(rc)
+            return n
+        nbytes, _ = self.checkpoint_size()
+        buf = np.empty(nbytes, np.uint8)
+        rc, n = self.save_map_into(buf)
+        self._chk(rc)
+        return buf[:n].tobytes()
+
+    def load_map_rc(self, buf, ptr=None, nbytes=0):
+        """khr_checkpoint_load; returns (return code, kept blocks) without raising.  ptr / nbytes: a raw host pointer instead"""
+        kept = C.c_int64(0)
+        if ptr is not None:
+            return self.lib.khr_checkpoint_load(self.h, C.c_void_p(ptr), int(nbytes), C.byref(kept)), kept.value
+        a = _byte_view(buf)
+        rc = self.lib.khr_checkpoint_load(self.h, C.c_void_p(a.ctypes.data if a.size else None), a.size, C.byref(kept))
+        return rc, kept.value
+
+    def load_map(self, buf):
+        """Restore a checkpoint stream into this context's EMPTY map; returns the number of blocks kept (a sharded context keeps
+        the blocks it owns)."""
+        rc, kept = self.load_map_rc(buf)
+        self._chk(rc)
+        return kept
 
     SLICE_FIELDS = ("block_xy", "positions", "distance", "weight", "last_observed", "flags")
 

@@ -34,6 +34,7 @@
 #include "khr_kernels_fuse.h"
 #include "khr_kernels_objects.h"
 #include "khr_kernels_slice.h"
+#include "khr_kernels_checkpoint.h"
 
 using namespace khr;
 
@@ -368,6 +369,16 @@ struct khr_ctx {
   uint8_t* d_slice_stage = nullptr;
   uint8_t* h_slice_stage = nullptr;
   uint32_t slice_cap = 0, slice_hint = 0;
+  // map checkpoints (khr_checkpoint_save / _load): two chunk staging areas of kCkptStageBytes each (created at the first call; their
+  // page-locked mirrors only when a caller passes pageable memory), the chunk's slot list, the load's error word, and per
+  // staging area one event for "filled" and one for "drained"
+  uint8_t* d_ckpt[2] = {nullptr, nullptr};
+  uint8_t* h_ckpt[2] = {nullptr, nullptr};
+  size_t ckpt_stage_bytes = 0;
+  uint32_t* d_ckpt_slots[2] = {nullptr, nullptr};
+  uint32_t ckpt_slots_cap = 0;
+  uint32_t* d_ckpt_err = nullptr;
+  hipEvent_t ev_ckpt_filled[2] = {nullptr, nullptr}, ev_ckpt_drained[2] = {nullptr, nullptr};
   // timing
   uint32_t timing = 0;  // bit i = timer i enabled
   std::vector<TimingRec> pending;
@@ -1118,6 +1129,14 @@ void khr_destroy(khr_ctx* c) {
   if (c->d_slice_keys) { hipFree(c->d_slice_keys); hipFree(c->d_slice_count); }
   if (c->d_slice_stage) hipFree(c->d_slice_stage);
   if (c->h_slice_stage) hipHostFree(c->h_slice_stage);
+  for (int i = 0; i < 2; ++i) {
+    if (c->d_ckpt[i]) hipFree(c->d_ckpt[i]);
+    if (c->h_ckpt[i]) hipHostFree(c->h_ckpt[i]);
+    if (c->d_ckpt_slots[i]) hipFree(c->d_ckpt_slots[i]);
+    if (c->ev_ckpt_filled[i]) hipEventDestroy(c->ev_ckpt_filled[i]);
+    if (c->ev_ckpt_drained[i]) hipEventDestroy(c->ev_ckpt_drained[i]);
+  }
+  if (c->d_ckpt_err) hipFree(c->d_ckpt_err);
   if (c->pending_snapshot) khr_snapshot_release(c->pending_snapshot);
   if (c->snap_stream) {
     hipStreamSynchronize(c->snap_stream);
@@ -4648,6 +4667,37 @@ struct SliceLayout {
   }
 };
 
+// the sort keys of khr_map_slice and khr_checkpoint_save (one u64 per pool slot, padded to a power of two) + their count word
+static int ensureSortKeys(khr_ctx* c) {
+  if (c->d_slice_keys) return KHR_OK;
+  const uint32_t sort_len = slicePadded(c->m.capacity);
+  if (hipMalloc(reinterpret_cast<void**>(&c->d_slice_keys), sizeof(uint64_t) * sort_len) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&c->d_slice_count), sizeof(uint32_t)) != hipSuccess) {
+    if (c->d_slice_keys) hipFree(c->d_slice_keys);
+    c->d_slice_keys = nullptr;
+    return fail(KHR_ENOMEM, "sort keys (%u words)", sort_len);
+  }
+  return KHR_OK;
+}
+// ascending bitonic sort of d_slice_keys[0, *d_slice_count) on the context's stream (khr_kernels_slice.h)
+static int sortKeys(khr_ctx* c) {
+  const uint32_t sort_len = slicePadded(c->m.capacity);
+  hipLaunchKernelGGL(k_slice_sort_tile, dim3(std::max(1u, sort_len / kSliceSortTile)), dim3(kSliceSortThreads), 0, c->stream,
+                     c->d_slice_keys, c->d_slice_count, 0u);
+  HIP_TRY(hipGetLastError());
+  for (uint32_t k = 2 * kSliceSortTile; k <= sort_len; k <<= 1) {  // multi-pass: stages beyond the count's length exit on the device
+    for (uint32_t j = k / 2; j >= kSliceSortTile; j >>= 1) {
+      hipLaunchKernelGGL(k_slice_sort_step, dim3(std::min(gridFor(sort_len / 2), 1024)), dim3(256), 0, c->stream, c->d_slice_keys,
+                         c->d_slice_count, k, j);
+      HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_slice_sort_tile, dim3(sort_len / kSliceSortTile), dim3(kSliceSortThreads), 0, c->stream, c->d_slice_keys,
+                       c->d_slice_count, k);
+    HIP_TRY(hipGetLastError());
+  }
+  return KHR_OK;
+}
+
 static int sliceGrow(khr_ctx* c, uint32_t need) {
   const uint32_t cap = std::min<uint32_t>(std::max<uint32_t>(need + need / 2, 64u), c->m.capacity);
   const SliceLayout L(cap, static_cast<size_t>(c->p.vps) * c->p.vps);
@@ -4674,14 +4724,9 @@ int khr_map_slice(khr_ctx* c, int64_t voxel_z, int64_t cap, int32_t* block_xy, f
   const int64_t vps = c->p.vps, np = vps * vps;
   const int64_t bz = (voxel_z >= 0 ? voxel_z : voxel_z - (vps - 1)) / vps, lz = voxel_z - bz * vps;  // floor division
   if (bz < -(1 << 20) || bz >= (1 << 20)) return KHR_OK;  // (beyond the block index range: no block lies there)
-  const uint32_t sort_len = slicePadded(c->m.capacity);
-  if (!c->d_slice_keys) {
-    if (hipMalloc(reinterpret_cast<void**>(&c->d_slice_keys), sizeof(uint64_t) * sort_len) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->d_slice_count), sizeof(uint32_t)) != hipSuccess) {
-      if (c->d_slice_keys) hipFree(c->d_slice_keys);
-      c->d_slice_keys = nullptr;
-      return fail(KHR_ENOMEM, "slice sort keys (%u words)", sort_len);
-    }
+  {
+    const int rc = ensureSortKeys(c);
+    if (rc) return rc;
   }
   if (!c->d_slice_stage) {
     const int rc = sliceGrow(c, 64u);
@@ -4729,20 +4774,9 @@ int khr_map_slice(khr_ctx* c, int64_t voxel_z, int64_t cap, int32_t* block_xy, f
   hipLaunchKernelGGL(k_slice_select, dim3(std::min(gridFor(c->m.capacity), 1024)), dim3(256), 0, c->stream, c->m, static_cast<int>(bz),
                      c->d_slice_count, c->d_slice_keys);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_slice_sort_tile, dim3(std::max(1u, sort_len / kSliceSortTile)), dim3(kSliceSortThreads), 0, c->stream,
-                     c->d_slice_keys, c->d_slice_count, 0u);
-  HIP_TRY(hipGetLastError());
-  for (uint32_t k = 2 * kSliceSortTile; k <= sort_len; k <<= 1) {  // multi-pass: stages beyond the count's length exit on the device
-    for (uint32_t j = k / 2; j >= kSliceSortTile; j >>= 1) {
-      hipLaunchKernelGGL(k_slice_sort_step, dim3(std::min(gridFor(sort_len / 2), 1024)), dim3(256), 0, c->stream, c->d_slice_keys,
-                         c->d_slice_count, k, j);
-      HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_slice_sort_tile, dim3(sort_len / kSliceSortTile), dim3(kSliceSortThreads), 0, c->stream, c->d_slice_keys,
-                       c->d_slice_count, k);
-    HIP_TRY(hipGetLastError());
-  }
-  int rc = gather();
+  int rc = sortKeys(c);
+  if (rc) return rc;
+  rc = gather();
   if (rc) return rc;
   uint32_t n_copied = std::min(c->slice_cap, c->slice_hint);
   HIP_TRY(hipMemcpyAsync(c->h_slice_stage, c->d_slice_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -4782,6 +4816,355 @@ int khr_map_digest(khr_ctx* c, uint64_t* out) {
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, acc, sizeof(uint64_t) * kDigestWords, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return KHR_OK;
+}
+
+// ---- map checkpoints (khr_checkpoint_size / _save / _load / _inspect; device side: khr_kernels_checkpoint.h) -------------------
+namespace {
+constexpr size_t kCkptStageBytes = 32u << 20;   // one staging area; two of them are the whole device footprint of a checkpoint
+constexpr uint32_t kCkptMaxChunkBlocks = 4096;  // (small blocks: bounds the chunk's slot list)
+const char* const kCkptSectionNames[KHR_CKPT_SECTIONS] = {"indices", "distance", "weight", "color", "last_observed", "last_occupied",
+                                                          "voxel_flags", "sem_label", "block_flags", "likelihoods"};
+
+// bytes of one block in each section (0 = the configuration has no such layer)
+struct CkptShape {
+  size_t per[KHR_CKPT_SECTIONS];
+  size_t per_block;
+  CkptShape(int vps, int with_tracking, int with_semantics, int num_labels) {
+    const size_t nv = static_cast<size_t>(vps) * vps * vps;
+    per[KHR_CKPT_INDICES] = 12;
+    per[KHR_CKPT_DISTANCE] = per[KHR_CKPT_WEIGHT] = per[KHR_CKPT_COLOR] = 4 * nv;
+    per[KHR_CKPT_LAST_OBSERVED] = per[KHR_CKPT_LAST_OCCUPIED] = with_tracking ? 8 * nv : 0;
+    per[KHR_CKPT_VOXEL_FLAGS] = nv;
+    per[KHR_CKPT_SEM_LABEL] = with_semantics ? 4 * nv : 0;
+    per[KHR_CKPT_BLOCK_FLAGS] = 1;
+    per[KHR_CKPT_LIKELIHOODS] = with_semantics ? 4 * nv * static_cast<size_t>(num_labels) : 0;
+    per_block = 0;
+    for (size_t b : per) per_block += b;
+  }
+};
+
+// section offsets and total length of a stream of n blocks
+void ckptOffsets(const CkptShape& sh, uint64_t n, uint64_t* offset, uint64_t* total) {
+  uint64_t at = KHR_CKPT_HEADER_BYTES;
+  for (int s = 0; s < KHR_CKPT_SECTIONS; ++s) {
+    offset[s] = sh.per[s] ? at : 0;
+    at += (sh.per[s] * n + 63) / 64 * 64;
+  }
+  *total = at;
+}
+
+khr_checkpoint_header ckptHeaderFor(const khr_config& cfg, uint64_t n) {
+  khr_checkpoint_header h{};
+  h.magic = KHR_CKPT_MAGIC;
+  h.version = KHR_CKPT_VERSION;
+  h.voxel_size = cfg.voxel_size;
+  h.voxels_per_side = cfg.voxels_per_side;
+  h.truncation_distance = cfg.truncation_distance;
+  h.with_semantics = cfg.with_semantics ? 1 : 0;
+  h.with_tracking = cfg.with_tracking ? 1 : 0;
+  h.num_labels = cfg.with_semantics ? cfg.num_labels : 0;
+  h.semantic_mode = cfg.with_semantics ? cfg.semantic_mode : 0;
+  h.header_bytes = KHR_CKPT_HEADER_BYTES;
+  h.num_blocks = n;
+  ckptOffsets(CkptShape(h.voxels_per_side, h.with_tracking, h.with_semantics, h.num_labels), n, h.offset, &h.total_bytes);
+  return h;
+}
+
+// the regions of a staging area laid out for chunks of `cb` blocks
+struct CkptStageLayout {
+  size_t off[KHR_CKPT_SECTIONS], bytes;
+  CkptStageLayout(const CkptShape& sh, size_t cb) {
+    size_t at = 0;
+    for (int s = 0; s < KHR_CKPT_SECTIONS; ++s) {
+      off[s] = at;
+      at += (sh.per[s] * cb + 255) / 256 * 256;
+    }
+    bytes = at;
+  }
+};
+CkptStage ckptStageViews(const CkptShape& sh, const CkptStageLayout& L, uint8_t* d) {
+  auto at = [&](int s) { return sh.per[s] ? d + L.off[s] : nullptr; };
+  CkptStage o{};
+  o.idx = reinterpret_cast<int32_t*>(at(KHR_CKPT_INDICES));
+  o.dist = reinterpret_cast<float*>(at(KHR_CKPT_DISTANCE));
+  o.weight = reinterpret_cast<float*>(at(KHR_CKPT_WEIGHT));
+  o.color = reinterpret_cast<uint32_t*>(at(KHR_CKPT_COLOR));
+  o.lobs = reinterpret_cast<uint64_t*>(at(KHR_CKPT_LAST_OBSERVED));
+  o.locc = reinterpret_cast<uint64_t*>(at(KHR_CKPT_LAST_OCCUPIED));
+  o.vfl = at(KHR_CKPT_VOXEL_FLAGS);
+  o.label = reinterpret_cast<uint32_t*>(at(KHR_CKPT_SEM_LABEL));
+  o.bfl = at(KHR_CKPT_BLOCK_FLAGS);
+  o.lik = reinterpret_cast<float*>(at(KHR_CKPT_LIKELIHOODS));
+  return o;
+}
+
+// blocks per chunk: what fits a staging area (at least one: a block larger than the area grows it)
+uint32_t ckptChunkBlocks(const CkptShape& sh) {
+  const size_t room = kCkptStageBytes - 256 * KHR_CKPT_SECTIONS;
+  return static_cast<uint32_t>(std::min<size_t>(kCkptMaxChunkBlocks, std::max<size_t>(1, room / sh.per_block)));
+}
+
+int ckptEnsureStage(khr_ctx* c, const CkptShape& sh, uint32_t cb, bool bounce) {
+  const size_t need = std::max(kCkptStageBytes, CkptStageLayout(sh, cb).bytes);
+  if (c->ckpt_stage_bytes < need) {
+    for (int i = 0; i < 2; ++i) {
+      if (c->d_ckpt[i]) HIP_TRY(hipFree(c->d_ckpt[i]));
+      if (c->h_ckpt[i]) HIP_TRY(hipHostFree(c->h_ckpt[i]));
+      c->d_ckpt[i] = c->h_ckpt[i] = nullptr;
+    }
+    c->ckpt_stage_bytes = 0;
+    for (int i = 0; i < 2; ++i)
+      if (hipMalloc(reinterpret_cast<void**>(&c->d_ckpt[i]), need) != hipSuccess) return fail(KHR_ENOMEM, "checkpoint staging of %zu bytes", need);
+    c->ckpt_stage_bytes = need;
+  }
+  for (int i = 0; i < 2 && bounce; ++i)
+    if (!c->h_ckpt[i] && hipHostMalloc(reinterpret_cast<void**>(&c->h_ckpt[i]), c->ckpt_stage_bytes, hipHostMallocDefault) != hipSuccess)
+      return fail(KHR_ENOMEM, "page-locked checkpoint staging of %zu bytes", c->ckpt_stage_bytes);
+  if (c->ckpt_slots_cap < cb) {
+    for (int i = 0; i < 2; ++i) {
+      if (c->d_ckpt_slots[i]) HIP_TRY(hipFree(c->d_ckpt_slots[i]));
+      c->d_ckpt_slots[i] = nullptr;
+    }
+    c->ckpt_slots_cap = 0;
+    for (int i = 0; i < 2; ++i)
+      if (hipMalloc(reinterpret_cast<void**>(&c->d_ckpt_slots[i]), sizeof(uint32_t) * cb) != hipSuccess) return fail(KHR_ENOMEM, "checkpoint slot list");
+    c->ckpt_slots_cap = cb;
+  }
+  if (!c->d_ckpt_err && hipMalloc(reinterpret_cast<void**>(&c->d_ckpt_err), sizeof(uint32_t)) != hipSuccess) return fail(KHR_ENOMEM, "checkpoint error word");
+  for (int i = 0; i < 2; ++i) {
+    if (!c->ev_ckpt_filled[i]) HIP_TRY(hipEventCreateWithFlags(&c->ev_ckpt_filled[i], hipEventDisableTiming));
+    if (!c->ev_ckpt_drained[i]) HIP_TRY(hipEventCreateWithFlags(&c->ev_ckpt_drained[i], hipEventDisableTiming));
+  }
+  if (!c->copy_stream) HIP_TRY(createStream(c, &c->copy_stream));
+  return KHR_OK;
+}
+
+// back to the empty map on the device and in the host mirrors (the failure exit of a load, and its first step)
+int ckptClearMap(khr_ctx* c) {
+  const size_t n = std::max<size_t>(static_cast<size_t>(c->m.ht_mask) + 1, c->m.capacity);
+  hipLaunchKernelGGL(k_reset_map, dim3(gridFor(n)), dim3(256), 0, c->stream, c->m);
+  HIP_TRY(hipGetLastError());
+  c->mesh_cur = 0;
+  c->mesh_total = 0;
+  c->mesh_stale = false;
+  c->host_index_valid = false, ++c->map_gen;
+  c->explicit_blocks = 0;
+  c->last_removed = 0;
+  c->removed_pending = false;
+  c->last_track_stamp = 0;
+  return KHR_OK;
+}
+}  // namespace
+
+int khr_checkpoint_inspect(const void* buffer, uint64_t n_bytes, khr_checkpoint_header* out) {
+  if (!buffer || !out) return fail(KHR_EINVAL, "null argument");
+  if (n_bytes < KHR_CKPT_HEADER_BYTES)
+    return fail(KHR_EINVAL, "checkpoint: truncated buffer (%llu bytes, the header alone has %d)", static_cast<unsigned long long>(n_bytes), KHR_CKPT_HEADER_BYTES);
+  khr_checkpoint_header h;
+  std::memcpy(&h, buffer, sizeof(h));
+  if (h.magic != KHR_CKPT_MAGIC) return fail(KHR_EINVAL, "checkpoint: bad magic 0x%08x (expected 0x%08x)", h.magic, KHR_CKPT_MAGIC);
+  if (h.version != KHR_CKPT_VERSION) return fail(KHR_EINVAL, "checkpoint: unknown format version %u (this library reads version %u)", h.version, KHR_CKPT_VERSION);
+  if (h.header_bytes != KHR_CKPT_HEADER_BYTES) return fail(KHR_EINVAL, "checkpoint: header_bytes %u, expected %d", h.header_bytes, KHR_CKPT_HEADER_BYTES);
+  if (h.voxels_per_side != 8 && h.voxels_per_side != 16) return fail(KHR_EINVAL, "checkpoint: voxels_per_side %d (must be 8 or 16)", h.voxels_per_side);
+  if (!(h.voxel_size > 0.f) || !(h.truncation_distance > 0.f)) return fail(KHR_EINVAL, "checkpoint: voxel_size / truncation_distance must be > 0");
+  if ((h.with_semantics | 1) != 1 || (h.with_tracking | 1) != 1) return fail(KHR_EINVAL, "checkpoint: with_semantics / with_tracking must be 0 or 1");
+  if (h.with_semantics ? (h.num_labels < 1 || h.num_labels > 65536) : (h.num_labels != 0 || h.semantic_mode != 0))
+    return fail(KHR_EINVAL, "checkpoint: num_labels %d / semantic_mode %d do not fit with_semantics %d", h.num_labels, h.semantic_mode, h.with_semantics);
+  if (h.num_blocks > (1ull << 32)) return fail(KHR_EINVAL, "checkpoint: block count %llu", static_cast<unsigned long long>(h.num_blocks));
+  uint64_t off[KHR_CKPT_SECTIONS], total = 0;
+  ckptOffsets(CkptShape(h.voxels_per_side, h.with_tracking, h.with_semantics, h.num_labels), h.num_blocks, off, &total);
+  for (int s = 0; s < KHR_CKPT_SECTIONS; ++s)
+    if (h.offset[s] != off[s])
+      return fail(KHR_EINVAL, "checkpoint: section %s at offset %llu, expected %llu", kCkptSectionNames[s], static_cast<unsigned long long>(h.offset[s]),
+                  static_cast<unsigned long long>(off[s]));
+  if (h.total_bytes != total) return fail(KHR_EINVAL, "checkpoint: total_bytes %llu, expected %llu", static_cast<unsigned long long>(h.total_bytes), static_cast<unsigned long long>(total));
+  if (n_bytes < total)
+    return fail(KHR_EINVAL, "checkpoint: truncated buffer (%llu bytes, the header claims %llu)", static_cast<unsigned long long>(n_bytes), static_cast<unsigned long long>(total));
+  *out = h;
+  return KHR_OK;
+}
+
+int khr_checkpoint_size(khr_ctx* c, uint64_t* n_bytes, int64_t* n_blocks) {
+  if (!c) return fail(KHR_EINVAL, "null ctx");
+  HIP_TRY(hipSetDevice(c->device));
+  const int rc = ensureHostIndex(c);
+  if (rc) return rc;
+  const khr_checkpoint_header h = ckptHeaderFor(c->cfg, c->host_index.size());
+  if (n_bytes) *n_bytes = h.total_bytes;
+  if (n_blocks) *n_blocks = static_cast<int64_t>(h.num_blocks);
+  return KHR_OK;
+}
+
+int khr_checkpoint_save(khr_ctx* c, void* buffer, uint64_t cap_bytes, uint64_t* n_bytes) {
+  if (!c || (!buffer && cap_bytes)) return fail(KHR_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = ensureSortKeys(c);
+  if (rc) return rc;
+  // select -> sort on the device; the count comes back with the one host wait in front of the transfer
+  HIP_TRY(hipMemsetAsync(c->d_slice_count, 0, sizeof(uint32_t), c->stream));
+  hipLaunchKernelGGL(k_ckpt_select, dim3(std::min(gridFor(c->m.capacity), 1024)), dim3(256), 0, c->stream, c->m, c->d_slice_count, c->d_slice_keys);
+  HIP_TRY(hipGetLastError());
+  if ((rc = sortKeys(c))) return rc;
+  uint32_t n = 0;
+  HIP_TRY(hipMemcpyAsync(&n, c->d_slice_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const khr_checkpoint_header h = ckptHeaderFor(c->cfg, n);
+  if (n_bytes) *n_bytes = h.total_bytes;
+  if (h.total_bytes > cap_bytes)
+    return fail(KHR_ENOMEM, "checkpoint: the stream of %u blocks has %llu bytes, the buffer %llu", n, static_cast<unsigned long long>(h.total_bytes),
+                static_cast<unsigned long long>(cap_bytes));
+  const CkptShape sh(h.voxels_per_side, h.with_tracking, h.with_semantics, h.num_labels);
+  const uint32_t cb = ckptChunkBlocks(sh);
+  const bool bounce = !pointerIs(buffer, 0);
+  if ((rc = ckptEnsureStage(c, sh, cb, bounce))) return rc;
+  const CkptStageLayout L(sh, cb);
+  uint8_t* const dst = static_cast<uint8_t*>(buffer);
+  // header, and zeros in the alignment gaps behind the sections (the stream is a function of the map alone)
+  std::memset(dst, 0, KHR_CKPT_HEADER_BYTES);
+  std::memcpy(dst, &h, sizeof(h));
+  for (int s = 0; s < KHR_CKPT_SECTIONS; ++s)
+    if (sh.per[s]) {
+      const uint64_t end = h.offset[s] + sh.per[s] * n, pad = (64 - end % 64) % 64;
+      std::memset(dst + end, 0, pad);
+    }
+  const uint32_t n_chunks = (n + cb - 1) / cb;
+  auto drain = [&](uint32_t chunk) {  // (pageable buffers) the chunk's sections out of the page-locked mirror
+    const uint32_t b0 = chunk * cb, nb = std::min(cb, n - b0);
+    for (int s = 0; s < KHR_CKPT_SECTIONS; ++s)
+      if (sh.per[s]) std::memcpy(dst + h.offset[s] + sh.per[s] * b0, c->h_ckpt[chunk & 1] + L.off[s], sh.per[s] * nb);
+  };
+  for (uint32_t i = 0; i < n_chunks; ++i) {
+    const int buf = i & 1;
+    const uint32_t b0 = i * cb, nb = std::min(cb, n - b0);
+    if (i >= 2) {  // the staging area is free once the copy of chunk i - 2 has left it
+      if (bounce) {
+        HIP_TRY(hipEventSynchronize(c->ev_ckpt_drained[buf]));
+        drain(i - 2);
+      }
+      HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_ckpt_drained[buf], 0));
+    }
+    rc = dispatchVps(c, [&](auto vps) {
+      hipLaunchKernelGGL((k_ckpt_pack<decltype(vps)::value>), dim3(nb), dim3(256), 0, c->stream, c->m, c->p, c->d_slice_keys, c->d_slice_count, b0,
+                         nb, ckptStageViews(sh, L, c->d_ckpt[buf]), c->last_track_stamp);
+      HIP_TRY(hipGetLastError());
+      return KHR_OK;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(c->ev_ckpt_filled[buf], c->stream));
+    HIP_TRY(hipStreamWaitEvent(c->copy_stream, c->ev_ckpt_filled[buf], 0));
+    for (int s = 0; s < KHR_CKPT_SECTIONS; ++s)
+      if (sh.per[s]) {
+        uint8_t* const to = bounce ? c->h_ckpt[buf] + L.off[s] : dst + h.offset[s] + sh.per[s] * b0;
+        HIP_TRY(hipMemcpyAsync(to, c->d_ckpt[buf] + L.off[s], sh.per[s] * nb, hipMemcpyDeviceToHost, c->copy_stream));
+      }
+    HIP_TRY(hipEventRecord(c->ev_ckpt_drained[buf], c->copy_stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->copy_stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (bounce)
+    for (uint32_t i = n_chunks >= 2 ? n_chunks - 2 : 0; i < n_chunks; ++i) drain(i);
+  return KHR_OK;
+}
+
+int khr_checkpoint_load(khr_ctx* c, const void* buffer, uint64_t n_bytes, int64_t* n_kept) {
+  if (!c || !buffer) return fail(KHR_EINVAL, "null argument");
+  if (n_kept) *n_kept = 0;
+  khr_checkpoint_header h;
+  int rc = khr_checkpoint_inspect(buffer, n_bytes, &h);
+  if (rc) return rc;
+  const khr_checkpoint_header mine = ckptHeaderFor(c->cfg, 0);
+#define KHR_CKPT_FIELD(name, fmt, cast)                                                                                        \
+  if (h.name != mine.name)                                                                                                     \
+    return fail(KHR_EINVAL, "checkpoint: " #name " is " fmt " in the stream and " fmt " in this context", static_cast<cast>(h.name), \
+                static_cast<cast>(mine.name));
+  KHR_CKPT_FIELD(voxel_size, "%.9g", double)
+  KHR_CKPT_FIELD(voxels_per_side, "%d", int)
+  KHR_CKPT_FIELD(truncation_distance, "%.9g", double)
+  KHR_CKPT_FIELD(with_semantics, "%d", int)
+  KHR_CKPT_FIELD(with_tracking, "%d", int)
+  KHR_CKPT_FIELD(num_labels, "%d", int)
+  KHR_CKPT_FIELD(semantic_mode, "%d", int)
+#undef KHR_CKPT_FIELD
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = ensureHostIndex(c))) return rc;
+  if (!c->host_index.empty()) return fail(KHR_ESTATE, "checkpoint: the map holds %zu blocks; a load needs an empty map (khr_reset_map)", c->host_index.size());
+  const uint8_t* const src = static_cast<const uint8_t*>(buffer);
+  const uint32_t n = static_cast<uint32_t>(h.num_blocks);
+  // blocks this rank keeps, counted on the host: a stream that cannot fit is refused before the map is touched
+  uint64_t kept = 0;
+  {
+    const int32_t* idx = reinterpret_cast<const int32_t*>(src + h.offset[KHR_CKPT_INDICES]);
+    for (uint32_t b = 0; b < n; ++b) {
+      int32_t v[3];
+      std::memcpy(v, idx + 3 * static_cast<size_t>(b), sizeof(v));
+      for (int a = 0; a < 3; ++a)
+        if (v[a] < -(1 << 20) || v[a] >= (1 << 20)) return fail(KHR_EINVAL, "checkpoint: block %u has index (%d, %d, %d), out of range", b, v[0], v[1], v[2]);
+      kept += ownerOf(v[0], v[1], v[2], c->p.world) == c->p.rank ? 1 : 0;
+    }
+  }
+  if (kept > c->m.capacity)
+    return fail(KHR_ENOMEM, "checkpoint: %llu blocks to keep, max_blocks is %u", static_cast<unsigned long long>(kept), c->m.capacity);
+  const CkptShape sh(h.voxels_per_side, h.with_tracking, h.with_semantics, h.num_labels);
+  const uint32_t cb = ckptChunkBlocks(sh);
+  const bool bounce = !pointerIs(buffer, 0);
+  if ((rc = ckptEnsureStage(c, sh, cb, bounce))) return rc;
+  const CkptStageLayout L(sh, cb);
+  // canonical empty state first (an emptied map may have any free list), then chunk by chunk: copy, insert, scatter
+  if ((rc = ckptClearMap(c))) return rc;
+  HIP_TRY(hipMemsetAsync(c->d_ckpt_err, 0, sizeof(uint32_t), c->stream));
+  const uint32_t n_chunks = (n + cb - 1) / cb;
+  for (uint32_t i = 0; i < n_chunks; ++i) {
+    const int buf = i & 1;
+    const uint32_t b0 = i * cb, nb = std::min(cb, n - b0);
+    if (i >= 2) {
+      if (bounce) HIP_TRY(hipEventSynchronize(c->ev_ckpt_filled[buf]));               // the mirror's chunk i - 2 has been copied
+      HIP_TRY(hipStreamWaitEvent(c->copy_stream, c->ev_ckpt_drained[buf], 0));        // the kernels of chunk i - 2 have read the staging
+    }
+    for (int s = 0; s < KHR_CKPT_SECTIONS; ++s)
+      if (sh.per[s]) {
+        const uint8_t* from = src + h.offset[s] + sh.per[s] * b0;
+        if (bounce) {
+          std::memcpy(c->h_ckpt[buf] + L.off[s], from, sh.per[s] * nb);
+          from = c->h_ckpt[buf] + L.off[s];
+        }
+        HIP_TRY(hipMemcpyAsync(c->d_ckpt[buf] + L.off[s], from, sh.per[s] * nb, hipMemcpyHostToDevice, c->copy_stream));
+      }
+    HIP_TRY(hipEventRecord(c->ev_ckpt_filled[buf], c->copy_stream));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_ckpt_filled[buf], 0));
+    const CkptStage in = ckptStageViews(sh, L, c->d_ckpt[buf]);
+    hipLaunchKernelGGL(k_ckpt_insert, dim3(gridFor(nb)), dim3(256), 0, c->stream, c->m, c->p, in.idx, in.bfl, nb, c->d_ckpt_slots[buf], c->d_ckpt_err);
+    HIP_TRY(hipGetLastError());
+    rc = dispatchVps(c, [&](auto vps) {
+      hipLaunchKernelGGL((k_ckpt_unpack<decltype(vps)::value>), dim3(nb), dim3(256), 0, c->stream, c->m, c->p, c->d_ckpt_slots[buf], nb, in);
+      HIP_TRY(hipGetLastError());
+      return KHR_OK;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(c->ev_ckpt_drained[buf], c->stream));
+  }
+  rc = dispatchVps(c, [&](auto vps) {
+    hipLaunchKernelGGL((k_ckpt_rebuild<decltype(vps)::value>), dim3(std::max(1u, std::min(c->m.capacity, 4096u))), dim3(256), 0, c->stream, c->m, c->p, c->wpb);
+    HIP_TRY(hipGetLastError());
+    return KHR_OK;
+  });
+  if (rc) return rc;
+  uint32_t err = 0, live = 0;
+  HIP_TRY(hipMemcpyAsync(&err, c->d_ckpt_err, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(&live, &c->m.counters[C_N_LIVE], sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipStreamSynchronize(c->copy_stream));
+  if (err || live != kept) {
+    if ((rc = ckptClearMap(c))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (err & kCkptErrDuplicate) return fail(KHR_EINVAL, "checkpoint: duplicate block index in the stream (met its twin at the hash insert)");
+    if (err & kCkptErrIndex) return fail(KHR_EINVAL, "checkpoint: block index out of range");
+    if (err & kCkptErrPool) return fail(KHR_ENOMEM, "checkpoint: the block pool (max_blocks %u) ran out during the load", c->m.capacity);
+    return fail(KHR_EDEVICE, "checkpoint: %u blocks restored, %llu expected", live, static_cast<unsigned long long>(kept));
+  }
+  c->host_index_valid = false, ++c->map_gen;
+  c->stats = khr_stats{};
+  if (n_kept) *n_kept = static_cast<int64_t>(kept);
   return KHR_OK;
 }
 

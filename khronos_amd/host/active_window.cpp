@@ -2,6 +2,9 @@
 // (khronos/src/active_window/active_window.cpp:73-286) on top of the C ABI.  See active_window.h.
 #include "active_window.h"
 
+#define __HIP_PLATFORM_AMD__ 1
+#include <hip/hip_runtime_api.h>
+
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -10,6 +13,7 @@
 #include <mutex>
 #include <sstream>
 #include <stdexcept>
+#include <fstream>
 
 namespace khronos {
 
@@ -1049,3 +1053,57 @@ void ObjectWorkerPool::workerLoop(size_t worker) {
 }
 
 }  // namespace khronos
+
+// ---- hydra::VolumetricMap::save / load (hydra_compat.h) -------------------------------------------------------------------
+namespace hydra {
+namespace {
+// page-locked where possible (the checkpoint calls then copy straight to and from it), pageable otherwise
+struct BounceBuffer {
+  uint8_t* p = nullptr;
+  bool pinned = false;
+  explicit BounceBuffer(size_t bytes) {
+    void* q = nullptr;
+    if (hipHostMalloc(&q, bytes ? bytes : 1, hipHostMallocDefault) == hipSuccess) {
+      p = static_cast<uint8_t*>(q);
+      pinned = true;
+    } else {
+      (void)hipGetLastError();
+      p = static_cast<uint8_t*>(std::malloc(bytes ? bytes : 1));
+      if (!p) throw std::runtime_error("VolumetricMap: no memory for a checkpoint buffer of " + std::to_string(bytes) + " bytes");
+    }
+  }
+  ~BounceBuffer() {
+    if (pinned) (void)hipHostFree(p);
+    else std::free(p);
+  }
+  BounceBuffer(const BounceBuffer&) = delete;
+  BounceBuffer& operator=(const BounceBuffer&) = delete;
+};
+}  // namespace
+
+size_t VolumetricMap::save(const std::string& path) const {
+  uint64_t bytes = 0;
+  if (khr_checkpoint_size(ctx_, &bytes, nullptr) != KHR_OK) throw std::runtime_error(std::string("khr_checkpoint_size: ") + khr_last_error());
+  BounceBuffer buf(static_cast<size_t>(bytes));
+  uint64_t written = 0;
+  if (khr_checkpoint_save(ctx_, buf.p, bytes, &written) != KHR_OK) throw std::runtime_error(std::string("khr_checkpoint_save: ") + khr_last_error());
+  std::ofstream out(path, std::ios::binary | std::ios::trunc);
+  out.write(reinterpret_cast<const char*>(buf.p), static_cast<std::streamsize>(written));
+  out.close();
+  if (!out) throw std::runtime_error("VolumetricMap::save: cannot write " + path);
+  return static_cast<size_t>(written);
+}
+
+size_t VolumetricMap::load(const std::string& path) {
+  std::ifstream in(path, std::ios::binary | std::ios::ate);
+  if (!in) throw std::runtime_error("VolumetricMap::load: cannot open " + path);
+  const size_t bytes = static_cast<size_t>(in.tellg());
+  in.seekg(0);
+  BounceBuffer buf(bytes);
+  in.read(reinterpret_cast<char*>(buf.p), static_cast<std::streamsize>(bytes));
+  if (!in) throw std::runtime_error("VolumetricMap::load: cannot read " + path);
+  int64_t kept = 0;
+  if (khr_checkpoint_load(ctx_, buf.p, bytes, &kept) != KHR_OK) throw std::runtime_error(std::string("khr_checkpoint_load: ") + khr_last_error());
+  return static_cast<size_t>(kept);
+}
+}  // namespace hydra

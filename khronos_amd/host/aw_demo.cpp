@@ -2,7 +2,7 @@
 // thread drives the reference (spinOnce per InputPacket, finishMapping at shutdown), and prints a JSON
 // summary that tests/test_gpu_host.py compares with the step-wise C-ABI path and the oracle.
 // usage: aw_demo <config.yaml> <width> <height> <frames> [object_label]
-//        aw_demo --slices | --bench | --rayver ... (below)
+//        aw_demo --slices | --checkpoint | --bench | --rayver ... (below)
 //   object_label >= 0: the stand-in detector / tracker below; otherwise the plugins named in the config
 #include <execinfo.h>
 #include <csignal>
@@ -381,6 +381,82 @@ static int slicesDemo(int argc, char** argv) {
   return agree == frames ? 0 : 3;
 }
 
+// aw_demo --checkpoint <config.yaml> <width> <height> <frames> [file]: runs the synthetic stream through an ActiveWindow, saves the live
+// map through getMap().save (hydra::VolumetricMap: khr_checkpoint_save around a file), loads the file into the empty map of a second
+// context of the same configuration and compares the two maps' whole-map digests.  One JSON line: both digests (12 words each),
+// both block counts, the file's bytes, save_ms and load_ms (wall clock, file I/O included).  Exit status 0 iff the maps are equal.
+static int checkpointDemo(int argc, char** argv) {
+  if (argc < 6) {
+    std::fprintf(stderr, "usage: aw_demo --checkpoint <config.yaml> <width> <height> <frames> [file]\n");
+    return 2;
+  }
+  std::ifstream in(argv[2]);
+  std::stringstream ss;
+  ss << in.rdbuf();
+  const int W = std::atoi(argv[3]), H = std::atoi(argv[4]), N = std::atoi(argv[5]);
+  const std::string path = argc > 6 ? argv[6] : "aw_demo_map.chk";
+  ActiveWindow::Config cfg = ActiveWindow::Config::fromYamlString(ss.str());
+  cfg.max_frame_pixels = static_cast<uint32_t>(W) * H;
+  auto out_queue = std::make_shared<ActiveWindow::OutputQueue>();
+  ActiveWindow aw(cfg, out_queue);
+  void* scene = synth_create(1234, 12, 1);
+  const size_t n = static_cast<size_t>(W) * H;
+  std::vector<float> depth(n);
+  std::vector<uint8_t> rgb(n * 3);
+  std::vector<int32_t> label(n);
+  for (int i = 0; i < N; ++i) {
+    hydra::InputPacket pkt;
+    pkt.timestamp_ns = static_cast<uint64_t>(std::llround((1.0 + 0.1 * i) * 1e9));
+    circlePose(0.1 * i, pkt.world_T_body);
+    pkt.sensor = {W, H, W / 2.f, W / 2.f, W / 2.f, H / 2.f, 0.1f, 5.f};
+    synth_render(scene, W, H, pkt.sensor.fx, pkt.sensor.fy, pkt.sensor.cx, pkt.sensor.cy, pkt.world_T_body, 0.1 * i, 5.f, 0.f,
+                 1234u + 7919u * i, depth.data(), rgb.data(), label.data(), 0);
+    pkt.depth = depth.data();
+    pkt.color = rgb.data();
+    pkt.labels = label.data();
+    aw.step(pkt);
+    hydra::ActiveWindowOutput::Ptr popped;
+    while (out_queue->pop(&popped)) {}
+  }
+  synth_destroy(scene);
+  using clk = std::chrono::steady_clock;
+  hydra::VolumetricMap& map = aw.getMap();
+  khr_sync(map.ctx());
+  const auto t0 = clk::now();
+  const size_t file_bytes = map.save(path);
+  const auto t1 = clk::now();
+  khr_config kc;
+  if (khr_get_config(map.ctx(), &kc) != KHR_OK) throw std::runtime_error(khr_last_error());
+  khr_ctx* ctx2 = nullptr;
+  if (khr_create(&kc, &ctx2) != KHR_OK) throw std::runtime_error(std::string("khr_create: ") + khr_last_error());
+  hydra::VolumetricMap map2(map.config, ctx2);
+  const auto t2 = clk::now();
+  const size_t kept = map2.load(path);
+  const auto t3 = clk::now();
+  uint64_t da[KHR_DIGEST_WORDS], db[KHR_DIGEST_WORDS];
+  if (khr_map_digest(map.ctx(), da) != KHR_OK || khr_map_digest(ctx2, db) != KHR_OK) throw std::runtime_error(khr_last_error());
+  const size_t blocks_a = map.numBlocks(), blocks_b = map2.numBlocks();
+  const bool same = std::memcmp(da, db, sizeof(da)) == 0 && blocks_a == blocks_b && kept == blocks_b &&
+                    map.allocatedBlockIndices() == map2.allocatedBlockIndices();
+  auto words = [](const uint64_t* d) {
+    std::string s = "[";
+    for (int i = 0; i < KHR_DIGEST_WORDS; ++i) {
+      char b[32];
+      std::snprintf(b, sizeof(b), "%s\"%016llx\"", i ? ", " : "", static_cast<unsigned long long>(d[i]));
+      s += b;
+    }
+    return s + "]";
+  };
+  std::printf("{\"what\": \"map checkpoint through hydra::VolumetricMap::save / load, %dx%d, %d frames\", \"digest_saved\": %s, \"digest_loaded\": %s, "
+              "\"blocks_saved\": %zu, \"blocks_loaded\": %zu, \"file_bytes\": %zu, \"save_ms\": %.3f, \"load_ms\": %.3f, \"equal\": %s}\n",
+              W, H, N, words(da).c_str(), words(db).c_str(), blocks_a, blocks_b, file_bytes,
+              std::chrono::duration<double, std::milli>(t1 - t0).count(), std::chrono::duration<double, std::milli>(t3 - t2).count(),
+              same ? "true" : "false");
+  khr_destroy(ctx2);
+  aw.finishMapping();
+  return same ? 0 : 3;
+}
+
 static void onSegv(int sig) {  // a crash must not look like an empty result: print where it happened
   void* bt[48];
   const int n = backtrace(bt, 48);
@@ -404,6 +480,14 @@ int main(int argc, char** argv) {
   if (argc >= 2 && std::string(argv[1]) == "--slices") {
     try {
       return slicesDemo(argc, argv);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "aw_demo: %s\n", e.what());
+      return 1;
+    }
+  }
+  if (argc >= 2 && std::string(argv[1]) == "--checkpoint") {
+    try {
+      return checkpointDemo(argc, argv);
     } catch (const std::exception& e) {
       std::fprintf(stderr, "aw_demo: %s\n", e.what());
       return 1;

@@ -298,6 +298,14 @@ class VolumetricMap {
     s.last_observed.resize(nv); s.flags.resize(nv);
     return s;
   }
+  // The map save / load role of hydra::VolumetricMap (un-vendored upstream; the reference's own tree has no counterpart): the live
+  // map as one checkpoint file (khr_checkpoint_save: the format is in include/khronos_amd.h) and back into an EMPTY map of the
+  // same configuration (khr_checkpoint_load; sharded contexts keep their own blocks).  File I/O around the two calls through a
+  // page-locked bounce buffer (pageable when that cannot be had).  save returns the file's bytes, load the blocks kept; both
+  // throw std::runtime_error with khr_last_error's text.  The mesh layer, the frame ring and the trackers are not part of a
+  // checkpoint.  (Defined in active_window.cpp.)
+  size_t save(const std::string& path) const;
+  size_t load(const std::string& path);
 
  private:
   khr_ctx* ctx_ = nullptr;
