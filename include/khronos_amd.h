@@ -504,6 +504,31 @@ int khr_map_slice(khr_ctx* ctx, int64_t voxel_z, int64_t cap, int32_t* block_xy,
                   uint64_t* last_observed, uint8_t* voxel_flags, int64_t* n_voxels);
 /* getVoxelKey((0, 0, height)).z as a global voxel index (ASSUMPTIONS.md A.10); needs no context and no device */
 int khr_slice_voxel_z(float height, float voxel_size, int32_t voxels_per_side, int64_t* voxel_z);
+/* The live map seen from a pose (ASSUMPTIONS.md A.12): one ray per pixel of `sensor`, marched at fixed z-depth steps through the
+ * map; the first crossing from an observed positive to an observed non-positive trilinear distance is the pixel's hit.
+ * Outputs, each W*H row-major, any may be NULL: depth (z-depth of the hit, metres), normal (3 per pixel, world frame, zero when
+ * the gradient's taps are not all observed), color_rgba (4 bytes per pixel), label (0 without semantics), vflags (KHR_VOX_*
+ * bits) of the voxel the hit lies in, status (0 none, 1 hit, 2 blocked: the ray met the inside of a surface without an observed
+ * front crossing, nothing is rendered through it).  Every output of a pixel that is not a hit is zero.
+ * on_device != 0: the pointers are device memory, written in stream order on the context's stream, no allocation and no host
+ * wait unless `stats` is given.  on_device == 0: host memory, filled when the call returns (through staging created at the first
+ * such call and grown to the largest image).  The map is only read.
+ * KHR_EINVAL (nothing written): NULL request, non-finite pose, width * height <= 0, max_range < min_range, min_range < 0,
+ * negative step_voxels, more than 65536 samples per ray; KHR_ESTATE: world_size > 1 (a shard cannot interpolate across faces it
+ * does not own). */
+typedef struct khr_render_request {
+  khr_sensor sensor;         /* width, height, fx, fy, cx, cy; min_range / max_range: z-depth limits of the march */
+  double world_T_sensor[16]; /* row-major 4x4, as khr_frame */
+  float step_voxels;         /* z-depth sample spacing in voxel sizes; 0 = 0.5 */
+  float min_weight;          /* a voxel counts as observed iff weight >= this; 0 = khr_config.mesh_min_weight */
+} khr_render_request;
+typedef struct khr_render_stats {
+  uint64_t n_hit, n_blocked;
+  uint64_t n_samples_total;     /* samples per ray * pixels */
+  uint64_t n_samples_evaluated; /* samples the march visited: neither passed over as empty space nor behind a ray's end */
+} khr_render_stats;
+int khr_render_view(khr_ctx* ctx, const khr_render_request* request, int on_device, float* depth, float* normal, uint8_t* color_rgba,
+                    uint32_t* label, uint8_t* vflags, uint8_t* status, khr_render_stats* stats);
 /* Order-independent 64-bit digests of the WHOLE map (every live block, every voxel), one word per layer, on the values
  * khr_download_block hands out:  digest[layer] = sum_b sum_i mix(mix(key(b) * G + layer * L + i) ^ value_bits) mod 2^64
  * (mix = splitmix64 finaliser, key = 3 x 21-bit packed block index; csrc/khr_kernels_aux.h: digestTerm).  Sums commute, so

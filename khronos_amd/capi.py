@@ -42,6 +42,14 @@ class KhrSensor(C.Structure):
                 ("cx", C.c_float), ("cy", C.c_float), ("min_range", C.c_float), ("max_range", C.c_float)]
 
 
+class KhrRenderRequest(C.Structure):
+    _fields_ = [("sensor", KhrSensor), ("world_T_sensor", C.c_double * 16), ("step_voxels", C.c_float), ("min_weight", C.c_float)]
+
+
+class KhrRenderStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_hit", "n_blocked", "n_samples_total", "n_samples_evaluated")]
+
+
 class KhrFrame(C.Structure):
     _fields_ = [("timestamp_ns", C.c_uint64), ("world_T_sensor", C.c_double * 16), ("depth", C.c_void_p),
                 ("color", C.c_void_p), ("label", C.c_void_p)]
@@ -104,7 +112,7 @@ EXPORTS = [
     "khr_rv_create", "khr_rv_destroy", "khr_rv_clear", "khr_rv_add_rays", "khr_rv_num_rays", "khr_rv_num_pairs", "khr_rv_check",
     "khr_snapshot_updated", "khr_take_snapshot", "khr_snapshot_num_blocks", "khr_snapshot_download", "khr_snapshot_download_extra", "khr_snapshot_download_begin", "khr_snapshot_download_end", "khr_snapshot_poll", "khr_fetch_mesh_launch", "khr_reserve_mesh_staging", "khr_reserve_snapshots", "khr_mirror_dynamic", "khr_snapshot_release",
     "khr_rv_check_stamps", "khr_get_config", "khr_cluster_voxels_launch", "khr_cluster_voxels_fetch", "khr_reset_map", "khr_depend_on", "khr_retain_slot", "khr_release_slot",
-    "khr_map_slice", "khr_slice_voxel_z",
+    "khr_map_slice", "khr_slice_voxel_z", "khr_render_view",
     "khr_checkpoint_size", "khr_checkpoint_save", "khr_checkpoint_load", "khr_checkpoint_inspect",
 ]
 
@@ -193,6 +201,7 @@ def load_library():
     lib.khr_download_block.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 9
     lib.khr_map_slice.argtypes = [vp, i64, i64] + [vp] * 7
     lib.khr_slice_voxel_z.argtypes = [C.c_float, C.c_float, C.c_int32, vp]
+    lib.khr_render_view.argtypes = [vp, C.POINTER(KhrRenderRequest), i32] + [vp] * 6 + [C.POINTER(KhrRenderStats)]
     lib.khr_checkpoint_size.argtypes = [vp, C.POINTER(u64), C.POINTER(i64)]
     lib.khr_checkpoint_save.argtypes = [vp, vp, u64, C.POINTER(u64)]
     lib.khr_checkpoint_load.argtypes = [vp, vp, u64, C.POINTER(i64)]
@@ -772,6 +781,54 @@ class FusionContext:
         res = {k: v[: n // (vps * vps)] if k == "block_xy" else v[:n] for k, v in out.items()}
         res["voxel_z"] = int(voxel_z)
         return res
+
+    RENDER_FIELDS = (("depth", np.float32, ()), ("normal", np.float32, (3,)), ("color", np.uint8, (4,)), ("label", np.uint32, ()),
+                     ("flags", np.uint8, ()), ("status", np.uint8, ()))
+
+    @staticmethod
+    def render_request(sensor, world_T_sensor, step_voxels=0.0, min_weight=0.0):
+        rq = KhrRenderRequest()
+        rq.sensor = sensor
+        T = np.ascontiguousarray(world_T_sensor, dtype=np.float64).reshape(16)
+        for i in range(16):
+            rq.world_T_sensor[i] = T[i]
+        rq.step_voxels, rq.min_weight = step_voxels, min_weight
+        return rq
+
+    def render_view_into(self, request, out, on_device=False, want_stats=True):
+        """khr_render_view into caller buffers (`out`: RENDER_FIELDS name -> contiguous array, or an integer device pointer with
+        on_device; absent / None = not rendered).  `request` may be None (the NULL request).  Returns (return code, stats dict or
+        None) without raising."""
+        st = KhrRenderStats()
+        ptrs = []
+        for name, _, _ in self.RENDER_FIELDS:
+            a = out.get(name)
+            ptrs.append(None if a is None else (C.c_void_p(int(a)) if on_device else _ptr(a)))
+        rc = self.lib.khr_render_view(self.h, None if request is None else C.byref(request), int(on_device), *ptrs,
+                                      C.byref(st) if want_stats else None)
+        stats = {n: int(getattr(st, n)) for n, _ in KhrRenderStats._fields_} if (want_stats and rc == 0) else None
+        return rc, stats
+
+    def render_view(self, sensor, pose, step_voxels=0, min_weight=0, device=False):
+        """The live map seen from `pose` through `sensor` (khr_render_view, ASSUMPTIONS.md A.12): dict with depth (H, W) float32,
+        normal (H, W, 3) float32 in the world frame, color (H, W, 4) uint8, label (H, W) uint32, flags (H, W) uint8 (VOX_* bits),
+        status (H, W) uint8 (0 none, 1 hit, 2 blocked) and stats (n_hit, n_blocked, n_samples_total, n_samples_evaluated).
+        device=True: the images are torch tensors on the context's device; the kernel writes every pixel on the context's stream
+        and the call returns when the counters have arrived, i.e. after the images are complete."""
+        H, W = int(sensor.height), int(sensor.width)
+        rq = self.render_request(sensor, pose, step_voxels, min_weight)
+        if device:
+            import torch
+            dev = torch.device("cuda", self.cfg.device)
+            tdt = {np.float32: torch.float32, np.uint8: torch.uint8, np.uint32: torch.int32}
+            out = {n: torch.empty((max(H, 0), max(W, 0)) + sh, dtype=tdt[dt], device=dev) for n, dt, sh in self.RENDER_FIELDS}
+            rc, stats = self.render_view_into(rq, {n: t.data_ptr() for n, t in out.items()}, on_device=True)
+        else:
+            out = {n: np.zeros((max(H, 0), max(W, 0)) + sh, dt) for n, dt, sh in self.RENDER_FIELDS}
+            rc, stats = self.render_view_into(rq, out)
+        self._chk(rc)
+        out["stats"] = stats
+        return out
 
     def mesh_halo_words(self):
         v = self.cfg.voxels_per_side

@@ -34,6 +34,7 @@
 #include "khr_kernels_fuse.h"
 #include "khr_kernels_objects.h"
 #include "khr_kernels_slice.h"
+#include "khr_kernels_render.h"
 #include "khr_kernels_checkpoint.h"
 
 using namespace khr;
@@ -369,6 +370,12 @@ struct khr_ctx {
   uint8_t* d_slice_stage = nullptr;
   uint8_t* h_slice_stage = nullptr;
   uint32_t slice_cap = 0, slice_hint = 0;
+  // rendered views (khr_render_view): the counters (created when a caller first asks for them) and the image staging of the host
+  // form (created at the first host-form call, grown to the largest image)
+  unsigned long long* d_render_stats = nullptr;
+  uint8_t* d_render_stage = nullptr;
+  uint8_t* h_render_stage = nullptr;  // page-locked mirror of d_render_stage
+  size_t render_stage_bytes = 0;
   // map checkpoints (khr_checkpoint_save / _load): two chunk staging areas of kCkptStageBytes each (created at the first call; their
   // page-locked mirrors only when a caller passes pageable memory), the chunk's slot list, the load's error word, and per
   // staging area one event for "filled" and one for "drained"
@@ -1129,6 +1136,9 @@ void khr_destroy(khr_ctx* c) {
   if (c->d_slice_keys) { hipFree(c->d_slice_keys); hipFree(c->d_slice_count); }
   if (c->d_slice_stage) hipFree(c->d_slice_stage);
   if (c->h_slice_stage) hipHostFree(c->h_slice_stage);
+  if (c->d_render_stats) hipFree(c->d_render_stats);
+  if (c->d_render_stage) hipFree(c->d_render_stage);
+  if (c->h_render_stage) hipHostFree(c->h_render_stage);
   for (int i = 0; i < 2; ++i) {
     if (c->d_ckpt[i]) hipFree(c->d_ckpt[i]);
     if (c->h_ckpt[i]) hipHostFree(c->h_ckpt[i]);
@@ -4805,6 +4815,105 @@ int khr_map_slice(khr_ctx* c, int64_t voxel_z, int64_t cap, int32_t* block_xy, f
   if (weight) std::memcpy(weight, h + L.weight, nv * 4);
   if (last_observed) std::memcpy(last_observed, h + L.obs, nv * 8);
   if (voxel_flags) std::memcpy(voxel_flags, h + L.flags, nv);
+  return KHR_OK;
+}
+
+// ---- the live map seen from a pose (khr_render_view; ASSUMPTIONS.md A.12, device side: khr_kernels_render.h) -------------------
+int khr_render_view(khr_ctx* c, const khr_render_request* rq, int on_device, float* depth, float* normal, uint8_t* color_rgba,
+                    uint32_t* label, uint8_t* vflags, uint8_t* status, khr_render_stats* stats) {
+  if (!c || !rq) return fail(KHR_EINVAL, "null argument");
+  const khr_sensor& sn = rq->sensor;
+  for (int i = 0; i < 16; ++i)
+    if (!std::isfinite(rq->world_T_sensor[i])) return fail(KHR_EINVAL, "world_T_sensor is not finite");
+  if (sn.width <= 0 || sn.height <= 0 || static_cast<int64_t>(sn.width) * sn.height > (int64_t(1) << 30))
+    return fail(KHR_EINVAL, "bad image size %d x %d", sn.width, sn.height);
+  if (!std::isfinite(sn.fx) || !std::isfinite(sn.fy) || sn.fx == 0.f || sn.fy == 0.f || !std::isfinite(sn.cx) || !std::isfinite(sn.cy))
+    return fail(KHR_EINVAL, "bad intrinsics");
+  if (!std::isfinite(sn.min_range) || !std::isfinite(sn.max_range) || sn.min_range < 0.f || sn.max_range < sn.min_range)
+    return fail(KHR_EINVAL, "bad range limits [%g, %g]", static_cast<double>(sn.min_range), static_cast<double>(sn.max_range));
+  if (!(rq->step_voxels >= 0.f) || !std::isfinite(rq->step_voxels)) return fail(KHR_EINVAL, "bad step_voxels %g", static_cast<double>(rq->step_voxels));
+  if (!(rq->min_weight >= 0.f)) return fail(KHR_EINVAL, "bad min_weight %g", static_cast<double>(rq->min_weight));
+  const float dt = (rq->step_voxels == 0.f ? 0.5f : rq->step_voxels) * c->p.vs;
+  const float n_steps = std::floor((sn.max_range - sn.min_range) / dt);
+  if (!(n_steps < 65536.f)) return fail(KHR_EINVAL, "more than 65536 samples per ray (step %g m over %g m)", static_cast<double>(dt),
+                                        static_cast<double>(sn.max_range - sn.min_range));
+  if (c->cfg.world_size > 1) return fail(KHR_ESTATE, "khr_render_view needs the whole map: world_size is %d", c->cfg.world_size);
+  HIP_TRY(hipSetDevice(c->device));
+  RenderView r{};
+  r.W = sn.width;
+  r.H = sn.height;
+  r.K = static_cast<int>(n_steps) + 1;
+  r.fx = sn.fx;
+  r.fy = sn.fy;
+  r.cx = sn.cx;
+  r.cy = sn.cy;
+  r.min_range = sn.min_range;
+  r.dt = dt;
+  r.min_weight = rq->min_weight == 0.f ? c->cfg.mesh_min_weight : rq->min_weight;
+  {
+    float R[9], t[3];
+    makePose(rq->world_T_sensor, R, t, r.Rw, r.tw);
+  }
+  const size_t n_px = static_cast<size_t>(sn.width) * sn.height;
+  // the images of the host form, one after the other in the device staging and its page-locked mirror
+  void* const host[6] = {depth, normal, color_rgba, label, vflags, status};
+  const size_t per_px[6] = {4, 12, 4, 4, 1, 1};
+  size_t off[6], stage_bytes = 0;
+  for (int f = 0; f < 6; ++f) {
+    off[f] = stage_bytes;
+    if (host[f]) stage_bytes += (n_px * per_px[f] + 255) / 256 * 256;
+  }
+  void* dev[6] = {depth, normal, color_rgba, label, vflags, status};
+  if (!on_device && stage_bytes) {
+    if (stage_bytes > c->render_stage_bytes) {
+      if (c->d_render_stage) HIP_TRY(hipFree(c->d_render_stage));
+      if (c->h_render_stage) HIP_TRY(hipHostFree(c->h_render_stage));
+      c->d_render_stage = c->h_render_stage = nullptr;
+      c->render_stage_bytes = 0;
+      if (hipMalloc(reinterpret_cast<void**>(&c->d_render_stage), stage_bytes) != hipSuccess)
+        return fail(KHR_ENOMEM, "render staging of %zu bytes", stage_bytes);
+      if (hipHostMalloc(reinterpret_cast<void**>(&c->h_render_stage), stage_bytes, hipHostMallocDefault) != hipSuccess) {
+        hipFree(c->d_render_stage);
+        c->d_render_stage = nullptr;
+        return fail(KHR_ENOMEM, "page-locked render staging of %zu bytes", stage_bytes);
+      }
+      c->render_stage_bytes = stage_bytes;
+    }
+    for (int f = 0; f < 6; ++f) dev[f] = host[f] ? c->d_render_stage + off[f] : nullptr;
+  }
+  r.depth = static_cast<float*>(dev[0]);
+  r.normal = static_cast<float*>(dev[1]);
+  r.color = static_cast<uint32_t*>(dev[2]);
+  r.label = static_cast<uint32_t*>(dev[3]);
+  r.vflags = static_cast<uint8_t*>(dev[4]);
+  r.status = static_cast<uint8_t*>(dev[5]);
+  if (stats) {
+    if (!c->d_render_stats && hipMalloc(reinterpret_cast<void**>(&c->d_render_stats), sizeof(unsigned long long) * RS_COUNT) != hipSuccess)
+      return fail(KHR_ENOMEM, "render counters");
+    HIP_TRY(hipMemsetAsync(c->d_render_stats, 0, sizeof(unsigned long long) * RS_COUNT, c->stream));
+    r.stats = c->d_render_stats;
+  }
+  const dim3 grid(static_cast<unsigned>((sn.width + 15) / 16), static_cast<unsigned>((sn.height + 15) / 16));
+  int rc = dispatchVps(c, [&](auto vps) {
+    hipLaunchKernelGGL((k_render_view<decltype(vps)::value>), grid, dim3(256), 0, c->stream, c->m, c->p, r);
+    HIP_TRY(hipGetLastError());
+    return KHR_OK;
+  });
+  if (rc) return rc;
+  unsigned long long h_stats[RS_COUNT] = {0, 0, 0, 0};
+  if (stats) HIP_TRY(hipMemcpyAsync(h_stats, c->d_render_stats, sizeof(h_stats), hipMemcpyDeviceToHost, c->stream));
+  if (!on_device && stage_bytes)
+    HIP_TRY(hipMemcpyAsync(c->h_render_stage, c->d_render_stage, stage_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (stats || (!on_device && stage_bytes)) HIP_TRY(hipStreamSynchronize(c->stream));
+  if (!on_device)
+    for (int f = 0; f < 6; ++f)
+      if (host[f]) std::memcpy(host[f], c->h_render_stage + off[f], n_px * per_px[f]);
+  if (stats) {
+    stats->n_hit = h_stats[RS_HIT];
+    stats->n_blocked = h_stats[RS_BLOCKED];
+    stats->n_samples_total = static_cast<uint64_t>(r.K) * n_px;
+    stats->n_samples_evaluated = h_stats[RS_VISITED];
+  }
   return KHR_OK;
 }
 

@@ -2,7 +2,7 @@
 // thread drives the reference (spinOnce per InputPacket, finishMapping at shutdown), and prints a JSON
 // summary that tests/test_gpu_host.py compares with the step-wise C-ABI path and the oracle.
 // usage: aw_demo <config.yaml> <width> <height> <frames> [object_label]
-//        aw_demo --slices | --checkpoint | --bench | --rayver ... (below)
+//        aw_demo --slices | --render | --checkpoint | --bench | --rayver ... (below)
 //   object_label >= 0: the stand-in detector / tracker below; otherwise the plugins named in the config
 #include <execinfo.h>
 #include <csignal>
@@ -381,6 +381,83 @@ static int slicesDemo(int argc, char** argv) {
   return agree == frames ? 0 : 3;
 }
 
+// 64-bit digest of an image's bytes: sum_i mix(i * L + byte_i) mod 2^64, mix = the splitmix64 step of khr_map_digest
+// (tests/test_gpu_render_view.py restates it in numpy)
+static uint64_t imageDigest(const void* data, size_t bytes) {
+  const uint8_t* b = static_cast<const uint8_t*>(data);
+  uint64_t sum = 0;
+  for (size_t i = 0; i < bytes; ++i) {
+    uint64_t x = static_cast<uint64_t>(i) * 0x632BE59BD9B4E019ull + b[i] + 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    sum += x ^ (x >> 31);
+  }
+  return sum;
+}
+
+// aw_demo --render <config.yaml> <width> <height> <frames> [step_voxels]: drives the synthetic stream through an ActiveWindow whose
+// Khronos sink renders the map at the LAST frame's own pose and sensor (VolumetricMap::render(frame): one call).  One JSON line:
+// the image shapes, the render counters, a 64-bit digest per image (imageDigest) and the call's wall-clock time.
+static int renderDemo(int argc, char** argv) {
+  if (argc < 6) {
+    std::fprintf(stderr, "usage: aw_demo --render <config.yaml> <width> <height> <frames> [step_voxels]\n");
+    return 2;
+  }
+  std::ifstream in(argv[2]);
+  std::stringstream ss;
+  ss << in.rdbuf();
+  const int W = std::atoi(argv[3]), H = std::atoi(argv[4]), N = std::atoi(argv[5]);
+  const float step_voxels = argc > 6 ? static_cast<float>(std::atof(argv[6])) : 0.f;
+  ActiveWindow::Config cfg = ActiveWindow::Config::fromYamlString(ss.str());
+  cfg.max_frame_pixels = static_cast<uint32_t>(W) * H;
+  auto out_queue = std::make_shared<ActiveWindow::OutputQueue>();
+  ActiveWindow aw(cfg, out_queue);
+  int frames = 0;
+  hydra::RenderedView view;
+  double render_ms = 0;
+  using clk = std::chrono::steady_clock;
+  aw.addKhronosSink([&](const FrameData& data, const VolumetricMap& map, const Tracks&) {
+    if (++frames != N) return;
+    khr_sync(map.ctx());
+    const auto t0 = clk::now();
+    view = map.render(data.input, step_voxels);
+    render_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+  });
+  void* scene = synth_create(1234, 12, 1);
+  const size_t n = static_cast<size_t>(W) * H;
+  std::vector<float> depth(n);
+  std::vector<uint8_t> rgb(n * 3);
+  std::vector<int32_t> label(n);
+  for (int i = 0; i < N; ++i) {
+    hydra::InputPacket pkt;
+    pkt.timestamp_ns = static_cast<uint64_t>(std::llround((1.0 + 0.1 * i) * 1e9));
+    circlePose(0.1 * i, pkt.world_T_body);
+    pkt.sensor = {W, H, W / 2.f, W / 2.f, W / 2.f, H / 2.f, 0.1f, 5.f};
+    synth_render(scene, W, H, pkt.sensor.fx, pkt.sensor.fy, pkt.sensor.cx, pkt.sensor.cy, pkt.world_T_body, 0.1 * i, 5.f, 0.f,
+                 1234u + 7919u * i, depth.data(), rgb.data(), label.data(), 0);
+    pkt.depth = depth.data();
+    pkt.color = rgb.data();
+    pkt.labels = label.data();
+    aw.step(pkt);
+    hydra::ActiveWindowOutput::Ptr popped;
+    while (out_queue->pop(&popped)) {}
+  }
+  aw.finishMapping();
+  synth_destroy(scene);
+  auto dg = [](const auto& v) { return static_cast<unsigned long long>(imageDigest(v.data(), v.size() * sizeof(v[0]))); };
+  std::printf("{\"what\": \"the live map rendered at the last frame's pose (VolumetricMap::render), %d frames\", \"frames\": %d, "
+              "\"shapes\": {\"depth\": [%d, %d], \"normal\": [%d, %d, 3], \"color\": [%d, %d, 4], \"label\": [%d, %d], \"flags\": [%d, %d], "
+              "\"status\": [%d, %d]}, \"stats\": {\"n_hit\": %llu, \"n_blocked\": %llu, \"n_samples_total\": %llu, \"n_samples_evaluated\": %llu}, "
+              "\"digests\": {\"depth\": \"%016llx\", \"normal\": \"%016llx\", \"color\": \"%016llx\", \"label\": \"%016llx\", "
+              "\"flags\": \"%016llx\", \"status\": \"%016llx\"}, \"render_ms\": %.3f}\n",
+              N, frames, view.height, view.width, view.height, view.width, view.height, view.width, view.height, view.width, view.height,
+              view.width, view.height, view.width, static_cast<unsigned long long>(view.stats.n_hit),
+              static_cast<unsigned long long>(view.stats.n_blocked), static_cast<unsigned long long>(view.stats.n_samples_total),
+              static_cast<unsigned long long>(view.stats.n_samples_evaluated), dg(view.depth), dg(view.normal), dg(view.color), dg(view.label),
+              dg(view.flags), dg(view.status), render_ms);
+  return frames == N && view.numPixels() == n ? 0 : 3;
+}
+
 // aw_demo --checkpoint <config.yaml> <width> <height> <frames> [file]: runs the synthetic stream through an ActiveWindow, saves the live
 // map through getMap().save (hydra::VolumetricMap: khr_checkpoint_save around a file), loads the file into the empty map of a second
 // context of the same configuration and compares the two maps' whole-map digests.  One JSON line: both digests (12 words each),
@@ -480,6 +557,14 @@ int main(int argc, char** argv) {
   if (argc >= 2 && std::string(argv[1]) == "--slices") {
     try {
       return slicesDemo(argc, argv);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "aw_demo: %s\n", e.what());
+      return 1;
+    }
+  }
+  if (argc >= 2 && std::string(argv[1]) == "--render") {
+    try {
+      return renderDemo(argc, argv);
     } catch (const std::exception& e) {
       std::fprintf(stderr, "aw_demo: %s\n", e.what());
       return 1;

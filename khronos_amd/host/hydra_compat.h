@@ -239,6 +239,21 @@ inline SlicePoints tsdfSlice(const MapSlice& s, float truncation_distance) {
   return r;
 }
 
+// The live map seen from a pose (VolumetricMap::render, khr_render_view; ASSUMPTIONS.md A.12): W x H row-major images.  A pixel
+// whose status is not kHit is zero in every image.
+struct RenderedView {
+  enum Status : uint8_t { kNone = 0, kHit = 1, kBlocked = 2 };
+  int width = 0, height = 0;
+  std::vector<float> depth;      // z-depth of the hit, metres
+  std::vector<float> normal;     // 3 per pixel, world frame
+  std::vector<uint8_t> color;    // rgba per pixel
+  std::vector<uint32_t> label;   // 0 without semantics
+  std::vector<uint8_t> flags;    // KHR_VOX_* bits of the voxel the hit lies in
+  std::vector<uint8_t> status;
+  khr_render_stats stats{};
+  size_t numPixels() const { return status.size(); }
+};
+
 // hydra::VolumetricMap role: here a handle on the HBM-resident map of a fusion context.
 class VolumetricMap {
  public:
@@ -297,6 +312,29 @@ class VolumetricMap {
     s.block_xy.resize(2 * (nv / np)); s.positions.resize(3 * nv); s.distance.resize(nv); s.weight.resize(nv);
     s.last_observed.resize(nv); s.flags.resize(nv);
     return s;
+  }
+  // The map rendered on the device from any pose (khr_render_view): depth, normal, colour, label, voxel flags and hit status per
+  // pixel of `sensor` (its min_range / max_range bound the march in z-depth).  step_voxels 0 = half a voxel, min_weight 0 = the
+  // mesh's minimum weight.  One call, one host wait.
+  RenderedView render(const Sensor& sensor, const double* world_T_sensor, float step_voxels = 0.f, float min_weight = 0.f) const {
+    khr_render_request rq{};
+    rq.sensor = {sensor.width, sensor.height, sensor.fx, sensor.fy, sensor.cx, sensor.cy, sensor.min_range, sensor.max_range};
+    for (int i = 0; i < 16; ++i) rq.world_T_sensor[i] = world_T_sensor[i];
+    rq.step_voxels = step_voxels;
+    rq.min_weight = min_weight;
+    RenderedView v;
+    v.width = sensor.width;
+    v.height = sensor.height;
+    const size_t n = sensor.width > 0 && sensor.height > 0 ? static_cast<size_t>(sensor.width) * sensor.height : 0;
+    v.depth.resize(n); v.normal.resize(3 * n); v.color.resize(4 * n); v.label.resize(n); v.flags.resize(n); v.status.resize(n);
+    if (khr_render_view(ctx_, &rq, 0, v.depth.data(), v.normal.data(), v.color.data(), v.label.data(), v.flags.data(), v.status.data(),
+                        &v.stats) != KHR_OK)
+      throw std::runtime_error(std::string("khr_render_view: ") + khr_last_error());
+    return v;
+  }
+  // what the map predicts for a frame: the view from the frame's own pose through its own sensor (a sink's model-to-frame check)
+  RenderedView render(const InputData& frame, float step_voxels = 0.f, float min_weight = 0.f) const {
+    return render(frame.sensor, frame.world_T_sensor, step_voxels, min_weight);
   }
   // The map save / load role of hydra::VolumetricMap (un-vendored upstream; the reference's own tree has no counterpart): the live
   // map as one checkpoint file (khr_checkpoint_save: the format is in include/khronos_amd.h) and back into an EMPTY map of the
