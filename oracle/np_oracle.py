@@ -332,7 +332,8 @@ def motion_clusters(cfg, point_map, seeds, W, H):
 # ---- frustum allocation of ProjectiveIntegrator::updateMap(allocate_blocks = true) (ASSUMPTIONS.md A.3) ----
 def visible_blocks(cfg, sensor, T):
     """block indices (n, 3) whose centre passes pointIsInViewFrustum(centre in the sensor frame, 0.8660254 * block_size),
-    vectorised over the (2n + 1)^3 candidate cube around the camera's block; fp32, the operation order of A.3."""
+    vectorised over the (2n + 1)^3 candidate cube around the camera's block; fp32, the operation order of A.3.
+    cfg["alloc_candidate"] == 1: the camera_offset reading (candidate points, as a set of the blocks that contain them)."""
     vps = cfg["voxels_per_side"]
     bs = f32(cfg["voxel_size"]) * f32(vps)
     bs_inv = f32(1) / bs
@@ -357,10 +358,19 @@ def visible_blocks(cfg, sensor, T):
 
     normals = [crossn(bl, tl), crossn(tr, br), crossn(tl, tr), crossn(br, bl)]  # left, right, top, bottom (inward)
     infl = f32(0.8660254) * bs
-    d = np.arange(-n, n + 1, dtype=np.int64)
-    dz, dy, dx = np.meshgrid(d, d, d, indexing="ij")
-    b = np.stack([bc[0] + dx.ravel(), bc[1] + dy.ravel(), bc[2] + dz.ravel()], axis=1)
-    c = (b.astype(np.float32) + f32(0.5)) * bs
+    if cfg.get("alloc_candidate", 0) == 1:
+        # camera_offset: the candidate POINT camera_W + offset * block_size is tested, the block that contains it is allocated
+        ms = int(np.floor((max_range + infl) * bs_inv))
+        d = np.arange(-ms, ms + 1, dtype=np.int64)
+        dz, dy, dx = np.meshgrid(d, d, d, indexing="ij")
+        c = np.stack([tw[0] + dx.ravel().astype(np.float32) * bs, tw[1] + dy.ravel().astype(np.float32) * bs,
+                      tw[2] + dz.ravel().astype(np.float32) * bs], axis=1)
+        b = np.floor(c * bs_inv).astype(np.int64)
+    else:
+        d = np.arange(-n, n + 1, dtype=np.int64)
+        dz, dy, dx = np.meshgrid(d, d, d, indexing="ij")
+        b = np.stack([bc[0] + dx.ravel(), bc[1] + dy.ravel(), bc[2] + dz.ravel()], axis=1)
+        c = (b.astype(np.float32) + f32(0.5)) * bs
     pc = [((R[r, 0] * c[:, 0] + R[r, 1] * c[:, 1]) + R[r, 2] * c[:, 2]) + t[r] for r in range(3)]
     ok = ~(pc[2] < -infl)
     n2 = (pc[0] * pc[0] + pc[1] * pc[1]) + pc[2] * pc[2]
@@ -369,4 +379,4 @@ def visible_blocks(cfg, sensor, T):
     for nrm in normals:
         dd = (pc[0] * nrm[0] + pc[1] * nrm[1]) + pc[2] * nrm[2]
         ok &= ~(dd < -infl)
-    return b[ok]
+    return np.unique(b[ok], axis=0) if cfg.get("alloc_candidate", 0) == 1 else b[ok]

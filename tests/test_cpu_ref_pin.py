@@ -73,10 +73,15 @@ def _same_partition(dyn_a, dyn_b):
 @needs_ref
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_oracle_equals_reference_code_over_a_sequence(case):
-    c = CASES[case]
+    run_sequence(case, CASES[case])
+
+
+def run_sequence(case, c, make_stream=SyntheticStream):
+    """the body of test_oracle_equals_reference_code_over_a_sequence; `make_stream`: SyntheticStream or a stream of the same scene
+    with another camera (tests/general_camera.py)"""
     cfg = _cfg(**c["cfg"])
     W, H = c["W"], c["H"]
-    s = SyntheticStream(W, H, threads=1)
+    s = make_stream(W, H, threads=1)
     sen = po.OrcSensor(W, H, s.fx, s.fy, s.cx, s.cy, 0.1, 5.0)
     m = po.OracleMap(cfg)
     r = pyref.RefMap(LIB, cfg)
@@ -473,11 +478,16 @@ def test_whole_active_window_equals_reference_code():
     -> clear), driven on the oracle with the independent tracker and the extraction restatement.  After EVERY frame: dynamic
     image, object image, tracks, the whole map's tracking state and block flags; at every output: its stamp (the rate limit of
     :158-160), archived blocks, cloned blocks, mesh size; at the end every extracted object."""
+    run_whole_active_window()
+
+
+def run_whole_active_window(make_stream=SyntheticStream):
+    """the body of test_whole_active_window_equals_reference_code, for any stream of the synthetic scene"""
     import py_tracker
     from extract_replica import extract_static
     from khronos_amd import default_config
     W, H, N = 160, 120, 34
-    s = SyntheticStream(W, H, threads=1)
+    s = make_stream(W, H, threads=1)
     cfg = _cfg(voxel_size=0.1, truncation_distance=0.3, md_min_cluster_size=20, md_min_separation_distance=2.0, md_max_range=5.0,
                temporal_window=0.9, temporal_buffer=0.4)
     osen = po.OrcSensor(W, H, s.fx, s.fy, s.cx, s.cy, 0.1, 5.0)
