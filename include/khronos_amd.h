@@ -529,6 +529,29 @@ typedef struct khr_render_stats {
 } khr_render_stats;
 int khr_render_view(khr_ctx* ctx, const khr_render_request* request, int on_device, float* depth, float* normal, uint8_t* color_rgba,
                     uint32_t* label, uint8_t* vflags, uint8_t* status, khr_render_stats* stats);
+/* The live map at world points (ASSUMPTIONS.md A.13): `points` holds 3 floats per point (x, y, z, metres, world frame).  Outputs,
+ * one entry per point, any may be NULL: distance (the trilinear signed distance, metres), gradient (3 per point, d(distance) /
+ * d(metres), central differences one voxel to either side in index space, not normalised), and of the voxel the point lies in:
+ * weight (not interpolated), color_rgba (4 bytes per point), label (0 without semantics), vflags (KHR_VOX_* bits), last_observed
+ * (0 without tracking); status: KHR_QP_VALUE iff all eight taps of the distance are observed (weight >= min_weight; 0 =
+ * khr_config.mesh_min_weight), KHR_QP_GRADIENT iff the taps of all six shifted samples are too, KHR_QP_VOXEL iff the point's
+ * voxel lies in an allocated block.  Every output of a point whose bit is clear is zero.  A NULL output removes its work:
+ * without gradient, status and stats only the eight taps of the distance are read (status and stats report all three bits, so
+ * they cost the gradient's taps), without an attribute output the voxel is not read.
+ * on_device != 0: every pointer is device memory, the work is issued in stream order on the context's stream, no allocation and
+ * no host wait unless `stats` is given.  on_device == 0: host memory, filled when the call returns (through staging created at
+ * the first such call and grown to the largest batch).  The map is only read.  n == 0: KHR_OK, nothing touched, zeroed stats.
+ * KHR_EINVAL (nothing written): n < 0, NULL points with n > 0, negative or non-finite min_weight; KHR_ESTATE: world_size > 1 (a
+ * shard cannot interpolate across faces it does not own). */
+typedef struct khr_query_stats {
+  uint64_t n_value, n_gradient, n_voxel; /* points with KHR_QP_VALUE / _GRADIENT / _VOXEL */
+} khr_query_stats;
+#define KHR_QP_VALUE 1
+#define KHR_QP_GRADIENT 2
+#define KHR_QP_VOXEL 4
+int khr_query_points(khr_ctx* ctx, int64_t n, const float* points, float min_weight, int on_device, float* distance, float* gradient,
+                     float* weight, uint8_t* color_rgba, uint32_t* label, uint8_t* vflags, uint64_t* last_observed, uint8_t* status,
+                     khr_query_stats* stats);
 /* Order-independent 64-bit digests of the WHOLE map (every live block, every voxel), one word per layer, on the values
  * khr_download_block hands out:  digest[layer] = sum_b sum_i mix(mix(key(b) * G + layer * L + i) ^ value_bits) mod 2^64
  * (mix = splitmix64 finaliser, key = 3 x 21-bit packed block index; csrc/khr_kernels_aux.h: digestTerm).  Sums commute, so

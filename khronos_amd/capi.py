@@ -50,6 +50,13 @@ class KhrRenderStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("n_hit", "n_blocked", "n_samples_total", "n_samples_evaluated")]
 
 
+class KhrQueryStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_value", "n_gradient", "n_voxel")]
+
+
+KHR_QP_VALUE, KHR_QP_GRADIENT, KHR_QP_VOXEL = 1, 2, 4
+
+
 class KhrFrame(C.Structure):
     _fields_ = [("timestamp_ns", C.c_uint64), ("world_T_sensor", C.c_double * 16), ("depth", C.c_void_p),
                 ("color", C.c_void_p), ("label", C.c_void_p)]
@@ -112,7 +119,7 @@ EXPORTS = [
     "khr_rv_create", "khr_rv_destroy", "khr_rv_clear", "khr_rv_add_rays", "khr_rv_num_rays", "khr_rv_num_pairs", "khr_rv_check",
     "khr_snapshot_updated", "khr_take_snapshot", "khr_snapshot_num_blocks", "khr_snapshot_download", "khr_snapshot_download_extra", "khr_snapshot_download_begin", "khr_snapshot_download_end", "khr_snapshot_poll", "khr_fetch_mesh_launch", "khr_reserve_mesh_staging", "khr_reserve_snapshots", "khr_mirror_dynamic", "khr_snapshot_release",
     "khr_rv_check_stamps", "khr_get_config", "khr_cluster_voxels_launch", "khr_cluster_voxels_fetch", "khr_reset_map", "khr_depend_on", "khr_retain_slot", "khr_release_slot",
-    "khr_map_slice", "khr_slice_voxel_z", "khr_render_view",
+    "khr_map_slice", "khr_slice_voxel_z", "khr_render_view", "khr_query_points",
     "khr_checkpoint_size", "khr_checkpoint_save", "khr_checkpoint_load", "khr_checkpoint_inspect",
 ]
 
@@ -202,6 +209,7 @@ def load_library():
     lib.khr_map_slice.argtypes = [vp, i64, i64] + [vp] * 7
     lib.khr_slice_voxel_z.argtypes = [C.c_float, C.c_float, C.c_int32, vp]
     lib.khr_render_view.argtypes = [vp, C.POINTER(KhrRenderRequest), i32] + [vp] * 6 + [C.POINTER(KhrRenderStats)]
+    lib.khr_query_points.argtypes = [vp, i64, vp, C.c_float, i32] + [vp] * 8 + [C.POINTER(KhrQueryStats)]
     lib.khr_checkpoint_size.argtypes = [vp, C.POINTER(u64), C.POINTER(i64)]
     lib.khr_checkpoint_save.argtypes = [vp, vp, u64, C.POINTER(u64)]
     lib.khr_checkpoint_load.argtypes = [vp, vp, u64, C.POINTER(i64)]
@@ -826,6 +834,47 @@ class FusionContext:
         else:
             out = {n: np.zeros((max(H, 0), max(W, 0)) + sh, dt) for n, dt, sh in self.RENDER_FIELDS}
             rc, stats = self.render_view_into(rq, out)
+        self._chk(rc)
+        out["stats"] = stats
+        return out
+
+    QUERY_FIELDS = (("distance", np.float32, ()), ("gradient", np.float32, (3,)), ("weight", np.float32, ()), ("color", np.uint8, (4,)),
+                    ("label", np.uint32, ()), ("flags", np.uint8, ()), ("last_observed", np.uint64, ()), ("status", np.uint8, ()))
+
+    def query_points_into(self, n, points, out, min_weight=0.0, on_device=False, want_stats=True):
+        """khr_query_points into caller buffers.  `points`: a contiguous float32 array of 3 * n values, or an integer device pointer
+        with on_device, or None (the NULL pointer); `out`: QUERY_FIELDS name -> contiguous array, or an integer device pointer with
+        on_device; absent / None = not computed.  Returns (return code, stats dict or None) without raising."""
+        st = KhrQueryStats()
+        ptrs = []
+        for name, _, _ in self.QUERY_FIELDS:
+            a = out.get(name)
+            ptrs.append(None if a is None else (C.c_void_p(int(a)) if on_device else _ptr(a)))
+        pts = None if points is None else (C.c_void_p(int(points)) if on_device else _ptr(points))
+        rc = self.lib.khr_query_points(self.h, int(n), pts, float(min_weight), int(on_device), *ptrs, C.byref(st) if want_stats else None)
+        stats = {k: int(getattr(st, k)) for k, _ in KhrQueryStats._fields_} if (want_stats and rc == 0) else None
+        return rc, stats
+
+    def query_points(self, points, min_weight=0, device=False):
+        """The live map at world points (khr_query_points, ASSUMPTIONS.md A.13).  `points`: (n, 3) float32, metres, world frame (a
+        torch tensor on the context's device with device=True).  Returns a dict: distance (n,) float32, gradient (n, 3) float32
+        (d(distance) / d(metres), not normalised), and of the voxel each point lies in weight (n,) float32, color (n, 4) uint8,
+        label (n,) uint32, flags (n,) uint8 (VOX_* bits), last_observed (n,) uint64; status (n,) uint8 (KHR_QP_* bits) and stats
+        (n_value, n_gradient, n_voxel).  Every output of a point whose status bit is clear is zero.  device=True: the outputs are
+        torch tensors on the context's device, complete when the call returns (it waits for the counters)."""
+        if device:
+            import torch
+            dev = torch.device("cuda", self.cfg.device)
+            pts = torch.as_tensor(points, dtype=torch.float32, device=dev).reshape(-1, 3).contiguous()
+            n = int(pts.shape[0])
+            tdt = {np.float32: torch.float32, np.uint8: torch.uint8, np.uint32: torch.int32, np.uint64: torch.int64}
+            out = {k: torch.empty((n,) + sh, dtype=tdt[dt], device=dev) for k, dt, sh in self.QUERY_FIELDS}
+            rc, stats = self.query_points_into(n, pts.data_ptr(), {k: t.data_ptr() for k, t in out.items()}, min_weight, on_device=True)
+        else:
+            pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+            n = len(pts)
+            out = {k: np.zeros((n,) + sh, dt) for k, dt, sh in self.QUERY_FIELDS}
+            rc, stats = self.query_points_into(n, pts, out, min_weight)
         self._chk(rc)
         out["stats"] = stats
         return out

@@ -7,6 +7,7 @@
 // resolved in registers: the hash table is probed on a block change only.  No LDS.
 #pragma once
 #include "khr_device.h"
+#include "khr_map_read.h"
 
 namespace khr {
 
@@ -19,7 +20,7 @@ constexpr bool kRenderSkip = true;
 #endif
 
 enum RenderStat : int { RS_HIT = 0, RS_BLOCKED, RS_VISITED, RS_COUNT = 4 };
-constexpr float kRenderIndexLimit = 1073741824.f;  // |p * voxel_size_inv - 0.5| at or beyond 2^30 (or NaN): no voxel there
+constexpr float kRenderIndexLimit = kMapIndexLimit;
 
 struct RenderView {
   int W, H, K;  // K samples per ray
@@ -41,9 +42,7 @@ struct RenderBlockCache {
 
 // pool slot of block (bx, by, bz), kInvalidSlot when it is not allocated (or lies beyond the 21-bit index range of the keys)
 __device__ inline uint32_t renderSlot(const DevMap& m, RenderBlockCache& c, int bx, int by, int bz) {
-  constexpr uint32_t R = 1u << 20;
-  if (static_cast<uint32_t>(bx) + R >= 2u * R || static_cast<uint32_t>(by) + R >= 2u * R || static_cast<uint32_t>(bz) + R >= 2u * R)
-    return kInvalidSlot;
+  if (!blockInKeyRange(bx, by, bz)) return kInvalidSlot;
   const uint64_t key = packKey(bx, by, bz);
   if (key == c.k0) return c.s0;
   const uint32_t s = key == c.k1 ? c.s1 : htLookup(m, key);
@@ -111,11 +110,7 @@ __device__ inline bool renderSample(const DevMap& m, const DevParams& p, RenderB
 #pragma unroll
   for (int t = 0; t < 8; ++t) seen = seen && (w[t] >= min_weight);
   if (!seen) return false;
-  // x first, then y, then z
-  const float c00 = v[0] + f[0] * (v[1] - v[0]), c10 = v[2] + f[0] * (v[3] - v[2]);
-  const float c01 = v[4] + f[0] * (v[5] - v[4]), c11 = v[6] + f[0] * (v[7] - v[6]);
-  const float c0 = c00 + f[1] * (c10 - c00), c1 = c01 + f[1] * (c11 - c01);
-  *d = c0 + f[2] * (c1 - c0);
+  *d = trilinear(v, f);
   return true;
 }
 
@@ -148,12 +143,8 @@ __device__ inline int renderSkipTo(const DevParams& p, const RenderView& r, floa
   return static_cast<int>(fmin(q, static_cast<double>(r.K - 1))) + 1;
 }
 
-__device__ inline void renderStatAdd(unsigned long long* counter, uint32_t lane_value) {
-  uint32_t sum = lane_value;  // (a wave's total stays far below 2^32: 64 lanes x 65536 samples)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
-  if (laneId() == 0 && sum) atomicAdd(counter, static_cast<unsigned long long>(sum));
-}
+// (a wave's total stays far below 2^32: 64 lanes x 65536 samples)
+__device__ inline void renderStatAdd(unsigned long long* counter, uint32_t lane_value) { waveStatAdd(counter, lane_value); }
 
 template <int VPS>
 __global__ __launch_bounds__(256) void k_render_view(DevMap m, DevParams p, RenderView r) {

@@ -35,6 +35,7 @@
 #include "khr_kernels_objects.h"
 #include "khr_kernels_slice.h"
 #include "khr_kernels_render.h"
+#include "khr_kernels_query.h"
 #include "khr_kernels_checkpoint.h"
 
 using namespace khr;
@@ -376,6 +377,11 @@ struct khr_ctx {
   uint8_t* d_render_stage = nullptr;
   uint8_t* h_render_stage = nullptr;  // page-locked mirror of d_render_stage
   size_t render_stage_bytes = 0;
+  // point queries (khr_query_points): the same pair for its counters and the point / output staging of the host form
+  unsigned long long* d_query_stats = nullptr;
+  uint8_t* d_query_stage = nullptr;
+  uint8_t* h_query_stage = nullptr;  // page-locked mirror of d_query_stage
+  size_t query_stage_bytes = 0;
   // map checkpoints (khr_checkpoint_save / _load): two chunk staging areas of kCkptStageBytes each (created at the first call; their
   // page-locked mirrors only when a caller passes pageable memory), the chunk's slot list, the load's error word, and per
   // staging area one event for "filled" and one for "drained"
@@ -1139,6 +1145,9 @@ void khr_destroy(khr_ctx* c) {
   if (c->d_render_stats) hipFree(c->d_render_stats);
   if (c->d_render_stage) hipFree(c->d_render_stage);
   if (c->h_render_stage) hipHostFree(c->h_render_stage);
+  if (c->d_query_stats) hipFree(c->d_query_stats);
+  if (c->d_query_stage) hipFree(c->d_query_stage);
+  if (c->h_query_stage) hipHostFree(c->h_query_stage);
   for (int i = 0; i < 2; ++i) {
     if (c->d_ckpt[i]) hipFree(c->d_ckpt[i]);
     if (c->h_ckpt[i]) hipHostFree(c->h_ckpt[i]);
@@ -4913,6 +4922,97 @@ int khr_render_view(khr_ctx* c, const khr_render_request* rq, int on_device, flo
     stats->n_blocked = h_stats[RS_BLOCKED];
     stats->n_samples_total = static_cast<uint64_t>(r.K) * n_px;
     stats->n_samples_evaluated = h_stats[RS_VISITED];
+  }
+  return KHR_OK;
+}
+
+// ---- the live map at world points (khr_query_points; ASSUMPTIONS.md A.13, device side: khr_kernels_query.h) --------------------
+int khr_query_points(khr_ctx* c, int64_t n, const float* points, float min_weight, int on_device, float* distance, float* gradient,
+                     float* weight, uint8_t* color_rgba, uint32_t* label, uint8_t* vflags, uint64_t* last_observed, uint8_t* status,
+                     khr_query_stats* stats) {
+  if (!c) return fail(KHR_EINVAL, "null argument");
+  if (n < 0) return fail(KHR_EINVAL, "negative point count %lld", static_cast<long long>(n));
+  if (n > 0 && !points) return fail(KHR_EINVAL, "null points");
+  if (!(min_weight >= 0.f) || !std::isfinite(min_weight)) return fail(KHR_EINVAL, "bad min_weight %g", static_cast<double>(min_weight));
+  if (c->cfg.world_size > 1) return fail(KHR_ESTATE, "khr_query_points needs the whole map: world_size is %d", c->cfg.world_size);
+  if (n == 0) {
+    if (stats) *stats = khr_query_stats{0, 0, 0};
+    return KHR_OK;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t np = static_cast<size_t>(n);
+  // the host form: the points, then the outputs, one after the other in the device staging and its page-locked mirror
+  void* const host[8] = {distance, gradient, weight, color_rgba, label, vflags, last_observed, status};
+  const size_t per_pt[8] = {4, 12, 4, 4, 4, 1, 8, 1};
+  size_t off[8], stage_bytes = (np * 12 + 255) / 256 * 256;
+  const size_t out_begin = stage_bytes;
+  for (int f = 0; f < 8; ++f) {
+    off[f] = stage_bytes;
+    if (host[f]) stage_bytes += (np * per_pt[f] + 255) / 256 * 256;
+  }
+  void* dev[8] = {distance, gradient, weight, color_rgba, label, vflags, last_observed, status};
+  const float* d_points = points;
+  if (!on_device) {
+    if (stage_bytes > c->query_stage_bytes) {
+      if (c->d_query_stage) HIP_TRY(hipFree(c->d_query_stage));
+      if (c->h_query_stage) HIP_TRY(hipHostFree(c->h_query_stage));
+      c->d_query_stage = c->h_query_stage = nullptr;
+      c->query_stage_bytes = 0;
+      if (hipMalloc(reinterpret_cast<void**>(&c->d_query_stage), stage_bytes) != hipSuccess)
+        return fail(KHR_ENOMEM, "query staging of %zu bytes", stage_bytes);
+      if (hipHostMalloc(reinterpret_cast<void**>(&c->h_query_stage), stage_bytes, hipHostMallocDefault) != hipSuccess) {
+        hipFree(c->d_query_stage);
+        c->d_query_stage = nullptr;
+        return fail(KHR_ENOMEM, "page-locked query staging of %zu bytes", stage_bytes);
+      }
+      c->query_stage_bytes = stage_bytes;
+    }
+    std::memcpy(c->h_query_stage, points, np * 12);
+    HIP_TRY(hipMemcpyAsync(c->d_query_stage, c->h_query_stage, np * 12, hipMemcpyHostToDevice, c->stream));
+    d_points = reinterpret_cast<const float*>(c->d_query_stage);
+    for (int f = 0; f < 8; ++f) dev[f] = host[f] ? c->d_query_stage + off[f] : nullptr;
+  }
+  if (stats) {
+    if (!c->d_query_stats && hipMalloc(reinterpret_cast<void**>(&c->d_query_stats), sizeof(unsigned long long) * QS_COUNT) != hipSuccess)
+      return fail(KHR_ENOMEM, "query counters");
+    HIP_TRY(hipMemsetAsync(c->d_query_stats, 0, sizeof(unsigned long long) * QS_COUNT, c->stream));
+  }
+  constexpr size_t kChunk = size_t(1) << 30;  // points per launch (the grid's x extent)
+  for (size_t first = 0; first < np; first += kChunk) {
+    QueryPoints q{};
+    q.n = static_cast<long long>(np - first < kChunk ? np - first : kChunk);
+    q.points = d_points + 3 * first;
+    q.min_weight = min_weight == 0.f ? c->cfg.mesh_min_weight : min_weight;
+    q.distance = dev[0] ? static_cast<float*>(dev[0]) + first : nullptr;
+    q.gradient = dev[1] ? static_cast<float*>(dev[1]) + 3 * first : nullptr;
+    q.weight = dev[2] ? static_cast<float*>(dev[2]) + first : nullptr;
+    q.color = dev[3] ? static_cast<uint32_t*>(dev[3]) + first : nullptr;
+    q.label = dev[4] ? static_cast<uint32_t*>(dev[4]) + first : nullptr;
+    q.vflags = dev[5] ? static_cast<uint8_t*>(dev[5]) + first : nullptr;
+    q.last_observed = dev[6] ? static_cast<uint64_t*>(dev[6]) + first : nullptr;
+    q.status = dev[7] ? static_cast<uint8_t*>(dev[7]) + first : nullptr;
+    q.stats = stats ? c->d_query_stats : nullptr;
+    const dim3 grid(static_cast<unsigned>((q.n + 255) / 256));
+    int rc = dispatchVps(c, [&](auto vps) {
+      hipLaunchKernelGGL((k_query_points<decltype(vps)::value>), grid, dim3(256), 0, c->stream, c->m, c->p, q);
+      HIP_TRY(hipGetLastError());
+      return KHR_OK;
+    });
+    if (rc) return rc;
+  }
+  unsigned long long h_stats[QS_COUNT] = {0, 0, 0, 0};
+  if (stats) HIP_TRY(hipMemcpyAsync(h_stats, c->d_query_stats, sizeof(h_stats), hipMemcpyDeviceToHost, c->stream));
+  const bool copy_back = !on_device && stage_bytes > out_begin;
+  if (copy_back)
+    HIP_TRY(hipMemcpyAsync(c->h_query_stage + out_begin, c->d_query_stage + out_begin, stage_bytes - out_begin, hipMemcpyDeviceToHost, c->stream));
+  if (stats || !on_device) HIP_TRY(hipStreamSynchronize(c->stream));  // (host form: the point staging is free again on return)
+  if (copy_back)
+    for (int f = 0; f < 8; ++f)
+      if (host[f]) std::memcpy(host[f], c->h_query_stage + off[f], np * per_pt[f]);
+  if (stats) {
+    stats->n_value = h_stats[QS_VALUE];
+    stats->n_gradient = h_stats[QS_GRADIENT];
+    stats->n_voxel = h_stats[QS_VOXEL];
   }
   return KHR_OK;
 }

@@ -2,7 +2,7 @@
 // thread drives the reference (spinOnce per InputPacket, finishMapping at shutdown), and prints a JSON
 // summary that tests/test_gpu_host.py compares with the step-wise C-ABI path and the oracle.
 // usage: aw_demo <config.yaml> <width> <height> <frames> [object_label]
-//        aw_demo --slices | --render | --checkpoint | --bench | --rayver ... (below)
+//        aw_demo --slices | --render | --query | --checkpoint | --bench | --rayver ... (below)
 //   object_label >= 0: the stand-in detector / tracker below; otherwise the plugins named in the config
 #include <execinfo.h>
 #include <csignal>
@@ -14,6 +14,7 @@
 #include <fstream>
 #include <iostream>
 #include <sstream>
+#include <unordered_map>
 
 #include <chrono>
 
@@ -381,6 +382,248 @@ static int slicesDemo(int argc, char** argv) {
   return agree == frames ? 0 : 3;
 }
 
+// ASSUMPTIONS.md A.13 restated on the host over a cloneBlock loop (the only way a sink could ask "what does the map say at this
+// point" before khr_query_points): every block a tap falls into is copied whole, once per call, then each point's seven samples
+// are interpolated tap by tap.
+struct QueryByBlockCopies {
+  const VolumetricMap& map;
+  int vps, sh;
+  float vs_inv, min_weight;
+  bool with_semantics, with_tracking;
+  std::unordered_map<uint64_t, std::unique_ptr<hydra::BlockCopy>> blocks;  // allocated blocks; copied when first touched
+  uint64_t last_key = ~0ull;
+  const hydra::BlockCopy* last = nullptr;
+
+  static uint64_t key(int64_t bx, int64_t by, int64_t bz) {
+    return static_cast<uint64_t>(bx + (1 << 20)) | (static_cast<uint64_t>(by + (1 << 20)) << 21) | (static_cast<uint64_t>(bz + (1 << 20)) << 42);
+  }
+  explicit QueryByBlockCopies(const VolumetricMap& m) : map(m) {
+    khr_config kc;
+    if (khr_get_config(map.ctx(), &kc) != KHR_OK) throw std::runtime_error(khr_last_error());
+    vps = kc.voxels_per_side;
+    sh = vps == 16 ? 4 : 3;
+    vs_inv = 1.f / kc.voxel_size;
+    min_weight = kc.mesh_min_weight;
+    with_semantics = kc.with_semantics != 0;
+    with_tracking = kc.with_tracking != 0;
+    for (const auto& idx : map.allocatedBlockIndices()) blocks.emplace(key(idx[0], idx[1], idx[2]), nullptr);
+  }
+  // the block of global voxel (x, y, z), null when it is not allocated; *lin = the voxel's place in it
+  const hydra::BlockCopy* voxel(int64_t x, int64_t y, int64_t z, size_t* lin) {
+    const int64_t bx = x >> sh, by = y >> sh, bz = z >> sh, R = 1 << 20;
+    if (bx < -R || bx >= R || by < -R || by >= R || bz < -R || bz >= R) return nullptr;
+    *lin = static_cast<size_t>((x & (vps - 1)) + vps * ((y & (vps - 1)) + vps * (z & (vps - 1))));
+    const uint64_t k = key(bx, by, bz);
+    if (k == last_key) return last;
+    auto it = blocks.find(k);
+    const hydra::BlockCopy* b = nullptr;
+    if (it != blocks.end()) {
+      if (!it->second)
+        it->second = std::make_unique<hydra::BlockCopy>(map.cloneBlock({static_cast<int32_t>(bx), static_cast<int32_t>(by), static_cast<int32_t>(bz)}));
+      b = it->second.get();
+    }
+    last_key = k;
+    last = b;
+    return b;
+  }
+  bool sample(const int64_t* j, const float* f, float* d) {
+    float v[8];
+    bool valid = true;
+    for (int t = 0; t < 8; ++t) {
+      size_t lin = 0;
+      const hydra::BlockCopy* b = voxel(j[0] + (t & 1), j[1] + ((t >> 1) & 1), j[2] + (t >> 2), &lin);
+      valid = valid && b && b->weight[lin] >= min_weight;
+      v[t] = b ? b->distance[lin] : 0.f;
+    }
+    const float c00 = v[0] + f[0] * (v[1] - v[0]), c10 = v[2] + f[0] * (v[3] - v[2]);
+    const float c01 = v[4] + f[0] * (v[5] - v[4]), c11 = v[6] + f[0] * (v[7] - v[6]);
+    const float c0 = c00 + f[1] * (c10 - c00), c1 = c01 + f[1] * (c11 - c01);
+    *d = c0 + f[2] * (c1 - c0);
+    return valid;
+  }
+  hydra::PointSamples run(const std::vector<float>& points) {
+    const size_t n = points.size() / 3;
+    hydra::PointSamples s;
+    s.distance.assign(n, 0.f); s.gradient.assign(3 * n, 0.f); s.weight.assign(n, 0.f); s.color.assign(4 * n, 0); s.label.assign(n, 0u);
+    s.flags.assign(n, 0); s.last_observed.assign(n, 0ull); s.status.assign(n, 0);
+    constexpr float kLimit = 1073741824.f;
+    for (size_t i = 0; i < n; ++i) {
+      const float* p = &points[3 * i];
+      float g[3], f[3];
+      int64_t i0[3];
+      bool in_range = true;
+      for (int a = 0; a < 3; ++a) {
+        g[a] = p[a] * vs_inv - 0.5f;
+        in_range = in_range && std::fabs(g[a]) < kLimit;
+      }
+      if (!in_range) continue;
+      for (int a = 0; a < 3; ++a) {
+        const float fl = std::floor(g[a]);
+        i0[a] = static_cast<int64_t>(fl);
+        f[a] = g[a] - fl;
+      }
+      uint8_t status = 0;
+      float d = 0.f;
+      if (sample(i0, f, &d)) {
+        status |= KHR_QP_VALUE;
+        s.distance[i] = d;
+      }
+      float grad[3];
+      bool all = true;
+      for (int a = 0; a < 3; ++a) {
+        int64_t jp[3] = {i0[0], i0[1], i0[2]}, jm[3] = {i0[0], i0[1], i0[2]};
+        jp[a] += 1;
+        jm[a] -= 1;
+        float dp = 0.f, dm = 0.f;
+        all = sample(jp, f, &dp) && all;
+        all = sample(jm, f, &dm) && all;
+        grad[a] = (dp - dm) * (0.5f * vs_inv);
+      }
+      if (all) {
+        status |= KHR_QP_GRADIENT;
+        for (int a = 0; a < 3; ++a) s.gradient[3 * i + a] = grad[a];
+      }
+      float gi[3];
+      bool ok = true;
+      for (int a = 0; a < 3; ++a) {
+        gi[a] = std::floor(p[a] * vs_inv);
+        ok = ok && std::fabs(gi[a]) < kLimit;
+      }
+      size_t lin = 0;
+      const hydra::BlockCopy* b = ok ? voxel(static_cast<int64_t>(gi[0]), static_cast<int64_t>(gi[1]), static_cast<int64_t>(gi[2]), &lin) : nullptr;
+      if (b) {
+        status |= KHR_QP_VOXEL;
+        s.weight[i] = b->weight[lin];
+        std::memcpy(&s.color[4 * i], &b->color[4 * lin], 4);
+        if (with_semantics) s.label[i] = b->semantic_label[lin];
+        s.flags[i] = b->flags[lin];
+        if (with_tracking) s.last_observed[i] = b->last_observed[lin];
+      }
+      s.status[i] = status;
+      s.stats.n_value += (status & KHR_QP_VALUE) != 0;
+      s.stats.n_gradient += (status & KHR_QP_GRADIENT) != 0;
+      s.stats.n_voxel += (status & KHR_QP_VOXEL) != 0;
+    }
+    return s;
+  }
+};
+
+static const char* queryDifference(const hydra::PointSamples& a, const hydra::PointSamples& b) {
+  if (!(a.status == b.status)) return "status";
+  if (!sameBits(a.distance, b.distance)) return "distance";
+  if (!sameBits(a.gradient, b.gradient)) return "gradient";
+  if (!sameBits(a.weight, b.weight)) return "weight";
+  if (!(a.color == b.color)) return "color";
+  if (!(a.label == b.label)) return "label";
+  if (!(a.flags == b.flags)) return "flags";
+  if (!(a.last_observed == b.last_observed)) return "last_observed";
+  if (a.stats.n_value != b.stats.n_value || a.stats.n_gradient != b.stats.n_gradient || a.stats.n_voxel != b.stats.n_voxel) return "stats";
+  return nullptr;
+}
+
+// aw_demo --query <config.yaml> <width> <height> <frames> [points]: a Khronos sink asks the map about the frame's own back-projected
+// depth pixels (at most `points` of them; 0 = all), in image order and shuffled with a fixed seed, every frame twice: through
+// VolumetricMap::query (khr_query_points) and through the cloneBlock loop above, checks the two bit for bit and times both (the
+// device is drained before each).  One JSON line: per-frame means after kWarm frames.
+static int queryDemo(int argc, char** argv) {
+  if (argc < 6) {
+    std::fprintf(stderr, "usage: aw_demo --query <config.yaml> <width> <height> <frames> [points]\n");
+    return 2;
+  }
+  std::ifstream in(argv[2]);
+  std::stringstream ss;
+  ss << in.rdbuf();
+  const int W = std::atoi(argv[3]), H = std::atoi(argv[4]), N = std::atoi(argv[5]);
+  const size_t max_points = argc > 6 ? static_cast<size_t>(std::atoll(argv[6])) : 0;
+  constexpr int kWarm = 3;  // frames before the averages (the query staging grows on the first calls)
+  ActiveWindow::Config cfg = ActiveWindow::Config::fromYamlString(ss.str());
+  cfg.max_frame_pixels = static_cast<uint32_t>(W) * H;
+  auto out_queue = std::make_shared<ActiveWindow::OutputQueue>();
+  ActiveWindow aw(cfg, out_queue);
+  int frames = 0, agree = 0, timed = 0;
+  double ms[4] = {0, 0, 0, 0}, n_points = 0;  // device ordered, copies ordered, device shuffled, copies shuffled
+  khr_query_stats last_stats{};
+  std::string first_mismatch;
+  using clk = std::chrono::steady_clock;
+  aw.addKhronosSink([&](const FrameData& data, const VolumetricMap& map, const Tracks&) {
+    const std::vector<float> vm = data.input.vertexMap(), range = data.input.rangeImage();
+    if (range.empty() || vm.size() != 3 * range.size()) throw std::runtime_error("aw_demo --query: the frame's range image / vertex map are not available");
+    std::vector<float> ordered;
+    for (size_t i = 0; i < range.size() && (max_points == 0 || ordered.size() < 3 * max_points); ++i)
+      if (range[i] > 0.f) ordered.insert(ordered.end(), {vm[3 * i], vm[3 * i + 1], vm[3 * i + 2]});
+    const size_t np = ordered.size() / 3;
+    std::vector<float> shuffled = ordered;
+    uint64_t rng = 0x9E3779B97F4A7C15ull;  // splitmix64, Fisher-Yates
+    for (size_t i = np; i > 1; --i) {
+      uint64_t x = (rng += 0x9E3779B97F4A7C15ull);
+      x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+      x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+      const size_t j = static_cast<size_t>((x ^ (x >> 31)) % i);
+      for (int a = 0; a < 3; ++a) std::swap(shuffled[3 * (i - 1) + a], shuffled[3 * j + a]);
+    }
+    bool ok = true;
+    double t_ms[4];
+    for (int pass = 0; pass < 2; ++pass) {
+      const std::vector<float>& pts = pass ? shuffled : ordered;
+      khr_sync(map.ctx());
+      const auto t0 = clk::now();
+      const hydra::PointSamples a = map.query(pts);
+      const auto t1 = clk::now();
+      QueryByBlockCopies host(map);
+      const hydra::PointSamples b = host.run(pts);
+      const auto t2 = clk::now();
+      t_ms[2 * pass] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+      t_ms[2 * pass + 1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
+      const char* diff = queryDifference(a, b);
+      if (diff) {
+        ok = false;
+        if (first_mismatch.empty())
+          first_mismatch = "frame " + std::to_string(frames) + (pass ? " shuffled: " : " ordered: ") + diff + " differs";
+      }
+      if (!pass) last_stats = a.stats;
+    }
+    if (ok) ++agree;
+    if (frames >= kWarm) {
+      for (int k = 0; k < 4; ++k) ms[k] += t_ms[k];
+      n_points += static_cast<double>(np);
+      ++timed;
+    }
+    ++frames;
+  });
+  void* scene = synth_create(1234, 12, 1);
+  const size_t n = static_cast<size_t>(W) * H;
+  std::vector<float> depth(n);
+  std::vector<uint8_t> rgb(n * 3);
+  std::vector<int32_t> label(n);
+  for (int i = 0; i < N; ++i) {
+    hydra::InputPacket pkt;
+    pkt.timestamp_ns = static_cast<uint64_t>(std::llround((1.0 + 0.1 * i) * 1e9));
+    circlePose(0.1 * i, pkt.world_T_body);
+    pkt.sensor = {W, H, W / 2.f, W / 2.f, W / 2.f, H / 2.f, 0.1f, 5.f};
+    synth_render(scene, W, H, pkt.sensor.fx, pkt.sensor.fy, pkt.sensor.cx, pkt.sensor.cy, pkt.world_T_body, 0.1 * i, 5.f, 0.f,
+                 1234u + 7919u * i, depth.data(), rgb.data(), label.data(), 0);
+    pkt.depth = depth.data();
+    pkt.color = rgb.data();
+    pkt.labels = label.data();
+    aw.step(pkt);
+    hydra::ActiveWindowOutput::Ptr popped;
+    while (out_queue->pop(&popped)) {}
+  }
+  aw.finishMapping();
+  synth_destroy(scene);
+  const double d = timed ? static_cast<double>(timed) : 1.0, pts = n_points / d;
+  auto rate = [&](double total_ms) { return total_ms > 0 ? pts / (total_ms / d * 1e-3) : 0.0; };
+  std::printf("{\"what\": \"the live map at the frame's back-projected depth pixels (VolumetricMap::query vs a cloneBlock loop), %dx%d, voxel %.4g m\", "
+              "\"frames\": %d, \"agree_frames\": %d, \"first_mismatch\": \"%s\", \"timed_frames\": %d, \"points_mean\": %.1f, "
+              "\"device_query_ms\": %.4f, \"block_copy_ms\": %.4f, \"device_points_per_s\": %.4g, \"block_copy_points_per_s\": %.4g, "
+              "\"device_query_shuffled_ms\": %.4f, \"block_copy_shuffled_ms\": %.4f, \"device_shuffled_points_per_s\": %.4g, "
+              "\"block_copy_shuffled_points_per_s\": %.4g, \"last_stats\": {\"n_value\": %llu, \"n_gradient\": %llu, \"n_voxel\": %llu}}\n",
+              W, H, static_cast<double>(cfg.volumetric_map.voxel_size), frames, agree, first_mismatch.c_str(), timed, pts, ms[0] / d, ms[1] / d,
+              rate(ms[0]), rate(ms[1]), ms[2] / d, ms[3] / d, rate(ms[2]), rate(ms[3]), static_cast<unsigned long long>(last_stats.n_value),
+              static_cast<unsigned long long>(last_stats.n_gradient), static_cast<unsigned long long>(last_stats.n_voxel));
+  return agree == frames && frames == N ? 0 : 3;
+}
+
 // 64-bit digest of an image's bytes: sum_i mix(i * L + byte_i) mod 2^64, mix = the splitmix64 step of khr_map_digest
 // (tests/test_gpu_render_view.py restates it in numpy)
 static uint64_t imageDigest(const void* data, size_t bytes) {
@@ -557,6 +800,14 @@ int main(int argc, char** argv) {
   if (argc >= 2 && std::string(argv[1]) == "--slices") {
     try {
       return slicesDemo(argc, argv);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "aw_demo: %s\n", e.what());
+      return 1;
+    }
+  }
+  if (argc >= 2 && std::string(argv[1]) == "--query") {
+    try {
+      return queryDemo(argc, argv);
     } catch (const std::exception& e) {
       std::fprintf(stderr, "aw_demo: %s\n", e.what());
       return 1;

@@ -254,6 +254,25 @@ struct RenderedView {
   size_t numPixels() const { return status.size(); }
 };
 
+// The live map at world points (VolumetricMap::query, khr_query_points; ASSUMPTIONS.md A.13): one entry per point.  Every value
+// of a point whose status bit is clear is zero.
+struct PointSamples {
+  enum Status : uint8_t { kValue = KHR_QP_VALUE, kGradient = KHR_QP_GRADIENT, kVoxel = KHR_QP_VOXEL };
+  std::vector<float> distance;          // trilinear signed distance, metres (kValue)
+  std::vector<float> gradient;          // 3 per point: d(distance) / d(metres), not normalised (kGradient)
+  std::vector<float> weight;            // of the voxel the point lies in, not interpolated (kVoxel, as the four below)
+  std::vector<uint8_t> color;           // rgba per point
+  std::vector<uint32_t> label;          // 0 without semantics
+  std::vector<uint8_t> flags;           // KHR_VOX_* bits
+  std::vector<uint64_t> last_observed;  // 0 without tracking
+  std::vector<uint8_t> status;
+  khr_query_stats stats{};
+  size_t size() const { return status.size(); }
+  bool hasValue(size_t i) const { return (status[i] & kValue) != 0; }
+  bool hasGradient(size_t i) const { return (status[i] & kGradient) != 0; }
+  bool hasVoxel(size_t i) const { return (status[i] & kVoxel) != 0; }
+};
+
 // hydra::VolumetricMap role: here a handle on the HBM-resident map of a fusion context.
 class VolumetricMap {
  public:
@@ -336,6 +355,20 @@ class VolumetricMap {
   RenderedView render(const InputData& frame, float step_voxels = 0.f, float min_weight = 0.f) const {
     return render(frame.sensor, frame.world_T_sensor, step_voxels, min_weight);
   }
+  // What the map says at world points (khr_query_points): `points` holds x, y, z per point.  min_weight 0 = the mesh's minimum
+  // weight.  One call, one host wait, no block copies; cloneBlock is for whole blocks.
+  PointSamples query(const std::vector<float>& points, float min_weight = 0.f) const {
+    if (points.size() % 3 != 0) throw std::runtime_error("VolumetricMap::query: points must hold 3 floats per point");
+    const size_t n = points.size() / 3;
+    PointSamples s;
+    s.distance.resize(n); s.gradient.resize(3 * n); s.weight.resize(n); s.color.resize(4 * n); s.label.resize(n); s.flags.resize(n);
+    s.last_observed.resize(n); s.status.resize(n);
+    if (khr_query_points(ctx_, static_cast<int64_t>(n), points.data(), min_weight, 0, s.distance.data(), s.gradient.data(), s.weight.data(),
+                         s.color.data(), s.label.data(), s.flags.data(), s.last_observed.data(), s.status.data(), &s.stats) != KHR_OK)
+      throw std::runtime_error(std::string("khr_query_points: ") + khr_last_error());
+    return s;
+  }
+  PointSamples query(float x, float y, float z, float min_weight = 0.f) const { return query(std::vector<float>{x, y, z}, min_weight); }
   // The map save / load role of hydra::VolumetricMap (un-vendored upstream; the reference's own tree has no counterpart): the live
   // map as one checkpoint file (khr_checkpoint_save: the format is in include/khronos_amd.h) and back into an EMPTY map of the
   // same configuration (khr_checkpoint_load; sharded contexts keep their own blocks).  File I/O around the two calls through a
