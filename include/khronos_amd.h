@@ -552,6 +552,68 @@ typedef struct khr_query_stats {
 int khr_query_points(khr_ctx* ctx, int64_t n, const float* points, float min_weight, int on_device, float* distance, float* gradient,
                      float* weight, uint8_t* color_rgba, uint32_t* label, uint8_t* vflags, uint64_t* last_observed, uint8_t* status,
                      khr_query_stats* stats);
+/* The live map as a registration target (ASSUMPTIONS.md A.14): point-to-TSDF alignment of a point list or a depth image.  No
+ * reference counterpart.  A source point p (source frame) goes to p_W = R p + t with world_T_source rounded to float as frame
+ * ingest rounds it; the residual is khr_query_points' distance d at p_W, the Jacobian of a twist (omega, v) in world axes about
+ * the sensor origin is J = ((p_W - t) x g, g) with g khr_query_points' gradient.
+ * Source, exactly one of
+ *   points != NULL (or n == 0): n points, 3 floats each; `weights` has n entries;
+ *   depth  != NULL: a sensor.width x sensor.height depth image (metres); the pixels (u, v) with u % stride == 0 and v % stride == 0
+ *     are back-projected as khr_upload_frame does; a pixel counts when its depth is positive, finite and within
+ *     [sensor.min_range, sensor.max_range]; `weights` has width * height entries and is indexed by pixel.
+ * weights == NULL means 1.  A point is an inlier iff it has KHR_QP_GRADIENT, |d| <= gate (0 = the truncation distance; the
+ * effective gate may not exceed 64 m), g.g <= 16, every |(p_W - t)_a| < 64 m and 0 < weight <= 1.  huber_delta > 0 scales an inlier
+ * with |d| > huber_delta by huber_delta / |d|; 0 = no robust factor.
+ * khr_align_linearize: one evaluation.  words[KHR_ALIGN_WORDS] (always host memory), sums over the inliers modulo 2^64 of
+ * llrint(2^24 * weight * rho * x) as two's-complement integers:
+ *   [0, 21)  H[a][b], a <= b, row by row: x = J_a J_b          [21, 27)  b[a]: x = J_a d          [27]  e: x = d^2
+ *   [28] inliers   [29] points with KHR_QP_GRADIENT   [30] valid source points   [31] sum_w: x = 1, the sum of weight * rho
+ * Integer sums: the words depend neither on the order of the points nor on the launch shape.  on_device != 0: the source and the
+ * weights are device memory read in stream order; on_device == 0: host memory, copied through staging created at the first such
+ * call and grown to the largest source.  One host wait per call.  The map is only read.
+ * KHR_EINVAL (nothing written): NULL request or words, both or neither of points / depth with n > 0, n < 0, more than 2^20
+ * sources (points, or pixels of the strided grid), stride < 1, bad sensor, non-finite pose, negative or non-finite min_weight /
+ * gate / huber_delta, an effective gate above 64 m; KHR_ESTATE: world_size > 1.  n == 0: KHR_OK, zero words. */
+#define KHR_ALIGN_WORDS 32
+#define KHR_ALIGN_MAX_SOURCES (1 << 20)
+typedef struct khr_align_request {
+  int64_t n;                /* point form: number of points */
+  const float* points;      /* point form: 3 floats per point, source frame */
+  const float* depth;       /* depth form: width * height f32 metres */
+  khr_sensor sensor;        /* depth form */
+  int32_t stride;           /* depth form: >= 1 */
+  const float* weights;     /* per point / per pixel, NULL = 1 */
+  double world_T_source[16]; /* row-major 4x4, as khr_frame */
+  float min_weight;         /* a voxel counts as observed iff weight >= this; 0 = khr_config.mesh_min_weight */
+  float gate;               /* largest |d| of an inlier, metres; 0 = khr_config.truncation_distance */
+  float huber_delta;        /* metres; 0 = off */
+} khr_align_request;
+int khr_align_linearize(khr_ctx* ctx, const khr_align_request* request, int on_device, uint64_t* words);
+/* Gauss-Newton on the host over khr_align_linearize, at most max_iterations times: one linearisation (one wait) at the current
+ * pose; H, b, e = words * 2^-24 as doubles; (H + lambda diag(H)) xi = -b solved by a 6x6 Cholesky factorisation in double;
+ * R <- exp(omega^) R, t <- t + v applied to the double pose; stop once |omega| < eps_rot and |v| < eps_trans.
+ * options == NULL: max_iterations 10, min_inliers 64, lambda 1e-4, eps_rot 1e-5 rad, eps_trans 1e-5 m; max_iterations <= 0 means
+ * 10, min_inliers < 6 means 6.  result (may be NULL): iterations = updates applied; converged; n_inlier / rmse of the first and of
+ * the last linearisation -- the last linearisation is the one the last update was computed from, the returned pose itself is not
+ * evaluated again; rmse = sqrt(e / sum_w), words 27 and 31 as doubles: the denominator is the sum of weight * rho over the inliers
+ * (the inlier count only with unit weights and no Huber factor), so scaling every weight leaves rmse where it is; 0 when sum_w is 0; H (21, upper triangle row by row) and b (6) of the last linearisation, undamped.
+ * KHR_ENOTFOUND: a linearisation had fewer than min_inliers inliers, or the factorisation met a non-positive pivot: "keep the
+ * prior" -- world_T_source_out is the request's pose and result holds what was reached.  Errors of khr_align_linearize pass
+ * through with nothing written. */
+typedef struct khr_align_options {
+  int32_t max_iterations;
+  int32_t min_inliers;
+  double lambda;
+  double eps_rot, eps_trans;
+} khr_align_options;
+typedef struct khr_align_result {
+  int32_t iterations, converged;
+  uint64_t n_inlier_first, n_inlier_last;
+  double rmse_first, rmse_last;
+  double H[21], b[6];
+} khr_align_result;
+int khr_align_frame(khr_ctx* ctx, const khr_align_request* request, int on_device, const khr_align_options* options,
+                    double* world_T_source_out, khr_align_result* result);
 /* Order-independent 64-bit digests of the WHOLE map (every live block, every voxel), one word per layer, on the values
  * khr_download_block hands out:  digest[layer] = sum_b sum_i mix(mix(key(b) * G + layer * L + i) ^ value_bits) mod 2^64
  * (mix = splitmix64 finaliser, key = 3 x 21-bit packed block index; csrc/khr_kernels_aux.h: digestTerm).  Sums commute, so

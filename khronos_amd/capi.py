@@ -57,6 +57,25 @@ class KhrQueryStats(C.Structure):
 KHR_QP_VALUE, KHR_QP_GRADIENT, KHR_QP_VOXEL = 1, 2, 4
 
 
+class KhrAlignRequest(C.Structure):
+    _fields_ = [("n", C.c_int64), ("points", C.c_void_p), ("depth", C.c_void_p), ("sensor", KhrSensor), ("stride", C.c_int32),
+                ("weights", C.c_void_p), ("world_T_source", C.c_double * 16), ("min_weight", C.c_float), ("gate", C.c_float),
+                ("huber_delta", C.c_float)]
+
+
+class KhrAlignOptions(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("min_inliers", C.c_int32), ("lambda_", C.c_double), ("eps_rot", C.c_double),
+                ("eps_trans", C.c_double)]
+
+
+class KhrAlignResult(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("n_inlier_first", C.c_uint64), ("n_inlier_last", C.c_uint64),
+                ("rmse_first", C.c_double), ("rmse_last", C.c_double), ("H", C.c_double * 21), ("b", C.c_double * 6)]
+
+
+KHR_ALIGN_WORDS, KHR_ALIGN_MAX_SOURCES = 32, 1 << 20
+
+
 class KhrFrame(C.Structure):
     _fields_ = [("timestamp_ns", C.c_uint64), ("world_T_sensor", C.c_double * 16), ("depth", C.c_void_p),
                 ("color", C.c_void_p), ("label", C.c_void_p)]
@@ -120,6 +139,7 @@ EXPORTS = [
     "khr_snapshot_updated", "khr_take_snapshot", "khr_snapshot_num_blocks", "khr_snapshot_download", "khr_snapshot_download_extra", "khr_snapshot_download_begin", "khr_snapshot_download_end", "khr_snapshot_poll", "khr_fetch_mesh_launch", "khr_reserve_mesh_staging", "khr_reserve_snapshots", "khr_mirror_dynamic", "khr_snapshot_release",
     "khr_rv_check_stamps", "khr_get_config", "khr_cluster_voxels_launch", "khr_cluster_voxels_fetch", "khr_reset_map", "khr_depend_on", "khr_retain_slot", "khr_release_slot",
     "khr_map_slice", "khr_slice_voxel_z", "khr_render_view", "khr_query_points",
+    "khr_align_linearize", "khr_align_frame",
     "khr_checkpoint_size", "khr_checkpoint_save", "khr_checkpoint_load", "khr_checkpoint_inspect",
 ]
 
@@ -210,6 +230,8 @@ def load_library():
     lib.khr_slice_voxel_z.argtypes = [C.c_float, C.c_float, C.c_int32, vp]
     lib.khr_render_view.argtypes = [vp, C.POINTER(KhrRenderRequest), i32] + [vp] * 6 + [C.POINTER(KhrRenderStats)]
     lib.khr_query_points.argtypes = [vp, i64, vp, C.c_float, i32] + [vp] * 8 + [C.POINTER(KhrQueryStats)]
+    lib.khr_align_linearize.argtypes = [vp, C.POINTER(KhrAlignRequest), i32, vp]
+    lib.khr_align_frame.argtypes = [vp, C.POINTER(KhrAlignRequest), i32, C.POINTER(KhrAlignOptions), vp, C.POINTER(KhrAlignResult)]
     lib.khr_checkpoint_size.argtypes = [vp, C.POINTER(u64), C.POINTER(i64)]
     lib.khr_checkpoint_save.argtypes = [vp, vp, u64, C.POINTER(u64)]
     lib.khr_checkpoint_load.argtypes = [vp, vp, u64, C.POINTER(i64)]
@@ -878,6 +900,104 @@ class FusionContext:
         self._chk(rc)
         out["stats"] = stats
         return out
+
+    def align_request(self, pose, points=None, depth=None, sensor=None, stride=1, weights=None, min_weight=0.0, gate=0.0, huber_delta=0.0,
+                      device=False, n=None):
+        """a khr_align_request plus the arrays it points into (keep the second value alive for the duration of the call).  Host
+        form: `points` (n, 3) / `depth` (H, W) / `weights` are converted to contiguous float32 arrays; device=True: they are integer
+        device pointers (points: pass `n`)."""
+        rq = KhrAlignRequest()
+        keep = []
+
+        def ptr(a):
+            if a is None:
+                return None
+            if device:
+                return int(a)
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            keep.append(a)
+            return a.ctypes.data
+
+        if points is not None:
+            if device and n is None:
+                raise ValueError("a device point list needs n, the number of points")
+            rq.n = int(n) if n is not None else int(np.asarray(points).size // 3)
+            rq.points = ptr(points)
+        elif n is not None:
+            rq.n = int(n)
+        if depth is not None:
+            rq.depth = ptr(depth)
+        if sensor is not None:
+            rq.sensor = sensor
+        rq.stride = int(stride)
+        rq.weights = ptr(weights)
+        T = np.ascontiguousarray(pose, dtype=np.float64).reshape(16)
+        for i in range(16):
+            rq.world_T_source[i] = T[i]
+        rq.min_weight, rq.gate, rq.huber_delta = float(min_weight), float(gate), float(huber_delta)
+        return rq, keep
+
+    def align_linearize_into(self, request, words, on_device=False):
+        """khr_align_linearize into `words` (a uint64 array of at least KHR_ALIGN_WORDS entries, or None for the NULL pointer);
+        `request` may be None.  Returns the return code without raising."""
+        return self.lib.khr_align_linearize(self.h, None if request is None else C.byref(request), int(on_device), _ptr(words))
+
+    def align_linearize(self, pose, points=None, depth=None, sensor=None, stride=1, weights=None, min_weight=0.0, gate=0.0,
+                        huber_delta=0.0, device=False, n=None):
+        """One linearisation of the point-to-map registration at `pose` (khr_align_linearize, ASSUMPTIONS.md A.14): the 32 uint64
+        words -- H's upper triangle (21), b (6), e, n_inlier, n_gradient, n_source, the sum of w rho -- of a point list (`points` (n, 3), source
+        frame) or of a depth image (`depth` (H, W), `sensor`, `stride`).  device=True: points / depth / weights are device
+        pointers."""
+        rq, keep = self.align_request(pose, points, depth, sensor, stride, weights, min_weight, gate, huber_delta, device, n)
+        words = np.zeros(KHR_ALIGN_WORDS, np.uint64)
+        self._chk(self.align_linearize_into(rq, words, on_device=device))
+        return words
+
+    @staticmethod
+    def align_unpack(words):
+        """(H (6, 6) float64, b (6,), e, n_inlier) from the words of align_linearize"""
+        v = np.asarray(words, np.uint64).view(np.int64).astype(np.float64) * 2.0 ** -24
+        H = np.zeros((6, 6))
+        k = 0
+        for a in range(6):
+            for b in range(a, 6):
+                H[a, b] = H[b, a] = v[k]
+                k += 1
+        return H, v[21:27].copy(), float(v[27]), int(words[28])
+
+    def align_frame_into(self, request, pose_out, on_device=False, max_iterations=10, min_inliers=64, lam=1e-4, eps_rot=1e-5, eps_trans=1e-5,
+                         default_options=False):
+        """khr_align_frame: (return code, result dict) without raising; `pose_out`: float64 array of 16 (or None)."""
+        opt = KhrAlignOptions(int(max_iterations), int(min_inliers), float(lam), float(eps_rot), float(eps_trans))
+        res = KhrAlignResult()
+        rc = self.lib.khr_align_frame(self.h, None if request is None else C.byref(request), int(on_device),
+                                      None if default_options else C.byref(opt), _ptr(pose_out), C.byref(res))
+        out = dict(iterations=int(res.iterations), converged=bool(res.converged), n_inlier_first=int(res.n_inlier_first),
+                   n_inlier_last=int(res.n_inlier_last), rmse_first=float(res.rmse_first), rmse_last=float(res.rmse_last),
+                   H=np.array(res.H[:], np.float64), b=np.array(res.b[:], np.float64))
+        return rc, out
+
+    def _align(self, rq, device, opts):
+        pose = np.zeros(16, np.float64)
+        rc, res = self.align_frame_into(rq, pose, on_device=device, **opts)
+        if rc != KHR_ENOTFOUND:
+            self._chk(rc)
+        res["found"] = rc == 0
+        return pose.reshape(4, 4), res
+
+    def align_points(self, points, prior, weights=None, min_weight=0.0, gate=0.0, huber_delta=0.0, device=False, n=None, **options):
+        """Register a point list (source frame) against the live map, starting from `prior` (4x4 world_T_source): returns (pose
+        (4, 4) float64, result dict).  result["found"] is False when the map did not constrain the pose (KHR_ENOTFOUND): the pose
+        returned is then the prior.  options: max_iterations, min_inliers, lam, eps_rot, eps_trans."""
+        rq, keep = self.align_request(prior, points=points, weights=weights, min_weight=min_weight, gate=gate, huber_delta=huber_delta,
+                                      device=device, n=n)
+        return self._align(rq, device, options)
+
+    def align_depth(self, depth, sensor, prior, stride=1, weights=None, min_weight=0.0, gate=0.0, huber_delta=0.0, device=False, **options):
+        """The same for a depth image seen through `sensor`, every `stride`-th pixel of every `stride`-th row."""
+        rq, keep = self.align_request(prior, depth=depth, sensor=sensor, stride=stride, weights=weights, min_weight=min_weight, gate=gate,
+                                      huber_delta=huber_delta, device=device)
+        return self._align(rq, device, options)
 
     def mesh_halo_words(self):
         v = self.cfg.voxels_per_side

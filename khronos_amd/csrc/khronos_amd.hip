@@ -36,6 +36,7 @@
 #include "khr_kernels_slice.h"
 #include "khr_kernels_render.h"
 #include "khr_kernels_query.h"
+#include "khr_kernels_align.h"
 #include "khr_kernels_checkpoint.h"
 
 using namespace khr;
@@ -382,6 +383,13 @@ struct khr_ctx {
   uint8_t* d_query_stage = nullptr;
   uint8_t* h_query_stage = nullptr;  // page-locked mirror of d_query_stage
   size_t query_stage_bytes = 0;
+  // registration (khr_align_linearize): the accumulator (its words 128 bytes apart) with its page-locked mirror, and the source /
+  // weight staging of the host form
+  unsigned long long* d_align_acc = nullptr;
+  unsigned long long* h_align_acc = nullptr;
+  uint8_t* d_align_stage = nullptr;
+  uint8_t* h_align_stage = nullptr;  // page-locked mirror of d_align_stage
+  size_t align_stage_bytes = 0;
   // map checkpoints (khr_checkpoint_save / _load): two chunk staging areas of kCkptStageBytes each (created at the first call; their
   // page-locked mirrors only when a caller passes pageable memory), the chunk's slot list, the load's error word, and per
   // staging area one event for "filled" and one for "drained"
@@ -1148,6 +1156,10 @@ void khr_destroy(khr_ctx* c) {
   if (c->d_query_stats) hipFree(c->d_query_stats);
   if (c->d_query_stage) hipFree(c->d_query_stage);
   if (c->h_query_stage) hipHostFree(c->h_query_stage);
+  if (c->d_align_acc) hipFree(c->d_align_acc);
+  if (c->h_align_acc) hipHostFree(c->h_align_acc);
+  if (c->d_align_stage) hipFree(c->d_align_stage);
+  if (c->h_align_stage) hipHostFree(c->h_align_stage);
   for (int i = 0; i < 2; ++i) {
     if (c->d_ckpt[i]) hipFree(c->d_ckpt[i]);
     if (c->h_ckpt[i]) hipHostFree(c->h_ckpt[i]);
@@ -5014,6 +5026,286 @@ int khr_query_points(khr_ctx* c, int64_t n, const float* points, float min_weigh
     stats->n_gradient = h_stats[QS_GRADIENT];
     stats->n_voxel = h_stats[QS_VOXEL];
   }
+  return KHR_OK;
+}
+
+// ---- the live map as a registration target (khr_align_linearize / khr_align_frame; ASSUMPTIONS.md A.14, device side:
+// khr_kernels_align.h) ---------------------------------------------------------------------------------------------------------
+namespace {
+
+struct AlignPlan {
+  bool depth_form = false;
+  long long n = 0;       // lanes
+  size_t src_bytes = 0;  // source bytes, weight bytes (0 without weights)
+  size_t w_bytes = 0;
+  int ws = 0;
+  float min_weight = 0.f, gate = 0.f;
+};
+
+// the request's checks (nothing is touched before they pass)
+int alignCheck(khr_ctx* c, const khr_align_request* rq, AlignPlan* pl) {
+  if (!c || !rq) return fail(KHR_EINVAL, "null argument");
+  for (int i = 0; i < 16; ++i)
+    if (!std::isfinite(rq->world_T_source[i])) return fail(KHR_EINVAL, "world_T_source is not finite");
+  if (!(rq->min_weight >= 0.f) || !std::isfinite(rq->min_weight)) return fail(KHR_EINVAL, "bad min_weight %g", static_cast<double>(rq->min_weight));
+  if (!(rq->gate >= 0.f) || !std::isfinite(rq->gate)) return fail(KHR_EINVAL, "bad gate %g", static_cast<double>(rq->gate));
+  if (!(rq->huber_delta >= 0.f) || !std::isfinite(rq->huber_delta)) return fail(KHR_EINVAL, "bad huber_delta %g", static_cast<double>(rq->huber_delta));
+  pl->gate = rq->gate == 0.f ? c->cfg.truncation_distance : rq->gate;
+  if (!(pl->gate <= 64.f)) return fail(KHR_EINVAL, "gate %g m: the sums are proven not to wrap up to 64 m", static_cast<double>(pl->gate));
+  pl->min_weight = rq->min_weight == 0.f ? c->cfg.mesh_min_weight : rq->min_weight;
+  if (rq->points && rq->depth) return fail(KHR_EINVAL, "both a point list and a depth image");
+  if (rq->depth) {
+    const khr_sensor& sn = rq->sensor;
+    if (rq->stride < 1) return fail(KHR_EINVAL, "stride %d", rq->stride);
+    if (sn.width <= 0 || sn.height <= 0 || static_cast<int64_t>(sn.width) * sn.height > (int64_t(1) << 30))
+      return fail(KHR_EINVAL, "bad image size %d x %d", sn.width, sn.height);
+    if (!std::isfinite(sn.fx) || !std::isfinite(sn.fy) || sn.fx == 0.f || sn.fy == 0.f || !std::isfinite(sn.cx) || !std::isfinite(sn.cy))
+      return fail(KHR_EINVAL, "bad intrinsics");
+    if (!std::isfinite(sn.min_range) || !std::isfinite(sn.max_range) || sn.min_range < 0.f || sn.max_range < sn.min_range)
+      return fail(KHR_EINVAL, "bad range limits [%g, %g]", static_cast<double>(sn.min_range), static_cast<double>(sn.max_range));
+    pl->depth_form = true;
+    // (in 64 bits: width + stride - 1 may pass 2^31)
+    const long long st = rq->stride;
+    pl->ws = static_cast<int>((sn.width + st - 1) / st);
+    pl->n = static_cast<long long>(pl->ws) * ((sn.height + st - 1) / st);
+    pl->src_bytes = static_cast<size_t>(sn.width) * sn.height * 4;
+    pl->w_bytes = rq->weights ? pl->src_bytes : 0;
+  } else {
+    if (rq->n < 0) return fail(KHR_EINVAL, "negative point count %lld", static_cast<long long>(rq->n));
+    if (rq->n > 0 && !rq->points) return fail(KHR_EINVAL, "neither a point list nor a depth image");
+    pl->n = rq->n;
+    pl->src_bytes = static_cast<size_t>(rq->n) * 12;
+    pl->w_bytes = rq->weights ? static_cast<size_t>(rq->n) * 4 : 0;
+  }
+  if (pl->n > KHR_ALIGN_MAX_SOURCES) return fail(KHR_EINVAL, "%lld sources, at most %d per call", pl->n, KHR_ALIGN_MAX_SOURCES);
+  if (c->cfg.world_size > 1) return fail(KHR_ESTATE, "khr_align_linearize needs the whole map: world_size is %d", c->cfg.world_size);
+  return KHR_OK;
+}
+
+// the accumulator pair, and for a host source its copy in the device staging (queued on the stream); *d_src / *d_w: what the kernel reads
+int alignPrepare(khr_ctx* c, const khr_align_request* rq, const AlignPlan& pl, int on_device, const float** d_src, const float** d_w) {
+  HIP_TRY(hipSetDevice(c->device));
+  constexpr size_t acc_bytes = sizeof(unsigned long long) * kAlignWords * kAlignAccStride;
+  if (!c->d_align_acc && hipMalloc(reinterpret_cast<void**>(&c->d_align_acc), acc_bytes) != hipSuccess) return fail(KHR_ENOMEM, "align accumulator");
+  if (!c->h_align_acc && hipHostMalloc(reinterpret_cast<void**>(&c->h_align_acc), acc_bytes, hipHostMallocDefault) != hipSuccess)
+    return fail(KHR_ENOMEM, "page-locked align accumulator");
+  const float* src = pl.depth_form ? rq->depth : rq->points;
+  *d_src = src;
+  *d_w = rq->weights;
+  if (on_device || pl.n == 0) return KHR_OK;
+  const size_t w_off = (pl.src_bytes + 255) / 256 * 256, stage_bytes = w_off + (pl.w_bytes + 255) / 256 * 256;
+  if (stage_bytes > c->align_stage_bytes) {
+    if (c->d_align_stage) HIP_TRY(hipFree(c->d_align_stage));
+    if (c->h_align_stage) HIP_TRY(hipHostFree(c->h_align_stage));
+    c->d_align_stage = c->h_align_stage = nullptr;
+    c->align_stage_bytes = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&c->d_align_stage), stage_bytes) != hipSuccess)
+      return fail(KHR_ENOMEM, "align staging of %zu bytes", stage_bytes);
+    if (hipHostMalloc(reinterpret_cast<void**>(&c->h_align_stage), stage_bytes, hipHostMallocDefault) != hipSuccess) {
+      hipFree(c->d_align_stage);
+      c->d_align_stage = nullptr;
+      return fail(KHR_ENOMEM, "page-locked align staging of %zu bytes", stage_bytes);
+    }
+    c->align_stage_bytes = stage_bytes;
+  }
+  std::memcpy(c->h_align_stage, src, pl.src_bytes);
+  HIP_TRY(hipMemcpyAsync(c->d_align_stage, c->h_align_stage, pl.src_bytes, hipMemcpyHostToDevice, c->stream));
+  *d_src = reinterpret_cast<const float*>(c->d_align_stage);
+  if (pl.w_bytes) {
+    std::memcpy(c->h_align_stage + w_off, rq->weights, pl.w_bytes);
+    HIP_TRY(hipMemcpyAsync(c->d_align_stage + w_off, c->h_align_stage + w_off, pl.w_bytes, hipMemcpyHostToDevice, c->stream));
+    *d_w = reinterpret_cast<const float*>(c->d_align_stage + w_off);
+  }
+  return KHR_OK;
+}
+
+// one evaluation at `pose` over a device-resident source: zero, launch, copy back, one wait
+int alignEvaluate(khr_ctx* c, const khr_align_request* rq, const AlignPlan& pl, const float* d_src, const float* d_w, const double* pose,
+                  uint64_t* words) {
+  if (pl.n == 0) {
+    std::memset(words, 0, sizeof(uint64_t) * KHR_ALIGN_WORDS);
+    return KHR_OK;
+  }
+  constexpr size_t acc_bytes = sizeof(unsigned long long) * kAlignWords * kAlignAccStride;
+  AlignArgs a{};
+  a.n = static_cast<uint32_t>(pl.n);
+  a.points = pl.depth_form ? nullptr : d_src;
+  a.depth = pl.depth_form ? d_src : nullptr;
+  a.weights = d_w;
+  a.W = static_cast<uint32_t>(pl.depth_form ? rq->sensor.width : 0);
+  a.ws = static_cast<uint32_t>(pl.depth_form ? pl.ws : 1);
+  a.stride = static_cast<uint32_t>(pl.depth_form ? rq->stride : 1);
+  a.fx = rq->sensor.fx;
+  a.fy = rq->sensor.fy;
+  a.cx = rq->sensor.cx;
+  a.cy = rq->sensor.cy;
+  a.min_range = rq->sensor.min_range;
+  a.max_range = rq->sensor.max_range;
+  {
+    float R[9], t[3];
+    makePose(pose, R, t, a.Rw, a.tw);
+  }
+  a.min_weight = pl.min_weight;
+  a.gate = pl.gate;
+  a.huber_delta = rq->huber_delta;
+  a.acc = c->d_align_acc;
+  HIP_TRY(hipMemsetAsync(c->d_align_acc, 0, acc_bytes, c->stream));
+  const dim3 grid(static_cast<unsigned>((pl.n + 255) / 256));  // (at most 4096 workgroups: n <= 2^20)
+  const bool depth_form = pl.depth_form;
+  int rc = dispatchVps(c, [&](auto vps) {
+    if (depth_form)
+      hipLaunchKernelGGL((k_align_linearize<decltype(vps)::value, ALIGN_DEPTH>), grid, dim3(256), 0, c->stream, c->m, c->p, a);
+    else
+      hipLaunchKernelGGL((k_align_linearize<decltype(vps)::value, ALIGN_POINTS>), grid, dim3(256), 0, c->stream, c->m, c->p, a);
+    HIP_TRY(hipGetLastError());
+    return KHR_OK;
+  });
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(c->h_align_acc, c->d_align_acc, acc_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int w = 0; w < KHR_ALIGN_WORDS; ++w) words[w] = c->h_align_acc[static_cast<size_t>(w) * kAlignAccStride];
+  return KHR_OK;
+}
+
+// L L^T = A for the 6 x 6 symmetric A (upper triangle read), then L y = rhs, L^T x = y; false at a pivot that is not positive
+bool alignCholeskySolve(const double (&A)[6][6], const double (&rhs)[6], double (&x)[6]) {
+  double L[6][6] = {};
+  for (int j = 0; j < 6; ++j) {
+    double s = A[j][j];
+    for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
+    if (!(s > 0.0) || !std::isfinite(s)) return false;
+    L[j][j] = std::sqrt(s);
+    for (int i = j + 1; i < 6; ++i) {
+      double v = A[j][i];
+      for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+      L[i][j] = v / L[j][j];
+    }
+  }
+  double y[6];
+  for (int i = 0; i < 6; ++i) {
+    double v = rhs[i];
+    for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
+    y[i] = v / L[i][i];
+  }
+  for (int i = 5; i >= 0; --i) {
+    double v = y[i];
+    for (int k = i + 1; k < 6; ++k) v -= L[k][i] * x[k];
+    x[i] = v / L[i][i];
+  }
+  return true;
+}
+
+// R <- exp(omega^) R, t <- t + v on the row-major 4 x 4 double pose (Rodrigues; the series below 1e-8 rad)
+void alignApplyTwist(double* T, const double (&xi)[6]) {
+  const double wx = xi[0], wy = xi[1], wz = xi[2];
+  const double th2 = (wx * wx + wy * wy) + wz * wz, th = std::sqrt(th2);
+  double A, B;  // sin(th) / th, (1 - cos(th)) / th^2
+  if (th < 1e-8) {
+    A = 1.0 - th2 / 6.0;
+    B = 0.5 - th2 / 24.0;
+  } else {
+    A = std::sin(th) / th;
+    B = (1.0 - std::cos(th)) / th2;
+  }
+  const double K[3][3] = {{0.0, -wz, wy}, {wz, 0.0, -wx}, {-wy, wx, 0.0}};
+  double E[3][3];
+  for (int r = 0; r < 3; ++r)
+    for (int cc = 0; cc < 3; ++cc) {
+      double k2 = 0.0;
+      for (int k = 0; k < 3; ++k) k2 += K[r][k] * K[k][cc];
+      E[r][cc] = (r == cc ? 1.0 : 0.0) + A * K[r][cc] + B * k2;
+    }
+  double Rn[3][3];
+  for (int r = 0; r < 3; ++r)
+    for (int cc = 0; cc < 3; ++cc) {
+      double v = 0.0;
+      for (int k = 0; k < 3; ++k) v += E[r][k] * T[4 * k + cc];
+      Rn[r][cc] = v;
+    }
+  for (int r = 0; r < 3; ++r) {
+    for (int cc = 0; cc < 3; ++cc) T[4 * r + cc] = Rn[r][cc];
+    T[4 * r + 3] += xi[3 + r];
+  }
+}
+
+}  // namespace
+
+int khr_align_linearize(khr_ctx* c, const khr_align_request* rq, int on_device, uint64_t* words) {
+  AlignPlan pl;
+  if (!words) return fail(KHR_EINVAL, "null argument");
+  int rc = alignCheck(c, rq, &pl);
+  if (rc) return rc;
+  const float *d_src = nullptr, *d_w = nullptr;
+  if ((rc = alignPrepare(c, rq, pl, on_device, &d_src, &d_w))) return rc;
+  return alignEvaluate(c, rq, pl, d_src, d_w, rq->world_T_source, words);
+}
+
+int khr_align_frame(khr_ctx* c, const khr_align_request* rq, int on_device, const khr_align_options* options, double* world_T_source_out,
+                    khr_align_result* result) {
+  AlignPlan pl;
+  if (!world_T_source_out) return fail(KHR_EINVAL, "null argument");
+  int rc = alignCheck(c, rq, &pl);
+  if (rc) return rc;
+  khr_align_options o{10, 64, 1e-4, 1e-5, 1e-5};
+  if (options) o = *options;
+  if (!(o.lambda >= 0.0) || !std::isfinite(o.lambda) || !(o.eps_rot >= 0.0) || !(o.eps_trans >= 0.0))
+    return fail(KHR_EINVAL, "bad align options (lambda %g, eps_rot %g, eps_trans %g)", o.lambda, o.eps_rot, o.eps_trans);
+  if (o.max_iterations <= 0) o.max_iterations = 10;
+  if (o.min_inliers < 6) o.min_inliers = 6;
+  const float *d_src = nullptr, *d_w = nullptr;
+  if ((rc = alignPrepare(c, rq, pl, on_device, &d_src, &d_w))) return rc;  // (a host source is staged once for all iterations)
+  khr_align_result res{};
+  double T[16];
+  std::memcpy(T, rq->world_T_source, sizeof(T));
+  const double scale = 1.0 / 16777216.0;
+  bool lost = false;
+  for (int it = 0; it < o.max_iterations; ++it) {
+    uint64_t words[KHR_ALIGN_WORDS];
+    if ((rc = alignEvaluate(c, rq, pl, d_src, d_w, T, words))) return rc;
+    double H[6][6], b[6];
+    int w = 0;
+    for (int r = 0; r < 6; ++r)
+      for (int cc = r; cc < 6; ++cc, ++w) {
+        res.H[w] = static_cast<double>(static_cast<int64_t>(words[w])) * scale;
+        H[r][cc] = H[cc][r] = res.H[w];
+      }
+    for (int r = 0; r < 6; ++r) b[r] = res.b[r] = static_cast<double>(static_cast<int64_t>(words[AW_B + r])) * scale;
+    const uint64_t n_in = words[AW_INLIER];
+    const double e = static_cast<double>(static_cast<int64_t>(words[AW_E])) * scale;
+    const double sum_w = static_cast<double>(words[AW_WEIGHT]) * scale;  // sum of weight * rho over the inliers
+    const double rmse = sum_w > 0.0 ? std::sqrt(e / sum_w) : 0.0;
+    if (it == 0) {
+      res.n_inlier_first = n_in;
+      res.rmse_first = rmse;
+    }
+    res.n_inlier_last = n_in;
+    res.rmse_last = rmse;
+    if (n_in < static_cast<uint64_t>(o.min_inliers)) {
+      lost = true;
+      break;
+    }
+    double A[6][6], rhs[6], xi[6];
+    for (int r = 0; r < 6; ++r) {
+      for (int cc = 0; cc < 6; ++cc) A[r][cc] = H[r][cc];
+      A[r][r] = H[r][r] + o.lambda * H[r][r];
+      rhs[r] = -b[r];
+    }
+    if (!alignCholeskySolve(A, rhs, xi)) {
+      lost = true;
+      break;
+    }
+    alignApplyTwist(T, xi);
+    res.iterations = it + 1;
+    const double nw = std::sqrt((xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2]), nv = std::sqrt((xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5]);
+    if (nw < o.eps_rot && nv < o.eps_trans) {
+      res.converged = 1;
+      break;
+    }
+  }
+  std::memcpy(world_T_source_out, lost ? rq->world_T_source : T, sizeof(T));
+  if (result) *result = res;
+  if (lost) return fail(KHR_ENOTFOUND, "alignment lost after %d updates: %llu inliers (at least %d), or a singular system", res.iterations,
+                        static_cast<unsigned long long>(res.n_inlier_last), o.min_inliers);
   return KHR_OK;
 }
 

@@ -2,7 +2,7 @@
 // thread drives the reference (spinOnce per InputPacket, finishMapping at shutdown), and prints a JSON
 // summary that tests/test_gpu_host.py compares with the step-wise C-ABI path and the oracle.
 // usage: aw_demo <config.yaml> <width> <height> <frames> [object_label]
-//        aw_demo --slices | --render | --query | --checkpoint | --bench | --rayver ... (below)
+//        aw_demo --slices | --render | --query | --align | --checkpoint | --bench | --rayver ... (below)
 //   object_label >= 0: the stand-in detector / tracker below; otherwise the plugins named in the config
 #include <execinfo.h>
 #include <csignal>
@@ -701,6 +701,138 @@ static int renderDemo(int argc, char** argv) {
   return frames == N && view.numPixels() == n ? 0 : 3;
 }
 
+// aw_demo --align <config.yaml> <width> <height> <frames> [stride]: drives the synthetic stream through an ActiveWindow whose Khronos
+// sink, at the LAST frame, perturbs the frame's own pose by about 1 degree and 3 cm and lets the map pull it back
+// (VolumetricMap::align: khr_align_frame).  The frame goes in three ways -- the converted frame (InputData), the raw depth image and
+// the host's back-projection of its strided pixels as a point list -- which must give the same pose bit for bit.  One JSON line: the
+// true pose, the prior, the returned pose, the rotation (rad) and translation (m) errors before and after, the loop's counters and
+// the call's wall-clock time.  Exit status 0 iff the pose was found, both errors shrank and the three forms agree.
+static void poseError(const double* T, const double* truth, double* rot, double* trans) {
+  double tr = 0, d2 = 0;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) tr += T[4 * r + c] * truth[4 * r + c];  // trace(R truth^T)
+    const double d = T[4 * r + 3] - truth[4 * r + 3];
+    d2 += d * d;
+  }
+  const double cs = std::min(1.0, std::max(-1.0, 0.5 * (tr - 1.0)));
+  *rot = std::acos(cs);
+  *trans = std::sqrt(d2);
+}
+
+static int alignDemo(int argc, char** argv) {
+  if (argc < 6) {
+    std::fprintf(stderr, "usage: aw_demo --align <config.yaml> <width> <height> <frames> [stride]\n");
+    return 2;
+  }
+  std::ifstream in(argv[2]);
+  std::stringstream ss;
+  ss << in.rdbuf();
+  const int W = std::atoi(argv[3]), H = std::atoi(argv[4]), N = std::atoi(argv[5]);
+  hydra::AlignOptions opt;
+  if (argc > 6) opt.stride = std::atoi(argv[6]);
+  ActiveWindow::Config cfg = ActiveWindow::Config::fromYamlString(ss.str());
+  cfg.max_frame_pixels = static_cast<uint32_t>(W) * H;
+  auto out_queue = std::make_shared<ActiveWindow::OutputQueue>();
+  ActiveWindow aw(cfg, out_queue);
+  const size_t n = static_cast<size_t>(W) * H;
+  std::vector<float> depth(n);
+  std::vector<uint8_t> rgb(n * 3);
+  std::vector<int32_t> label(n);
+  int frames = 0;
+  double truth[16], prior[16];
+  hydra::Alignment from_frame, from_depth, from_points;
+  size_t n_points = 0;
+  double align_ms = 0;
+  using clk = std::chrono::steady_clock;
+  aw.addKhronosSink([&](const FrameData& data, const VolumetricMap& map, const Tracks&) {
+    if (++frames != N) return;
+    std::memcpy(truth, data.input.world_T_sensor, sizeof(truth));
+    // prior = exp(omega^) R, t + v with |omega| = 0.0175 rad, |v| = 0.029 m (Rodrigues)
+    const double w[3] = {0.010, -0.008, 0.012}, v[3] = {0.020, -0.015, 0.015};
+    const double th = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]), A = std::sin(th) / th, B = (1.0 - std::cos(th)) / (th * th);
+    const double K[3][3] = {{0, -w[2], w[1]}, {w[2], 0, -w[0]}, {-w[1], w[0], 0}};
+    std::memcpy(prior, truth, sizeof(prior));
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) {
+        double s = 0;
+        for (int k = 0; k < 3; ++k) {
+          double e = (r == k ? 1.0 : 0.0) + A * K[r][k];
+          for (int j = 0; j < 3; ++j) e += B * K[r][j] * K[j][k];
+          s += e * truth[4 * k + c];
+        }
+        prior[4 * r + c] = s;
+      }
+      prior[4 * r + 3] = truth[4 * r + 3] + v[r];
+    }
+    khr_sync(map.ctx());
+    const auto t0 = clk::now();
+    from_frame = map.align(data.input, prior, opt);
+    align_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    const hydra::Sensor& sn = data.input.sensor;
+    from_depth = map.align(sn, depth.data(), prior, opt);
+    std::vector<float> pts;
+    for (int y = 0; y < H; y += opt.stride)
+      for (int x = 0; x < W; x += opt.stride) {
+        const float z = depth[static_cast<size_t>(y) * W + x];
+        if (!(z > 0.f) || !std::isfinite(z) || z < sn.min_range || z > sn.max_range) continue;
+        const float xn = (static_cast<float>(x) - sn.cx) / sn.fx, yn = (static_cast<float>(y) - sn.cy) / sn.fy;
+        const float px = xn * z, py = yn * z;
+        pts.push_back(px);
+        pts.push_back(py);
+        pts.push_back(z);
+      }
+    n_points = pts.size() / 3;
+    from_points = map.align(pts, prior, opt);
+  });
+  void* scene = synth_create(1234, 12, 1);
+  for (int i = 0; i < N; ++i) {
+    hydra::InputPacket pkt;
+    pkt.timestamp_ns = static_cast<uint64_t>(std::llround((1.0 + 0.1 * i) * 1e9));
+    circlePose(0.1 * i, pkt.world_T_body);
+    pkt.sensor = {W, H, W / 2.f, W / 2.f, W / 2.f, H / 2.f, 0.1f, 5.f};
+    synth_render(scene, W, H, pkt.sensor.fx, pkt.sensor.fy, pkt.sensor.cx, pkt.sensor.cy, pkt.world_T_body, 0.1 * i, 5.f, 0.f,
+                 1234u + 7919u * i, depth.data(), rgb.data(), label.data(), 0);
+    pkt.depth = depth.data();
+    pkt.color = rgb.data();
+    pkt.labels = label.data();
+    aw.step(pkt);
+    hydra::ActiveWindowOutput::Ptr popped;
+    while (out_queue->pop(&popped)) {}
+  }
+  aw.finishMapping();
+  synth_destroy(scene);
+  if (frames != N) return 3;
+  auto same = [](const hydra::Alignment& a, const hydra::Alignment& b) {
+    return std::memcmp(a.world_T_source, b.world_T_source, sizeof(a.world_T_source)) == 0 && a.found == b.found && a.iterations == b.iterations &&
+           a.n_inlier_first == b.n_inlier_first && a.n_inlier_last == b.n_inlier_last && std::memcmp(a.H, b.H, sizeof(a.H)) == 0 &&
+           std::memcmp(a.b, b.b, sizeof(a.b)) == 0;
+  };
+  auto mat = [](const double* T) {
+    std::string s = "[";
+    for (int i = 0; i < 16; ++i) {
+      char b[40];
+      std::snprintf(b, sizeof(b), "%s%.17g", i ? ", " : "", T[i]);
+      s += b;
+    }
+    return s + "]";
+  };
+  double r0, t0, r1, t1;
+  poseError(prior, truth, &r0, &t0);
+  poseError(from_frame.world_T_source, truth, &r1, &t1);
+  const bool depth_same = same(from_frame, from_depth), points_same = same(from_depth, from_points);
+  std::printf("{\"what\": \"a perturbed pose of the last frame pulled back by the map (VolumetricMap::align), %d frames\", \"frames\": %d, "
+              "\"stride\": %d, \"truth\": %s, \"prior\": %s, \"pose\": %s, \"found\": %s, \"iterations\": %d, \"converged\": %s, "
+              "\"n_inlier_first\": %llu, \"n_inlier_last\": %llu, \"rmse_first\": %.17g, \"rmse_last\": %.17g, \"rot_error_prior\": %.9g, "
+              "\"trans_error_prior\": %.9g, \"rot_error\": %.9g, \"trans_error\": %.9g, \"n_points\": %zu, \"depth_form_equal\": %s, "
+              "\"point_form_equal\": %s, \"align_ms\": %.3f}\n",
+              N, frames, opt.stride, mat(truth).c_str(), mat(prior).c_str(), mat(from_frame.world_T_source).c_str(),
+              from_frame.found ? "true" : "false", from_frame.iterations, from_frame.converged ? "true" : "false",
+              static_cast<unsigned long long>(from_frame.n_inlier_first), static_cast<unsigned long long>(from_frame.n_inlier_last),
+              from_frame.rmse_first, from_frame.rmse_last, r0, t0, r1, t1, n_points, depth_same ? "true" : "false",
+              points_same ? "true" : "false", align_ms);
+  return from_frame.found && r1 < r0 && t1 < t0 && depth_same && points_same ? 0 : 3;
+}
+
 // aw_demo --checkpoint <config.yaml> <width> <height> <frames> [file]: runs the synthetic stream through an ActiveWindow, saves the live
 // map through getMap().save (hydra::VolumetricMap: khr_checkpoint_save around a file), loads the file into the empty map of a second
 // context of the same configuration and compares the two maps' whole-map digests.  One JSON line: both digests (12 words each),
@@ -816,6 +948,14 @@ int main(int argc, char** argv) {
   if (argc >= 2 && std::string(argv[1]) == "--render") {
     try {
       return renderDemo(argc, argv);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "aw_demo: %s\n", e.what());
+      return 1;
+    }
+  }
+  if (argc >= 2 && std::string(argv[1]) == "--align") {
+    try {
+      return alignDemo(argc, argv);
     } catch (const std::exception& e) {
       std::fprintf(stderr, "aw_demo: %s\n", e.what());
       return 1;

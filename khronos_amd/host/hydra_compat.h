@@ -273,6 +273,33 @@ struct PointSamples {
   bool hasVoxel(size_t i) const { return (status[i] & kVoxel) != 0; }
 };
 
+// A frame or a point set registered against the live map (VolumetricMap::align, khr_align_frame; ASSUMPTIONS.md A.14).  `found`
+// false: the map did not constrain the pose (too few inliers or a singular system) and world_T_source is the prior -- keep it.
+struct AlignOptions {
+  int stride = 4;            // depth form: every stride-th pixel of every stride-th row
+  float gate = 0.f;          // largest |distance| of an inlier, metres; 0 = the truncation distance
+  float huber_delta = 0.f;   // metres; 0 = no robust factor
+  float min_weight = 0.f;    // 0 = the mesh's minimum weight
+  khr_align_options solver{10, 64, 1e-4, 1e-5, 1e-5};  // max_iterations, min_inliers, lambda, eps_rot, eps_trans
+};
+struct Alignment {
+  double world_T_source[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  bool found = false;
+  int iterations = 0;  // updates applied
+  bool converged = false;
+  uint64_t n_inlier_first = 0, n_inlier_last = 0;
+  double rmse_first = 0, rmse_last = 0;  // sqrt(sum w rho d^2 / sum w rho) over the inliers of the first / last linearisation
+  double H[21] = {}, b[6] = {};          // the last linearisation's normal equations: H's upper triangle row by row, undamped
+  // H as a full 6 x 6 row-major matrix, twist order (omega, v): the information matrix of the pose up to the residual's variance
+  std::array<double, 36> information() const {
+    std::array<double, 36> m{};
+    int k = 0;
+    for (int r = 0; r < 6; ++r)
+      for (int c = r; c < 6; ++c, ++k) m[6 * r + c] = m[6 * c + r] = H[k];
+    return m;
+  }
+};
+
 // hydra::VolumetricMap role: here a handle on the HBM-resident map of a fusion context.
 class VolumetricMap {
  public:
@@ -369,6 +396,43 @@ class VolumetricMap {
     return s;
   }
   PointSamples query(float x, float y, float z, float min_weight = 0.f) const { return query(std::vector<float>{x, y, z}, min_weight); }
+  // Registers a depth image (host memory, sensor.width x sensor.height metres) against the map, starting from `prior`
+  // (world_T_sensor, row-major 4 x 4): Gauss-Newton over khr_align_linearize, one host wait per iteration, the map only read.  Call
+  // it with the odometry prior before the frame is fused, and fuse with the returned pose.  Throws on a bad request.
+  Alignment align(const Sensor& sensor, const float* depth, const double* prior, const AlignOptions& opt = AlignOptions(),
+                  const float* weights = nullptr) const {
+    khr_align_request rq = alignRequest(prior, opt);
+    rq.depth = depth;
+    rq.sensor = {sensor.width, sensor.height, sensor.fx, sensor.fy, sensor.cx, sensor.cy, sensor.min_range, sensor.max_range};
+    rq.stride = opt.stride;
+    rq.weights = weights;
+    return alignRun(rq, opt);
+  }
+  // the same for a converted frame: its depth image is the one the frame slot (or the output's copy) holds
+  Alignment align(const InputData& frame, const double* prior, const AlignOptions& opt = AlignOptions()) const {
+    std::vector<float> depth = frame.depthImage();
+    if (depth.empty() && frame.ctx && frame.slot >= 0) {
+      khr_frame_copy* fc = nullptr;
+      if (khr_frame_copy_create(frame.ctx, frame.slot, &fc) != 0 || !fc) throw std::runtime_error(std::string("khr_frame_copy_create: ") + khr_last_error());
+      depth.resize(frame.numPixels());
+      const int rc = khr_frame_copy_download(fc, depth.data(), nullptr, nullptr, nullptr, nullptr);
+      khr_frame_copy_release(fc);
+      if (rc != 0) throw std::runtime_error(std::string("khr_frame_copy_download: ") + khr_last_error());
+    }
+    if (depth.empty()) throw std::runtime_error("VolumetricMap::align: the frame's depth image is not available");
+    return align(frame.sensor, depth.data(), prior, opt);
+  }
+  // the same for a point list: x, y, z per point in the source frame, `weights` one per point or empty
+  Alignment align(const std::vector<float>& points, const double* prior, const AlignOptions& opt = AlignOptions(),
+                  const std::vector<float>& weights = {}) const {
+    if (points.size() % 3 != 0) throw std::runtime_error("VolumetricMap::align: points must hold 3 floats per point");
+    if (!weights.empty() && weights.size() != points.size() / 3) throw std::runtime_error("VolumetricMap::align: one weight per point");
+    khr_align_request rq = alignRequest(prior, opt);
+    rq.n = static_cast<int64_t>(points.size() / 3);
+    rq.points = points.data();
+    rq.weights = weights.empty() ? nullptr : weights.data();
+    return alignRun(rq, opt);
+  }
   // The map save / load role of hydra::VolumetricMap (un-vendored upstream; the reference's own tree has no counterpart): the live
   // map as one checkpoint file (khr_checkpoint_save: the format is in include/khronos_amd.h) and back into an EMPTY map of the
   // same configuration (khr_checkpoint_load; sharded contexts keep their own blocks).  File I/O around the two calls through a
@@ -379,6 +443,31 @@ class VolumetricMap {
   size_t load(const std::string& path);
 
  private:
+  static khr_align_request alignRequest(const double* prior, const AlignOptions& opt) {
+    khr_align_request rq{};
+    for (int i = 0; i < 16; ++i) rq.world_T_source[i] = prior[i];
+    rq.stride = 1;
+    rq.min_weight = opt.min_weight;
+    rq.gate = opt.gate;
+    rq.huber_delta = opt.huber_delta;
+    return rq;
+  }
+  Alignment alignRun(const khr_align_request& rq, const AlignOptions& opt) const {
+    Alignment a;
+    khr_align_result res{};
+    const int rc = khr_align_frame(ctx_, &rq, 0, &opt.solver, a.world_T_source, &res);
+    if (rc != KHR_OK && rc != KHR_ENOTFOUND) throw std::runtime_error(std::string("khr_align_frame: ") + khr_last_error());
+    a.found = rc == KHR_OK;
+    a.iterations = res.iterations;
+    a.converged = res.converged != 0;
+    a.n_inlier_first = res.n_inlier_first;
+    a.n_inlier_last = res.n_inlier_last;
+    a.rmse_first = res.rmse_first;
+    a.rmse_last = res.rmse_last;
+    for (int i = 0; i < 21; ++i) a.H[i] = res.H[i];
+    for (int i = 0; i < 6; ++i) a.b[i] = res.b[i];
+    return a;
+  }
   khr_ctx* ctx_ = nullptr;
   mutable size_t slice_hint_ = 0;  // voxels of the last slice: the first guess of the next call's buffers
 };
