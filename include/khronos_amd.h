@@ -372,7 +372,12 @@ int khr_pixel_iou(khr_ctx* ctx, int slot, const khr_pixel_ref* refs, int n_refs,
 int khr_forward_instances(khr_ctx* ctx, int slot, float max_range, const int32_t* background_ids, int n_background, int max_id,
                           khr_cluster* out);
 /* replaces: hydra::MeshIntegrator::generateMesh(map, only_mesh_updated, clear_flag)
- * (active_window.cpp:223, mesh_object_extractor.cpp:267) */
+ * (active_window.cpp:223, mesh_object_extractor.cpp:267).
+ * A mesh that needs more than max_mesh_vertices vertices is found out on the device: this call still returns KHR_OK and the
+ * mesh queries after it (khr_mesh_num_vertices, khr_download_mesh, khr_fetch_mesh, khr_get_stats) return KHR_ENOMEM with both
+ * numbers in khr_last_error, until the next khr_generate_mesh.  Such a call changes neither the map nor a block's
+ * KHR_BLK_MESH_UPDATED flag, and the mesh of before it is what the next khr_generate_mesh starts from: blocks that call does
+ * not regenerate keep their earlier vertices. */
 int khr_generate_mesh(khr_ctx* ctx, int only_mesh_updated, int clear_flag);
 /* Mesh halo for sharded maps (no reference equivalent).  Marching cubes of a block reads the x = 0 / y = 0 /
  * z = 0 voxel planes of its +x/+y/+z neighbours (7 blocks); with hash-range sharding those usually live on

@@ -1045,9 +1045,24 @@ __device__ inline void meshMoveBlocks(const DevMap& m, const uint8_t* __restrict
                                       const uint32_t* __restrict__ old_offset, const MeshBuffers& src, const MeshBuffers& dst,
                                       uint32_t max_vertices, uint32_t bid, uint32_t nb) {
   const uint32_t total = new_offset[m.capacity];
-  if (total > max_vertices || total == 0u) return;
+  if (total == 0u) return;
   const uint32_t n_slots = m.counters[C_MAX_SLOT];
   if (n_slots == 0u) return;
+  if (total > max_vertices) {
+    // overflow: the emit pass writes nothing and no descriptor changes, but the host flips the two vertex buffers without
+    // waiting for the outcome -- so the previous mesh moves over as it is, every vertex to the place its descriptor names
+    // (all max_vertices entries: an error path, and no kernel knows the extent of the old buffer's live part)
+    const size_t nth = static_cast<size_t>(nb) * blockDim.x;
+    for (size_t i = static_cast<size_t>(bid) * blockDim.x + threadIdx.x; i < max_vertices; i += nth) {
+      dst.points[3 * i] = src.points[3 * i];
+      dst.points[3 * i + 1] = src.points[3 * i + 1];
+      dst.points[3 * i + 2] = src.points[3 * i + 2];
+      dst.colors[i] = src.colors[i];
+      dst.labels[i] = src.labels[i];
+      dst.stamps[i] = src.stamps[i];
+    }
+    return;
+  }
   const float* __restrict__ const s_pts = src.points;
   const uint32_t* __restrict__ const s_col = src.colors;
   const uint32_t* __restrict__ const s_lab = src.labels;
@@ -1594,6 +1609,9 @@ __global__ __launch_bounds__(256) void k_mesh_prepare(DevMap m, uint32_t require
                                                      uint32_t* __restrict__ n_work, uint8_t* __restrict__ regen,
                                                      uint32_t* __restrict__ new_count, uint32_t* __restrict__ old_offset) {
   const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  // every meshing starts without the overflow mark of an earlier one (the emit pass of THIS call sets it again, in stream order,
+  // if this call's mesh does not fit either): one overflow must not fail every later mesh of the context
+  if (s == 0u) m.counters[C_MESH_OVERFLOW] = 0u;
   bool listed = false;
   uint32_t count = 0u, offset = 0u;
   if (s < m.counters[C_MAX_SLOT]) {

@@ -1047,6 +1047,43 @@ int orc_set_distance(orc_map* m, int32_t bx, int32_t by, int32_t bz, const float
   return 0;
 }
 
+int orc_put_block(orc_map* m, int32_t bx, int32_t by, int32_t bz, const float* distance, const float* weight,
+                  const uint8_t* color, const uint64_t* last_observed, const uint64_t* last_occupied, const uint8_t* flags,
+                  const uint32_t* sem_label, const float* likelihoods, uint8_t block_flags) {
+  Block* b = m->allocate({bx, by, bz});
+  const int K = m->cfg.num_labels;
+  for (int i = 0; i < m->nvox; ++i) {
+    if (distance) b->tsdf[i].distance = distance[i];
+    if (weight) b->tsdf[i].weight = weight[i];
+    if (color) {
+      b->tsdf[i].r = color[4 * i]; b->tsdf[i].g = color[4 * i + 1];
+      b->tsdf[i].b = color[4 * i + 2]; b->tsdf[i].a = color[4 * i + 3];
+    }
+    if (m->cfg.with_tracking) {
+      if (last_observed) b->tracking[i].last_observed = last_observed[i];
+      if (last_occupied) b->tracking[i].last_occupied = last_occupied[i];
+      if (flags) {
+        b->tracking[i].active = (flags[i] & 1) != 0;
+        b->tracking[i].ever_free = (flags[i] & 2) != 0;
+        b->tracking[i].to_remove = (flags[i] & 4) != 0;
+      }
+    }
+    if (m->cfg.with_semantics) {
+      if (flags) b->semantic[i].empty = (flags[i] & 8) == 0;
+      if (sem_label) b->semantic[i].semantic_label = sem_label[i];
+      if (likelihoods)
+        for (int k = 0; k < K; ++k)
+          b->likelihoods[static_cast<size_t>(i) * K + k] =
+              b->semantic[i].empty ? 0.f : likelihoods[static_cast<size_t>(k) * m->nvox + i];
+    }
+  }
+  b->updated = (block_flags & 1) != 0;
+  b->mesh_updated = (block_flags & 2) != 0;
+  b->tracking_updated = (block_flags & 4) != 0;
+  b->has_active_data = (block_flags & 8) != 0;
+  return 0;
+}
+
 int orc_get_block(const orc_map* m, int32_t bx, int32_t by, int32_t bz, float* distance, float* weight,
                   uint8_t* color, uint64_t* last_observed, uint64_t* last_occupied, uint8_t* flags,
                   uint32_t* sem_label, float* likelihoods, uint8_t* block_flags) {

@@ -213,6 +213,14 @@ int orc_get_block(const orc_map* m, int32_t bx, int32_t by, int32_t bz, float* d
 /* overwrite the TSDF distances of one block (oracle/ref_recipe/ref_harness.cpp: the reference's own pruning loop,
  * mesh_object_extractor.cpp:246-264, runs on a copy of an object map and hands its result back for meshing). 0 if found */
 int orc_set_distance(orc_map* m, int32_t bx, int32_t by, int32_t bz, const float* distance);
+/* write one whole block, allocating it if it is absent: the arrays orc_get_block hands out (any pointer may be NULL: that layer
+ * keeps its value; likelihoods [k][voxel], zeroed for a voxel whose flags lack bit3) and its block-flag byte.  Tracking / semantic
+ * layers the configuration lacks are ignored.  With it a test puts hand-built voxel content into the oracle -- the same content a
+ * checkpoint stream (khronos_amd/checkpoint.py) puts into a live device map.  returns 0 */
+int orc_put_block(orc_map* m, int32_t bx, int32_t by, int32_t bz, const float* distance, const float* weight,
+                  const uint8_t* color /*4n*/, const uint64_t* last_observed, const uint64_t* last_occupied,
+                  const uint8_t* flags, const uint32_t* sem_label, const float* likelihoods /* K*n, [k][voxel] */,
+                  uint8_t block_flags);
 /* ProjectiveIntegrator::computeLabel as a callback (the virtual hook a subclass overrides, contract: object_integrator.cpp:58-81):
  * called for every voxel measurement that survived the range / truncation tests, with its sdf and interpolation weights (pixels
  * (u, v)[4], weights[4]); returns 0 = skip this voxel, 1 = integrate, *label_out = the label to fuse (< 0: none).  With a hook

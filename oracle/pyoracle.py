@@ -130,6 +130,7 @@ def load():
     lib.orc_block_indices.argtypes = [vp, vp, i64]
     lib.orc_block_indices.restype = i64
     lib.orc_get_block.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 9
+    lib.orc_put_block.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 8 + [C.c_uint8]
     lib.orc_map_digest.argtypes = [vp, vp]
     lib.orc_map_digest.restype = None
     _lib = lib
@@ -351,6 +352,28 @@ class OracleMap:
         out = np.zeros(12, np.uint64)
         self.lib.orc_map_digest(self.h, _ptr(out))
         return out
+
+    def put_block(self, idx, block):
+        """orc_put_block: write one whole block (allocated if absent) from a dict shaped like get_block's; a missing / None
+        layer keeps its value, `block_flags` defaults to 0."""
+        nv, K = self.nvox, max(1, self.cfg.num_labels)
+        shapes = {"distance": (np.float32, (nv,)), "weight": (np.float32, (nv,)), "color": (np.uint8, (nv, 4)),
+                  "last_observed": (np.uint64, (nv,)), "last_occupied": (np.uint64, (nv,)), "flags": (np.uint8, (nv,)),
+                  "sem_label": (np.uint32, (nv,)), "likelihoods": (np.float32, (K, nv))}
+        a = {}
+        for name, (dt, shape) in shapes.items():
+            v = block.get(name)
+            a[name] = None if v is None else np.ascontiguousarray(v, dtype=dt).reshape(shape)
+        rc = self.lib.orc_put_block(self.h, int(idx[0]), int(idx[1]), int(idx[2]), _ptr(a["distance"]), _ptr(a["weight"]),
+                                    _ptr(a["color"]), _ptr(a["last_observed"]), _ptr(a["last_occupied"]), _ptr(a["flags"]),
+                                    _ptr(a["sem_label"]), _ptr(a["likelihoods"]), int(block.get("block_flags", 0)) & 0xF)
+        assert rc == 0
+
+    def put_blocks(self, indices, layers):
+        """put_block for every block of (indices, layers) as khronos_amd.checkpoint.pack takes / unpack returns them"""
+        from khronos_amd import checkpoint as ck
+        for i, idx in enumerate(np.asarray(indices, np.int32).reshape(-1, 3)):
+            self.put_block(idx, ck.block_view(layers, i))
 
     def get_block(self, idx, likelihoods=True):
         nv, K = self.nvox, max(1, self.cfg.num_labels)

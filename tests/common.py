@@ -222,3 +222,61 @@ class PinnedArray:
         if self.ptr:
             DeviceArray._hip.hipHostFree(self.ptr)
             self.ptr = None
+
+
+def tri_soup(mesh):
+    """a mesh as an order-independent list of triangles with their attributes (sorted by the nine coordinates)"""
+    t = mesh["points"].reshape(-1, 9)
+    lab = mesh["labels"].reshape(-1, 3)
+    st = mesh["stamps"].reshape(-1, 3)
+    col = mesh["colors"].reshape(-1, 12)
+    order = np.lexsort(t.T[::-1])
+    return t[order], lab[order], st[order], col[order]
+
+
+def record_mesh_halo_exchange(shards, only_mesh_updated, cap_req=4096, cap_rec=256):
+    """the whole-record mesh halo between `shards` (one context per rank): requests all-gathered, every rank answers what it owns,
+    answers all-gathered and imported.  Returns the number of valid records."""
+    reqs = [c.mesh_halo_requests(cap_req, only_mesh_updated=only_mesh_updated) for c in shards]
+    assert all(n <= cap_req for _, n in reqs)
+    all_req = np.concatenate([r for r, _ in reqs])
+    recs = np.concatenate([c.mesh_halo_export(all_req, cap_rec) for c in shards])
+    for c in shards:
+        c.mesh_halo_import(recs)
+    return int((recs[:, 2] == 1).sum())
+
+
+def compact_mesh_halo_exchange(shards, only_mesh_updated, cap=4096, cap_words=1 << 20):
+    """the compact mesh halo (khr_mesh_halo_requests_sorted / _plan / _answer / _adopt) between `shards`: the all-gather of the
+    requests and the all-to-all-v of the answers are device copies between the shards' buffers, with the counts khr_mesh_halo_plan
+    derives.  Returns (headers u64 [world, 8 * world], device buffers): the adopted answers stay where they are, so the buffers
+    are freed (DeviceArray.free) only after the shards' next generate_mesh."""
+    world = len(shards)
+    hw = 8 * world
+    row = (hw + cap) * 8
+    req = DeviceArray(np.zeros((world, hw + cap), np.uint64))
+    send = [DeviceArray(np.zeros(cap_words, np.uint32)) for _ in range(world)]
+    recv = [DeviceArray(np.zeros(cap_words, np.uint32)) for _ in range(world)]
+    try:
+        for r, c in enumerate(shards):
+            assert c.mesh_halo_requests_sorted(req.data_ptr() + r * row, cap, only_mesh_updated=only_mesh_updated) <= cap
+        headers = np.stack([req.read(r * row, hw * 8).view(np.uint64) for r in range(world)])
+        assert all(int(headers[r, 0]) == int(headers[r, 1:].sum()) for r in range(world))
+        plans = [c.mesh_halo_plan(headers) for c in shards]
+        for r, c in enumerate(shards):
+            n_ans = c.mesh_halo_answer(req.data_ptr(), cap, headers, send[r].data_ptr(), cap_words)
+            assert n_ans == sum(int(headers[q, 8 * r + k]) for q in range(world) for k in range(1, 8))
+            c.sync()
+        for r in range(world):
+            rc_, rd = plans[r][2], plans[r][3]
+            for q in range(world):
+                assert int(plans[q][0][r]) == int(rc_[q]), "what q sends to r is what r expects from q"
+                recv[r].copy_from(4 * int(rd[q]), send[q], 4 * int(plans[q][1][r]), 4 * int(rc_[q]))
+        for r, c in enumerate(shards):
+            c.mesh_halo_adopt(req.data_ptr() + r * row, headers[r], recv[r].data_ptr(), plans[r][3])
+            c.sync()
+        return headers, (req, send, recv)
+    except BaseException:
+        for d in [req] + send + recv:
+            d.free()
+        raise
