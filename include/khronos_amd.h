@@ -838,6 +838,10 @@ int khr_tick_live_bound(khr_ctx* ctx, int64_t* out_device, int n_out, int index)
  * Accumulates between khr_timing_reset calls; returns total ms and launch count. */
 /* development probe: the debug buffer (KHR_DEBUG & 16: timestamps of the motion detector's last k_md_comp_lds launch) */
 int khr_debug_read(khr_ctx* ctx, unsigned long long* out, int64_t n);
+/* development probe: how many HIP resources the library's owners hold in this process right now -- out[0] device buffers,
+ * [1] page-locked blocks, [2] events, [3] streams.  A context, snapshot, frame copy or ray verificator that has been destroyed
+ * leaves all four where they were before it was created (the leak tests). */
+int khr_debug_live_resources(int64_t out[4]);
 int khr_timing_enable(khr_ctx* ctx, int enable);
 int khr_timing_reset(khr_ctx* ctx);
 int khr_timing_get(khr_ctx* ctx, int which, double* total_ms, uint64_t* launches);

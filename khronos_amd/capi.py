@@ -141,6 +141,7 @@ EXPORTS = [
     "khr_map_slice", "khr_slice_voxel_z", "khr_render_view", "khr_query_points",
     "khr_align_linearize", "khr_align_frame",
     "khr_checkpoint_size", "khr_checkpoint_save", "khr_checkpoint_load", "khr_checkpoint_inspect",
+    "khr_debug_live_resources",
 ]
 
 _lib = None
@@ -266,6 +267,7 @@ def load_library():
     lib.khr_fetch_mesh.restype = i64
     lib.khr_fetch_mesh_into.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.khr_debug_read.argtypes = [vp, vp, i64]
+    lib.khr_debug_live_resources.argtypes = [C.POINTER(i64)]
     lib.khr_tick_ingest.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
     lib.khr_tick_seed_counts.argtypes = [vp, vp, i32]
     lib.khr_tick_live_bound.argtypes = [vp, vp, i32, i32]
@@ -301,6 +303,15 @@ def default_config(**overrides):
             raise KeyError(k)
         setattr(cfg, k, v)
     return cfg
+
+
+def live_resources():
+    """Process-wide counts of the HIP resources the library holds right now: (device buffers, page-locked blocks, events, streams)."""
+    out = (C.c_int64 * 4)()
+    rc = load_library().khr_debug_live_resources(out)
+    if rc != 0:
+        raise KhronosAmdError("khr_debug_live_resources failed (%d)" % rc)
+    return tuple(out)
 
 
 def _ptr(a):

@@ -12,15 +12,15 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/khronos_amd.h"
 #include "khr_device.h"
+#include "khr_owned.h"  // DevBuf / Stream; declares khr_set_last_error (khronos_amd.hip), which rvFail reports through
 
 using namespace khr;
-
-extern "C" void khr_set_last_error(const char* text);  // khronos_amd.hip
 
 namespace {
 
@@ -155,21 +155,18 @@ __global__ __launch_bounds__(256) void k_rv_query_keys(const float* __restrict__
   idx[q] = q;
 }
 
+// at least `need` elements (x 2, at least 1024); the first `keep` elements survive a growth
 template <typename T>
-int growBuffer(T** buf, size_t* cap, size_t need, size_t keep, hipStream_t stream) {
-  if (need <= *cap) return KHR_OK;
-  size_t nc = std::max<size_t>(need, std::max<size_t>(1024, *cap * 2));
-  T* nb = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&nb), nc * sizeof(T));
-  if (e != hipSuccess) return rvFail(KHR_ENOMEM, "hipMalloc", e);
-  if (*buf && keep) {
-    e = hipMemcpyAsync(nb, *buf, keep * sizeof(T), hipMemcpyDeviceToDevice, stream);
+int growBuffer(DevBuf<T>& buf, size_t need, size_t keep, hipStream_t stream) {
+  if (need <= buf.count()) return KHR_OK;
+  DevBuf<T> nb;
+  if (int rc = nb.alloc(std::max<size_t>(need, std::max<size_t>(1024, buf.count() * 2)))) return rc;  // (the owner left the text)
+  if (buf && keep) {
+    hipError_t e = hipMemcpyAsync(nb, buf, keep * sizeof(T), hipMemcpyDeviceToDevice, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) { hipFree(nb); return rvFail(KHR_EDEVICE, "buffer growth copy", e); }
+    if (e != hipSuccess) return rvFail(KHR_EDEVICE, "buffer growth copy", e);
   }
-  if (*buf) hipFree(*buf);
-  *buf = nb;
-  *cap = nc;
+  buf = std::move(nb);
   return KHR_OK;
 }
 
@@ -181,46 +178,49 @@ static int fillStamps(khr_rayver* rv);
 struct khr_rayver {
   float block_size = 1.f, inv = 1.f, radial_tol = 0.1f, depth_tol = 0.1f;
   int device = 0;
-  hipStream_t stream = nullptr;
+  Stream stream;  // (declared before the buffers: destroyed after them)
   // rays
-  uint64_t* d_stamp = nullptr; size_t cap_stamp = 0;
-  float* d_src = nullptr; size_t cap_src = 0;
-  float* d_tgt = nullptr; size_t cap_tgt = 0;
+  DevBuf<uint64_t> d_stamp;
+  DevBuf<float> d_src;
+  DevBuf<float> d_tgt;
   size_t n_rays = 0;
   // sorted, unique (block key, ray index) pairs + a second set of buffers for sort / compaction
-  uint64_t* d_keys[2] = {nullptr, nullptr}; size_t cap_keys[2] = {0, 0};
-  uint32_t* d_vals[2] = {nullptr, nullptr}; size_t cap_vals[2] = {0, 0};
+  DevBuf<uint64_t> d_keys[2];
+  DevBuf<uint32_t> d_vals[2];
   size_t n_pairs = 0;
-  uint32_t* d_u32a = nullptr; size_t cap_u32a = 0;  // counts / flags
-  uint32_t* d_u32b = nullptr; size_t cap_u32b = 0;  // offsets
-  void* d_temp = nullptr; size_t cap_temp = 0;
+  DevBuf<uint32_t> d_u32a;  // counts / flags
+  DevBuf<uint32_t> d_u32b;  // offsets
+  DevBuf<uint8_t> d_temp;   // hipcub's scratch
   // last query (khr_rv_check -> khr_rv_check_stamps)
-  float* d_pts = nullptr; size_t cap_pts = 0;
-  uint64_t* d_t0 = nullptr; size_t cap_t0 = 0;
-  uint64_t* d_t1 = nullptr; size_t cap_t1 = 0;
-  uint32_t* d_np = nullptr; size_t cap_np = 0;
-  uint32_t* d_na = nullptr; size_t cap_na = 0;
-  uint32_t* d_op = nullptr; size_t cap_op = 0;
-  uint32_t* d_oa = nullptr; size_t cap_oa = 0;
-  uint64_t* d_outp = nullptr; size_t cap_outp = 0;
-  uint64_t* d_outa = nullptr; size_t cap_outa = 0;
-  uint64_t* d_qkey[2] = {nullptr, nullptr}; size_t cap_qkey[2] = {0, 0};
-  uint32_t* d_qidx[2] = {nullptr, nullptr}; size_t cap_qidx[2] = {0, 0};
+  DevBuf<float> d_pts;
+  DevBuf<uint64_t> d_t0;
+  DevBuf<uint64_t> d_t1;
+  DevBuf<uint32_t> d_np, d_na, d_op, d_oa;
+  DevBuf<uint64_t> d_outp, d_outa;
+  DevBuf<uint64_t> d_qkey[2];
+  DevBuf<uint32_t> d_qidx[2];
   size_t last_m = 0;
   uint64_t last_present = 0, last_absent = 0;
   bool stamps_filled = false;  // d_outp / d_outa hold the stamp lists of the latest check
   // khr_rv_detect_changes
-  uint8_t* d_fwd = nullptr; size_t cap_fwd = 0;
-  uint64_t* d_vote = nullptr; size_t cap_vote = 0;  // [2 * m] closest_absent, furthest_persistent
-  uint8_t* d_vflags = nullptr; size_t cap_vflags = 0;
+  DevBuf<uint8_t> d_fwd;
+  DevBuf<uint64_t> d_vote;  // [2 * m] closest_absent, furthest_persistent
+  DevBuf<uint8_t> d_vflags;
 };
+
+// hipcub's scratch: at least *tb bytes; *tb = what there is.  A failure returns KHR_EDEVICE, as this growth always has, with the owner's text
+static int rvTemp(khr_rayver* rv, size_t* tb) {
+  if (rv->d_temp.reserve(*tb)) return KHR_EDEVICE;
+  *tb = rv->d_temp.count();
+  return KHR_OK;
+}
 
 // the stamp lists of the latest khr_rv_check, materialised on the device (per point at the offsets of the exclusive sums)
 static int fillStamps(khr_rayver* rv) {
   if (rv->stamps_filled) return KHR_OK;
   int rc = KHR_OK;
-  if ((rc = growBuffer(&rv->d_outp, &rv->cap_outp, std::max<size_t>(rv->last_present, 1), 0, rv->stream))) return rc;
-  if ((rc = growBuffer(&rv->d_outa, &rv->cap_outa, std::max<size_t>(rv->last_absent, 1), 0, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_outp, std::max<size_t>(rv->last_present, 1), 0, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_outa, std::max<size_t>(rv->last_absent, 1), 0, rv->stream))) return rc;
   const size_t M = rv->last_m;
   const int grid = static_cast<int>((M + 255) / 256);
   hipLaunchKernelGGL((k_rv_check<true>), dim3(grid), dim3(256), 0, rv->stream, rv->d_pts, rv->d_t0, rv->d_t1, static_cast<uint32_t>(M),
@@ -345,17 +345,14 @@ int khr_rv_create(float block_size, float radial_tolerance, float depth_toleranc
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return rvFail(KHR_EDEVICE, "no HIP device available (no CPU fallback)");
   if (device < 0 || device >= ndev) return rvFail(KHR_EINVAL, "device out of range");
   RV_TRY(hipSetDevice(device));
-  auto* rv = new khr_rayver();
+  auto rv = std::make_unique<khr_rayver>();
   rv->block_size = block_size;
   rv->inv = 1.f / block_size;  // spatial_hash::Grid(block_size)
   rv->radial_tol = radial_tolerance;
   rv->depth_tol = depth_tolerance;
   rv->device = device;
-  if (hipStreamCreateWithFlags(&rv->stream, hipStreamNonBlocking) != hipSuccess) {
-    delete rv;
-    return rvFail(KHR_EDEVICE, "hipStreamCreate failed");
-  }
-  *out = rv;
+  if (rv->stream.create(hipStreamNonBlocking)) return rvFail(KHR_EDEVICE, "hipStreamCreate failed");  // (this call's text, as before)
+  *out = rv.release();
   return KHR_OK;
 }
 
@@ -363,17 +360,6 @@ void khr_rv_destroy(khr_rayver* rv) {
   if (!rv) return;
   hipSetDevice(rv->device);
   hipStreamSynchronize(rv->stream);
-  for (void* p : {static_cast<void*>(rv->d_stamp), static_cast<void*>(rv->d_src), static_cast<void*>(rv->d_tgt),
-                  static_cast<void*>(rv->d_keys[0]), static_cast<void*>(rv->d_keys[1]), static_cast<void*>(rv->d_vals[0]),
-                  static_cast<void*>(rv->d_vals[1]), static_cast<void*>(rv->d_u32a), static_cast<void*>(rv->d_u32b), rv->d_temp,
-                  static_cast<void*>(rv->d_pts), static_cast<void*>(rv->d_t0), static_cast<void*>(rv->d_t1),
-                  static_cast<void*>(rv->d_np), static_cast<void*>(rv->d_na), static_cast<void*>(rv->d_op),
-                  static_cast<void*>(rv->d_oa), static_cast<void*>(rv->d_outp), static_cast<void*>(rv->d_outa),
-                  static_cast<void*>(rv->d_qkey[0]), static_cast<void*>(rv->d_qkey[1]), static_cast<void*>(rv->d_qidx[0]),
-                  static_cast<void*>(rv->d_qidx[1]), static_cast<void*>(rv->d_fwd), static_cast<void*>(rv->d_vote),
-                  static_cast<void*>(rv->d_vflags)})
-    if (p) hipFree(p);
-  hipStreamDestroy(rv->stream);
   delete rv;
 }
 
@@ -396,15 +382,15 @@ int khr_rv_add_rays(khr_rayver* rv, int64_t n, const uint64_t* stamps, const flo
   const size_t first = rv->n_rays, total = first + static_cast<size_t>(n);
   if (total > 0xfffffff0ull) return rvFail(KHR_ENOMEM, "more than 2^32 rays");
   int rc = KHR_OK;
-  if ((rc = growBuffer(&rv->d_stamp, &rv->cap_stamp, total, first, rv->stream))) return rc;
-  if ((rc = growBuffer(&rv->d_src, &rv->cap_src, 3 * total, 3 * first, rv->stream))) return rc;
-  if ((rc = growBuffer(&rv->d_tgt, &rv->cap_tgt, 3 * total, 3 * first, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_stamp, total, first, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_src, 3 * total, 3 * first, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_tgt, 3 * total, 3 * first, rv->stream))) return rc;
   RV_TRY(hipMemcpyAsync(rv->d_stamp + first, stamps, sizeof(uint64_t) * n, hipMemcpyHostToDevice, rv->stream));
   RV_TRY(hipMemcpyAsync(rv->d_src + 3 * first, sources, sizeof(float) * 3 * n, hipMemcpyHostToDevice, rv->stream));
   RV_TRY(hipMemcpyAsync(rv->d_tgt + 3 * first, targets, sizeof(float) * 3 * n, hipMemcpyHostToDevice, rv->stream));
   // samples per new ray -> offsets
-  if ((rc = growBuffer(&rv->d_u32a, &rv->cap_u32a, static_cast<size_t>(n) + 1, 0, rv->stream))) return rc;
-  if ((rc = growBuffer(&rv->d_u32b, &rv->cap_u32b, static_cast<size_t>(n) + 1, 0, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_u32a, static_cast<size_t>(n) + 1, 0, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_u32b, static_cast<size_t>(n) + 1, 0, rv->stream))) return rc;
   const float step = rv->block_size / 4;
   const int grid = static_cast<int>((n + 255) / 256);
   RV_TRY(hipMemsetAsync(rv->d_u32a + n, 0, sizeof(uint32_t), rv->stream));
@@ -413,14 +399,7 @@ int khr_rv_add_rays(khr_rayver* rv, int64_t n, const uint64_t* stamps, const flo
   auto scan = [&](const uint32_t* in, uint32_t* outp, size_t count) -> int {
     size_t tb = 0;
     RV_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, outp, static_cast<int>(count), rv->stream));
-    if (tb > rv->cap_temp) {
-      if (rv->d_temp) hipFree(rv->d_temp);
-      rv->d_temp = nullptr;
-      rv->cap_temp = 0;
-      RV_TRY(hipMalloc(&rv->d_temp, tb));
-      rv->cap_temp = tb;
-    }
-    tb = rv->cap_temp;
+    if (int rct = rvTemp(rv, &tb)) return rct;
     RV_TRY(hipcub::DeviceScan::ExclusiveSum(rv->d_temp, tb, in, outp, static_cast<int>(count), rv->stream));
     return KHR_OK;
   };
@@ -430,10 +409,10 @@ int khr_rv_add_rays(khr_rayver* rv, int64_t n, const uint64_t* stamps, const flo
   RV_TRY(hipStreamSynchronize(rv->stream));
   const size_t old_pairs = rv->n_pairs, all = old_pairs + n_new;
   if (all > 0xfffffff0ull) return rvFail(KHR_ENOMEM, "more than 2^32 (block, ray) pairs");
-  if ((rc = growBuffer(&rv->d_keys[0], &rv->cap_keys[0], all, old_pairs, rv->stream))) return rc;
-  if ((rc = growBuffer(&rv->d_vals[0], &rv->cap_vals[0], all, old_pairs, rv->stream))) return rc;
-  if ((rc = growBuffer(&rv->d_keys[1], &rv->cap_keys[1], all, 0, rv->stream))) return rc;
-  if ((rc = growBuffer(&rv->d_vals[1], &rv->cap_vals[1], all, 0, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_keys[0], all, old_pairs, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_vals[0], all, old_pairs, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_keys[1], all, 0, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_vals[1], all, 0, rv->stream))) return rc;
   hipLaunchKernelGGL((k_rv_march<true>), dim3(grid), dim3(256), 0, rv->stream, rv->d_src, rv->d_tgt, static_cast<uint32_t>(first),
                      static_cast<uint32_t>(n), rv->inv, step, nullptr, rv->d_u32b, rv->d_keys[0] + old_pairs, rv->d_vals[0] + old_pairs);
   RV_TRY(hipGetLastError());
@@ -442,22 +421,15 @@ int khr_rv_add_rays(khr_rayver* rv, int64_t n, const uint64_t* stamps, const flo
   // stable sort by block key: within a block the pairs stay in ray order (old rays first, then the new ones)
   {
     size_t tb = 0;
-    RV_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, rv->d_keys[0], rv->d_keys[1], rv->d_vals[0], rv->d_vals[1],
+    RV_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, rv->d_keys[0].get(), rv->d_keys[1].get(), rv->d_vals[0].get(), rv->d_vals[1].get(),
                                               static_cast<int>(all), 0, 63, rv->stream));
-    if (tb > rv->cap_temp) {
-      if (rv->d_temp) hipFree(rv->d_temp);
-      rv->d_temp = nullptr;
-      rv->cap_temp = 0;
-      RV_TRY(hipMalloc(&rv->d_temp, tb));
-      rv->cap_temp = tb;
-    }
-    tb = rv->cap_temp;
-    RV_TRY(hipcub::DeviceRadixSort::SortPairs(rv->d_temp, tb, rv->d_keys[0], rv->d_keys[1], rv->d_vals[0], rv->d_vals[1],
+    if (int rct = rvTemp(rv, &tb)) return rct;
+    RV_TRY(hipcub::DeviceRadixSort::SortPairs(rv->d_temp, tb, rv->d_keys[0].get(), rv->d_keys[1].get(), rv->d_vals[0].get(), rv->d_vals[1].get(),
                                               static_cast<int>(all), 0, 63, rv->stream));
   }
   // set semantics (block_seen_by_rays_[index].insert): drop repeated (block, ray) pairs
-  if ((rc = growBuffer(&rv->d_u32a, &rv->cap_u32a, all + 1, 0, rv->stream))) return rc;
-  if ((rc = growBuffer(&rv->d_u32b, &rv->cap_u32b, all + 1, 0, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_u32a, all + 1, 0, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_u32b, all + 1, 0, rv->stream))) return rc;
   const int g2 = static_cast<int>((all + 255) / 256);
   RV_TRY(hipMemsetAsync(rv->d_u32a + all, 0, sizeof(uint32_t), rv->stream));
   hipLaunchKernelGGL(k_rv_unique_flag, dim3(g2), dim3(256), 0, rv->stream, rv->d_keys[1], rv->d_vals[1], static_cast<uint32_t>(all), rv->d_u32a);
@@ -484,13 +456,13 @@ int khr_rv_check(khr_rayver* rv, int64_t m, const float* points, const uint64_t*
   RV_TRY(hipSetDevice(rv->device));
   int rc = KHR_OK;
   const size_t M = static_cast<size_t>(m);
-  if ((rc = growBuffer(&rv->d_pts, &rv->cap_pts, 3 * M, 0, rv->stream))) return rc;
-  if ((rc = growBuffer(&rv->d_t0, &rv->cap_t0, M, 0, rv->stream))) return rc;
-  if ((rc = growBuffer(&rv->d_t1, &rv->cap_t1, M, 0, rv->stream))) return rc;
-  if ((rc = growBuffer(&rv->d_np, &rv->cap_np, M + 1, 0, rv->stream))) return rc;
-  if ((rc = growBuffer(&rv->d_na, &rv->cap_na, M + 1, 0, rv->stream))) return rc;
-  if ((rc = growBuffer(&rv->d_op, &rv->cap_op, M + 1, 0, rv->stream))) return rc;
-  if ((rc = growBuffer(&rv->d_oa, &rv->cap_oa, M + 1, 0, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_pts, 3 * M, 0, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_t0, M, 0, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_t1, M, 0, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_np, M + 1, 0, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_na, M + 1, 0, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_op, M + 1, 0, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_oa, M + 1, 0, rv->stream))) return rc;
   RV_TRY(hipMemcpyAsync(rv->d_pts, points, sizeof(float) * 3 * M, hipMemcpyHostToDevice, rv->stream));
   RV_TRY(hipMemcpyAsync(rv->d_t0, earliest, sizeof(uint64_t) * M, hipMemcpyHostToDevice, rv->stream));
   RV_TRY(hipMemcpyAsync(rv->d_t1, latest, sizeof(uint64_t) * M, hipMemcpyHostToDevice, rv->stream));
@@ -499,24 +471,17 @@ int khr_rv_check(khr_rayver* rv, int64_t m, const float* points, const uint64_t*
   const int grid = static_cast<int>((M + 255) / 256);
   // visit order: queries sorted by block key
   for (int b = 0; b < 2; ++b) {
-    if ((rc = growBuffer(&rv->d_qkey[b], &rv->cap_qkey[b], M, 0, rv->stream))) return rc;
-    if ((rc = growBuffer(&rv->d_qidx[b], &rv->cap_qidx[b], M, 0, rv->stream))) return rc;
+    if ((rc = growBuffer(rv->d_qkey[b], M, 0, rv->stream))) return rc;
+    if ((rc = growBuffer(rv->d_qidx[b], M, 0, rv->stream))) return rc;
   }
   hipLaunchKernelGGL(k_rv_query_keys, dim3(grid), dim3(256), 0, rv->stream, rv->d_pts, static_cast<uint32_t>(M), rv->inv, rv->d_qkey[0],
                      rv->d_qidx[0]);
   {
     size_t tb = 0;
-    RV_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, rv->d_qkey[0], rv->d_qkey[1], rv->d_qidx[0], rv->d_qidx[1], static_cast<int>(M),
+    RV_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, rv->d_qkey[0].get(), rv->d_qkey[1].get(), rv->d_qidx[0].get(), rv->d_qidx[1].get(), static_cast<int>(M),
                                               0, 63, rv->stream));
-    if (tb > rv->cap_temp) {
-      if (rv->d_temp) hipFree(rv->d_temp);
-      rv->d_temp = nullptr;
-      rv->cap_temp = 0;
-      RV_TRY(hipMalloc(&rv->d_temp, tb));
-      rv->cap_temp = tb;
-    }
-    tb = rv->cap_temp;
-    RV_TRY(hipcub::DeviceRadixSort::SortPairs(rv->d_temp, tb, rv->d_qkey[0], rv->d_qkey[1], rv->d_qidx[0], rv->d_qidx[1], static_cast<int>(M),
+    if (int rct = rvTemp(rv, &tb)) return rct;
+    RV_TRY(hipcub::DeviceRadixSort::SortPairs(rv->d_temp, tb, rv->d_qkey[0].get(), rv->d_qkey[1].get(), rv->d_qidx[0].get(), rv->d_qidx[1].get(), static_cast<int>(M),
                                               0, 63, rv->stream));
   }
   hipLaunchKernelGGL((k_rv_check<false>), dim3(grid), dim3(256), 0, rv->stream, rv->d_pts, rv->d_t0, rv->d_t1, static_cast<uint32_t>(M),
@@ -528,14 +493,7 @@ int khr_rv_check(khr_rayver* rv, int64_t m, const float* points, const uint64_t*
     const uint32_t* in = which ? rv->d_na : rv->d_np;
     uint32_t* outp = which ? rv->d_oa : rv->d_op;
     RV_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, outp, static_cast<int>(M + 1), rv->stream));
-    if (tb > rv->cap_temp) {
-      if (rv->d_temp) hipFree(rv->d_temp);
-      rv->d_temp = nullptr;
-      rv->cap_temp = 0;
-      RV_TRY(hipMalloc(&rv->d_temp, tb));
-      rv->cap_temp = tb;
-    }
-    tb = rv->cap_temp;
+    if (int rct = rvTemp(rv, &tb)) return rct;
     RV_TRY(hipcub::DeviceScan::ExclusiveSum(rv->d_temp, tb, in, outp, static_cast<int>(M + 1), rv->stream));
   }
   uint32_t tp = 0, ta = 0;
@@ -585,10 +543,10 @@ int khr_rv_detect_changes(khr_rayver* rv, float temporal_resolution, int64_t win
   int rc = fillStamps(rv);
   if (rc) return rc;
   const size_t M = rv->last_m;
-  if ((rc = growBuffer(&rv->d_vote, &rv->cap_vote, 2 * M, 0, rv->stream))) return rc;
-  if ((rc = growBuffer(&rv->d_vflags, &rv->cap_vflags, M, 0, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_vote, 2 * M, 0, rv->stream))) return rc;
+  if ((rc = growBuffer(rv->d_vflags, M, 0, rv->stream))) return rc;
   if (forward) {
-    if ((rc = growBuffer(&rv->d_fwd, &rv->cap_fwd, M, 0, rv->stream))) return rc;
+    if ((rc = growBuffer(rv->d_fwd, M, 0, rv->stream))) return rc;
     RV_TRY(hipMemcpyAsync(rv->d_fwd, forward, M, hipMemcpyHostToDevice, rv->stream));
   }
   hipLaunchKernelGGL(k_rv_vote, dim3(static_cast<uint32_t>(M)), dim3(64), 0, rv->stream, rv->d_op, rv->d_oa, rv->d_outp, rv->d_outa,

@@ -29,6 +29,7 @@
 
 #include "../../include/khronos_amd.h"
 #include "khr_device.h"
+#include "khr_owned.h"
 #include "khr_kernels_aux.h"
 #include "khr_kernels_fusion.h"
 #include "khr_kernels_fuse.h"
@@ -61,8 +62,19 @@ int fail(int code, const char* fmt, ...) {
     if (_e != hipSuccess)                                                                          \
       return fail(KHR_EDEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
   } while (0)
+#define KHR_TRY(expr)                  \
+  do {                                 \
+    if (int _rc = (expr)) return _rc;  \
+  } while (0)
+
+// a chain of allocations that stops at its first failure: the argument is evaluated only while `rc` is still KHR_OK
+#define KHR_CHAIN(...)                       \
+  do {                                       \
+    if (rc == KHR_OK) rc = (__VA_ARGS__);    \
+  } while (0)
 
 struct FrameSlot {
+  // the slot's own planes: views into blocks the context's `allocs` own (khr_create)
   float* depth = nullptr;
   float* range = nullptr;
   uint32_t* rgba = nullptr;
@@ -97,7 +109,7 @@ struct FrameSlot {
 
 struct TimingRec {
   int which;
-  hipEvent_t a, b;
+  Event a, b;
 };
 
 constexpr int kNumTimers = 13;  // 0..7: kernel groups; 8..12: single kernels (k_marching_cubes count / emit, k_tracking_update, k_ever_free, k_snapshot_pack)
@@ -112,17 +124,25 @@ struct khr_ctx {
   DevParams p{};
   DevMap m{};
   int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+  // Lifetime: a member either owns its resource (DevBuf / PinnedBuf / Event / Stream, khr_owned.h) or is a view of memory another
+  // member owns and says so.  The streams come first, so that they are destroyed last: behind every buffer and event.
+  Stream stream;  // the context's own, or the caller's (khr_set_stream: referred to, not owned)
   // second stream for the object detector / voxel-set kernels: they only read the frame, so they run beside the
   // volumetric kernels of the same frame instead of in front of them.  ev_aux orders it behind the main stream where
   // it has to be (the frame's ingest, a painted dynamic image), ev_aux_done orders consumers of the object image behind it.
-  hipStream_t aux_stream = nullptr;
-  hipEvent_t ev_aux = nullptr, ev_aux_done = nullptr;
+  Stream aux_stream;
+  Stream copy_stream;  // khr_snapshot_download_begin: device -> host copies beside the frames' kernels
+  Stream snap_stream;  // khr_process_frame: the output's snapshot beside its marching cubes (both only read the voxel layers)
+  Stream mc_stream;    // khr_process_frame: the output's marching cubes beside the tracking pass
+  // pinned host input (KHR_PF_INPUT_PINNED / khr_ingest_ahead_host): the frame's three planes travel on a stream of their own
+  // into the ring slot, the ingest kernel waits for them on the device; the host does not wait (round 5)
+  Stream h2d_stream;
+  Event ev_aux, ev_aux_done;
   // batches queued on the auxiliary stream are numbered; aux_seq_done = the latest one the host KNOWS to be complete
   // (a ticket it waited for, an idle stream): a frame slot is only re-ingested when its last batch is
   uint64_t aux_seq_issued = 0, aux_seq_done = 0, obj_seq = 0, cv_seq[2] = {0, 0};
-  std::vector<void*> allocs;
+  std::vector<DevBuf<uint8_t>> allocs;  // every buffer that lives as long as the context (devAlloc); the raw pointers below without
+                                        // an owner type, DevMap m, MeshBuffers mesh[] and the frame slots' planes are views into these
   std::vector<FrameSlot> slots;
   int next_slot = 0;
   std::unique_ptr<std::atomic<int>[]> slot_leases;  // khr_retain_slot: frames somebody still reads are not overwritten
@@ -136,8 +156,7 @@ struct khr_ctx {
   uint32_t* d_tick_work = nullptr;
   uint32_t* d_tick_counts = nullptr;
   uint32_t* d_tick_seeds = nullptr;
-  uint32_t* h_tick = nullptr;
-  uint32_t* d_tick_host = nullptr;
+  PinnedBuf<uint32_t> h_tick;
   uint32_t tick_ticket = 0;
   std::vector<uint32_t> tick_seed_host;  // seed counts of the latest khr_tick_ingest (collected lazily)
   int tick_seed_n = 0, tick_seed_collected = 0;
@@ -150,10 +169,8 @@ struct khr_ctx {
   bool defer_fold = false, fold_pending = false;  // k_fuse's item records: folded by the next k_tracking_select instead of k_fuse_fold
   int stream_priority = 0;  // +1 the active window's streams (highest), -1 an object mini-map's (lowest), 0 default (env KHR_STREAM_PRIORITY=0)
   unsigned char* d_fuse_sink = nullptr;  // k_fuse: one 256-byte sink line per wave (kUpdateStatSlots workgroups x 16 waves)
-  uint32_t* d_pix_scratch = nullptr;  // khr_pixel_iou: mask image + counters (allocated on first use)
-  size_t pix_words = 0;
-  uint8_t* d_inst = nullptr;          // khr_forward_instances: per-id accumulators
-  size_t inst_bytes = 0;
+  DevBuf<uint32_t> d_pix_scratch;  // khr_pixel_iou: mask image + counters (allocated on first use)
+  DevBuf<uint8_t> d_inst;          // khr_forward_instances: per-id accumulators
   uint4* d_work4 = nullptr;       // update list of k_fuse: two descriptor arrays of item_cap entries (FuseList)
   uint4* d_tick_work4 = nullptr;  // tick path: two arrays per camera
   // tick path, one-launch form (tickUnion): the cameras' arguments on the device, one byte per wave item (camera bits)
@@ -162,7 +179,20 @@ struct khr_ctx {
   bool tick_mask_dirty = false;
   uint32_t item_cap = 0;          // max_blocks x wave items per block
   // snapshots of the updated blocks (khr_snapshot_updated): arenas of released snapshots are reused
-  struct SnapArena { uint8_t* ptr; size_t bytes; volatile uint32_t* h_count; uint32_t* d_count_host_view; };
+  struct SnapArena {
+    DevBuf<uint8_t> buf;        // the packed blocks
+    PinnedBuf<uint32_t> count;  // {blocks found, ticket}, written by the pack kernel through the device view
+    volatile uint32_t* h_count() const { return count.get(); }
+    int alloc(size_t bytes) {
+      if (buf.alloc(bytes)) return fail(KHR_ENOMEM, "snapshot arena of %zu bytes", bytes);
+      if (count.alloc(16)) {
+        buf.reset();
+        return fail(KHR_ENOMEM, "snapshot pinned words");
+      }
+      count[0] = count[1] = 0;
+      return KHR_OK;
+    }
+  };
   // shared with the snapshots handed out: an output may outlive its ActiveWindow in the consumer's queue, so a release
   // after khr_destroy must still be safe (it then frees the arena instead of pooling it)
   struct SnapPool {
@@ -174,53 +204,48 @@ struct khr_ctx {
   // khr_frame_copy: device blocks of 16 bytes per pixel, pooled like the snapshot arenas (a copy may outlive the context)
   struct FramePool {
     std::mutex mu;
-    std::vector<std::pair<uint8_t*, size_t>> free;
+    std::vector<DevBuf<uint8_t>> free;
     bool dead = false;
   };
   std::shared_ptr<FramePool> frame_pool = std::make_shared<FramePool>();
   khr_snapshot* pending_snapshot = nullptr;  // taken inside khr_process_frame(KHR_PF_SNAPSHOT)
-  hipStream_t copy_stream = nullptr;         // khr_snapshot_download_begin: device -> host copies beside the frames' kernels
-  hipStream_t snap_stream = nullptr;         // khr_process_frame: the output's snapshot beside its marching cubes (both only read the voxel layers)
-  hipStream_t snap_stream_override = nullptr;  // (set around khr_snapshot_updated by khr_process_frame)
-  hipEvent_t ev_snap_fork = nullptr, ev_snap_join = nullptr;
-  hipStream_t mc_stream = nullptr;           // khr_process_frame: the output's marching cubes beside the tracking pass
-  hipEvent_t ev_mc_fork = nullptr, ev_mc_join = nullptr;
+  hipStream_t snap_stream_override = nullptr;  // view (set around khr_snapshot_updated by khr_process_frame)
+  Event ev_snap_fork, ev_snap_join;
+  Event ev_mc_fork, ev_mc_join;
   bool fork_after_select = false;            // trackingPhase records ev_mc_fork behind k_tracking_select
   // upper bound of the blocks an explicitly allocated map holds (khr_allocate_blocks since the last khr_reset_map; 0 =
   // unknown): the update kernel of an `allocate = false` integration (object mini-maps) sizes its persistent grid from it
   // instead of filling the chip with workgroups that find no item
   uint64_t explicit_blocks = 0;
-  uint4* d_multi_list = nullptr;     // integrateUpdateMulti: the items by frame count (k_multi_order) + 4 counters behind them
-  uint32_t* d_frame_bits = nullptr;  // integrateUpdateMulti: k_multi_cull's (item, frame) bits
-  size_t frame_bits_words = 0;
-  FuseFrame* h_frames = nullptr;  // integrateUpdateMulti: per-frame arguments, pinned staging + device array
-  FuseFrame* d_frames = nullptr;
-  hipEvent_t ev_frames = nullptr;
+  DevBuf<uint4> d_multi_list;       // integrateUpdateMulti: the items by frame count (k_multi_order) + 4 counters behind them
+  DevBuf<uint32_t> d_frame_bits;    // integrateUpdateMulti: k_multi_cull's (item, frame) bits
+  PinnedBuf<FuseFrame> h_frames;    // integrateUpdateMulti: per-frame arguments, pinned staging + device array
+  DevBuf<FuseFrame> d_frames;
+  Event ev_frames;
   uint32_t snap_ticket = 0;
   uint32_t wpb = 0;               // wave items per block of this context's k_fuse instantiation
   int fuse_zsplit = 2;            // z ranges per x-y patch of that instantiation
   // remote halo (multi-GPU): records gathered from the other ranks + their index
-  uint64_t* d_halo_recs = nullptr;
-  const uint64_t* halo_view = nullptr;  // records in use: d_halo_recs, or the caller's device buffer (imported in place)
-  uint64_t* d_halo_keys = nullptr;
-  uint32_t* d_halo_vals = nullptr;
-  uint32_t halo_cap_total = 0, halo_recs_cap = 0, halo_mask = 0, halo_n = 0;
+  DevBuf<uint64_t> d_halo_recs;
+  const uint64_t* halo_view = nullptr;  // view, records in use: d_halo_recs, or the caller's device buffer (imported in place)
+  DevBuf<uint64_t> d_halo_keys;
+  DevBuf<uint32_t> d_halo_vals;
+  uint32_t halo_cap_total = 0, halo_mask = 0, halo_n = 0;
   // remote mesh halo (three low voxel planes of blocks owned by other ranks)
-  uint32_t* d_mh_recs = nullptr;
-  const uint32_t* mh_view = nullptr;  // the imported mesh halo records: d_mh_recs, or the caller's buffer (on_device = 2)
-  uint64_t* d_mh_keys = nullptr;
-  uint32_t* d_mh_vals = nullptr;
+  DevBuf<uint32_t> d_mh_recs;
+  const uint32_t* mh_view = nullptr;  // view, the imported mesh halo records: d_mh_recs, or the caller's buffer (on_device = 2)
+  DevBuf<uint64_t> d_mh_keys;
+  DevBuf<uint32_t> d_mh_vals;
   uint32_t mh_cap_total = 0, mh_mask = 0, mh_n = 0;
   uint8_t* d_mh_flag = nullptr;
   // compact mesh halo (khr_mesh_halo_requests_sorted / _answer / _adopt)
-  uint32_t* d_mh2_scratch = nullptr;  // cnt | base | cursor (8 * kMeshHaloMaxWorld each) | total
-  uint64_t* d_mh2_keys = nullptr;
-  uint32_t* d_mh2_offs = nullptr;
+  DevBuf<uint32_t> d_mh2_scratch;  // cnt | base | cursor (8 * kMeshHaloMaxWorld each) | total
+  DevBuf<uint64_t> d_mh2_keys;
+  DevBuf<uint32_t> d_mh2_offs;
   uint32_t mh2_ht = 0;
   bool mh_compact = false;
-  uint32_t* h_pinned = nullptr;  // [0] seed pixels of the last motion pass, [1] removed count, [2] count / [3] ticket written by
+  PinnedBuf<uint32_t> h_pinned;  // [0] seed pixels of the last motion pass, [1] removed count, [2] count / [3] ticket written by
                                  // k_motion_pixels (zero-copy)
-  uint32_t* d_pinned = nullptr;  // device view of h_pinned
   uint32_t seed_ticket = 0;
   bool seed_publish_pending = false;
   bool seed_by_ticket = false;   // motionFinish waits for the ticket (k_motion_pixels) instead of ev_seed (key import)
@@ -233,41 +258,36 @@ struct khr_ctx {
   uint64_t map_gen = 1, counters_gen = 0;        // block set generation / generation h_counters was read at (mesh download)
   int last_frame_slot = -1;                      // khr_process_frame: slot of the frame queued last
   // pinned host staging (downloads, block-index uploads): grow-only; one transfer batch in flight per buffer
-  void* h_stage = nullptr;
-  size_t h_stage_bytes = 0;
-  uint32_t* h_totals = nullptr;  // refreshMeshTotals' own pinned words
-  void* h_up = nullptr;                          // upload staging (khr_allocate_blocks: page-locked, read by the kernel in place)
-  size_t h_up_bytes = 0;
-  hipEvent_t ev_ingest = nullptr;                // khr_process_frame: this frame's main-stream ingest is queued
-  hipEvent_t ev_up = nullptr;                    // the last upload out of h_up has been consumed
-  hipStream_t ingest_stream = nullptr;           // khr_process_frame: ingest on the auxiliary stream (set around khr_upload_frame)
+  PinnedBuf<void> h_stage;
+  PinnedBuf<uint32_t> h_totals;  // refreshMeshTotals' own pinned words
+  PinnedBuf<void> h_up;                          // upload staging (khr_allocate_blocks: page-locked, read by the kernel in place)
+  Event ev_ingest;                               // khr_process_frame: this frame's main-stream ingest is queued
+  Event ev_up;                                   // the last upload out of h_up has been consumed
+  hipStream_t ingest_stream = nullptr;           // view, khr_process_frame: ingest on the auxiliary stream (set around khr_upload_frame)
   // frames handed over with khr_ingest_ahead[_host], oldest first, waiting for their khr_process_frame calls.  Up to kMaxAhead: a
   // frontend that hands frame i + 1 over BEFORE it calls khr_process_frame for frame i keeps the copy engine busy across the
   // host's wait inside that call (round 5: with one entry the host-to-device copy of a 720p frame, ~205 us, started only after
   // the call had returned and the main stream idled behind it -- rocprofv3 timeline)
   struct AheadEntry { int slot; int ev; bool host; };
   std::vector<AheadEntry> ahead_q;
-  hipEvent_t ev_ahead[2] = {nullptr, nullptr};      // conversion of the entry finished (auxiliary stream)
-  hipEvent_t ev_ahead_h2d[2] = {nullptr, nullptr};  // host planes of the entry have arrived (host-to-device stream)
+  Event ev_ahead[2];      // conversion of the entry finished (auxiliary stream)
+  Event ev_ahead_h2d[2];  // host planes of the entry have arrived (host-to-device stream)
   int ahead_ev_next = 0;
-  hipEvent_t* h2d_ev_target = nullptr;              // (set around khr_upload_frame: which event the pinned copy records)
-  // pinned host input (KHR_PF_INPUT_PINNED / khr_ingest_ahead_host): the frame's three planes travel on a stream of their own
-  // into the ring slot, the ingest kernel waits for them on the device; the host does not wait (round 5)
-  hipStream_t h2d_stream = nullptr;
-  hipEvent_t ev_h2d = nullptr;
+  Event* h2d_ev_target = nullptr;  // view (set around khr_upload_frame: which event the pinned copy records)
+  Event ev_h2d;                    // the pinned copy's own event (h2d_stream)
   bool h2d_pending = false;    // a copy out of caller memory is queued: the caller's buffers are released by the next call / khr_sync
   bool host_input_pinned = false;  // (set around khr_upload_frame by the callers that were told the memory is page-locked)
   uint64_t h2d_bytes = 0;      // bytes queued through the pinned path (statistics)
   int ef_parity = 0, ef_cur = 0;  // which of C_N_EF / C_N_EF2 the next / the latest tracking pass fills
-  hipEvent_t ev_seed = nullptr;
+  Event ev_seed;
   uint32_t last_removed = 0;
-  khr_ctx* dep_src = nullptr;     // khr_depend_on: this context's stream already waits for that context's earlier work
-  hipEvent_t ev_dep = nullptr, ev_dep_aux = nullptr;
+  khr_ctx* dep_src = nullptr;     // view, khr_depend_on: this context's stream already waits for that context's earlier work
+  Event ev_dep, ev_dep_aux;
   uint64_t last_track_stamp = 0;  // stamp of the latest tracking pass = last_occupied of every VOX_OCC voxel
   bool removed_pending = false;
   int4* d_removed = nullptr;
   // khr_process_frame(KHR_PF_OUTPUT): the list of the blocks about to be archived, published early (k_removed_publish)
-  int4* h_removed_early = nullptr;       // page-locked, max_blocks entries
+  PinnedBuf<int4> h_removed_early;       // page-locked, max_blocks entries
   uint32_t* d_removed_early_n = nullptr; // [0] count, [1] workgroups done
   uint32_t removed_early_ticket = 0;     // h_pinned[11] (count in h_pinned[10]); 0 = the last archival has no early list
   bool removed_early = false;
@@ -278,7 +298,8 @@ struct khr_ctx {
   void* d_cub_temp = nullptr;
   // motion detector voxel tables (seed table followed by boundary table) and compact lists
   uint64_t* d_md_keys = nullptr;
-  uint32_t *d_md_counts = nullptr, *d_md_ids = nullptr, *d_md_n = nullptr, *d_md_adj = nullptr;
+  uint32_t *d_md_counts = nullptr, *d_md_ids = nullptr, *d_md_adj = nullptr;
+  uint32_t* d_md_n = nullptr;  // view: the first words of the head block {S, B, R, 0} + component records (owned by allocs)
   uint64_t *d_md_seed_keys = nullptr, *d_md_bnd_keys = nullptr;
   uint32_t *d_md_seed_counts = nullptr, *d_md_bnd_counts = nullptr;
   int32_t *d_md_seed_final = nullptr, *d_md_bnd_final = nullptr;
@@ -295,7 +316,7 @@ struct khr_ctx {
   uint32_t *d_md_parent = nullptr, *d_md_rootidx = nullptr;
   CompAcc* d_md_comp_acc = nullptr;
   int32_t* d_md_comp_final = nullptr;
-  uint8_t* h_md_head = nullptr;  // pinned mirror of the head + records, then the final ids going back
+  PinnedBuf<uint8_t> h_md_head;  // pinned mirror of the head + records, then the final ids going back
   bool md_host_walk = false;     // KHR_MD_HOST_WALK=1: always cluster on the host (A/B switch, results identical)
   uint32_t md_lds_max = kCompLds;  // KHR_MD_LDS_MAX=n: seed count up to which the single-workgroup LDS labelling is used
   uint32_t md_mask = 0, md_list_cap = 0;
@@ -306,18 +327,15 @@ struct khr_ctx {
   bool md_defer_summary = false;    // clusterSummaryLaunch only notes the request (md_summary_pending = largest id)
   int md_summary_pending = -1;
   uint32_t md_last_seeds = 0;       // seed voxels of the previous seed frame (predicts which component path is needed)
-  uint8_t* d_md_head_host = nullptr;  // device view of h_md_head
   uint32_t* d_md_edges = nullptr;     // seed-seed edge list of the latest seed frame (k_md_adjacency -> k_md_comp_lds)
   uint32_t* d_md_scratch4 = nullptr;  // 4 words k_publish may zero
   std::vector<uint64_t> h_md_seed_keys, h_md_bnd_keys;
   std::vector<uint32_t> h_md_seed_counts, h_md_bnd_counts, h_md_adj;
-  uint32_t* h_md_walk = nullptr;     // page-locked block the host walk's lists travel through (kernels read / write it: no copy engine)
-  size_t h_md_walk_words = 0;
-  hipEvent_t ev_md_walk_up = nullptr;  // the last upload out of it has been consumed
+  PinnedBuf<uint32_t> h_md_walk;     // page-locked block the host walk's lists travel through (kernels read / write it: no copy engine)
+  Event ev_md_walk_up;               // the last upload out of it has been consumed
   std::vector<int32_t> h_md_seed_final, h_md_bnd_final;
   std::vector<ClusterAcc> h_md_acc;
-  ClusterAcc* h_md_acc_pinned = nullptr;   // summaries of the latest seed frame (k_publish_cluster_acc), ticket h_pinned[7]
-  ClusterAcc* d_md_acc_host = nullptr;     // device view of it
+  PinnedBuf<ClusterAcc> h_md_acc_pinned;   // summaries of the latest seed frame (k_publish_cluster_acc), ticket h_pinned[7]
   uint32_t md_acc_ticket = 0;
   int md_acc_slot = -1;                    // the frame slot the published summaries belong to
   size_t cub_temp_bytes = 0;
@@ -325,10 +343,12 @@ struct khr_ctx {
   bool obj_configured = false;
   khr_object_detector_config obj_cfg{};
   std::vector<int32_t> obj_labels;  // sorted, unique
-  int32_t* d_obj_labels = nullptr;
+  DevBuf<int32_t> d_obj_labels;     // (replaced whenever the detector is configured again)
   uint64_t* d_gv_keys = nullptr;
   uint32_t gv_mask = 0;
-  uint32_t *d_gv_parent = nullptr, *d_gv_rootidx = nullptr, *d_gv_node = nullptr, *d_gv_n = nullptr;
+  uint32_t *d_gv_parent = nullptr, *d_gv_rootidx = nullptr, *d_gv_node = nullptr;
+  // views into ONE head block of allocs: the detector's counters, its records, and the voxel-set requests' counters / keys
+  uint32_t* d_gv_n = nullptr;
   ObjAcc* d_obj_acc = nullptr;
   int32_t* d_obj_final = nullptr;
   uint64_t* d_cv_list = nullptr;
@@ -337,16 +357,14 @@ struct khr_ctx {
   uint32_t* d_gv_done = nullptr;    // completion counter of k_gv_release_publish
   bool gv_clean = false;            // the (group, voxel) table is empty (every request gives it back empty)
   bool gv_counters_clean[3] = {false, false, false};  // request counters zeroed by their last k_publish: detect, voxels 0 / 1
-  uint8_t* h_obj_head = nullptr;   // pinned: {roots, flags, -, -} + the cluster records (first download kObjHead of them)
-  hipEvent_t ev_obj = nullptr;
+  PinnedBuf<uint8_t> h_obj_head;   // pinned: {roots, flags, -, -} + the cluster records (first download kObjHead of them)
+  Event ev_obj;
   int obj_pending_slot = -1;       // objectsLaunch issued, objectsFinish outstanding
   // asynchronous per-cluster voxel sets, one request per id image (0 dynamic, 1 object)
-  uint32_t* d_cv_n[2] = {nullptr, nullptr};
+  uint32_t* d_cv_n[2] = {nullptr, nullptr};    // views (see d_gv_n)
   uint64_t* d_cv_keys[2] = {nullptr, nullptr};
-  uint8_t* h_cv[2] = {nullptr, nullptr};  // pinned: {count, flags, -, -} + keys
-  uint8_t* d_cv_host[2] = {nullptr, nullptr};  // device views of h_cv / h_obj_head
-  uint8_t* d_obj_head_host = nullptr;
-  hipEvent_t ev_cv[2] = {nullptr, nullptr};
+  PinnedBuf<uint8_t> h_cv[2];  // pinned: {count, flags, -, -} + keys
+  Event ev_cv[2];
   int cv_pending_slot[2] = {-1, -1};
   uint32_t obj_ticket = 0, cv_ticket[2] = {0, 0};  // h_pinned[4] / [5], [6]
   int3 cv_origin[2]{};
@@ -367,76 +385,73 @@ struct khr_ctx {
   std::vector<uint32_t> host_flags;
   // map slices (khr_map_slice): sort keys (nextpow2(capacity) words) + count, created at the first slice; the SoA staging and its
   // page-locked mirror (same layout, count word in front) grow on demand; slice_hint = blocks the next call copies up front
-  uint64_t* d_slice_keys = nullptr;
-  uint32_t* d_slice_count = nullptr;
-  uint8_t* d_slice_stage = nullptr;
-  uint8_t* h_slice_stage = nullptr;
+  DevBuf<uint64_t> d_slice_keys;
+  DevBuf<uint32_t> d_slice_count;
+  DevBuf<uint8_t> d_slice_stage;
+  PinnedBuf<uint8_t> h_slice_stage;
   uint32_t slice_cap = 0, slice_hint = 0;
   // rendered views (khr_render_view): the counters (created when a caller first asks for them) and the image staging of the host
   // form (created at the first host-form call, grown to the largest image)
-  unsigned long long* d_render_stats = nullptr;
-  uint8_t* d_render_stage = nullptr;
-  uint8_t* h_render_stage = nullptr;  // page-locked mirror of d_render_stage
-  size_t render_stage_bytes = 0;
+  DevBuf<unsigned long long> d_render_stats;
+  DevBuf<uint8_t> d_render_stage;
+  PinnedBuf<uint8_t> h_render_stage;  // page-locked mirror of d_render_stage
   // point queries (khr_query_points): the same pair for its counters and the point / output staging of the host form
-  unsigned long long* d_query_stats = nullptr;
-  uint8_t* d_query_stage = nullptr;
-  uint8_t* h_query_stage = nullptr;  // page-locked mirror of d_query_stage
-  size_t query_stage_bytes = 0;
+  DevBuf<unsigned long long> d_query_stats;
+  DevBuf<uint8_t> d_query_stage;
+  PinnedBuf<uint8_t> h_query_stage;  // page-locked mirror of d_query_stage
   // registration (khr_align_linearize): the accumulator (its words 128 bytes apart) with its page-locked mirror, and the source /
   // weight staging of the host form
-  unsigned long long* d_align_acc = nullptr;
-  unsigned long long* h_align_acc = nullptr;
-  uint8_t* d_align_stage = nullptr;
-  uint8_t* h_align_stage = nullptr;  // page-locked mirror of d_align_stage
-  size_t align_stage_bytes = 0;
+  DevBuf<unsigned long long> d_align_acc;
+  PinnedBuf<unsigned long long> h_align_acc;
+  DevBuf<uint8_t> d_align_stage;
+  PinnedBuf<uint8_t> h_align_stage;  // page-locked mirror of d_align_stage
   // map checkpoints (khr_checkpoint_save / _load): two chunk staging areas of kCkptStageBytes each (created at the first call; their
   // page-locked mirrors only when a caller passes pageable memory), the chunk's slot list, the load's error word, and per
   // staging area one event for "filled" and one for "drained"
-  uint8_t* d_ckpt[2] = {nullptr, nullptr};
-  uint8_t* h_ckpt[2] = {nullptr, nullptr};
-  size_t ckpt_stage_bytes = 0;
-  uint32_t* d_ckpt_slots[2] = {nullptr, nullptr};
-  uint32_t ckpt_slots_cap = 0;
-  uint32_t* d_ckpt_err = nullptr;
-  hipEvent_t ev_ckpt_filled[2] = {nullptr, nullptr}, ev_ckpt_drained[2] = {nullptr, nullptr};
+  DevBuf<uint8_t> d_ckpt[2];
+  PinnedBuf<uint8_t> h_ckpt[2];
+  DevBuf<uint32_t> d_ckpt_slots[2];
+  DevBuf<uint32_t> d_ckpt_err;
+  Event ev_ckpt_filled[2], ev_ckpt_drained[2];
   // timing
   uint32_t timing = 0;  // bit i = timer i enabled
   std::vector<TimingRec> pending;
-  std::vector<hipEvent_t> event_pool;
+  std::vector<Event> event_pool;  // timing events that are free (created with timing; the ones in use sit in `pending`)
   double t_ms[kNumTimers] = {0};
   uint64_t t_n[kNumTimers] = {0};
 };
 
 namespace {
 
+// a timing event: out of the pool of free ones, or a new one
+Event takeEvent(khr_ctx* c) {
+  Event e;
+  if (!c->event_pool.empty()) {
+    e = std::move(c->event_pool.back());
+    c->event_pool.pop_back();
+  } else {
+    e.ensure(hipEventDefault);
+  }
+  return e;
+}
+
 struct ScopedTimer {
   khr_ctx* c;
   int which;
-  hipEvent_t a = nullptr, b = nullptr;
+  Event a, b;
   bool on = false;
   ScopedTimer(khr_ctx* ctx, int w) : c(ctx), which(w) {
     on = w >= 0 && ((c->timing >> w) & 1u);
     if (on) {
-      auto get = [&]() {
-        hipEvent_t e = nullptr;
-        if (!c->event_pool.empty()) {
-          e = c->event_pool.back();
-          c->event_pool.pop_back();
-        } else {
-          hipEventCreate(&e);
-        }
-        return e;
-      };
-      a = get();
-      b = get();
+      a = takeEvent(c);
+      b = takeEvent(c);
       hipEventRecord(a, c->stream);
     }
   }
   ~ScopedTimer() {
     if (on) {
       hipEventRecord(b, c->stream);
-      c->pending.push_back({which, a, b});
+      c->pending.push_back({which, std::move(a), std::move(b)});
     }
   }
 };
@@ -444,22 +459,12 @@ struct ScopedTimer {
 // Single-kernel timers use the start / stop events of the dispatch packet itself (hipExtLaunchKernelGGL): the same
 // begin / end timestamps rocprofv3 reports, and no extra barrier packets in the stream.  ScopedTimer (event records
 // around a group of launches) costs ~5 us of stream time per bracket.
-hipEvent_t takeEvent(khr_ctx* c) {
-  hipEvent_t e = nullptr;
-  if (!c->event_pool.empty()) {
-    e = c->event_pool.back();
-    c->event_pool.pop_back();
-  } else {
-    hipEventCreate(&e);
-  }
-  return e;
-}
 #define KHR_LAUNCH_TIMED_ON(which, strm, kernel, grid, block, ...)                                     \
   do {                                                                                                 \
     if ((c->timing >> (which)) & 1u) {                                                                 \
-      hipEvent_t ev_a = takeEvent(c), ev_b = takeEvent(c);                                             \
+      Event ev_a = takeEvent(c), ev_b = takeEvent(c);                                                  \
       hipExtLaunchKernelGGL(kernel, grid, block, 0, strm, ev_a, ev_b, 0, __VA_ARGS__);                 \
-      c->pending.push_back({(which), ev_a, ev_b});                                                     \
+      c->pending.push_back({(which), std::move(ev_a), std::move(ev_b)});                               \
     } else {                                                                                           \
       hipLaunchKernelGGL(kernel, grid, block, 0, strm, __VA_ARGS__);                                   \
     }                                                                                                  \
@@ -475,32 +480,29 @@ void resolveTimers(khr_ctx* c) {
       c->t_ms[r.which] += ms;
       c->t_n[r.which] += 1;
     }
-    c->event_pool.push_back(r.a);
-    c->event_pool.push_back(r.b);
+    c->event_pool.push_back(std::move(r.a));
+    c->event_pool.push_back(std::move(r.b));
   }
   c->pending.clear();
 }
 
 // temporary device buffer of the host-pointer variants of the exchange calls (tests / non-RCCL callers): freed on
 // every exit path; hipFree waits for the device, so work still using the buffer is finished first
-struct DevTemp {
-  void* p = nullptr;
-  ~DevTemp() {
-    if (p) hipFree(p);
-  }
+struct DevTemp : DevBuf<uint8_t> {
   template <typename T>
-  T* as() const { return static_cast<T*>(p); }
+  T* as() const { return reinterpret_cast<T*>(get()); }
 };
 
+// a buffer that lives as long as the context: owned by c->allocs, *out is a view of it
 template <typename T>
 int devAlloc(khr_ctx* c, T** out, size_t count, bool zero = true) {
-  void* p = nullptr;
   const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-  hipError_t e = hipMalloc(&p, bytes);
-  if (e != hipSuccess) return fail(KHR_ENOMEM, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-  c->allocs.push_back(p);
+  DevBuf<uint8_t> b;
+  if (int rc = b.alloc(bytes)) return rc;
+  void* p = b.get();
+  c->allocs.push_back(std::move(b));
   if (zero) {
-    e = hipMemsetAsync(p, 0, bytes, c->stream);
+    const hipError_t e = hipMemsetAsync(p, 0, bytes, c->stream);
     if (e != hipSuccess) return fail(KHR_EDEVICE, "hipMemset failed: %s", hipGetErrorString(e));
   }
   *out = static_cast<T*>(p);
@@ -572,16 +574,24 @@ DevFrustum makeFrustum(const khr_ctx* c, const DevFrame& f) {
   return fr;
 }
 
+// a device staging block and its page-locked mirror (the host forms of the map readers) grow together: both are released before
+// either is allocated again, and a failure leaves both empty.  The caller has waited for whatever used the old pair.
+int reserveStagePair(DevBuf<uint8_t>& d, PinnedBuf<uint8_t>& h, size_t bytes, const char* what) {
+  if (bytes <= d.count() && bytes <= h.count()) return KHR_OK;
+  d.reset();
+  h.reset();
+  if (d.alloc(bytes)) return fail(KHR_ENOMEM, "%s staging of %zu bytes", what, bytes);
+  if (h.alloc(bytes)) {
+    d.reset();
+    return fail(KHR_ENOMEM, "page-locked %s staging of %zu bytes", what, bytes);
+  }
+  return KHR_OK;
+}
+
 // grow-only pinned staging; contents are undefined after a call that grows it
 int ensureStage(khr_ctx* c, size_t bytes) {
-  if (bytes <= c->h_stage_bytes) return KHR_OK;
-  if (c->h_stage) HIP_TRY(hipHostFree(c->h_stage));
-  c->h_stage = nullptr;
-  c->h_stage_bytes = 0;
-  const size_t want = std::max<size_t>(bytes + bytes / 2, 1u << 20);
-  if (hipHostMalloc(&c->h_stage, want, hipHostMallocDefault) != hipSuccess) return fail(KHR_ENOMEM, "pinned staging of %zu bytes", want);
-  c->h_stage_bytes = want;
-  return KHR_OK;
+  if (bytes <= c->h_stage.count()) return KHR_OK;
+  return c->h_stage.reserve(std::max<size_t>(bytes + bytes / 2, 1u << 20));
 }
 
 int readCounters(khr_ctx* c) {
@@ -746,11 +756,12 @@ static std::vector<khr_ctx*> g_live_ctx;
 // kernel chain -- the "one run in ten" late seed count (profiles/r06_seed_latency.txt, state 0xa: main stream idle, auxiliary busy).
 // The active window's streams (16^3 blocks) are created at the highest priority, the object mini-maps' (8^3) at the lowest: different
 // priority levels never share a hardware queue, and the dispatcher prefers the window's workgroups when both have some ready.
-static hipError_t createStream(khr_ctx* c, hipStream_t* out) {
+static int createStream(khr_ctx* c, Stream& out) {
   int lo = 0, hi = 0;  // (numerically: greatest = lowest priority)
   if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess || lo == hi || c->stream_priority == 0)
-    return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
-  return hipStreamCreateWithPriority(out, hipStreamNonBlocking, c->stream_priority > 0 ? hi : lo);
+    return out.create(hipStreamNonBlocking);
+  const int prio = c->stream_priority > 0 ? hi : lo;
+  return out.create(hipStreamNonBlocking, &prio);
 }
 
 static bool ctxIsLive(khr_ctx* c) {
@@ -780,14 +791,14 @@ int khr_depend_on(khr_ctx* c, khr_ctx* other) {
   HIP_TRY(hipSetDevice(c->device));
   // (events owned by the DEPENDENT context: khr_depend_on may be called from a worker thread while the other context's
   // own thread keeps using its events)
-  if (!c->ev_dep_aux) HIP_TRY(hipEventCreateWithFlags(&c->ev_dep_aux, hipEventDisableTiming));
+  KHR_TRY(c->ev_dep_aux.ensure());
   if (c->stream == other->stream) {
     HIP_TRY(hipEventRecord(c->ev_dep_aux, other->aux_stream));
     HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_dep_aux, 0));
     c->dep_src = other;
     return KHR_OK;
   }
-  if (!c->ev_dep) HIP_TRY(hipEventCreateWithFlags(&c->ev_dep, hipEventDisableTiming));
+  KHR_TRY(c->ev_dep.ensure());
   HIP_TRY(hipEventRecord(c->ev_dep, other->stream));
   HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_dep, 0));
   // ... and behind its object detector (the object images of its frame slots)
@@ -858,7 +869,9 @@ int khr_create(const khr_config* cfg, khr_ctx** out) {
   if (cfg->device < 0 || cfg->device >= ndev) return fail(KHR_EINVAL, "device %d out of range (%d devices)", cfg->device, ndev);
   HIP_TRY(hipSetDevice(cfg->device));
 
-  auto* c = new khr_ctx();
+  // (every failure below leaves through this owner, i.e. through khr_destroy: the one teardown path)
+  std::unique_ptr<khr_ctx, void (*)(khr_ctx*)> owner(new khr_ctx(), khr_destroy);
+  khr_ctx* c = owner.get();
   c->cfg = *cfg;
   c->device = cfg->device;
   {
@@ -866,37 +879,19 @@ int khr_create(const khr_config* cfg, khr_ctx** out) {
     static const int prio_window = std::getenv("KHR_WINDOW_PRIORITY") ? std::atoi(std::getenv("KHR_WINDOW_PRIORITY")) : 0;
     c->stream_priority = prio_off ? 0 : (cfg->voxels_per_side == 8 ? -1 : prio_window);
   }
-  if (createStream(c, &c->stream) != hipSuccess) {
-    delete c;
-    return fail(KHR_EDEVICE, "hipStreamCreate failed");
-  }
-  c->own_stream = true;
-  if (createStream(c, &c->aux_stream) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_aux, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_aux_done, hipEventDisableTiming) != hipSuccess) {
-    delete c;
+  if (createStream(c, c->stream)) return fail(KHR_EDEVICE, "hipStreamCreate failed");
+  if (createStream(c, c->aux_stream) || c->ev_aux.ensure() || c->ev_aux_done.ensure())
     return fail(KHR_EDEVICE, "auxiliary stream / event creation failed");
-  }
-  if (hipHostMalloc(reinterpret_cast<void**>(&c->h_pinned), 64, hipHostMallocDefault) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_seed, hipEventDisableTiming) != hipSuccess) {
-    delete c;
-    return fail(KHR_EDEVICE, "pinned scratch / event creation failed");
-  }
+  if (c->h_pinned.alloc(16) || c->ev_seed.ensure()) return fail(KHR_EDEVICE, "pinned scratch / event creation failed");
   std::memset(c->h_pinned, 0, 64);
   // staging buffers up front: growing them later means hipHostMalloc / hipMalloc in the middle of a run (hundreds of us,
   // and hipMalloc stalls every stream of the device)
   // (object mini-maps take their whole block list through it, khr_allocate_blocks per extraction: sized for a full pool -- round 5:
   // an extraction whose list outgrew the 64 KB grew it from its worker thread, and the hipMalloc waited 5 - 11 ms for the window's
   // frames to leave the device idle, profiles/r05_host_input_marks.txt)
-  c->h_up_bytes = std::max<size_t>(1u << 16, cfg->voxels_per_side == 8 ? sizeof(int32_t) * 3 * static_cast<size_t>(cfg->max_blocks) : 0);
-  if (ensureStage(c, 1u << 20) != KHR_OK || hipHostMalloc(&c->h_up, c->h_up_bytes, hipHostMallocDefault) != hipSuccess) {
-    delete c;
+  if (ensureStage(c, 1u << 20) != KHR_OK ||
+      c->h_up.alloc(std::max<size_t>(1u << 16, cfg->voxels_per_side == 8 ? sizeof(int32_t) * 3 * static_cast<size_t>(cfg->max_blocks) : 0)))
     return fail(KHR_ENOMEM, "pinned staging buffers");
-  }
-  if (hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_pinned), c->h_pinned, 0) != hipSuccess) {
-    delete c;
-    return fail(KHR_EDEVICE, "hipHostGetDevicePointer failed");
-  }
 
   DevParams& p = c->p;
   deriveMetricParams(*cfg, p);
@@ -933,41 +928,40 @@ int khr_create(const khr_config* cfg, khr_ctx** out) {
   m.ht_mask = ht - 1;
   m.capacity = static_cast<uint32_t>(cap);
   int rc = KHR_OK;
-  auto A = [&](int r) { if (rc == KHR_OK) rc = r; };
-  A(devAlloc(c, &m.ht_keys, ht, false));
-  A(devAlloc(c, &m.ht_vals, ht));
-  A(devAlloc(c, &m.blk_index, cap));
-  A(devAlloc(c, &m.blk_flags, cap));
-  A(devAlloc(c, &m.dist, cap * nv, false));
-  A(devAlloc(c, &m.weight, cap * nv, false));
-  A(devAlloc(c, &m.color, cap * nv, false));
-  A(devAlloc(c, &m.vflags, cap * nv, false));
-  A(devAlloc(c, &m.sem_label, cfg->with_semantics ? cap * nv : 1, false));
-  if (devAlloc(c, &m.lik, cfg->with_semantics ? cap * nv * p.KS : 1, false) != KHR_OK) {
+  KHR_CHAIN(devAlloc(c, &m.ht_keys, ht, false));
+  KHR_CHAIN(devAlloc(c, &m.ht_vals, ht));
+  KHR_CHAIN(devAlloc(c, &m.blk_index, cap));
+  KHR_CHAIN(devAlloc(c, &m.blk_flags, cap));
+  KHR_CHAIN(devAlloc(c, &m.dist, cap * nv, false));
+  KHR_CHAIN(devAlloc(c, &m.weight, cap * nv, false));
+  KHR_CHAIN(devAlloc(c, &m.color, cap * nv, false));
+  KHR_CHAIN(devAlloc(c, &m.vflags, cap * nv, false));
+  KHR_CHAIN(devAlloc(c, &m.sem_label, cfg->with_semantics ? cap * nv : 1, false));
+  if (rc == KHR_OK && devAlloc(c, &m.lik, cfg->with_semantics ? cap * nv * p.KS : 1, false) != KHR_OK) {
     // (the largest layer of the pool: say what it needs and what the switch saves)
     fail(KHR_ENOMEM, "the label-likelihood layer of %zu blocks needs %.2f GB (%d floats per voxel%s); khr_config.packed_likelihood_rows = 1 "
                      "stores %d per voxel, a smaller max_blocks less of everything", static_cast<size_t>(cap),
          1e-9 * static_cast<double>(cap) * nv * p.KS * 4, p.KS, p.KS != p.K ? ": rows padded to 128-byte lines" : "", p.K);
-    A(KHR_ENOMEM);
+    KHR_CHAIN(KHR_ENOMEM);
   }
-  A(devAlloc(c, &m.last_obs, cfg->with_tracking ? cap * nv : 1, false));
-  A(devAlloc(c, &m.last_occ, cfg->with_tracking ? cap * nv : 1, false));
-  A(devAlloc(c, &m.trk_lim, cfg->with_tracking ? cap * 2 : 2));
-  A(devAlloc(c, &m.freebits, cfg->with_tracking ? cap * (nv / 64) : 1, false));
-  A(devAlloc(c, &m.obs, cfg->with_tracking ? cap * (nv / 64) : 1, false));
-  A(devAlloc(c, &m.free_slots, cap, false));
-  A(devAlloc(c, &m.counters, C_COUNT));
-  A(devAlloc(c, &m.stats, S_COUNT));
-  A(devAlloc(c, &m.mesh_desc, cap));
-  A(devAlloc(c, &c->d_work, cap));
-  A(devAlloc(c, &c->d_new, cap));
-  A(devAlloc(c, &c->d_ef, cap));
-  A(devAlloc(c, &c->d_trk_proc, cap));
-  A(devAlloc(c, &c->d_dbg, 4096 * 4 * 12));
-  A(devAlloc(c, &c->d_digest, kDigestWords));
-  A(devAlloc(c, &c->d_wg_stats, 2 * kUpdateStatSlots));
-  A(devAlloc(c, &c->d_fuse_sink, static_cast<size_t>(kUpdateStatSlots) * 16 * 256, false));
-  A(devAlloc(c, &c->d_fetch_done, 4));
+  KHR_CHAIN(devAlloc(c, &m.last_obs, cfg->with_tracking ? cap * nv : 1, false));
+  KHR_CHAIN(devAlloc(c, &m.last_occ, cfg->with_tracking ? cap * nv : 1, false));
+  KHR_CHAIN(devAlloc(c, &m.trk_lim, cfg->with_tracking ? cap * 2 : 2));
+  KHR_CHAIN(devAlloc(c, &m.freebits, cfg->with_tracking ? cap * (nv / 64) : 1, false));
+  KHR_CHAIN(devAlloc(c, &m.obs, cfg->with_tracking ? cap * (nv / 64) : 1, false));
+  KHR_CHAIN(devAlloc(c, &m.free_slots, cap, false));
+  KHR_CHAIN(devAlloc(c, &m.counters, C_COUNT));
+  KHR_CHAIN(devAlloc(c, &m.stats, S_COUNT));
+  KHR_CHAIN(devAlloc(c, &m.mesh_desc, cap));
+  KHR_CHAIN(devAlloc(c, &c->d_work, cap));
+  KHR_CHAIN(devAlloc(c, &c->d_new, cap));
+  KHR_CHAIN(devAlloc(c, &c->d_ef, cap));
+  KHR_CHAIN(devAlloc(c, &c->d_trk_proc, cap));
+  KHR_CHAIN(devAlloc(c, &c->d_dbg, 4096 * 4 * 12));
+  KHR_CHAIN(devAlloc(c, &c->d_digest, kDigestWords));
+  KHR_CHAIN(devAlloc(c, &c->d_wg_stats, 2 * kUpdateStatSlots));
+  KHR_CHAIN(devAlloc(c, &c->d_fuse_sink, static_cast<size_t>(kUpdateStatSlots) * 16 * 256, false));
+  KHR_CHAIN(devAlloc(c, &c->d_fetch_done, 4));
   {
     // shards of a >= 4-rank map and small frames (up to 640 x 480 pixels) see few blocks per launch: 8 z ranges per patch
     // instead of 4 halve the longest dependent chain (an item's band rounds) and double the items the waves can share.
@@ -977,89 +971,76 @@ int khr_create(const khr_config* cfg, khr_ctx** out) {
     c->wpb = static_cast<uint32_t>((cfg->voxels_per_side * cfg->voxels_per_side / 64) * zs);
     c->item_cap = static_cast<uint32_t>(cap) * c->wpb;
   }
-  A(devAlloc(c, &c->d_work4, 2 * static_cast<size_t>(c->item_cap), false));
+  KHR_CHAIN(devAlloc(c, &c->d_work4, 2 * static_cast<size_t>(c->item_cap), false));
   if (cfg->voxels_per_side == 8 && rc == KHR_OK) {
     // an object mini-map: the buffers of its multi-frame update now, not at the first extraction -- that one runs beside the window's
     // frames, and a hipMalloc / hipHostMalloc there waits for (and stalls) every stream of the device (round 6: one run of the
     // driver's command in ten had a 3 ms step at its first extraction)
     const size_t bits_words = static_cast<size_t>(c->item_cap) * 4;  // four words per item = 128 buffered frames
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->h_frames), sizeof(FuseFrame) * kMaxMultiFrames, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->d_frames), sizeof(FuseFrame) * kMaxMultiFrames) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_frames, hipEventDisableTiming) != hipSuccess ||
-        hipEventRecord(c->ev_frames, c->stream) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->d_frame_bits), bits_words * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->d_multi_list), sizeof(uint4) * 2 * c->item_cap + 16) != hipSuccess)
+    if (c->h_frames.alloc(kMaxMultiFrames) || c->d_frames.alloc(kMaxMultiFrames) || c->ev_frames.ensure() ||
+        hipEventRecord(c->ev_frames, c->stream) != hipSuccess || c->d_frame_bits.alloc(bits_words) ||
+        c->d_multi_list.alloc(2 * static_cast<size_t>(c->item_cap) + 1))  // (+ 1 uint4 = the 4 counters)
       rc = fail(KHR_ENOMEM, "buffers of the multi-frame update");
-    else
-      c->frame_bits_words = bits_words;
     // ... and the small page-locked block and events its first extraction would otherwise create on the worker's thread
-    if (rc == KHR_OK && (hipHostMalloc(reinterpret_cast<void**>(&c->h_totals), sizeof(uint32_t) * (C_COUNT + 2), hipHostMallocDefault) != hipSuccess ||
-                         hipEventCreateWithFlags(&c->ev_up, hipEventDisableTiming) != hipSuccess || hipEventRecord(c->ev_up, c->stream) != hipSuccess ||
-                         hipEventCreateWithFlags(&c->ev_dep, hipEventDisableTiming) != hipSuccess ||
-                         hipEventCreateWithFlags(&c->ev_dep_aux, hipEventDisableTiming) != hipSuccess))
+    if (rc == KHR_OK && (c->h_totals.alloc(C_COUNT + 2) || c->ev_up.ensure() || hipEventRecord(c->ev_up, c->stream) != hipSuccess ||
+                         c->ev_dep.ensure() || c->ev_dep_aux.ensure()))
       rc = fail(KHR_ENOMEM, "page-locked words / events of an object mini-map");
   }
-  A(devAlloc(c, &m.blk_band, cap * kBandSlots));
-  A(devAlloc(c, &c->d_removed, cap));
-  A(devAlloc(c, &c->d_mesh_count, cap + 1));
-  A(devAlloc(c, &c->d_mesh_offset, cap + 1));
-  A(devAlloc(c, &c->d_regen, cap));
-  A(devAlloc(c, &c->d_mesh_old_off, cap + 1));
-  A(devAlloc(c, &c->d_mh_flag, cap));
-  A(devAlloc(c, &c->d_mesh_nwork, 8));
+  KHR_CHAIN(devAlloc(c, &m.blk_band, cap * kBandSlots));
+  KHR_CHAIN(devAlloc(c, &c->d_removed, cap));
+  KHR_CHAIN(devAlloc(c, &c->d_mesh_count, cap + 1));
+  KHR_CHAIN(devAlloc(c, &c->d_mesh_offset, cap + 1));
+  KHR_CHAIN(devAlloc(c, &c->d_regen, cap));
+  KHR_CHAIN(devAlloc(c, &c->d_mesh_old_off, cap + 1));
+  KHR_CHAIN(devAlloc(c, &c->d_mh_flag, cap));
+  KHR_CHAIN(devAlloc(c, &c->d_mesh_nwork, 8));
   const size_t npx = cfg->max_frame_pixels;
-  A(devAlloc(c, &c->d_keys, npx, false));
-  A(devAlloc(c, &c->d_pix, npx, false));
+  KHR_CHAIN(devAlloc(c, &c->d_keys, npx, false));
+  KHR_CHAIN(devAlloc(c, &c->d_pix, npx, false));
   {
     // voxel tables: every pixel can at most open one voxel; 2x slots keep probing short
     uint32_t ts = 1;
     while (ts < 2 * npx) ts <<= 1;
     c->md_mask = ts - 1;
     c->md_list_cap = static_cast<uint32_t>(std::min<size_t>(npx, 1u << 20));
-    A(devAlloc(c, &c->d_md_keys, 3 * static_cast<size_t>(ts), false));
-    A(devAlloc(c, &c->d_md_counts, 3 * static_cast<size_t>(ts), false));
-    A(devAlloc(c, &c->d_md_ids, 3 * static_cast<size_t>(ts), false));
+    KHR_CHAIN(devAlloc(c, &c->d_md_keys, 3 * static_cast<size_t>(ts), false));
+    KHR_CHAIN(devAlloc(c, &c->d_md_counts, 3 * static_cast<size_t>(ts), false));
+    KHR_CHAIN(devAlloc(c, &c->d_md_ids, 3 * static_cast<size_t>(ts), false));
     {
       uint8_t* head = nullptr;
-      A(devAlloc(c, &head, 16 + sizeof(CompAcc) * kCompCap));
+      KHR_CHAIN(devAlloc(c, &head, 16 + sizeof(CompAcc) * kCompCap));
       c->d_md_n = reinterpret_cast<uint32_t*>(head);
     }
-    A(devAlloc(c, &c->d_md_parent, c->md_list_cap, false));
-    A(devAlloc(c, &c->d_md_rootidx, c->md_list_cap, false));
-    A(devAlloc(c, &c->d_md_edges, c->md_list_cap, false));
-    A(devAlloc(c, &c->d_md_comp_acc, c->md_list_cap, false));
-    A(devAlloc(c, &c->d_md_comp_final, kCompCap));
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->h_md_head), 16 + sizeof(CompAcc) * kCompCap, hipHostMallocDefault) != hipSuccess ||
-        hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_md_head_host), c->h_md_head, 0) != hipSuccess)
-      A(KHR_ENOMEM);
-    A(devAlloc(c, &c->d_md_scratch4, 16));  // [0..3] words k_publish may zero, [8..13] voxel box of the seed voxels
+    KHR_CHAIN(devAlloc(c, &c->d_md_parent, c->md_list_cap, false));
+    KHR_CHAIN(devAlloc(c, &c->d_md_rootidx, c->md_list_cap, false));
+    KHR_CHAIN(devAlloc(c, &c->d_md_edges, c->md_list_cap, false));
+    KHR_CHAIN(devAlloc(c, &c->d_md_comp_acc, c->md_list_cap, false));
+    KHR_CHAIN(devAlloc(c, &c->d_md_comp_final, kCompCap));
+    KHR_CHAIN(c->h_md_head.alloc(16 + sizeof(CompAcc) * kCompCap));
+    KHR_CHAIN(devAlloc(c, &c->d_md_scratch4, 16));  // [0..3] words k_publish may zero, [8..13] voxel box of the seed voxels
     c->md_host_walk = std::getenv("KHR_MD_HOST_WALK") != nullptr;
     if (const char* e = std::getenv("KHR_MD_LDS_MAX")) c->md_lds_max = std::min<uint32_t>(kCompLds, static_cast<uint32_t>(std::atoi(e)));
-    A(devAlloc(c, &c->d_md_seed_keys, c->md_list_cap, false));
-    A(devAlloc(c, &c->d_md_bnd_keys, c->md_list_cap, false));
-    A(devAlloc(c, &c->d_md_seed_counts, c->md_list_cap, false));
-    A(devAlloc(c, &c->d_md_bnd_counts, c->md_list_cap, false));
-    A(devAlloc(c, &c->d_md_seed_final, c->md_list_cap, false));
-    A(devAlloc(c, &c->d_md_bnd_final, c->md_list_cap, false));
-    A(devAlloc(c, &c->d_md_bnd_deg, c->md_list_cap, false));
-    A(devAlloc(c, &c->d_md_bnd_mask, c->md_list_cap, false));
-    A(devAlloc(c, &c->d_md_adj, static_cast<size_t>(c->md_list_cap) * 26, false));
+    KHR_CHAIN(devAlloc(c, &c->d_md_seed_keys, c->md_list_cap, false));
+    KHR_CHAIN(devAlloc(c, &c->d_md_bnd_keys, c->md_list_cap, false));
+    KHR_CHAIN(devAlloc(c, &c->d_md_seed_counts, c->md_list_cap, false));
+    KHR_CHAIN(devAlloc(c, &c->d_md_bnd_counts, c->md_list_cap, false));
+    KHR_CHAIN(devAlloc(c, &c->d_md_seed_final, c->md_list_cap, false));
+    KHR_CHAIN(devAlloc(c, &c->d_md_bnd_final, c->md_list_cap, false));
+    KHR_CHAIN(devAlloc(c, &c->d_md_bnd_deg, c->md_list_cap, false));
+    KHR_CHAIN(devAlloc(c, &c->d_md_bnd_mask, c->md_list_cap, false));
+    KHR_CHAIN(devAlloc(c, &c->d_md_adj, static_cast<size_t>(c->md_list_cap) * 26, false));
     {  // the host walk's page-locked block, for 16 k seed voxels to begin with (grown on demand: a growth is a hipHostMalloc inside a frame)
-      const size_t want = std::min<size_t>(c->md_list_cap, 16384) * (3 + 26 + 3) + 16;
-      if (hipHostMalloc(reinterpret_cast<void**>(&c->h_md_walk), want * 4, hipHostMallocDefault) != hipSuccess) A(KHR_ENOMEM);
-      else c->h_md_walk_words = want;
+      KHR_CHAIN(c->h_md_walk.alloc(std::min<size_t>(c->md_list_cap, 16384) * (3 + 26 + 3) + 16));
     }
     // (not zeroed: devAlloc's memset is queued on the context's NON-BLOCKING stream, and the synchronous copy of the reduction
     //  identities below runs on the null stream -- nothing orders the two, and a memset that lands second leaves zeros, i.e.
     //  boxes clamped at 0 for the first seed frame's clusters.  Found by tests/test_gpu_ref_pin.py.)
-    A(devAlloc(c, &c->d_md_acc, 256, false));
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->h_md_acc_pinned), sizeof(ClusterAcc) * 256, hipHostMallocDefault) != hipSuccess ||
-        hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_md_acc_host), c->h_md_acc_pinned, 0) != hipSuccess)
-      A(KHR_ENOMEM);
+    KHR_CHAIN(devAlloc(c, &c->d_md_acc, 256, false));
+    KHR_CHAIN(c->h_md_acc_pinned.alloc(256));
     {
       std::vector<ClusterAcc> init(256);
       for (auto& a : init) clusterAccReset(a);
-      if (rc == KHR_OK && hipMemcpy(c->d_md_acc, init.data(), sizeof(ClusterAcc) * 256, hipMemcpyHostToDevice) != hipSuccess) A(KHR_EDEVICE);
+      KHR_CHAIN(hipMemcpy(c->d_md_acc, init.data(), sizeof(ClusterAcc) * 256, hipMemcpyHostToDevice) != hipSuccess ? KHR_EDEVICE : KHR_OK);
     }
   }
   if (rc == KHR_OK) {
@@ -1067,34 +1048,31 @@ int khr_create(const khr_config* cfg, khr_ctx** out) {
     hipcub::DeviceScan::ExclusiveSum(nullptr, t3, c->d_mesh_count, c->d_mesh_offset, static_cast<int>(cap + 1), c->stream);
     c->cub_temp_bytes = t3 + 256;
     uint8_t* tmp = nullptr;
-    A(devAlloc(c, &tmp, c->cub_temp_bytes, false));
+    KHR_CHAIN(devAlloc(c, &tmp, c->cub_temp_bytes, false));
     c->d_cub_temp = tmp;
   }
   for (int b = 0; b < 2 && rc == KHR_OK; ++b) {
-    A(devAlloc(c, &c->mesh[b].points, cfg->max_mesh_vertices * 3, false));
-    A(devAlloc(c, &c->mesh[b].colors, cfg->max_mesh_vertices, false));
-    A(devAlloc(c, &c->mesh[b].labels, cfg->max_mesh_vertices, false));
-    A(devAlloc(c, &c->mesh[b].stamps, cfg->max_mesh_vertices, false));
+    KHR_CHAIN(devAlloc(c, &c->mesh[b].points, cfg->max_mesh_vertices * 3, false));
+    KHR_CHAIN(devAlloc(c, &c->mesh[b].colors, cfg->max_mesh_vertices, false));
+    KHR_CHAIN(devAlloc(c, &c->mesh[b].labels, cfg->max_mesh_vertices, false));
+    KHR_CHAIN(devAlloc(c, &c->mesh[b].stamps, cfg->max_mesh_vertices, false));
   }
   c->slots.resize(cfg->num_frame_slots);
   c->slot_leases.reset(new std::atomic<int>[cfg->num_frame_slots]);
   for (uint32_t i = 0; i < cfg->num_frame_slots; ++i) c->slot_leases[i].store(0);
   for (auto& s : c->slots) {
     if (rc != KHR_OK) break;
-    A(devAlloc(c, &s.depth, npx, false));
-    A(devAlloc(c, &s.range, npx + 4, false));  // + pad: k_fuse gathers pixel pairs (u0, u0 + 1) with one 8-byte load
-    A(devAlloc(c, &s.rgba, npx + 4, false));   // + pad: the band phase gathers colour pixel pairs like the range samples
-    A(devAlloc(c, &s.label, npx, false));
-    A(devAlloc(c, &s.dyn, npx));
-    A(devAlloc(c, &s.dynw, npx, false));
-    A(devAlloc(c, &s.obj, npx));
-    A(devAlloc(c, &s.rgb_staging, npx * 3, false));
-    A(devAlloc(c, &s.tile_max, npx / 16 + 64, false));
+    KHR_CHAIN(devAlloc(c, &s.depth, npx, false));
+    KHR_CHAIN(devAlloc(c, &s.range, npx + 4, false));  // + pad: k_fuse gathers pixel pairs (u0, u0 + 1) with one 8-byte load
+    KHR_CHAIN(devAlloc(c, &s.rgba, npx + 4, false));   // + pad: the band phase gathers colour pixel pairs like the range samples
+    KHR_CHAIN(devAlloc(c, &s.label, npx, false));
+    KHR_CHAIN(devAlloc(c, &s.dyn, npx));
+    KHR_CHAIN(devAlloc(c, &s.dynw, npx, false));
+    KHR_CHAIN(devAlloc(c, &s.obj, npx));
+    KHR_CHAIN(devAlloc(c, &s.rgb_staging, npx * 3, false));
+    KHR_CHAIN(devAlloc(c, &s.tile_max, npx / 16 + 64, false));
   }
-  if (rc != KHR_OK) {
-    khr_destroy(c);
-    return rc;
-  }
+  if (rc != KHR_OK) return rc;
   // initial state: empty hash, free list = identity, constant tables
   hipError_t e = hipMemsetAsync(m.ht_keys, 0xff, sizeof(uint64_t) * ht, c->stream);
   if (e == hipSuccess) {
@@ -1108,18 +1086,16 @@ int khr_create(const khr_config* cfg, khr_ctx** out) {
     if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(g_mc_ntri), kMcNumTris, sizeof(kMcNumTris));
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   }
-  if (e != hipSuccess) {
-    khr_destroy(c);
-    return fail(KHR_EDEVICE, "context initialisation failed: %s", hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(KHR_EDEVICE, "context initialisation failed: %s", hipGetErrorString(e));
   {
     std::lock_guard<std::mutex> lock(g_live_mu);
     g_live_ctx.push_back(c);
   }
-  *out = c;
+  *out = owner.release();
   return KHR_OK;
 }
 
+// What depends on order is here; everything else is released by the members' destructors (the streams last).
 void khr_destroy(khr_ctx* c) {
   if (!c) return;
   {
@@ -1127,109 +1103,20 @@ void khr_destroy(khr_ctx* c) {
     g_live_ctx.erase(std::remove(g_live_ctx.begin(), g_live_ctx.end(), c), g_live_ctx.end());
   }
   hipSetDevice(c->device);
-  if (c->stream) hipStreamSynchronize(c->stream);
-  if (c->aux_stream) hipStreamSynchronize(c->aux_stream);
+  for (Stream* st : {&c->stream, &c->aux_stream, &c->h2d_stream, &c->snap_stream, &c->mc_stream, &c->copy_stream})
+    if (*st) hipStreamSynchronize(*st);
   resolveTimers(c);
-  for (hipEvent_t e : c->event_pool) hipEventDestroy(e);
-  for (void* p : c->allocs) hipFree(p);
-  if (c->d_halo_recs) hipFree(c->d_halo_recs);
-  if (c->d_halo_keys) { hipFree(c->d_halo_keys); hipFree(c->d_halo_vals); }
-  if (c->d_mh_recs) { hipFree(c->d_mh_recs); hipFree(c->d_mh_keys); hipFree(c->d_mh_vals); }
-  if (c->d_mh2_scratch) hipFree(c->d_mh2_scratch);
-  if (c->h_md_walk) hipHostFree(c->h_md_walk);
-  if (c->ev_md_walk_up) hipEventDestroy(c->ev_md_walk_up);
-  if (c->d_mh2_keys) { hipFree(c->d_mh2_keys); hipFree(c->d_mh2_offs); }
-  if (c->d_pix_scratch) hipFree(c->d_pix_scratch);
-  if (c->h2d_stream) { hipStreamSynchronize(c->h2d_stream); hipStreamDestroy(c->h2d_stream); }
-  if (c->ev_h2d) hipEventDestroy(c->ev_h2d);
-  for (int i = 0; i < 2; ++i) {
-    if (c->ev_ahead[i]) hipEventDestroy(c->ev_ahead[i]);
-    if (c->ev_ahead_h2d[i]) hipEventDestroy(c->ev_ahead_h2d[i]);
-  }
-  if (c->d_inst) hipFree(c->d_inst);
-  if (c->d_slice_keys) { hipFree(c->d_slice_keys); hipFree(c->d_slice_count); }
-  if (c->d_slice_stage) hipFree(c->d_slice_stage);
-  if (c->h_slice_stage) hipHostFree(c->h_slice_stage);
-  if (c->d_render_stats) hipFree(c->d_render_stats);
-  if (c->d_render_stage) hipFree(c->d_render_stage);
-  if (c->h_render_stage) hipHostFree(c->h_render_stage);
-  if (c->d_query_stats) hipFree(c->d_query_stats);
-  if (c->d_query_stage) hipFree(c->d_query_stage);
-  if (c->h_query_stage) hipHostFree(c->h_query_stage);
-  if (c->d_align_acc) hipFree(c->d_align_acc);
-  if (c->h_align_acc) hipHostFree(c->h_align_acc);
-  if (c->d_align_stage) hipFree(c->d_align_stage);
-  if (c->h_align_stage) hipHostFree(c->h_align_stage);
-  for (int i = 0; i < 2; ++i) {
-    if (c->d_ckpt[i]) hipFree(c->d_ckpt[i]);
-    if (c->h_ckpt[i]) hipHostFree(c->h_ckpt[i]);
-    if (c->d_ckpt_slots[i]) hipFree(c->d_ckpt_slots[i]);
-    if (c->ev_ckpt_filled[i]) hipEventDestroy(c->ev_ckpt_filled[i]);
-    if (c->ev_ckpt_drained[i]) hipEventDestroy(c->ev_ckpt_drained[i]);
-  }
-  if (c->d_ckpt_err) hipFree(c->d_ckpt_err);
   if (c->pending_snapshot) khr_snapshot_release(c->pending_snapshot);
-  if (c->snap_stream) {
-    hipStreamSynchronize(c->snap_stream);
-    hipStreamDestroy(c->snap_stream);
-    c->snap_stream = nullptr;
-  }
-  if (c->ev_snap_fork) hipEventDestroy(c->ev_snap_fork);
-  if (c->ev_snap_join) hipEventDestroy(c->ev_snap_join);
-  if (c->mc_stream) {
-    hipStreamSynchronize(c->mc_stream);
-    hipStreamDestroy(c->mc_stream);
-    c->mc_stream = nullptr;
-  }
-  if (c->ev_mc_fork) hipEventDestroy(c->ev_mc_fork);
-  if (c->ev_mc_join) hipEventDestroy(c->ev_mc_join);
-  if (c->copy_stream) {
-    hipStreamSynchronize(c->copy_stream);
-    hipStreamDestroy(c->copy_stream);
-    c->copy_stream = nullptr;
-  }
   {
     std::lock_guard<std::mutex> lock(c->snap_pool->mu);
     c->snap_pool->dead = true;  // snapshots still held by a consumer free their arenas themselves from now on
-    for (auto& a : c->snap_pool->free) {
-      hipFree(a.ptr);
-      hipHostFree(const_cast<uint32_t*>(a.h_count));
-    }
     c->snap_pool->free.clear();
   }
   {
     std::lock_guard<std::mutex> lock(c->frame_pool->mu);
     c->frame_pool->dead = true;  // frame copies still held by a consumer free their blocks themselves from now on
-    for (auto& b : c->frame_pool->free) hipFree(b.first);
     c->frame_pool->free.clear();
   }
-  if (c->d_frame_bits) hipFree(c->d_frame_bits);
-  if (c->d_multi_list) hipFree(c->d_multi_list);
-  if (c->h_frames) hipHostFree(c->h_frames);
-  if (c->d_frames) hipFree(c->d_frames);
-  if (c->ev_frames) hipEventDestroy(c->ev_frames);
-  if (c->h_pinned) hipHostFree(c->h_pinned);
-  if (c->h_removed_early) hipHostFree(c->h_removed_early);
-  if (c->h_stage) hipHostFree(c->h_stage);
-  if (c->h_totals) hipHostFree(c->h_totals);
-  if (c->h_up) hipHostFree(c->h_up);
-  if (c->ev_up) hipEventDestroy(c->ev_up);
-  if (c->ev_ingest) hipEventDestroy(c->ev_ingest);
-  if (c->h_tick) hipHostFree(c->h_tick);
-  if (c->h_obj_head) hipHostFree(c->h_obj_head);
-  if (c->h_md_acc_pinned) hipHostFree(c->h_md_acc_pinned);
-  if (c->ev_obj) hipEventDestroy(c->ev_obj);
-  for (int w = 0; w < 2; ++w) {
-    if (c->h_cv[w]) hipHostFree(c->h_cv[w]);
-    if (c->ev_cv[w]) hipEventDestroy(c->ev_cv[w]);
-  }
-  if (c->ev_seed) hipEventDestroy(c->ev_seed);
-  if (c->ev_dep) hipEventDestroy(c->ev_dep);
-  if (c->ev_dep_aux) hipEventDestroy(c->ev_dep_aux);
-  if (c->ev_aux) hipEventDestroy(c->ev_aux);
-  if (c->ev_aux_done) hipEventDestroy(c->ev_aux_done);
-  if (c->aux_stream) hipStreamDestroy(c->aux_stream);
-  if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
   delete c;
 }
 
@@ -1237,17 +1124,11 @@ int khr_set_stream(khr_ctx* c, void* hip_stream) {
   if (!c) return fail(KHR_EINVAL, "null ctx");
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(hipStreamSynchronize(c->aux_stream));
-  if (c->own_stream) {
-    hipStreamDestroy(c->stream);
-    c->own_stream = false;
-  }
   if (hip_stream) {
-    c->stream = static_cast<hipStream_t>(hip_stream);
-  } else {
-    HIP_TRY(createStream(c, &c->stream));
-    c->own_stream = true;
+    c->stream.refer(static_cast<hipStream_t>(hip_stream));
+    return KHR_OK;
   }
-  return KHR_OK;
+  return createStream(c, c->stream);
 }
 
 int khr_sync(khr_ctx* c) {
@@ -1335,12 +1216,11 @@ int khr_upload_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fram
     // Pageable memory: copies on the ingest's own stream and a host wait below (the caller may reuse the memory at once).
     hipStream_t cs = c->stream;
     if (pinned) {
-      if (!c->h2d_stream) HIP_TRY(createStream(c, &c->h2d_stream));
-      hipEvent_t& evh0 = c->h2d_ev_target ? *c->h2d_ev_target : c->ev_h2d;
-      if (!evh0) HIP_TRY(hipEventCreateWithFlags(&evh0, hipEventDisableTiming));
+      if (!c->h2d_stream) KHR_TRY(createStream(c, c->h2d_stream));
+      KHR_TRY((c->h2d_ev_target ? *c->h2d_ev_target : c->ev_h2d).ensure());
       cs = c->h2d_stream;
       if (ist == c->stream) {  // main-stream ingest: the slot's previous readers are ordered in front of it, so must the copy be
-        if (!c->ev_ingest) HIP_TRY(hipEventCreateWithFlags(&c->ev_ingest, hipEventDisableTiming));
+        KHR_TRY(c->ev_ingest.ensure());
         HIP_TRY(hipEventRecord(c->ev_ingest, c->stream));
         HIP_TRY(hipStreamWaitEvent(cs, c->ev_ingest, 0));
       }
@@ -1356,7 +1236,7 @@ int khr_upload_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fram
       label_src = s.label;
     }
     if (pinned) {
-      hipEvent_t& evh = c->h2d_ev_target ? *c->h2d_ev_target : c->ev_h2d;
+      const Event& evh = c->h2d_ev_target ? *c->h2d_ev_target : c->ev_h2d;
       HIP_TRY(hipEventRecord(evh, cs));
       HIP_TRY(hipStreamWaitEvent(ist, evh, 0));
       if (!c->h2d_ev_target) c->h2d_pending = true;
@@ -1406,7 +1286,7 @@ int khr_download_frame(khr_ctx* c, int slot, float* range, float* vertex_map, in
   if (dynamic_image) HIP_TRY(hipMemcpyAsync(dynamic_image, s.dyn, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   if (vertex_map) {
     DevTemp tmpv;
-    HIP_TRY(hipMalloc(&tmpv.p, n * 3 * sizeof(float)));
+    KHR_TRY(tmpv.alloc(n * 3 * sizeof(float)));
     float* d_v = tmpv.as<float>();
     hipLaunchKernelGGL(k_vertex_map, dim3(gridFor(n)), dim3(256), 0, c->stream, makeDevFrame(c, s), d_v);
     HIP_TRY(hipMemcpyAsync(vertex_map, d_v, n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -1418,10 +1298,9 @@ int khr_download_frame(khr_ctx* c, int slot, float* range, float* vertex_map, in
 
 struct khr_frame_copy {
   std::shared_ptr<khr_ctx::FramePool> pool;
-  uint8_t* block = nullptr;
-  size_t bytes = 0;
+  DevBuf<uint8_t> block;  // (out of the pool: may be larger than this frame needs)
   int device = 0;
-  hipEvent_t ready = nullptr;  // recorded behind the copy kernel
+  Event ready;  // recorded behind the copy kernel
   DevFrame f{};                // intrinsics + pose of the frame; the plane pointers refer to `block`
   size_t n = 0, n_pad = 0;
 };
@@ -1435,33 +1314,29 @@ int khr_frame_copy_create(khr_ctx* c, int slot, khr_frame_copy** out) {
   auto fc = std::make_unique<khr_frame_copy>();
   fc->pool = c->frame_pool;
   fc->device = c->device;
-  fc->bytes = 16 * n_pad;
+  const size_t bytes = 16 * n_pad;
   {
     std::lock_guard<std::mutex> lock(c->frame_pool->mu);
     auto& fr = c->frame_pool->free;
     for (size_t i = 0; i < fr.size(); ++i)
-      if (fr[i].second >= fc->bytes) {
-        fc->block = fr[i].first;
-        fc->bytes = fr[i].second;
+      if (fr[i].count() >= bytes) {
+        fc->block = std::move(fr[i]);
         fr.erase(fr.begin() + static_cast<long>(i));
         break;
       }
   }
-  if (!fc->block && hipMalloc(reinterpret_cast<void**>(&fc->block), fc->bytes) != hipSuccess) return fail(KHR_ENOMEM, "frame copy (%zu bytes)", fc->bytes);
-  if (hipEventCreateWithFlags(&fc->ready, hipEventDisableTiming) != hipSuccess) {
-    hipFree(fc->block);
-    return fail(KHR_EDEVICE, "event");
-  }
+  if (!fc->block && fc->block.alloc(bytes)) return fail(KHR_ENOMEM, "frame copy (%zu bytes)", bytes);
+  if (fc->ready.ensure()) return fail(KHR_EDEVICE, "event");
   // (the slot's planes are allocated for max_frame_pixels: reading the padding of the last 16-byte vector is inside the allocation)
   if (s.aux_seq) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_aux_done, 0));  // (an ingest queued on the auxiliary stream)
   hipLaunchKernelGGL(k_frame_copy, dim3(512), dim3(256), 0, c->stream, reinterpret_cast<const uint4*>(s.vDepth()),
                      reinterpret_cast<const uint4*>(s.vRange()), s.has_color ? reinterpret_cast<const uint4*>(s.vRgba()) : nullptr,
-                     s.has_label ? reinterpret_cast<const uint4*>(s.vLabel()) : nullptr, reinterpret_cast<uint4*>(fc->block),
+                     s.has_label ? reinterpret_cast<const uint4*>(s.vLabel()) : nullptr, reinterpret_cast<uint4*>(fc->block.get()),
                      static_cast<uint32_t>(n_pad / 4));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(fc->ready, c->stream));
   fc->f = makeDevFrame(c, s);
-  fc->f.depth = reinterpret_cast<const float*>(fc->block);
+  fc->f.depth = reinterpret_cast<const float*>(fc->block.get());
   fc->f.range = reinterpret_cast<const float*>(fc->block + 4 * n_pad);
   fc->f.rgba = reinterpret_cast<const uint32_t*>(fc->block + 8 * n_pad);
   fc->f.label = reinterpret_cast<const int32_t*>(fc->block + 12 * n_pad);
@@ -1483,14 +1358,14 @@ int khr_frame_copy_download(khr_frame_copy* fc, float* depth, float* range, uint
   if (labels) HIP_TRY(hipMemcpy(labels, fc->f.label, n * 4, hipMemcpyDeviceToHost));
   if (color_rgb || vertex_map) {
     DevTemp tmp;
-    HIP_TRY(hipMalloc(&tmp.p, n * 12));
+    KHR_TRY(tmp.alloc(n * 12));
     if (color_rgb) {
       hipLaunchKernelGGL(k_rgba_to_rgb, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, nullptr, fc->f.rgba, tmp.as<uint8_t>(), static_cast<uint32_t>(n));
-      HIP_TRY(hipMemcpy(color_rgb, tmp.p, n * 3, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(color_rgb, tmp.get(), n * 3, hipMemcpyDeviceToHost));
     }
     if (vertex_map) {
       hipLaunchKernelGGL(k_vertex_map, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, nullptr, fc->f, tmp.as<float>());
-      HIP_TRY(hipMemcpy(vertex_map, tmp.p, n * 12, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(vertex_map, tmp.get(), n * 12, hipMemcpyDeviceToHost));
     }
   }
   return KHR_OK;
@@ -1499,20 +1374,12 @@ int khr_frame_copy_download(khr_frame_copy* fc, float* depth, float* range, uint
 void khr_frame_copy_release(khr_frame_copy* fc) {
   if (!fc) return;
   hipSetDevice(fc->device);
-  if (fc->ready) {
-    hipEventSynchronize(fc->ready);  // (the block goes back to the pool: nothing may still be writing it)
-    hipEventDestroy(fc->ready);
-  }
-  bool pooled = false;
+  if (fc->ready) hipEventSynchronize(fc->ready);  // (the block goes back to the pool: nothing may still be writing it)
   {
     std::lock_guard<std::mutex> lock(fc->pool->mu);
-    if (!fc->pool->dead && fc->pool->free.size() < 8) {
-      fc->pool->free.emplace_back(fc->block, fc->bytes);
-      pooled = true;
-    }
+    if (!fc->pool->dead && fc->pool->free.size() < 8) fc->pool->free.push_back(std::move(fc->block));
   }
-  if (!pooled) hipFree(fc->block);
-  delete fc;
+  delete fc;  // (frees the block unless the pool took it)
 }
 
 int khr_copy_frame_image(khr_ctx* c, int slot, int which, void* device_dst) {
@@ -1560,7 +1427,7 @@ static int integrateAlloc(khr_ctx* c, FrameSlot& s, const DevFrame& f, int alloc
     const int S = 2 * fr.n_steps + 1;
     const size_t total = static_cast<size_t>(S) * S * S;
     hipLaunchKernelGGL(k_alloc_visible, dim3(gridFor(total)), dim3(256), 0, c->stream, m, c->p, f, fr, c->d_work, c->d_new,
-                       c->d_pinned + 2, c->seed_publish_pending ? c->seed_ticket : 0u, &m.counters[C_N_VISIBLE], 0);
+                       c->h_pinned.dev() + 2, c->seed_publish_pending ? c->seed_ticket : 0u, &m.counters[C_N_VISIBLE], 0);
     c->seed_publish_pending = false;
     hipLaunchKernelGGL(k_init_cull, dim3(1024 + 1024), dim3(256), 0, c->stream, m, c->p, f, c->d_new, c->d_work,
                        FuseList{c->d_work4, c->d_work4 + c->item_cap, c->item_cap, &m.counters[C_N_ITEMS0]}, c->wpb,
@@ -1667,10 +1534,8 @@ static int integrateUpdateMulti(khr_ctx* c, khr_ctx* src, const int* src_slots, 
   if (!defcfg) return 1;
   // per-frame arguments: pinned staging -> device array (reused only after the previous batch's copy has been consumed)
   if (!c->h_frames) {
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->h_frames), sizeof(FuseFrame) * kMaxMultiFrames, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->d_frames), sizeof(FuseFrame) * kMaxMultiFrames) != hipSuccess)
-      return fail(KHR_ENOMEM, "frame argument staging");
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_frames, hipEventDisableTiming));
+    if (c->h_frames.alloc(kMaxMultiFrames) || c->d_frames.alloc(kMaxMultiFrames)) return fail(KHR_ENOMEM, "frame argument staging");
+    KHR_TRY(c->ev_frames.ensure());
   } else {
     HIP_TRY(hipEventSynchronize(c->ev_frames));
   }
@@ -1682,11 +1547,9 @@ static int integrateUpdateMulti(khr_ctx* c, khr_ctx* src, const int* src_slots, 
   // the frames' arguments reach the device array through a kernel that reads the page-locked staging block (not a hipMemcpyAsync:
   // issued from an extraction worker's thread it can sit for milliseconds behind the window thread's frame transfers, round 5)
   {
-    void* hf_dev = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&hf_dev, c->h_frames, 0));
     const uint32_t n_words = static_cast<uint32_t>(sizeof(FuseFrame) / 4) * static_cast<uint32_t>(n_frames);
-    hipLaunchKernelGGL(k_copy_words, dim3((n_words + 255) / 256), dim3(256), 0, c->stream, static_cast<const uint32_t*>(hf_dev),
-                       reinterpret_cast<uint32_t*>(c->d_frames), n_words);
+    hipLaunchKernelGGL(k_copy_words, dim3((n_words + 255) / 256), dim3(256), 0, c->stream, reinterpret_cast<const uint32_t*>(c->h_frames.dev()),
+                       reinterpret_cast<uint32_t*>(c->d_frames.get()), n_words);
   }
   HIP_TRY(hipEventRecord(c->ev_frames, c->stream));
   static_cast<FuseFrame&>(a) = c->h_frames[0];  // (the head frame; k_fuse2 itself reads a.frames)
@@ -1696,21 +1559,16 @@ static int integrateUpdateMulti(khr_ctx* c, khr_ctx* src, const int* src_slots, 
   if (c->item_cap > 0) {
     const int n_words = (n_frames + 31) / 32;
     const size_t need = static_cast<size_t>(c->item_cap) * static_cast<size_t>(n_words);
-    if (need > c->frame_bits_words) {  // (grown in steps of four words per item = 128 frames: a worker thread's hipMalloc waits for the device)
+    if (need > c->d_frame_bits.count()) {  // (grown in steps of four words per item = 128 frames: a worker thread's hipMalloc waits for the device)
       const size_t want = static_cast<size_t>(c->item_cap) * static_cast<size_t>((n_words + 3) / 4 * 4);
       HIP_TRY(hipStreamSynchronize(c->stream));
-      if (c->d_frame_bits) HIP_TRY(hipFree(c->d_frame_bits));
-      c->d_frame_bits = nullptr;
-      c->frame_bits_words = 0;
-      if (hipMalloc(reinterpret_cast<void**>(&c->d_frame_bits), want * sizeof(uint32_t)) != hipSuccess)
-        return fail(KHR_ENOMEM, "frame bits of the multi-frame update (%zu bytes)", want * sizeof(uint32_t));
-      c->frame_bits_words = want;
+      if (c->d_frame_bits.reserve(want)) return fail(KHR_ENOMEM, "frame bits of the multi-frame update (%zu bytes)", want * sizeof(uint32_t));
     }
     const uint64_t tests = static_cast<uint64_t>(c->explicit_blocks > 0 ? std::min<uint64_t>(c->explicit_blocks, c->m.capacity) : c->m.capacity) *
                            c->wpb * static_cast<uint64_t>(n_words) * 32u;
     const unsigned grid = static_cast<unsigned>(std::min<uint64_t>((tests + 255) / 256, 8192));
     hipLaunchKernelGGL((k_multi_cull<8>), dim3(std::max(1u, grid)), dim3(256), 0, c->stream, c->m.blk_flags, c->m.blk_index, &c->m.counters[C_MAX_SLOT],
-                       c->p.vs, c->p.bs, c->p.trunc, static_cast<const FuseFrame*>(c->d_frames), n_frames, n_words, c->wpb, BLK_LIVE, c->d_frame_bits);
+                       c->p.vs, c->p.bs, c->p.trunc, static_cast<const FuseFrame*>(c->d_frames.get()), n_frames, n_words, c->wpb, BLK_LIVE, c->d_frame_bits);
     HIP_TRY(hipGetLastError());
     a.frame_bits = c->d_frame_bits;
     a.frame_words = n_words;
@@ -1720,15 +1578,14 @@ static int integrateUpdateMulti(khr_ctx* c, khr_ctx* src, const int* src_slots, 
     // ... and the items in the order of their frame counts, the untouched ones left out (k_multi_order): a list of its own
     if (!c->d_multi_list) {
       HIP_TRY(hipStreamSynchronize(c->stream));
-      if (hipMalloc(reinterpret_cast<void**>(&c->d_multi_list), sizeof(uint4) * 2 * c->item_cap + 16) != hipSuccess)
-        return fail(KHR_ENOMEM, "item list of the multi-frame update");
+      if (c->d_multi_list.alloc(2 * static_cast<size_t>(c->item_cap) + 1)) return fail(KHR_ENOMEM, "item list of the multi-frame update");
     }
     uint32_t* const counts = reinterpret_cast<uint32_t*>(c->d_multi_list + 2 * static_cast<size_t>(c->item_cap));
     HIP_TRY(hipMemsetAsync(counts, 0, 16, c->stream));
     list = FuseList{c->d_multi_list, c->d_multi_list + c->item_cap, c->item_cap, counts};
     const uint64_t n_it = static_cast<uint64_t>(c->explicit_blocks > 0 ? std::min<uint64_t>(c->explicit_blocks, c->m.capacity) : c->m.capacity) * c->wpb;
     hipLaunchKernelGGL(k_multi_order, dim3(static_cast<unsigned>((n_it + 1023) / 1024)), dim3(1024), 0, c->stream, c->m.blk_flags, c->m.blk_index,
-                       &c->m.counters[C_MAX_SLOT], static_cast<const uint32_t*>(c->d_frame_bits), a.frame_words, n_frames, c->wpb, BLK_LIVE, list);
+                       &c->m.counters[C_MAX_SLOT], static_cast<const uint32_t*>(c->d_frame_bits.get()), a.frame_words, n_frames, c->wpb, BLK_LIVE, list);
     HIP_TRY(hipGetLastError());
   }
   constexpr int WPW = 8;
@@ -2012,10 +1869,8 @@ static int ensureTick(khr_ctx* c) {
   if (!rc) rc = devAlloc(c, &c->d_tick_frames, kMaxTick, false);
   if (!rc) rc = devAlloc(c, &c->d_tick_mask, c->item_cap / 4 + 1);
   if (rc) return rc;
-  if (hipHostMalloc(reinterpret_cast<void**>(&c->h_tick), 256, hipHostMallocDefault) != hipSuccess)
-    return fail(KHR_ENOMEM, "pinned tick block");
+  if (c->h_tick.alloc(64)) return fail(KHR_ENOMEM, "pinned tick block");
   std::memset(c->h_tick, 0, 256);
-  HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_tick_host), c->h_tick, 0));
   HIP_TRY(hipStreamSynchronize(c->stream));  // the zero-fills above
   return KHR_OK;
 }
@@ -2097,7 +1952,7 @@ int khr_tick_ingest(khr_ctx* c, const khr_sensor* sensor, const khr_frame* frame
       ++c->tick_ticket;
       if (c->tick_ticket == 0) ++c->tick_ticket;
       hipLaunchKernelGGL(k_tick_publish, dim3(1), dim3(64), 0, c->stream, c->d_tick_seeds, nb,
-                         c->d_tick_host, c->d_tick_host + 32, c->tick_ticket,
+                         c->h_tick.dev(), c->h_tick.dev() + 32, c->tick_ticket,
                          seed_counts_device ? reinterpret_cast<long long*>(seed_counts_device) + base : nullptr);
     }
     HIP_TRY(hipGetLastError());
@@ -2221,7 +2076,7 @@ int khr_tick_adopt(khr_ctx* c, const khr_sensor* sensor, const khr_converted_fra
     if (count_seeds) {
       ++c->tick_ticket;
       if (c->tick_ticket == 0) ++c->tick_ticket;
-      hipLaunchKernelGGL(k_tick_publish, dim3(1), dim3(64), 0, c->stream, c->d_tick_seeds, nb, c->d_tick_host, c->d_tick_host + 32,
+      hipLaunchKernelGGL(k_tick_publish, dim3(1), dim3(64), 0, c->stream, c->d_tick_seeds, nb, c->h_tick.dev(), c->h_tick.dev() + 32,
                          c->tick_ticket, seed_counts_device ? reinterpret_cast<long long*>(seed_counts_device) + base : nullptr);
     }
     HIP_TRY(hipGetLastError());
@@ -2349,7 +2204,7 @@ int khr_tick_integrate(khr_ctx* c, const int* slots, int n_frames, int use_mask,
           const int S = 2 * tf.fr[k].n_steps + 1;
           const size_t total = static_cast<size_t>(S) * S * S;
           hipLaunchKernelGGL(k_alloc_visible, dim3(gridFor(total)), dim3(256), 0, c->stream, m, c->p, t.f[k], tf.fr[k],
-                             c->d_tick_work + static_cast<size_t>(k) * cap, c->d_new, c->d_pinned + 2, 0u, &c->d_tick_counts[2 * k],
+                             c->d_tick_work + static_cast<size_t>(k) * cap, c->d_new, c->h_pinned.dev() + 2, 0u, &c->d_tick_counts[2 * k],
                              c->motion_ignore_epoch);
         }
       }
@@ -2402,7 +2257,7 @@ int khr_export_halo(khr_ctx* c, void* records, int64_t cap_records, int on_devic
   DevTemp holder;
   uint64_t* tmp = nullptr;
   if (!on_device) {
-    HIP_TRY(hipMalloc(&holder.p, bytes));
+    KHR_TRY(holder.alloc(bytes));
     dst = tmp = holder.as<uint64_t>();
   }
   HIP_TRY(hipMemsetAsync(c->d_mesh_nwork + 1, 0, sizeof(uint32_t), c->stream));
@@ -2433,23 +2288,17 @@ int khr_import_halo(khr_ctx* c, const void* records, int64_t n_records, int on_d
   while (ht < static_cast<uint64_t>(n_records) * 4) ht <<= 1;
   if (static_cast<uint64_t>(n_records) > c->halo_cap_total) {  // (re)allocate the remote table
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_halo_keys) { hipFree(c->d_halo_keys); hipFree(c->d_halo_vals); }
-    c->d_halo_keys = nullptr;
-    c->d_halo_vals = nullptr;
     c->halo_cap_total = 0;
-    HIP_TRY(hipMalloc(&c->d_halo_keys, sizeof(uint64_t) * ht));
-    HIP_TRY(hipMalloc(&c->d_halo_vals, sizeof(uint32_t) * ht));
+    c->d_halo_keys.reset(), c->d_halo_vals.reset();  // (both go before either comes back)
+    KHR_TRY(c->d_halo_keys.alloc(ht));
+    KHR_TRY(c->d_halo_vals.alloc(ht));
     c->halo_cap_total = static_cast<uint32_t>(n_records);
   }
   // the staging copy of the records exists only for host-side callers (on_device imports use the caller's buffer in place:
   // the RCCL tick pre-sizes the table with world x halo_cap records and would otherwise pin hundreds of MB it never reads)
-  if (!on_device && static_cast<uint64_t>(n_records) > c->halo_recs_cap) {
+  if (!on_device && static_cast<size_t>(n_records) * kHaloRecWords > c->d_halo_recs.count()) {
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_halo_recs) hipFree(c->d_halo_recs);
-    c->d_halo_recs = nullptr;
-    c->halo_recs_cap = 0;
-    HIP_TRY(hipMalloc(&c->d_halo_recs, static_cast<size_t>(n_records) * kHaloRecWords * sizeof(uint64_t)));
-    c->halo_recs_cap = static_cast<uint32_t>(n_records);
+    KHR_TRY(c->d_halo_recs.reserve(static_cast<size_t>(n_records) * kHaloRecWords));
   }
   c->halo_mask = ht - 1;
   // device records are used where they lie (the caller keeps the buffer until the next khr_update_tracking_phase(.., 2)
@@ -2541,7 +2390,7 @@ static int waitSeedCount(khr_ctx* c) {
     return KHR_OK;
   }
   if (c->seed_publish_pending) {
-    hipLaunchKernelGGL(k_publish_seed, dim3(1), dim3(1), 0, c->stream, c->m, c->d_pinned + 2, c->seed_ticket);
+    hipLaunchKernelGGL(k_publish_seed, dim3(1), dim3(1), 0, c->stream, c->m, c->h_pinned.dev() + 2, c->seed_ticket);
     HIP_TRY(hipGetLastError());
     c->seed_publish_pending = false;
   }
@@ -2588,8 +2437,8 @@ static int clusterSummaryLaunch(khr_ctx* c, FrameSlot& s, int max_id) {
   hipLaunchKernelGGL(k_cluster_summary, dim3(tiles), dim3(1024), 0, c->stream, makeDevFrame(c, s), s.dyn, c->d_md_acc,
                      s.dynw_valid ? static_cast<const uint8_t*>(s.dynw) : nullptr);
   if (++c->md_acc_ticket == 0) ++c->md_acc_ticket;
-  hipLaunchKernelGGL(k_publish_cluster_acc, dim3(1), dim3(256), 0, c->stream, c->d_md_acc, reinterpret_cast<uint32_t*>(c->d_md_acc_host),
-                     static_cast<uint32_t>(std::min(max_id + 1, 256)), c->d_pinned + 7, c->md_acc_ticket);
+  hipLaunchKernelGGL(k_publish_cluster_acc, dim3(1), dim3(256), 0, c->stream, c->d_md_acc, reinterpret_cast<uint32_t*>(c->h_md_acc_pinned.dev()),
+                     static_cast<uint32_t>(std::min(max_id + 1, 256)), c->h_pinned.dev() + 7, c->md_acc_ticket);
   HIP_TRY(hipGetLastError());
   c->md_acc_slot = static_cast<int>(&s - c->slots.data());
   return KHR_OK;
@@ -2674,8 +2523,8 @@ static int motionFinish(khr_ctx* c, FrameSlot& s) {
     HIP_TRY(hipGetLastError());
     // counters + the first component records -> pinned memory by a one-workgroup kernel, the host spins on the ticket
     if (++c->md_head_ticket == 0) ++c->md_head_ticket;
-    hipLaunchKernelGGL(k_publish, dim3(1), dim3(1024), 0, c->stream, c->d_md_n, reinterpret_cast<uint32_t*>(c->d_md_head_host),
-                       static_cast<uint32_t>(sizeof(CompAcc) / 4), kCompHead, c->d_pinned + 8, c->md_head_ticket, c->d_md_scratch4);
+    hipLaunchKernelGGL(k_publish, dim3(1), dim3(1024), 0, c->stream, c->d_md_n, reinterpret_cast<uint32_t*>(c->h_md_head.dev()),
+                       static_cast<uint32_t>(sizeof(CompAcc) / 4), kCompHead, c->h_pinned.dev() + 8, c->md_head_ticket, c->d_md_scratch4);
     HIP_TRY(hipGetLastError());
     return KHR_OK;
   };
@@ -2705,7 +2554,7 @@ static int motionFinish(khr_ctx* c, FrameSlot& s) {
   bool chain_queued = pre_px != 0 && c->h_pinned[0] <= pre_px;
   if (pre_px != 0 && !chain_queued) ++c->n_md_prelaunch_repeats;
   uint32_t mask = chain_queued ? pre_mask : maskFor(c->h_pinned[0]);
-  const uint32_t* cnt = reinterpret_cast<const uint32_t*>(c->h_md_head);
+  const uint32_t* cnt = reinterpret_cast<const uint32_t*>(c->h_md_head.get());
   for (int attempt = 0;; ++attempt) {
     if (!chain_queued) {
       const int rcl = launchChain(c->h_pinned[0], mask, with_global);
@@ -2784,7 +2633,7 @@ static int motionFinish(khr_ctx* c, FrameSlot& s) {
     if (!may_merge || merge_here) {
       c->stats.n_seeds = S;
       // applyClusterLevelFilters (:365-379) + ids of writeClustersToData (:381-399)
-      int32_t* fin = reinterpret_cast<int32_t*>(c->h_md_head);  // the records are no longer needed once ids are taken
+      int32_t* fin = reinterpret_cast<int32_t*>(c->h_md_head.get());  // the records are no longer needed once ids are taken
       std::vector<std::pair<int, uint64_t>> kept;
       std::vector<int32_t> tmp(R, 0);
       std::vector<uint64_t> gpx(R, 0);
@@ -2850,21 +2699,13 @@ static int motionFinish(khr_ctx* c, FrameSlot& s) {
   // the same time -- this frame's few kilobytes waited 7 ms (profiles/r05_host_consumer_40.txt).
   const size_t w_sk = 2 * static_cast<size_t>(S), w_sc = S, w_adj = static_cast<size_t>(S) * nn, w_bk = 2 * static_cast<size_t>(B), w_bc = B;
   const size_t walk_words = w_sk + w_sc + w_adj + w_bk + w_bc + 16;
-  if (walk_words > c->h_md_walk_words) {
-    if (c->ev_md_walk_up) HIP_TRY(hipEventSynchronize(c->ev_md_walk_up));
-    if (c->h_md_walk) HIP_TRY(hipHostFree(c->h_md_walk));
-    c->h_md_walk = nullptr;
-    c->h_md_walk_words = 0;
+  if (c->ev_md_walk_up) HIP_TRY(hipEventSynchronize(c->ev_md_walk_up));  // (the previous seed frame's upload reads the block)
+  if (walk_words > c->h_md_walk.count()) {
     const size_t want = std::max<size_t>(2 * walk_words, 1u << 18);
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->h_md_walk), want * 4, hipHostMallocDefault) != hipSuccess)
-      return fail(KHR_ENOMEM, "page-locked block of the motion detector's host walk (%zu bytes)", want * 4);
-    c->h_md_walk_words = want;
-  } else if (c->ev_md_walk_up) {
-    HIP_TRY(hipEventSynchronize(c->ev_md_walk_up));  // (the previous seed frame's upload reads the block)
+    if (c->h_md_walk.reserve(want)) return fail(KHR_ENOMEM, "page-locked block of the motion detector's host walk (%zu bytes)", want * 4);
   }
-  if (!c->ev_md_walk_up) HIP_TRY(hipEventCreateWithFlags(&c->ev_md_walk_up, hipEventDisableTiming));
-  uint32_t* walk_dev = nullptr;
-  HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&walk_dev), c->h_md_walk, 0));
+  KHR_TRY(c->ev_md_walk_up.ensure());
+  uint32_t* const walk_dev = c->h_md_walk.dev();
   {
     size_t o = 0;
     auto down = [&](const void* src, size_t words) {
@@ -3083,7 +2924,7 @@ int khr_motion_keys(khr_ctx* c, int slot, void* keys_out, int on_device, uint32_
   uint64_t* dst = static_cast<uint64_t*>(keys_out);
   DevTemp holder;
   if (!on_device) {
-    HIP_TRY(hipMalloc(&holder.p, sizeof(uint64_t) * n));
+    KHR_TRY(holder.alloc(sizeof(uint64_t) * n));
     dst = holder.as<uint64_t>();
   }
   hipLaunchKernelGGL(k_md_keys_export, dim3(gridFor(n)), dim3(256), 0, c->stream, c->d_keys, n, dst);
@@ -3111,8 +2952,8 @@ int khr_detect_motion_from_keys(khr_ctx* c, int slot, const void* keys, int on_d
   const uint64_t* src = static_cast<const uint64_t*>(keys);
   DevTemp holder;  // (freed when this call returns; hipFree waits for the kernels that read it)
   if (!on_device) {
-    HIP_TRY(hipMalloc(&holder.p, sizeof(uint64_t) * n));
-    HIP_TRY(hipMemcpyAsync(holder.p, keys, sizeof(uint64_t) * n, hipMemcpyHostToDevice, c->stream));
+    KHR_TRY(holder.alloc(sizeof(uint64_t) * n));
+    HIP_TRY(hipMemcpyAsync(holder.get(), keys, sizeof(uint64_t) * n, hipMemcpyHostToDevice, c->stream));
     src = holder.as<uint64_t>();
   }
   if (!s.dyn_clean) HIP_TRY(hipMemsetAsync(s.dyn, 0, sizeof(int32_t) * n, c->stream));
@@ -3249,35 +3090,30 @@ static int ensureGv(khr_ctx* c) {
   c->gv_mask = static_cast<uint32_t>(ts - 1);
   c->obj_root_cap = 1u << 16;
   int rc = KHR_OK;
-  auto A = [&](int r) { if (rc == KHR_OK) rc = r; };
-  A(devAlloc(c, &c->d_gv_keys, ts, false));
-  A(devAlloc(c, &c->d_gv_parent, ts, false));  // >= npx: also the per-pixel parent array of the 2D mode
-  A(devAlloc(c, &c->d_gv_rootidx, ts, false));
-  A(devAlloc(c, &c->d_gv_node, npx, false));
-  A(devAlloc(c, &c->d_gv_owners, npx, false));
-  A(devAlloc(c, &c->d_gv_done, 4));
+  KHR_CHAIN(devAlloc(c, &c->d_gv_keys, ts, false));
+  KHR_CHAIN(devAlloc(c, &c->d_gv_parent, ts, false));  // >= npx: also the per-pixel parent array of the 2D mode
+  KHR_CHAIN(devAlloc(c, &c->d_gv_rootidx, ts, false));
+  KHR_CHAIN(devAlloc(c, &c->d_gv_node, npx, false));
+  KHR_CHAIN(devAlloc(c, &c->d_gv_owners, npx, false));
+  KHR_CHAIN(devAlloc(c, &c->d_gv_done, 4));
   {
     // counters and cluster records are contiguous: one small copy brings both to the host
     uint8_t* head = nullptr;
-    A(devAlloc(c, &head, 16 + sizeof(ObjAcc) * c->obj_root_cap));
+    KHR_CHAIN(devAlloc(c, &head, 16 + sizeof(ObjAcc) * c->obj_root_cap));
     c->d_gv_n = reinterpret_cast<uint32_t*>(head);
     c->d_obj_acc = head ? reinterpret_cast<ObjAcc*>(head + 16) : nullptr;
   }
-  A(devAlloc(c, &c->d_obj_final, c->obj_root_cap, false));
+  KHR_CHAIN(devAlloc(c, &c->d_obj_final, c->obj_root_cap, false));
   for (int w = 0; w < 2; ++w) {
     uint8_t* head = nullptr;
-    A(devAlloc(c, &head, 16 + sizeof(uint64_t) * npx));
+    KHR_CHAIN(devAlloc(c, &head, 16 + sizeof(uint64_t) * npx));
     c->d_cv_n[w] = reinterpret_cast<uint32_t*>(head);
     c->d_cv_keys[w] = head ? reinterpret_cast<uint64_t*>(head + 16) : nullptr;
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->h_cv[w]), 16 + sizeof(uint64_t) * npx, hipHostMallocDefault) != hipSuccess ||
-        hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_cv_host[w]), c->h_cv[w], 0) != hipSuccess)
-      A(KHR_ENOMEM);
-    if (hipEventCreateWithFlags(&c->ev_cv[w], hipEventDisableTiming) != hipSuccess) A(KHR_EDEVICE);
+    KHR_CHAIN(c->h_cv[w].alloc(16 + sizeof(uint64_t) * npx));
+    KHR_CHAIN(c->ev_cv[w].ensure());
   }
-  if (hipHostMalloc(reinterpret_cast<void**>(&c->h_obj_head), 16 + sizeof(ObjAcc) * c->obj_root_cap, hipHostMallocDefault) != hipSuccess ||
-      hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_obj_head_host), c->h_obj_head, 0) != hipSuccess)
-    A(KHR_ENOMEM);
-  if (hipEventCreateWithFlags(&c->ev_obj, hipEventDisableTiming) != hipSuccess) A(KHR_EDEVICE);
+  KHR_CHAIN(c->h_obj_head.alloc(16 + sizeof(ObjAcc) * c->obj_root_cap));
+  KHR_CHAIN(c->ev_obj.ensure());
   if (rc == KHR_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = KHR_EDEVICE;  // zero-fills above vs the auxiliary stream
   return rc;
 }
@@ -3302,14 +3138,8 @@ int khr_configure_object_detector(khr_ctx* c, const khr_object_detector_config* 
   if (c->obj_labels.size() > kGvMaxGroup) return fail(KHR_EINVAL, "more than %u object labels", kGvMaxGroup);
   c->obj_cfg.object_labels = nullptr;
   c->obj_cfg.n_object_labels = static_cast<int32_t>(c->obj_labels.size());
-  if (c->d_obj_labels) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    hipFree(c->d_obj_labels);
-    c->allocs.erase(std::remove(c->allocs.begin(), c->allocs.end(), static_cast<void*>(c->d_obj_labels)), c->allocs.end());
-    c->d_obj_labels = nullptr;
-  }
-  rc = devAlloc(c, &c->d_obj_labels, c->obj_labels.size(), false);
-  if (rc) return rc;
+  if (c->d_obj_labels) HIP_TRY(hipStreamSynchronize(c->stream));
+  KHR_TRY(c->d_obj_labels.alloc(std::max<size_t>(c->obj_labels.size(), 1)));
   if (!c->obj_labels.empty()) {
     HIP_TRY(hipMemcpyAsync(c->d_obj_labels, c->obj_labels.data(), sizeof(int32_t) * c->obj_labels.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3370,12 +3200,12 @@ static int objectsLaunch(khr_ctx* c, int slot) {
   if (++c->obj_ticket == 0) ++c->obj_ticket;
   if (oc.use_3d) {
     hipLaunchKernelGGL(k_gv_release_publish, dim3(256), dim3(256), 0, c->aux_stream, c->d_gv_owners, c->d_gv_n + 2, c->d_gv_keys, c->d_gv_done,
-                       c->d_gv_n, reinterpret_cast<uint32_t*>(c->d_obj_head_host), static_cast<uint32_t>(sizeof(ObjAcc) / 4), kObjHead,
-                       c->d_pinned + 4, c->obj_ticket, c->d_gv_n);
+                       c->d_gv_n, reinterpret_cast<uint32_t*>(c->h_obj_head.dev()), static_cast<uint32_t>(sizeof(ObjAcc) / 4), kObjHead,
+                       c->h_pinned.dev() + 4, c->obj_ticket, c->d_gv_n);
     c->gv_clean = true;
   } else {
-    hipLaunchKernelGGL(k_publish, dim3(1), dim3(1024), 0, c->aux_stream, c->d_gv_n, reinterpret_cast<uint32_t*>(c->d_obj_head_host),
-                       static_cast<uint32_t>(sizeof(ObjAcc) / 4), kObjHead, c->d_pinned + 4, c->obj_ticket, c->d_gv_n);
+    hipLaunchKernelGGL(k_publish, dim3(1), dim3(1024), 0, c->aux_stream, c->d_gv_n, reinterpret_cast<uint32_t*>(c->h_obj_head.dev()),
+                       static_cast<uint32_t>(sizeof(ObjAcc) / 4), kObjHead, c->h_pinned.dev() + 4, c->obj_ticket, c->d_gv_n);
   }
   HIP_TRY(hipGetLastError());
   c->gv_counters_clean[0] = oc.use_3d != 0;  // (the 2D path resets them itself)
@@ -3397,7 +3227,7 @@ static int objectsFinish(khr_ctx* c, int slot) {
     if (rcw) return rcw;
     c->aux_seq_done = std::max(c->aux_seq_done, c->obj_seq);
   }
-  const uint32_t* cnt = reinterpret_cast<const uint32_t*>(c->h_obj_head);
+  const uint32_t* cnt = reinterpret_cast<const uint32_t*>(c->h_obj_head.get());
   if (cnt[1] & 1u) return fail(KHR_EINVAL, "object detector: a measured point lies more than %d grid cells from the sensor", kGvWindow);
   const uint32_t R = cnt[0];
   if (R > c->obj_root_cap) return fail(KHR_ENOMEM, "object detector: %u clusters exceed the capacity %u", R, c->obj_root_cap);
@@ -3502,7 +3332,7 @@ int khr_cluster_voxels_launch(khr_ctx* c, int slot, int which, float voxel_size)
   if (rc) return rc;
   FrameSlot& s = c->slots[slot];
   c->cv_pending_slot[which] = slot;
-  uint32_t* hc = reinterpret_cast<uint32_t*>(c->h_cv[which]);
+  uint32_t* hc = reinterpret_cast<uint32_t*>(c->h_cv[which].get());
   if (which == 1 && !s.has_obj) {  // no object image: nothing to look at
     hc[0] = hc[1] = 0;
     c->cv_ticket[which] = c->h_pinned[5 + which];  // nothing in flight: the fetch sees the current ticket
@@ -3530,8 +3360,8 @@ int khr_cluster_voxels_launch(khr_ctx* c, int slot, int which, float voxel_size)
   HIP_TRY(hipGetLastError());
   if (++c->cv_ticket[which] == 0) ++c->cv_ticket[which];
   hipLaunchKernelGGL(k_gv_release_publish, dim3(256), dim3(256), 0, c->aux_stream, c->d_gv_owners, c->d_cv_n[which], c->d_gv_keys, c->d_gv_done,
-                     c->d_cv_n[which], reinterpret_cast<uint32_t*>(c->d_cv_host[which]), 2u,
-                     static_cast<uint32_t>(std::min<size_t>(kCvHead, c->cfg.max_frame_pixels)), c->d_pinned + 5 + which, c->cv_ticket[which],
+                     c->d_cv_n[which], reinterpret_cast<uint32_t*>(c->h_cv[which].dev()), 2u,
+                     static_cast<uint32_t>(std::min<size_t>(kCvHead, c->cfg.max_frame_pixels)), c->h_pinned.dev() + 5 + which, c->cv_ticket[which],
                      c->d_cv_n[which]);
   HIP_TRY(hipGetLastError());
   c->gv_counters_clean[1 + which] = true;
@@ -3546,7 +3376,7 @@ int64_t khr_cluster_voxels_fetch(khr_ctx* c, int which, int32_t* ids_out, int64_
     if (!rcw) c->aux_seq_done = std::max(c->aux_seq_done, c->cv_seq[which]);
     if (rcw) return rcw;
   }
-  const uint32_t* cnt = reinterpret_cast<const uint32_t*>(c->h_cv[which]);
+  const uint32_t* cnt = reinterpret_cast<const uint32_t*>(c->h_cv[which].get());
   if (cnt[1] & 1u) return fail(KHR_EINVAL, "cluster voxels: a measured point lies more than %d voxels from the sensor", kGvWindow);
   if (cnt[1] & 2u) return fail(KHR_EINVAL, "cluster voxels: cluster id above %u", kGvMaxGroup);
   const uint32_t N = cnt[0];
@@ -3602,10 +3432,9 @@ int khr_pixel_iou(khr_ctx* c, int slot, const khr_pixel_ref* refs, int n_refs, i
   if (!cur.has_obj) return fail(KHR_ESTATE, "the frame has no object image (run the object detector first)");
   const size_t npx = c->cfg.max_frame_pixels;
   const size_t words = npx + kPixRefs + static_cast<size_t>(kPixRefs) * (static_cast<size_t>(max_id) + 1);
-  if (c->pix_words < words) {
-    if (c->d_pix_scratch) { HIP_TRY(hipStreamSynchronize(c->stream)); hipFree(c->d_pix_scratch); c->d_pix_scratch = nullptr; }
-    HIP_TRY(hipMalloc(&c->d_pix_scratch, words * sizeof(uint32_t)));
-    c->pix_words = words;
+  if (c->d_pix_scratch.count() < words) {
+    if (c->d_pix_scratch) HIP_TRY(hipStreamSynchronize(c->stream));
+    KHR_TRY(c->d_pix_scratch.reserve(words));
   }
   uint32_t* const d_mask = c->d_pix_scratch;
   uint32_t* const d_np = d_mask + npx;
@@ -3659,12 +3488,11 @@ int khr_forward_instances(khr_ctx* c, int slot, float max_range, const int32_t* 
   HIP_TRY(hipSetDevice(c->device));
   const size_t n_acc = static_cast<size_t>(max_id) + 1;
   const size_t bytes = sizeof(ObjAcc) * n_acc + 16 + sizeof(int32_t) * static_cast<size_t>(std::max(n_background, 1));
-  if (c->inst_bytes < bytes) {
-    if (c->d_inst) { HIP_TRY(hipStreamSynchronize(c->stream)); hipFree(c->d_inst); c->d_inst = nullptr; }
-    HIP_TRY(hipMalloc(&c->d_inst, bytes));
-    c->inst_bytes = bytes;
+  if (c->d_inst.count() < bytes) {
+    if (c->d_inst) HIP_TRY(hipStreamSynchronize(c->stream));
+    KHR_TRY(c->d_inst.reserve(bytes));
   }
-  ObjAcc* const d_acc = reinterpret_cast<ObjAcc*>(c->d_inst);
+  ObjAcc* const d_acc = reinterpret_cast<ObjAcc*>(c->d_inst.get());
   uint32_t* const d_flags = reinterpret_cast<uint32_t*>(c->d_inst + sizeof(ObjAcc) * n_acc);
   int32_t* const d_bg = reinterpret_cast<int32_t*>(c->d_inst + sizeof(ObjAcc) * n_acc + 16);
   if (n_background) HIP_TRY(hipMemcpyAsync(d_bg, background_ids, sizeof(int32_t) * n_background, hipMemcpyHostToDevice, c->stream));
@@ -3752,16 +3580,14 @@ int khr_generate_mesh(khr_ctx* c, int only_mesh_updated, int clear_flag) {
 // the archival's list ahead of the archival (khr_process_frame at output frames, behind the tracking pass)
 static int removedPublishLaunch(khr_ctx* c) {
   if (!c->h_removed_early) {
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->h_removed_early), sizeof(int4) * c->m.capacity, hipHostMallocDefault) != hipSuccess)
+    if (c->h_removed_early.alloc(c->m.capacity))
       return fail(KHR_ENOMEM, "page-locked list of archived blocks (%zu bytes)", sizeof(int4) * static_cast<size_t>(c->m.capacity));
     int rc = devAlloc(c, &c->d_removed_early_n, 2);
     if (rc) return rc;
   }
-  void* list_dev = nullptr;
-  HIP_TRY(hipHostGetDevicePointer(&list_dev, c->h_removed_early, 0));
   if (++c->removed_early_ticket == 0) ++c->removed_early_ticket;
-  hipLaunchKernelGGL(k_removed_publish, dim3(gridFor(c->m.capacity)), dim3(256), 0, c->stream, c->m, static_cast<int4*>(list_dev),
-                     c->d_removed_early_n, c->d_pinned + 10, c->removed_early_ticket);
+  hipLaunchKernelGGL(k_removed_publish, dim3(gridFor(c->m.capacity)), dim3(256), 0, c->stream, c->m, c->h_removed_early.dev(),
+                     c->d_removed_early_n, c->h_pinned.dev() + 10, c->removed_early_ticket);
   HIP_TRY(hipGetLastError());
   return KHR_OK;
 }
@@ -3793,7 +3619,7 @@ static int fetchRemoved(khr_ctx* c, int32_t* removed, int64_t cap, int64_t* n_re
     c->removed_pending = false;
     if (n_removed) *n_removed = ne;
     if (ne && removed && cap > 0) {
-      std::vector<int4> tmp(c->h_removed_early, c->h_removed_early + ne);
+      std::vector<int4> tmp(c->h_removed_early.get(), c->h_removed_early + ne);
       std::sort(tmp.begin(), tmp.end(), [](const int4& a, const int4& b) {
         return a.x != b.x ? a.x < b.x : (a.y != b.y ? a.y < b.y : a.z < b.z);
       });
@@ -3833,7 +3659,7 @@ int khr_mesh_halo_requests(khr_ctx* c, void* keys_out, int64_t cap, int only_mes
   DevTemp holder;
   uint64_t* tmp = nullptr;
   if (!on_device) {
-    HIP_TRY(hipMalloc(&holder.p, sizeof(uint64_t) * cap));
+    KHR_TRY(holder.alloc(sizeof(uint64_t) * cap));
     dst = tmp = holder.as<uint64_t>();
   }
   HIP_TRY(hipMemsetAsync(dst, 0, sizeof(uint64_t) * cap, c->stream));
@@ -3862,11 +3688,11 @@ int khr_mesh_halo_export(khr_ctx* c, const void* requests, int64_t n_requests, v
   uint32_t* rec_tmp = nullptr;
   if (!on_device) {
     if (n_requests) {
-      HIP_TRY(hipMalloc(&req_holder.p, sizeof(uint64_t) * n_requests));
-      HIP_TRY(hipMemcpyAsync(req_holder.p, requests, sizeof(uint64_t) * n_requests, hipMemcpyHostToDevice, c->stream));
+      KHR_TRY(req_holder.alloc(sizeof(uint64_t) * n_requests));
+      HIP_TRY(hipMemcpyAsync(req_holder.get(), requests, sizeof(uint64_t) * n_requests, hipMemcpyHostToDevice, c->stream));
       req = req_holder.as<uint64_t>();
     }
-    HIP_TRY(hipMalloc(&rec_holder.p, bytes));
+    KHR_TRY(rec_holder.alloc(bytes));
     dst = rec_tmp = rec_holder.as<uint32_t>();
   }
   HIP_TRY(hipMemsetAsync(c->d_mh_flag, 0, m.capacity, c->stream));
@@ -3904,17 +3730,16 @@ int khr_mesh_halo_import(khr_ctx* c, const void* records, int64_t n_records, int
   while (ht < static_cast<uint64_t>(n_records) * 4) ht <<= 1;
   if (static_cast<uint64_t>(n_records) > c->mh_cap_total) {
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_mh_recs) { hipFree(c->d_mh_recs); hipFree(c->d_mh_keys); hipFree(c->d_mh_vals); }
-    c->d_mh_recs = nullptr;
+    c->d_mh_recs.reset(), c->d_mh_keys.reset(), c->d_mh_vals.reset();
     // (in-place imports only need the index; the record copy buffer is allocated by the first copying import)
-    HIP_TRY(hipMalloc(&c->d_mh_keys, sizeof(uint64_t) * ht));
-    HIP_TRY(hipMalloc(&c->d_mh_vals, sizeof(uint32_t) * ht));
+    KHR_TRY(c->d_mh_keys.alloc(ht));
+    KHR_TRY(c->d_mh_vals.alloc(ht));
     c->mh_cap_total = static_cast<uint32_t>(n_records);
   }
   c->mh_mask = ht - 1;  // (a smaller import clears and probes a smaller part of the table)
   const uint32_t* view = static_cast<const uint32_t*>(records);
   if (!in_place) {
-    if (!c->d_mh_recs) HIP_TRY(hipMalloc(&c->d_mh_recs, static_cast<size_t>(c->mh_cap_total) * words * 4));
+    if (!c->d_mh_recs) KHR_TRY(c->d_mh_recs.alloc(static_cast<size_t>(c->mh_cap_total) * words));
     HIP_TRY(hipMemcpyAsync(c->d_mh_recs, records, static_cast<size_t>(n_records) * words * 4,
                            on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     view = c->d_mh_recs;
@@ -3963,7 +3788,7 @@ int khr_mesh_halo_requests_sorted(khr_ctx* c, void* requests_device, int64_t cap
   HIP_TRY(hipSetDevice(c->device));
   DevMap& m = c->m;
   constexpr int NB = 8 * kMeshHaloMaxWorld;
-  if (!c->d_mh2_scratch) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_mh2_scratch), sizeof(uint32_t) * (3 * NB + 1)));
+  if (!c->d_mh2_scratch) KHR_TRY(c->d_mh2_scratch.alloc(3 * NB + 1));
   uint32_t* const cnt = c->d_mh2_scratch;
   uint32_t* const base = cnt + NB;
   uint32_t* const cursor = base + NB;
@@ -4080,12 +3905,10 @@ int khr_mesh_halo_adopt(khr_ctx* c, const void* own_requests_device, const uint6
   while (ht < items * 2) ht <<= 1;
   if (ht > c->mh2_ht) {
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_mh2_keys) { hipFree(c->d_mh2_keys); hipFree(c->d_mh2_offs); }
-    c->d_mh2_keys = nullptr;
-    c->d_mh2_offs = nullptr;
     c->mh2_ht = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_mh2_keys), sizeof(uint64_t) * ht));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_mh2_offs), sizeof(uint32_t) * 8 * static_cast<size_t>(ht)));
+    c->d_mh2_keys.reset(), c->d_mh2_offs.reset();  // (both go before either comes back)
+    KHR_TRY(c->d_mh2_keys.reserve(ht));
+    KHR_TRY(c->d_mh2_offs.reserve(8 * static_cast<size_t>(ht)));
     c->mh2_ht = ht;
   }
   HIP_TRY(hipMemsetAsync(c->d_mh2_keys, 0xff, sizeof(uint64_t) * ht, c->stream));
@@ -4161,7 +3984,7 @@ static int ingestAhead(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fr
   // results the host waits for at the end of khr_process_frame (seen in the rocprofv3 timeline: main stream idle for 250 us)
   hipStream_t conv_stream = c->aux_stream;
   if (!on_device) {
-    if (!c->h2d_stream) HIP_TRY(createStream(c, &c->h2d_stream));
+    if (!c->h2d_stream) KHR_TRY(createStream(c, c->h2d_stream));
     conv_stream = c->h2d_stream;
   }
   c->ingest_stream = conv_stream;
@@ -4177,7 +4000,7 @@ static int ingestAhead(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fr
     if (!on_device && c->ev_ahead_h2d[evi]) hipEventSynchronize(c->ev_ahead_h2d[evi]);
     return rc;
   };
-  if (!c->ev_ahead[evi] && hipEventCreateWithFlags(&c->ev_ahead[evi], hipEventDisableTiming) != hipSuccess) return undo(fail(KHR_EDEVICE, "hipEventCreate failed"));
+  if (c->ev_ahead[evi].ensure()) return undo(fail(KHR_EDEVICE, "hipEventCreate failed"));
   if (hipEventRecord(c->ev_ahead[evi], conv_stream) != hipSuccess) return undo(fail(KHR_EDEVICE, "hipEventRecord failed"));
   if (on_device) c->slots[slot].aux_seq = ++c->aux_seq_issued;
   // The object detector only reads the frame: its kernels are queued right behind the conversion.  They then run beside the
@@ -4300,7 +4123,7 @@ int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fra
   }
   if (objects && !c->obj_configured) return fail(KHR_ESTATE, "KHR_PF_OBJECTS needs khr_configure_object_detector");
   if (objects && !early) {  // main-stream ingest: the object kernels (auxiliary stream) start behind it, not behind (1) - (2)
-    if (!c->ev_ingest) HIP_TRY(hipEventCreateWithFlags(&c->ev_ingest, hipEventDisableTiming));
+    KHR_TRY(c->ev_ingest.ensure());
     HIP_TRY(hipEventRecord(c->ev_ingest, c->stream));
   }
   // (1) per-pixel motion pass; its seed count comes back asynchronously ...
@@ -4367,9 +4190,9 @@ int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fra
   // their own stream behind k_tracking_select (which has folded the update's block flags) and joined before archival.
   const bool mc_fork = (flags & KHR_PF_OUTPUT) && (flags & KHR_PF_TRACKING) && c->cfg.with_tracking;
   if (mc_fork) {
-    if (!c->mc_stream) HIP_TRY(createStream(c, &c->mc_stream));
-    if (!c->ev_mc_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_mc_fork, hipEventDisableTiming));
-    if (!c->ev_mc_join) HIP_TRY(hipEventCreateWithFlags(&c->ev_mc_join, hipEventDisableTiming));
+    if (!c->mc_stream) KHR_TRY(createStream(c, c->mc_stream));
+    KHR_TRY(c->ev_mc_fork.ensure());
+    KHR_TRY(c->ev_mc_join.ensure());
     c->fork_after_select = true;
   }
   rc = (flags & KHR_PF_TRACKING) ? khr_update_tracking(c, frame->timestamp_ns) : KHR_OK;
@@ -4380,10 +4203,9 @@ int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fra
   const bool early_list = (flags & KHR_PF_OUTPUT) && c->cfg.with_tracking;
   if (mc_fork) {
     HIP_TRY(hipStreamWaitEvent(c->mc_stream, c->ev_mc_fork, 0));
-    hipStream_t main_stream = c->stream;
-    c->stream = c->mc_stream;  // (khr_generate_mesh queues everything on the context's stream)
+    std::swap(c->stream, c->mc_stream);  // (khr_generate_mesh queues everything on the context's stream; both owners stay members)
     rc = khr_generate_mesh(c, 1, 1);
-    c->stream = main_stream;
+    std::swap(c->stream, c->mc_stream);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(c->ev_mc_join, c->mc_stream));
   }
@@ -4397,9 +4219,9 @@ int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fra
       // things: the clone is forked onto its own stream beside the mesh kernels and joined before archival changes the map
       if (c->pending_snapshot) khr_snapshot_release(c->pending_snapshot);
       c->pending_snapshot = nullptr;
-      if (!c->snap_stream) HIP_TRY(createStream(c, &c->snap_stream));
-      if (!c->ev_snap_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_snap_fork, hipEventDisableTiming));
-      if (!c->ev_snap_join) HIP_TRY(hipEventCreateWithFlags(&c->ev_snap_join, hipEventDisableTiming));
+      if (!c->snap_stream) KHR_TRY(createStream(c, c->snap_stream));
+      KHR_TRY(c->ev_snap_fork.ensure());
+      KHR_TRY(c->ev_snap_join.ensure());
       HIP_TRY(hipEventRecord(c->ev_snap_fork, c->stream));
       HIP_TRY(hipStreamWaitEvent(c->snap_stream, c->ev_snap_fork, 0));
       const int64_t snap_cap = c->cfg.max_snapshot_blocks ? c->cfg.max_snapshot_blocks : 8192;  // (100 KB per block)
@@ -4461,28 +4283,21 @@ int khr_allocate_blocks(khr_ctx* c, const int32_t* indices, int64_t n) {
   // hipFree, which stall every stream of the device); the buffer is reused only after the previous upload was consumed
   const size_t bytes = sizeof(int32_t) * 3 * v.size();
   HT("ab_enter");
-  if (!c->ev_up) HIP_TRY(hipEventCreateWithFlags(&c->ev_up, hipEventDisableTiming));
-  else HIP_TRY(hipEventSynchronize(c->ev_up));
+  if (c->ev_up) HIP_TRY(hipEventSynchronize(c->ev_up));
+  KHR_TRY(c->ev_up.ensure());
   HT("ab_prev_upload_consumed");
-  if (bytes > c->h_up_bytes) {
+  if (bytes > c->h_up.count()) {
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->h_up) hipHostFree(c->h_up);
-    c->h_up = nullptr;
-    c->h_up_bytes = 0;
     const size_t want = std::max<size_t>(2 * bytes, 1u << 16);
-    if (hipHostMalloc(&c->h_up, want, hipHostMallocDefault) != hipSuccess)
-      return fail(KHR_ENOMEM, "block index staging of %zu bytes", want);
-    c->h_up_bytes = want;
+    if (c->h_up.reserve(want)) return fail(KHR_ENOMEM, "block index staging of %zu bytes", want);
   }
   std::memcpy(c->h_up, v.data(), bytes);
   // the kernel reads the indices straight out of the page-locked staging block (a few tens of KB over the link): round 5 -- a
   // hipMemcpyAsync here, issued from an extraction worker's thread, did not return for 7 ms while the window's thread kept the
   // copy path busy with its frames' planes (KHR_PF_INPUT_PINNED; profiles/r05_host_input_marks.txt)
-  void* up_dev = nullptr;
-  HIP_TRY(hipHostGetDevicePointer(&up_dev, c->h_up, 0));
   HIP_TRY(hipMemsetAsync(&c->m.counters[C_N_NEW], 0, sizeof(uint32_t), c->stream));
   c->explicit_blocks += v.size();
-  hipLaunchKernelGGL(k_alloc_list, dim3(gridFor(v.size())), dim3(256), 0, c->stream, c->m, static_cast<const int*>(up_dev),
+  hipLaunchKernelGGL(k_alloc_list, dim3(gridFor(v.size())), dim3(256), 0, c->stream, c->m, static_cast<const int*>(c->h_up.dev()),
                      static_cast<int>(v.size()), c->d_new);
   HIP_TRY(hipEventRecord(c->ev_up, c->stream));  // (the staging block is free again once the kernel has read it)
   hipLaunchKernelGGL(k_init_blocks, dim3(2048), dim3(256), 0, c->stream, c->m, c->p, c->d_new);
@@ -4702,10 +4517,8 @@ struct SliceLayout {
 static int ensureSortKeys(khr_ctx* c) {
   if (c->d_slice_keys) return KHR_OK;
   const uint32_t sort_len = slicePadded(c->m.capacity);
-  if (hipMalloc(reinterpret_cast<void**>(&c->d_slice_keys), sizeof(uint64_t) * sort_len) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&c->d_slice_count), sizeof(uint32_t)) != hipSuccess) {
-    if (c->d_slice_keys) hipFree(c->d_slice_keys);
-    c->d_slice_keys = nullptr;
+  if (c->d_slice_keys.alloc(sort_len) || c->d_slice_count.alloc(1)) {
+    c->d_slice_keys.reset();
     return fail(KHR_ENOMEM, "sort keys (%u words)", sort_len);
   }
   return KHR_OK;
@@ -4732,16 +4545,8 @@ static int sortKeys(khr_ctx* c) {
 static int sliceGrow(khr_ctx* c, uint32_t need) {
   const uint32_t cap = std::min<uint32_t>(std::max<uint32_t>(need + need / 2, 64u), c->m.capacity);
   const SliceLayout L(cap, static_cast<size_t>(c->p.vps) * c->p.vps);
-  if (c->d_slice_stage) HIP_TRY(hipFree(c->d_slice_stage));
-  if (c->h_slice_stage) HIP_TRY(hipHostFree(c->h_slice_stage));
-  c->d_slice_stage = c->h_slice_stage = nullptr;
   c->slice_cap = 0;
-  if (hipMalloc(reinterpret_cast<void**>(&c->d_slice_stage), L.bytes) != hipSuccess) return fail(KHR_ENOMEM, "slice staging of %zu bytes", L.bytes);
-  if (hipHostMalloc(reinterpret_cast<void**>(&c->h_slice_stage), L.bytes, hipHostMallocDefault) != hipSuccess) {
-    hipFree(c->d_slice_stage);
-    c->d_slice_stage = nullptr;
-    return fail(KHR_ENOMEM, "page-locked slice staging of %zu bytes", L.bytes);
-  }
+  KHR_TRY(reserveStagePair(c->d_slice_stage, c->h_slice_stage, L.bytes, "slice"));
   c->slice_cap = cap;
   return KHR_OK;
 }
@@ -4813,7 +4618,7 @@ int khr_map_slice(khr_ctx* c, int64_t voxel_z, int64_t cap, int32_t* block_xy, f
   HIP_TRY(hipMemcpyAsync(c->h_slice_stage, c->d_slice_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   if ((rc = copies(0, n_copied))) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  const uint32_t n = *reinterpret_cast<const uint32_t*>(c->h_slice_stage);
+  const uint32_t n = *reinterpret_cast<const uint32_t*>(c->h_slice_stage.get());
   if (n > c->slice_cap) {  // (the staging was too small and the gather wrote nothing: grow, gather again)
     if ((rc = sliceGrow(c, n))) return rc;
     if ((rc = gather())) return rc;
@@ -4886,20 +4691,7 @@ int khr_render_view(khr_ctx* c, const khr_render_request* rq, int on_device, flo
   }
   void* dev[6] = {depth, normal, color_rgba, label, vflags, status};
   if (!on_device && stage_bytes) {
-    if (stage_bytes > c->render_stage_bytes) {
-      if (c->d_render_stage) HIP_TRY(hipFree(c->d_render_stage));
-      if (c->h_render_stage) HIP_TRY(hipHostFree(c->h_render_stage));
-      c->d_render_stage = c->h_render_stage = nullptr;
-      c->render_stage_bytes = 0;
-      if (hipMalloc(reinterpret_cast<void**>(&c->d_render_stage), stage_bytes) != hipSuccess)
-        return fail(KHR_ENOMEM, "render staging of %zu bytes", stage_bytes);
-      if (hipHostMalloc(reinterpret_cast<void**>(&c->h_render_stage), stage_bytes, hipHostMallocDefault) != hipSuccess) {
-        hipFree(c->d_render_stage);
-        c->d_render_stage = nullptr;
-        return fail(KHR_ENOMEM, "page-locked render staging of %zu bytes", stage_bytes);
-      }
-      c->render_stage_bytes = stage_bytes;
-    }
+    KHR_TRY(reserveStagePair(c->d_render_stage, c->h_render_stage, stage_bytes, "render"));
     for (int f = 0; f < 6; ++f) dev[f] = host[f] ? c->d_render_stage + off[f] : nullptr;
   }
   r.depth = static_cast<float*>(dev[0]);
@@ -4909,8 +4701,7 @@ int khr_render_view(khr_ctx* c, const khr_render_request* rq, int on_device, flo
   r.vflags = static_cast<uint8_t*>(dev[4]);
   r.status = static_cast<uint8_t*>(dev[5]);
   if (stats) {
-    if (!c->d_render_stats && hipMalloc(reinterpret_cast<void**>(&c->d_render_stats), sizeof(unsigned long long) * RS_COUNT) != hipSuccess)
-      return fail(KHR_ENOMEM, "render counters");
+    if (!c->d_render_stats && c->d_render_stats.alloc(RS_COUNT)) return fail(KHR_ENOMEM, "render counters");
     HIP_TRY(hipMemsetAsync(c->d_render_stats, 0, sizeof(unsigned long long) * RS_COUNT, c->stream));
     r.stats = c->d_render_stats;
   }
@@ -4965,28 +4756,14 @@ int khr_query_points(khr_ctx* c, int64_t n, const float* points, float min_weigh
   void* dev[8] = {distance, gradient, weight, color_rgba, label, vflags, last_observed, status};
   const float* d_points = points;
   if (!on_device) {
-    if (stage_bytes > c->query_stage_bytes) {
-      if (c->d_query_stage) HIP_TRY(hipFree(c->d_query_stage));
-      if (c->h_query_stage) HIP_TRY(hipHostFree(c->h_query_stage));
-      c->d_query_stage = c->h_query_stage = nullptr;
-      c->query_stage_bytes = 0;
-      if (hipMalloc(reinterpret_cast<void**>(&c->d_query_stage), stage_bytes) != hipSuccess)
-        return fail(KHR_ENOMEM, "query staging of %zu bytes", stage_bytes);
-      if (hipHostMalloc(reinterpret_cast<void**>(&c->h_query_stage), stage_bytes, hipHostMallocDefault) != hipSuccess) {
-        hipFree(c->d_query_stage);
-        c->d_query_stage = nullptr;
-        return fail(KHR_ENOMEM, "page-locked query staging of %zu bytes", stage_bytes);
-      }
-      c->query_stage_bytes = stage_bytes;
-    }
+    KHR_TRY(reserveStagePair(c->d_query_stage, c->h_query_stage, stage_bytes, "query"));
     std::memcpy(c->h_query_stage, points, np * 12);
     HIP_TRY(hipMemcpyAsync(c->d_query_stage, c->h_query_stage, np * 12, hipMemcpyHostToDevice, c->stream));
-    d_points = reinterpret_cast<const float*>(c->d_query_stage);
+    d_points = reinterpret_cast<const float*>(c->d_query_stage.get());
     for (int f = 0; f < 8; ++f) dev[f] = host[f] ? c->d_query_stage + off[f] : nullptr;
   }
   if (stats) {
-    if (!c->d_query_stats && hipMalloc(reinterpret_cast<void**>(&c->d_query_stats), sizeof(unsigned long long) * QS_COUNT) != hipSuccess)
-      return fail(KHR_ENOMEM, "query counters");
+    if (!c->d_query_stats && c->d_query_stats.alloc(QS_COUNT)) return fail(KHR_ENOMEM, "query counters");
     HIP_TRY(hipMemsetAsync(c->d_query_stats, 0, sizeof(unsigned long long) * QS_COUNT, c->stream));
   }
   constexpr size_t kChunk = size_t(1) << 30;  // points per launch (the grid's x extent)
@@ -5086,31 +4863,18 @@ int alignCheck(khr_ctx* c, const khr_align_request* rq, AlignPlan* pl) {
 int alignPrepare(khr_ctx* c, const khr_align_request* rq, const AlignPlan& pl, int on_device, const float** d_src, const float** d_w) {
   HIP_TRY(hipSetDevice(c->device));
   constexpr size_t acc_bytes = sizeof(unsigned long long) * kAlignWords * kAlignAccStride;
-  if (!c->d_align_acc && hipMalloc(reinterpret_cast<void**>(&c->d_align_acc), acc_bytes) != hipSuccess) return fail(KHR_ENOMEM, "align accumulator");
-  if (!c->h_align_acc && hipHostMalloc(reinterpret_cast<void**>(&c->h_align_acc), acc_bytes, hipHostMallocDefault) != hipSuccess)
-    return fail(KHR_ENOMEM, "page-locked align accumulator");
+  constexpr size_t acc_words = acc_bytes / sizeof(unsigned long long);
+  if (!c->d_align_acc && c->d_align_acc.alloc(acc_words)) return fail(KHR_ENOMEM, "align accumulator");
+  if (!c->h_align_acc && c->h_align_acc.alloc(acc_words)) return fail(KHR_ENOMEM, "page-locked align accumulator");
   const float* src = pl.depth_form ? rq->depth : rq->points;
   *d_src = src;
   *d_w = rq->weights;
   if (on_device || pl.n == 0) return KHR_OK;
   const size_t w_off = (pl.src_bytes + 255) / 256 * 256, stage_bytes = w_off + (pl.w_bytes + 255) / 256 * 256;
-  if (stage_bytes > c->align_stage_bytes) {
-    if (c->d_align_stage) HIP_TRY(hipFree(c->d_align_stage));
-    if (c->h_align_stage) HIP_TRY(hipHostFree(c->h_align_stage));
-    c->d_align_stage = c->h_align_stage = nullptr;
-    c->align_stage_bytes = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&c->d_align_stage), stage_bytes) != hipSuccess)
-      return fail(KHR_ENOMEM, "align staging of %zu bytes", stage_bytes);
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->h_align_stage), stage_bytes, hipHostMallocDefault) != hipSuccess) {
-      hipFree(c->d_align_stage);
-      c->d_align_stage = nullptr;
-      return fail(KHR_ENOMEM, "page-locked align staging of %zu bytes", stage_bytes);
-    }
-    c->align_stage_bytes = stage_bytes;
-  }
+  KHR_TRY(reserveStagePair(c->d_align_stage, c->h_align_stage, stage_bytes, "align"));
   std::memcpy(c->h_align_stage, src, pl.src_bytes);
   HIP_TRY(hipMemcpyAsync(c->d_align_stage, c->h_align_stage, pl.src_bytes, hipMemcpyHostToDevice, c->stream));
-  *d_src = reinterpret_cast<const float*>(c->d_align_stage);
+  *d_src = reinterpret_cast<const float*>(c->d_align_stage.get());
   if (pl.w_bytes) {
     std::memcpy(c->h_align_stage + w_off, rq->weights, pl.w_bytes);
     HIP_TRY(hipMemcpyAsync(c->d_align_stage + w_off, c->h_align_stage + w_off, pl.w_bytes, hipMemcpyHostToDevice, c->stream));
@@ -5408,36 +5172,22 @@ uint32_t ckptChunkBlocks(const CkptShape& sh) {
 
 int ckptEnsureStage(khr_ctx* c, const CkptShape& sh, uint32_t cb, bool bounce) {
   const size_t need = std::max(kCkptStageBytes, CkptStageLayout(sh, cb).bytes);
-  if (c->ckpt_stage_bytes < need) {
-    for (int i = 0; i < 2; ++i) {
-      if (c->d_ckpt[i]) HIP_TRY(hipFree(c->d_ckpt[i]));
-      if (c->h_ckpt[i]) HIP_TRY(hipHostFree(c->h_ckpt[i]));
-      c->d_ckpt[i] = c->h_ckpt[i] = nullptr;
-    }
-    c->ckpt_stage_bytes = 0;
+  if (c->d_ckpt[0].count() < need || c->d_ckpt[1].count() < need) {  // (both areas, and their mirrors, have one size)
+    for (int i = 0; i < 2; ++i) c->d_ckpt[i].reset(), c->h_ckpt[i].reset();
     for (int i = 0; i < 2; ++i)
-      if (hipMalloc(reinterpret_cast<void**>(&c->d_ckpt[i]), need) != hipSuccess) return fail(KHR_ENOMEM, "checkpoint staging of %zu bytes", need);
-    c->ckpt_stage_bytes = need;
+      if (c->d_ckpt[i].alloc(need)) return fail(KHR_ENOMEM, "checkpoint staging of %zu bytes", need);
   }
   for (int i = 0; i < 2 && bounce; ++i)
-    if (!c->h_ckpt[i] && hipHostMalloc(reinterpret_cast<void**>(&c->h_ckpt[i]), c->ckpt_stage_bytes, hipHostMallocDefault) != hipSuccess)
-      return fail(KHR_ENOMEM, "page-locked checkpoint staging of %zu bytes", c->ckpt_stage_bytes);
-  if (c->ckpt_slots_cap < cb) {
-    for (int i = 0; i < 2; ++i) {
-      if (c->d_ckpt_slots[i]) HIP_TRY(hipFree(c->d_ckpt_slots[i]));
-      c->d_ckpt_slots[i] = nullptr;
-    }
-    c->ckpt_slots_cap = 0;
-    for (int i = 0; i < 2; ++i)
-      if (hipMalloc(reinterpret_cast<void**>(&c->d_ckpt_slots[i]), sizeof(uint32_t) * cb) != hipSuccess) return fail(KHR_ENOMEM, "checkpoint slot list");
-    c->ckpt_slots_cap = cb;
-  }
-  if (!c->d_ckpt_err && hipMalloc(reinterpret_cast<void**>(&c->d_ckpt_err), sizeof(uint32_t)) != hipSuccess) return fail(KHR_ENOMEM, "checkpoint error word");
+    if (!c->h_ckpt[i] && c->h_ckpt[i].alloc(c->d_ckpt[i].count()))
+      return fail(KHR_ENOMEM, "page-locked checkpoint staging of %zu bytes", c->d_ckpt[i].count());
+  for (int i = 0; i < 2; ++i)
+    if (c->d_ckpt_slots[i].reserve(cb)) return fail(KHR_ENOMEM, "checkpoint slot list");
+  if (!c->d_ckpt_err && c->d_ckpt_err.alloc(1)) return fail(KHR_ENOMEM, "checkpoint error word");
   for (int i = 0; i < 2; ++i) {
-    if (!c->ev_ckpt_filled[i]) HIP_TRY(hipEventCreateWithFlags(&c->ev_ckpt_filled[i], hipEventDisableTiming));
-    if (!c->ev_ckpt_drained[i]) HIP_TRY(hipEventCreateWithFlags(&c->ev_ckpt_drained[i], hipEventDisableTiming));
+    KHR_TRY(c->ev_ckpt_filled[i].ensure());
+    KHR_TRY(c->ev_ckpt_drained[i].ensure());
   }
-  if (!c->copy_stream) HIP_TRY(createStream(c, &c->copy_stream));
+  if (!c->copy_stream) KHR_TRY(createStream(c, c->copy_stream));
   return KHR_OK;
 }
 
@@ -5675,8 +5425,7 @@ static int refreshMeshTotals(khr_ctx* c) {
   // C_MAX_SLOT).  NOT the mesh staging block: a gather queued by khr_fetch_mesh_launch may be writing there, and its ticket
   // is header word 15 -- exactly where counter 13 of this copy used to land ("mesh gather was never published" whenever
   // statistics were read between the launch and the fetch: bench.py --output-copy host beyond ~30 steps)
-  if (!c->h_totals && hipHostMalloc(reinterpret_cast<void**>(&c->h_totals), sizeof(uint32_t) * (C_COUNT + 2), hipHostMallocDefault) != hipSuccess)
-    return fail(KHR_ENOMEM, "pinned block for the mesh totals");
+  if (!c->h_totals && c->h_totals.alloc(C_COUNT + 2)) return fail(KHR_ENOMEM, "pinned block for the mesh totals");
   uint32_t* hs = c->h_totals;
   HIP_TRY(hipMemcpyAsync(hs, c->d_mesh_offset + c->m.capacity, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(hs + 1, c->d_mesh_nwork, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -5717,8 +5466,8 @@ int64_t khr_download_updated(khr_ctx* c, int32_t* indices, float* distance, floa
   // staging: one allocation, carved per field
   const size_t bytes = tot * ((distance ? 4 : 0) + (weight ? 4 : 0) + (color_rgba ? 4 : 0) + ((last_observed && trk) ? 8 : 0) +
                               (voxel_flags ? 1 : 0) + ((sem_label && sem) ? 4 : 0)) + sizeof(uint32_t) * n + 256;
-  uint8_t* stage = nullptr;
-  HIP_TRY(hipMalloc(&stage, bytes));
+  DevTemp stage;  // (freed on every way out of this call)
+  KHR_TRY(stage.alloc(bytes));
   uint8_t* cur = stage;
   auto carve = [&](size_t b) { uint8_t* p = cur; cur += (b + 15) / 16 * 16; return p; };
   PackOut o{};
@@ -5745,7 +5494,6 @@ int64_t khr_download_updated(khr_ctx* c, int32_t* indices, float* distance, floa
     D(sem_label, o.sem_label, tot * 4);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   }
-  hipFree(stage);
   if (e != hipSuccess) return fail(KHR_EDEVICE, "download_updated failed: %s", hipGetErrorString(e));
   if (rc) return rc;
   if (last_observed && !trk) std::memset(last_observed, 0, tot * 8);
@@ -5758,7 +5506,7 @@ struct khr_snapshot {
   khr_ctx* ctx = nullptr;  // valid while !pool->dead
   std::shared_ptr<khr_ctx::SnapPool> pool;
   int device = 0;
-  khr_ctx::SnapArena arena{};
+  khr_ctx::SnapArena arena;
   uint32_t fields = 0, cap = 0, nvox = 0, ticket = 0;
   // carved from the arena
   uint32_t* d_count = nullptr;
@@ -5767,8 +5515,8 @@ struct khr_snapshot {
   PackOut o{};
   int64_t n = -1;        // blocks copied (known after the first wait)
   int64_t total = -1;    // updated blocks found (> cap: overflow)
-  hipEvent_t ev_packed = nullptr;  // recorded on the context's stream behind the pack kernel
-  hipEvent_t ev_copied = nullptr;  // khr_snapshot_download_begin: the last device -> host copy on the copy stream
+  Event ev_packed;  // recorded on the context's stream behind the pack kernel
+  Event ev_copied;  // khr_snapshot_download_begin: the last device -> host copy on the copy stream
   bool copying = false;
   int32_t* d_index3 = nullptr;  // carved from the arena: the block indices as (x, y, z) triples (khr_snapshot_download_begin)
 };
@@ -5797,25 +5545,13 @@ int khr_reserve_snapshots(khr_ctx* c, uint32_t fields, int64_t cap_blocks, int n
   size_t have = 0;
   {
     std::lock_guard<std::mutex> lock(c->snap_pool->mu);
-    for (const auto& a : c->snap_pool->free) have += a.bytes >= need ? 1 : 0;
+    for (const auto& a : c->snap_pool->free) have += a.buf.count() >= need ? 1 : 0;
   }
   for (size_t i = have; i < static_cast<size_t>(n_arenas); ++i) {
-    khr_ctx::SnapArena a{};
-    void* hc = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&a.ptr), need) != hipSuccess) return fail(KHR_ENOMEM, "snapshot arena of %zu bytes", need);
-    void* dv = nullptr;
-    if (hipHostMalloc(&hc, 64, hipHostMallocDefault) != hipSuccess || hipHostGetDevicePointer(&dv, hc, 0) != hipSuccess) {
-      hipFree(a.ptr);
-      if (hc) hipHostFree(hc);
-      return fail(KHR_ENOMEM, "snapshot pinned words");
-    }
-    a.bytes = need;
-    a.h_count = static_cast<volatile uint32_t*>(hc);
-    a.h_count[0] = 0;
-    a.h_count[1] = 0;
-    a.d_count_host_view = static_cast<uint32_t*>(dv);
+    khr_ctx::SnapArena a;
+    KHR_TRY(a.alloc(need));
     std::lock_guard<std::mutex> lock(c->snap_pool->mu);
-    c->snap_pool->free.push_back(a);
+    c->snap_pool->free.push_back(std::move(a));
   }
   return KHR_OK;
 }
@@ -5834,32 +5570,14 @@ int khr_snapshot_updated(khr_ctx* c, uint32_t fields, int64_t cap_blocks, khr_sn
     std::lock_guard<std::mutex> lock(c->snap_pool->mu);
     size_t best = fr.size();
     for (size_t i = 0; i < fr.size(); ++i)
-      if (fr[i].bytes >= need && (best == fr.size() || fr[i].bytes < fr[best].bytes)) best = i;
+      if (fr[i].buf.count() >= need && (best == fr.size() || fr[i].buf.count() < fr[best].buf.count())) best = i;
     if (best < fr.size()) {
-      snap->arena = fr[best];
+      snap->arena = std::move(fr[best]);
       fr.erase(fr.begin() + static_cast<long>(best));
     }
   }
-  if (!snap->arena.ptr) {
-    // first snapshots of a run: a device allocation (stalls the device once per arena; released arenas are reused)
-    void* hc = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&snap->arena.ptr), need) != hipSuccess) return fail(KHR_ENOMEM, "snapshot arena of %zu bytes", need);
-    if (hipHostMalloc(&hc, 64, hipHostMallocDefault) != hipSuccess) {
-      hipFree(snap->arena.ptr);
-      return fail(KHR_ENOMEM, "snapshot pinned words");
-    }
-    snap->arena.bytes = need;
-    snap->arena.h_count = static_cast<volatile uint32_t*>(hc);
-    snap->arena.h_count[0] = 0;
-    snap->arena.h_count[1] = 0;
-    void* dv = nullptr;
-    if (hipHostGetDevicePointer(&dv, hc, 0) != hipSuccess) {
-      hipFree(snap->arena.ptr);
-      hipHostFree(hc);
-      return fail(KHR_EDEVICE, "snapshot pinned words: no device view");
-    }
-    snap->arena.d_count_host_view = static_cast<uint32_t*>(dv);
-  }
+  // first snapshots of a run: a device allocation (stalls the device once per arena; released arenas are reused)
+  if (!snap->arena.buf) KHR_TRY(snap->arena.alloc(need));
   snap->ctx = c;
   snap->pool = c->snap_pool;
   snap->device = c->device;
@@ -5868,7 +5586,7 @@ int khr_snapshot_updated(khr_ctx* c, uint32_t fields, int64_t cap_blocks, khr_sn
   snap->nvox = static_cast<uint32_t>(nvox);
   snap->ticket = ++c->snap_ticket;
   if (snap->ticket == 0) snap->ticket = ++c->snap_ticket;
-  uint8_t* cur = snap->arena.ptr;
+  uint8_t* cur = snap->arena.buf;
   auto carve = [&](size_t b) { uint8_t* p = cur; cur += (b + 255) / 256 * 256; return p; };
   snap->d_count = reinterpret_cast<uint32_t*>(carve(256));
   snap->d_slots = reinterpret_cast<uint32_t*>(carve(cap * 4));
@@ -5887,24 +5605,24 @@ int khr_snapshot_updated(khr_ctx* c, uint32_t fields, int64_t cap_blocks, khr_sn
   snap->o.track_stamp = c->last_track_stamp;
   hipStream_t st = c->snap_stream_override ? c->snap_stream_override : c->stream;
   hipError_t e = hipMemsetAsync(snap->d_count, 0, 4, st);
+  int rc_ev = KHR_OK;
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_snapshot_select, dim3(gridFor(c->m.capacity)), dim3(256), 0, st, c->m, snap->d_count, snap->d_slots,
                        snap->d_index, snap->cap);
     dispatchVps(c, [&](auto vps) {
       KHR_LAUNCH_TIMED_ON(12, st, (k_snapshot_pack<decltype(vps)::value>), dim3(2048), dim3(256), c->m, snap->d_count, snap->d_slots,
-                          snap->cap, snap->o, snap->arena.d_count_host_view, snap->ticket);
+                          snap->cap, snap->o, snap->arena.count.dev(), snap->ticket);
       return KHR_OK;
     });
     e = hipGetLastError();
     // consumers on other streams (khr_snapshot_download_begin's copy stream) order themselves behind the pack kernel with this
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&snap->ev_packed, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(snap->ev_packed, st);
+    if (e == hipSuccess) rc_ev = snap->ev_packed.ensure();
+    if (e == hipSuccess && rc_ev == KHR_OK) e = hipEventRecord(snap->ev_packed, st);
   }
-  if (e != hipSuccess) {
-    if (snap->ev_packed) hipEventDestroy(snap->ev_packed);
+  if (e != hipSuccess || rc_ev != KHR_OK) {
     std::lock_guard<std::mutex> lock(c->snap_pool->mu);
-    c->snap_pool->free.push_back(snap->arena);
-    return fail(KHR_EDEVICE, "snapshot launch failed: %s", hipGetErrorString(e));
+    c->snap_pool->free.push_back(std::move(snap->arena));
+    return rc_ev != KHR_OK ? rc_ev : fail(KHR_EDEVICE, "snapshot launch failed: %s", hipGetErrorString(e));
   }
   *out = snap.release();
   return KHR_OK;
@@ -5922,11 +5640,11 @@ static int snapshotWait(khr_snapshot* s) {
   // the pack kernel's first thread publishes {count, ticket}; the host spins on the ticket (a blocking stream wait costs
   // hundreds of us of wake-up latency; the kernel is at most one output stage away)
   const auto t0 = std::chrono::steady_clock::now();
-  while (s->arena.h_count[1] != s->ticket) {
+  while (s->arena.h_count()[1] != s->ticket) {
     if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) return fail(KHR_EDEVICE, "snapshot was never produced (stream stuck?)");
     std::this_thread::yield();
   }
-  s->total = s->arena.h_count[0];
+  s->total = s->arena.h_count()[0];
   s->n = std::min<int64_t>(s->total, s->cap);
   return KHR_OK;
 }
@@ -5934,7 +5652,7 @@ static int snapshotWait(khr_snapshot* s) {
 // non-blocking: 1 once the snapshot's block count is known (its pack kernel has started), 0 before
 int khr_snapshot_poll(khr_snapshot* s) {
   if (!s) return fail(KHR_EINVAL, "null snapshot");
-  return (s->n >= 0 || s->arena.h_count[1] == s->ticket) ? 1 : 0;
+  return (s->n >= 0 || s->arena.h_count()[1] == s->ticket) ? 1 : 0;
 }
 
 int64_t khr_snapshot_num_blocks(khr_snapshot* s) {
@@ -6021,8 +5739,8 @@ int khr_snapshot_download_begin(khr_snapshot* s, int32_t* indices, float* distan
   }
   khr_ctx* c = s->ctx;
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->copy_stream) HIP_TRY(createStream(c, &c->copy_stream));
-  if (!s->ev_copied) HIP_TRY(hipEventCreateWithFlags(&s->ev_copied, hipEventDisableTiming));
+  if (!c->copy_stream) KHR_TRY(createStream(c, c->copy_stream));
+  KHR_TRY(s->ev_copied.ensure());
   HIP_TRY(hipStreamWaitEvent(c->copy_stream, s->ev_packed, 0));
   const size_t nv = s->nvox;
   if (n > 0) {
@@ -6062,19 +5780,12 @@ int64_t khr_snapshot_download_end(khr_snapshot* s) {
 void khr_snapshot_release(khr_snapshot* s) {
   if (!s) return;
   if (s->copying) (void)hipEventSynchronize(s->ev_copied);  // (the arena must not be recycled under a copy in flight)
-  if (s->ev_packed) hipEventDestroy(s->ev_packed);
-  if (s->ev_copied) hipEventDestroy(s->ev_copied);
   // the arena may be handed to the next snapshot right away: that one's kernels are queued behind this one's on the same
   // stream.  After khr_destroy (the consumer kept an output longer than the window lived) the arena is simply freed.
   {
     std::lock_guard<std::mutex> lock(s->pool->mu);
-    if (s->pool->dead) {
-      hipSetDevice(s->device);
-      hipFree(s->arena.ptr);
-      hipHostFree(const_cast<uint32_t*>(s->arena.h_count));
-    } else {
-      s->pool->free.push_back(s->arena);
-    }
+    if (s->pool->dead) hipSetDevice(s->device);  // (delete frees the arena)
+    else s->pool->free.push_back(std::move(s->arena));
   }
   delete s;
 }
@@ -6108,7 +5819,7 @@ int64_t khr_download_mesh(khr_ctx* c, float* points, uint8_t* colors_rgba, uint3
   const size_t o_l = o_c + al(colors_rgba ? all * 4 : 0), o_s = o_l + al(labels ? all * 4 : 0);
   const size_t bytes = o_s + al((first_seen || stamps) ? all * 8 : 0);
   if ((rc = ensureStage(c, bytes))) return rc;
-  char* st = static_cast<char*>(c->h_stage);
+  char* st = static_cast<char*>(c->h_stage.get());
   if (nslots) {
     HIP_TRY(hipMemcpyAsync(st + o_idx, c->m.blk_index, sizeof(int4) * nslots, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(st + o_flag, c->m.blk_flags, sizeof(uint32_t) * nslots, hipMemcpyDeviceToHost, c->stream));
@@ -6158,13 +5869,11 @@ int64_t khr_download_mesh(khr_ctx* c, float* points, uint8_t* colors_rgba, uint3
 // khr_generate_mesh (the vertex buffers flip there) and before any other call that uses the staging block.
 static int fetchMeshLaunch(khr_ctx* c) {
   const MeshBuffers& mb = c->mesh[c->mesh_cur];
-  void* d_stage = nullptr;
-  HIP_TRY(hipHostGetDevicePointer(&d_stage, c->h_stage, 0));
   ++c->fetch_ticket;
   if (c->fetch_ticket == 0) ++c->fetch_ticket;
-  static_cast<volatile uint32_t*>(c->h_stage)[15] = 0u;
+  static_cast<volatile uint32_t*>(c->h_stage.get())[15] = 0u;
   hipLaunchKernelGGL(k_mesh_gather, dim3(256), dim3(256), 0, c->stream, c->m, mb, c->d_mesh_offset + c->m.capacity,
-                     static_cast<uint32_t*>(d_stage), static_cast<uint64_t>(c->h_stage_bytes / 4), c->d_fetch_done, c->fetch_ticket);
+                     static_cast<uint32_t*>(c->h_stage.dev()), static_cast<uint64_t>(c->h_stage.count() / 4), c->d_fetch_done, c->fetch_ticket);
   HIP_TRY(hipGetLastError());
   HT("fetch_launched");
   return KHR_OK;
@@ -6178,15 +5887,10 @@ int khr_reserve_mesh_staging(khr_ctx* c, uint64_t n_vertices) {
   const size_t cap = c->m.capacity;
   const size_t bytes = 4096 + (sizeof(int4) + sizeof(uint32_t) + sizeof(MeshDesc) + 64) * cap + 40 * static_cast<size_t>(n_vertices);
   // (exactly this many bytes, not x 1.5: the caller named its bound)
-  if (bytes <= c->h_stage_bytes) return KHR_OK;  // (nothing is replaced: a gather queued by khr_fetch_mesh_launch stays valid)
+  if (bytes <= c->h_stage.count()) return KHR_OK;  // (nothing is replaced: a gather queued by khr_fetch_mesh_launch stays valid)
   HIP_TRY(hipStreamSynchronize(c->stream));  // (a gather in flight writes the block that is about to be replaced)
   c->fetch_pending = false;                  // ... and what it gathered goes with the block: the next khr_fetch_mesh starts over
-  if (c->h_stage) HIP_TRY(hipHostFree(c->h_stage));
-  c->h_stage = nullptr;
-  c->h_stage_bytes = 0;
-  if (hipHostMalloc(&c->h_stage, bytes, hipHostMallocDefault) != hipSuccess) return fail(KHR_ENOMEM, "pinned staging of %zu bytes", bytes);
-  c->h_stage_bytes = bytes;
-  return KHR_OK;
+  return c->h_stage.reserve(bytes);
 }
 
 int khr_fetch_mesh_launch(khr_ctx* c) {
@@ -6208,19 +5912,19 @@ int64_t khr_fetch_mesh(khr_ctx* c, khr_mesh_view* out) {
   HIP_TRY(hipSetDevice(c->device));
   int rc = ensureStage(c, 1u << 20);
   if (rc) return rc;
-  const uint32_t* h = static_cast<const uint32_t*>(c->h_stage);
+  const uint32_t* h = static_cast<const uint32_t*>(c->h_stage.get());
   for (int attempt = 0; attempt < 2; ++attempt) {
     const bool launched_before = attempt == 0 && c->fetch_pending;
     c->fetch_pending = false;
     if (!launched_before && (rc = fetchMeshLaunch(c))) return rc;
-    if ((rc = waitWord(c, static_cast<volatile uint32_t*>(c->h_stage) + 15, c->fetch_ticket, "mesh gather"))) return rc;
+    if ((rc = waitWord(c, static_cast<volatile uint32_t*>(c->h_stage.get()) + 15, c->fetch_ticket, "mesh gather"))) return rc;
     HT("fetch_arrived");
     if (h[2]) return fail(KHR_ENOMEM, "mesh needs %u vertices, max_mesh_vertices=%llu", h[0], static_cast<unsigned long long>(c->cfg.max_mesh_vertices));
     if (h[3]) break;
     if (attempt == 1) return fail(KHR_ENOMEM, "mesh staging of %u words", h[4]);
     const size_t need = static_cast<size_t>(h[4]) * 4;
     if ((rc = ensureStage(c, need))) return rc;
-    h = static_cast<const uint32_t*>(c->h_stage);
+    h = static_cast<const uint32_t*>(c->h_stage.get());
   }
   const uint32_t total_dev = h[0], nslots = h[1];
   c->mesh_total = total_dev;
@@ -6257,7 +5961,7 @@ int64_t khr_fetch_mesh(khr_ctx* c, khr_mesh_view* out) {
 int khr_fetch_mesh_into(khr_ctx* c, float* points, uint8_t* colors_rgba, uint32_t* labels, uint64_t* first_seen, uint64_t* stamps) {
   if (!c) return fail(KHR_EINVAL, "null ctx");
   if (!c->h_stage || c->fetch_ticket == 0) return fail(KHR_ESTATE, "no khr_fetch_mesh before khr_fetch_mesh_into");
-  const uint32_t* h = static_cast<const uint32_t*>(c->h_stage);
+  const uint32_t* h = static_cast<const uint32_t*>(c->h_stage.get());
   const MeshDesc* desc = reinterpret_cast<const MeshDesc*>(h + h[10]);
   const float* hp = reinterpret_cast<const float*>(h + h[11]);
   const uint32_t* hc = h + h[12];
@@ -6308,6 +6012,12 @@ int khr_debug_read(khr_ctx* c, unsigned long long* out, int64_t n) {
   return KHR_OK;
 }
 
+int khr_debug_live_resources(int64_t out[4]) {
+  if (!out) return fail(KHR_EINVAL, "null argument");
+  for (int k = 0; k < 4; ++k) out[k] = g_live[k].load(std::memory_order_relaxed);
+  return KHR_OK;
+}
+
 int khr_timing_enable(khr_ctx* c, int enable) {
   if (!c) return fail(KHR_EINVAL, "null ctx");
   if (enable && !c->timing) {
@@ -6316,16 +6026,16 @@ int khr_timing_enable(khr_ctx* c, int enable) {
     // for milliseconds (round 6: one run of the driver's command in twenty had a 2.7 ms wait for the seed count in its second step)
     HIP_TRY(hipSetDevice(c->device));
     while (c->event_pool.size() < 256) {
-      hipEvent_t e = nullptr;
-      HIP_TRY(hipEventCreate(&e));
-      c->event_pool.push_back(e);
+      Event e;
+      KHR_TRY(e.ensure(hipEventDefault));
+      c->event_pool.push_back(std::move(e));
     }
-    hipEvent_t a = takeEvent(c), b = takeEvent(c);
+    Event a = takeEvent(c), b = takeEvent(c);
     hipExtLaunchKernelGGL(k_copy_words, dim3(1), dim3(64), 0, c->stream, a, b, 0, static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), 0u);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventSynchronize(b));
-    c->event_pool.push_back(a);
-    c->event_pool.push_back(b);
+    c->event_pool.push_back(std::move(a));
+    c->event_pool.push_back(std::move(b));
   }
   c->timing = static_cast<uint32_t>(enable);
   return KHR_OK;
