@@ -557,6 +557,40 @@ typedef struct khr_query_stats {
 int khr_query_points(khr_ctx* ctx, int64_t n, const float* points, float min_weight, int on_device, float* distance, float* gradient,
                      float* weight, uint8_t* color_rgba, uint32_t* label, uint8_t* vflags, uint64_t* last_observed, uint8_t* status,
                      khr_query_stats* stats);
+/* The exact Euclidean distance field of a box of the live map (ASSUMPTIONS.md A.15).  No reference counterpart in its tree: the
+ * role is that of the distance-field stage its mapper configuration feeds the active window's TSDF into (freespace_places.gvd).
+ * Cells: with ratio r, cell c covers the global voxels [c r, (c + 1) r) per axis; cell_size = voxel_size * r; the box is `origin`
+ * (its first cell) and `dims` (cells per axis); outputs are ordered x + nx * (y + ny * z).  A voxel is observed iff its block is
+ * allocated and weight >= min_weight (0 = khr_config.mesh_min_weight); a cell is OBSERVED iff one of its voxels is, its value is
+ * the minimum distance over those, it is an OBSTACLE iff observed and value <= surface_distance, FREE iff observed and not an
+ * obstacle, UNKNOWN otherwise.  The obstacle set O is the OBSTACLE cells plus, with unknown_is_obstacle != 0, the UNKNOWN ones.
+ * d2 (squared cell units): outside O the least |c - o|^2 over O; inside O minus the least |c - f|^2 over the FREE cells, or 0 with
+ * positive_only != 0.  ONLY THE CELLS OF THE BOX TAKE PART: what lies outside does not exist for the call; pad the box by the
+ * range for values that are exact with respect to the whole map.  R = floor(max_distance / cell_size): |d2| > R^2 (or nothing to
+ * measure against) is out of range, d2 = +-KHR_DF_FAR and distance = +-max_distance; otherwise distance = +-cell_size *
+ * sqrt(|d2|) and the status has KHR_DF_IN_RANGE.  status: KHR_DF_OBSERVED, KHR_DF_OBSTACLE (the TSDF class, not membership of O),
+ * KHR_DF_IN_RANGE.  Any output may be NULL.
+ * on_device != 0: every pointer is device memory, the work is issued in stream order on the context's stream, no allocation beyond
+ * the context's work grids (grown to the largest box) and no host wait unless `stats` is given.  on_device == 0: host memory,
+ * filled when the call returns (through staging created at the first such call and grown to the largest box).  The map is only read.
+ * KHR_EINVAL (nothing written): NULL request, a dim < 1 or > KHR_DF_MAX_DIM, more than 2^24 cells, a ratio other than 1, 2, 4 or
+ * one that does not divide voxels_per_side, a box whose global voxel indices leave |i| < 2^30, a non-finite surface_distance, a
+ * negative or non-finite min_weight, max_distance not finite and positive, max_distance / cell_size >= 32768; KHR_ESTATE:
+ * world_size > 1. */
+#define KHR_DF_MAX_DIM 512
+#define KHR_DF_FAR (1 << 30)
+#define KHR_DF_OBSERVED 1
+#define KHR_DF_OBSTACLE 2
+#define KHR_DF_IN_RANGE 4
+typedef struct khr_df_request {
+  int32_t origin[3], dims[3];   /* cells */
+  int32_t ratio;                /* 1, 2, 4 */
+  float min_weight, max_distance, surface_distance;
+  int32_t unknown_is_obstacle, positive_only;
+} khr_df_request;
+typedef struct khr_df_stats { uint64_t n_observed, n_obstacle, n_free, n_in_range; } khr_df_stats;
+int khr_distance_field(khr_ctx* ctx, const khr_df_request* request, int on_device, float* distance, int32_t* d2, uint8_t* status,
+                       khr_df_stats* stats);
 /* The live map as a registration target (ASSUMPTIONS.md A.14): point-to-TSDF alignment of a point list or a depth image.  No
  * reference counterpart.  A source point p (source frame) goes to p_W = R p + t with world_T_source rounded to float as frame
  * ingest rounds it; the residual is khr_query_points' distance d at p_W, the Jacobian of a twist (omega, v) in world axes about

@@ -57,6 +57,20 @@ class KhrQueryStats(C.Structure):
 KHR_QP_VALUE, KHR_QP_GRADIENT, KHR_QP_VOXEL = 1, 2, 4
 
 
+class KhrDfRequest(C.Structure):
+    _fields_ = [("origin", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("ratio", C.c_int32), ("min_weight", C.c_float),
+                ("max_distance", C.c_float), ("surface_distance", C.c_float), ("unknown_is_obstacle", C.c_int32),
+                ("positive_only", C.c_int32)]
+
+
+class KhrDfStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_observed", "n_obstacle", "n_free", "n_in_range")]
+
+
+KHR_DF_OBSERVED, KHR_DF_OBSTACLE, KHR_DF_IN_RANGE = 1, 2, 4
+KHR_DF_MAX_DIM, KHR_DF_FAR = 512, 1 << 30
+
+
 class KhrAlignRequest(C.Structure):
     _fields_ = [("n", C.c_int64), ("points", C.c_void_p), ("depth", C.c_void_p), ("sensor", KhrSensor), ("stride", C.c_int32),
                 ("weights", C.c_void_p), ("world_T_source", C.c_double * 16), ("min_weight", C.c_float), ("gate", C.c_float),
@@ -139,7 +153,7 @@ EXPORTS = [
     "khr_snapshot_updated", "khr_take_snapshot", "khr_snapshot_num_blocks", "khr_snapshot_download", "khr_snapshot_download_extra", "khr_snapshot_download_begin", "khr_snapshot_download_end", "khr_snapshot_poll", "khr_fetch_mesh_launch", "khr_reserve_mesh_staging", "khr_reserve_snapshots", "khr_mirror_dynamic", "khr_snapshot_release",
     "khr_rv_check_stamps", "khr_get_config", "khr_cluster_voxels_launch", "khr_cluster_voxels_fetch", "khr_reset_map", "khr_depend_on", "khr_retain_slot", "khr_release_slot",
     "khr_map_slice", "khr_slice_voxel_z", "khr_render_view", "khr_query_points",
-    "khr_align_linearize", "khr_align_frame",
+    "khr_align_linearize", "khr_align_frame", "khr_distance_field",
     "khr_checkpoint_size", "khr_checkpoint_save", "khr_checkpoint_load", "khr_checkpoint_inspect",
     "khr_debug_live_resources",
 ]
@@ -231,6 +245,7 @@ def load_library():
     lib.khr_slice_voxel_z.argtypes = [C.c_float, C.c_float, C.c_int32, vp]
     lib.khr_render_view.argtypes = [vp, C.POINTER(KhrRenderRequest), i32] + [vp] * 6 + [C.POINTER(KhrRenderStats)]
     lib.khr_query_points.argtypes = [vp, i64, vp, C.c_float, i32] + [vp] * 8 + [C.POINTER(KhrQueryStats)]
+    lib.khr_distance_field.argtypes = [vp, C.POINTER(KhrDfRequest), i32, vp, vp, vp, C.POINTER(KhrDfStats)]
     lib.khr_align_linearize.argtypes = [vp, C.POINTER(KhrAlignRequest), i32, vp]
     lib.khr_align_frame.argtypes = [vp, C.POINTER(KhrAlignRequest), i32, C.POINTER(KhrAlignOptions), vp, C.POINTER(KhrAlignResult)]
     lib.khr_checkpoint_size.argtypes = [vp, C.POINTER(u64), C.POINTER(i64)]
@@ -909,6 +924,59 @@ class FusionContext:
             out = {k: np.zeros((n,) + sh, dt) for k, dt, sh in self.QUERY_FIELDS}
             rc, stats = self.query_points_into(n, pts, out, min_weight)
         self._chk(rc)
+        out["stats"] = stats
+        return out
+
+    DF_FIELDS = (("distance", np.float32), ("d2", np.int32), ("status", np.uint8))
+
+    @staticmethod
+    def df_request(origin, dims, ratio=1, max_distance=1.0, min_weight=0.0, surface_distance=0.0, unknown_is_obstacle=False,
+                   positive_only=False):
+        """a khr_df_request: `origin` (first cell) and `dims` (cells per axis) as x, y, z"""
+        rq = KhrDfRequest()
+        for a in range(3):
+            rq.origin[a], rq.dims[a] = int(origin[a]), int(dims[a])
+        rq.ratio = int(ratio)
+        rq.min_weight, rq.max_distance, rq.surface_distance = float(min_weight), float(max_distance), float(surface_distance)
+        rq.unknown_is_obstacle, rq.positive_only = int(bool(unknown_is_obstacle)), int(bool(positive_only))
+        return rq
+
+    def distance_field_into(self, request, out, on_device=False, want_stats=True):
+        """khr_distance_field into caller buffers (`out`: DF_FIELDS name -> contiguous array, or an integer device pointer with
+        on_device; absent / None = not written).  `request` may be None (the NULL request).  Returns (return code, stats dict or
+        None) without raising."""
+        st = KhrDfStats()
+        ptrs = []
+        for name, _ in self.DF_FIELDS:
+            a = out.get(name)
+            ptrs.append(None if a is None else (C.c_void_p(int(a)) if on_device else _ptr(a)))
+        rc = self.lib.khr_distance_field(self.h, None if request is None else C.byref(request), int(on_device), *ptrs,
+                                         C.byref(st) if want_stats else None)
+        stats = {k: int(getattr(st, k)) for k, _ in KhrDfStats._fields_} if (want_stats and rc == 0) else None
+        return rc, stats
+
+    def distance_field(self, origin, dims, ratio=1, max_distance=1.0, min_weight=0.0, surface_distance=0.0, unknown_is_obstacle=False,
+                       positive_only=False, device=False):
+        """The exact Euclidean distance field of a box of the live map (khr_distance_field, ASSUMPTIONS.md A.15).  `origin`: the
+        box's first cell, `dims`: cells per axis, both (x, y, z); a cell is `ratio` voxels wide.  Only the cells of the box take
+        part: pad the box by max_distance for values that are exact with respect to the whole map.  Returns a dict of arrays
+        shaped (nz, ny, nx): distance float32 (metres, negative inside obstacles unless positive_only, +-max_distance out of
+        range), d2 int32 (squared cell units, +-KHR_DF_FAR out of range), status uint8 (KHR_DF_* bits); cell_size; and stats
+        (n_observed, n_obstacle, n_free, n_in_range).  device=True: the arrays are torch tensors on the context's device, complete
+        when the call returns (it waits for the counters)."""
+        rq = self.df_request(origin, dims, ratio, max_distance, min_weight, surface_distance, unknown_is_obstacle, positive_only)
+        shape = tuple(max(int(d), 0) for d in (dims[2], dims[1], dims[0]))
+        if device:
+            import torch
+            dev = torch.device("cuda", self.cfg.device)
+            tdt = {np.float32: torch.float32, np.int32: torch.int32, np.uint8: torch.uint8}
+            out = {k: torch.empty(shape, dtype=tdt[dt], device=dev) for k, dt in self.DF_FIELDS}
+            rc, stats = self.distance_field_into(rq, {k: t.data_ptr() for k, t in out.items()}, on_device=True)
+        else:
+            out = {k: np.zeros(shape, dt) for k, dt in self.DF_FIELDS}
+            rc, stats = self.distance_field_into(rq, out)
+        self._chk(rc)
+        out["cell_size"] = float(np.float32(self.cfg.voxel_size) * np.float32(int(ratio)))
         out["stats"] = stats
         return out
 

@@ -37,6 +37,7 @@
 #include "khr_kernels_slice.h"
 #include "khr_kernels_render.h"
 #include "khr_kernels_query.h"
+#include "khr_kernels_distance.h"
 #include "khr_kernels_align.h"
 #include "khr_kernels_checkpoint.h"
 
@@ -399,6 +400,12 @@ struct khr_ctx {
   DevBuf<unsigned long long> d_query_stats;
   DevBuf<uint8_t> d_query_stage;
   PinnedBuf<uint8_t> h_query_stage;  // page-locked mirror of d_query_stage
+  // distance fields (khr_distance_field): the two int32 work grids (grown to the largest box), the counters, and the output
+  // staging of the host form with its page-locked mirror
+  DevBuf<int32_t> d_df_outer, d_df_inner;
+  DevBuf<unsigned long long> d_df_stats;
+  DevBuf<uint8_t> d_df_stage;
+  PinnedBuf<uint8_t> h_df_stage;
   // registration (khr_align_linearize): the accumulator (its words 128 bytes apart) with its page-locked mirror, and the source /
   // weight staging of the host form
   DevBuf<unsigned long long> d_align_acc;
@@ -4802,6 +4809,127 @@ int khr_query_points(khr_ctx* c, int64_t n, const float* points, float min_weigh
     stats->n_value = h_stats[QS_VALUE];
     stats->n_gradient = h_stats[QS_GRADIENT];
     stats->n_voxel = h_stats[QS_VOXEL];
+  }
+  return KHR_OK;
+}
+
+// ---- the exact Euclidean distance field of a box of the live map (khr_distance_field; ASSUMPTIONS.md A.15, device side:
+// khr_kernels_distance.h) -----------------------------------------------------------------------------------------------------
+int khr_distance_field(khr_ctx* c, const khr_df_request* rq, int on_device, float* distance, int32_t* d2, uint8_t* status, khr_df_stats* stats) {
+  if (!c || !rq) return fail(KHR_EINVAL, "null argument");
+  const int ratio = rq->ratio, vps = c->cfg.voxels_per_side;
+  if (ratio != 1 && ratio != 2 && ratio != 4) return fail(KHR_EINVAL, "ratio %d: 1, 2 or 4", ratio);
+  if (vps % ratio != 0) return fail(KHR_EINVAL, "ratio %d does not divide voxels_per_side %d", ratio, vps);
+  uint64_t cells = 1;
+  for (int a = 0; a < 3; ++a) {
+    if (rq->dims[a] < 1 || rq->dims[a] > KHR_DF_MAX_DIM) return fail(KHR_EINVAL, "dims[%d] = %d: 1 .. %d", a, rq->dims[a], KHR_DF_MAX_DIM);
+    cells *= static_cast<uint64_t>(rq->dims[a]);
+    const int64_t lo = static_cast<int64_t>(rq->origin[a]) * ratio, hi = (static_cast<int64_t>(rq->origin[a]) + rq->dims[a]) * ratio - 1;
+    if (lo <= -(int64_t(1) << 30) || hi >= (int64_t(1) << 30)) return fail(KHR_EINVAL, "the box leaves the voxel index range on axis %d", a);
+  }
+  if (cells > (uint64_t(1) << 24)) return fail(KHR_EINVAL, "%llu cells: at most 2^24", static_cast<unsigned long long>(cells));
+  if (!std::isfinite(rq->surface_distance)) return fail(KHR_EINVAL, "surface_distance is not finite");
+  if (!(rq->min_weight >= 0.f) || !std::isfinite(rq->min_weight)) return fail(KHR_EINVAL, "bad min_weight %g", static_cast<double>(rq->min_weight));
+  if (!(rq->max_distance > 0.f) || !std::isfinite(rq->max_distance)) return fail(KHR_EINVAL, "bad max_distance %g", static_cast<double>(rq->max_distance));
+  const float cell_size = c->p.vs * static_cast<float>(ratio);
+  const float reach = rq->max_distance / cell_size;
+  if (!(reach < 32768.f)) return fail(KHR_EINVAL, "max_distance %g m is %g cells: fewer than 32768", static_cast<double>(rq->max_distance), static_cast<double>(reach));
+  if (c->cfg.world_size > 1) return fail(KHR_ESTATE, "khr_distance_field needs the whole map: world_size is %d", c->cfg.world_size);
+  HIP_TRY(hipSetDevice(c->device));
+  const int R = static_cast<int>(std::floor(reach));
+  const size_t n = static_cast<size_t>(cells);
+  const bool with_inner = rq->positive_only == 0;
+  // the work grids grow on demand; what may still read the old ones is waited for first
+  if (c->d_df_outer.count() < n || (with_inner && c->d_df_inner.count() < n)) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->d_df_outer.reserve(n) || (with_inner && c->d_df_inner.reserve(n))) return fail(KHR_ENOMEM, "distance field work grids of %zu cells", n);
+  }
+  // the host form: the outputs one after the other in the device staging and its page-locked mirror
+  void* const host[3] = {distance, d2, status};
+  const size_t per_cell[3] = {4, 4, 1};
+  size_t off[3], stage_bytes = 0;
+  for (int f = 0; f < 3; ++f) {
+    off[f] = stage_bytes;
+    if (host[f]) stage_bytes += (n * per_cell[f] + 255) / 256 * 256;
+  }
+  void* dev[3] = {distance, d2, status};
+  if (!on_device && stage_bytes) {
+    if (stage_bytes > c->d_df_stage.count() || stage_bytes > c->h_df_stage.count()) HIP_TRY(hipStreamSynchronize(c->stream));
+    KHR_TRY(reserveStagePair(c->d_df_stage, c->h_df_stage, stage_bytes, "distance field"));
+    for (int f = 0; f < 3; ++f) dev[f] = host[f] ? c->d_df_stage + off[f] : nullptr;
+  }
+  if (stats) {
+    if (!c->d_df_stats && c->d_df_stats.alloc(DFS_COUNT)) return fail(KHR_ENOMEM, "distance field counters");
+    HIP_TRY(hipMemsetAsync(c->d_df_stats, 0, sizeof(unsigned long long) * DFS_COUNT, c->stream));
+  }
+  const int nx = rq->dims[0], ny = rq->dims[1], nz = rq->dims[2];
+  auto floorDiv = [](int64_t a, int64_t b) { return static_cast<int>(a >= 0 ? a / b : -((-a + b - 1) / b)); };
+  DfGather g{};
+  g.box.ox = rq->origin[0], g.box.oy = rq->origin[1], g.box.oz = rq->origin[2];
+  g.box.nx = nx, g.box.ny = ny, g.box.nz = nz;
+  const int cps = vps / ratio;  // cells per block side
+  g.box.bx0 = floorDiv(rq->origin[0], cps), g.box.by0 = floorDiv(rq->origin[1], cps), g.box.bz0 = floorDiv(rq->origin[2], cps);
+  const dim3 blocks(static_cast<unsigned>(floorDiv(static_cast<int64_t>(rq->origin[0]) + nx - 1, cps) - g.box.bx0 + 1),
+                    static_cast<unsigned>(floorDiv(static_cast<int64_t>(rq->origin[1]) + ny - 1, cps) - g.box.by0 + 1),
+                    static_cast<unsigned>(floorDiv(static_cast<int64_t>(rq->origin[2]) + nz - 1, cps) - g.box.bz0 + 1));
+  g.min_weight = rq->min_weight == 0.f ? c->cfg.mesh_min_weight : rq->min_weight;
+  g.surface_distance = rq->surface_distance;
+  g.unknown_is_obstacle = rq->unknown_is_obstacle;
+  g.outer = c->d_df_outer;
+  g.inner = with_inner ? c->d_df_inner.get() : nullptr;
+  g.status = static_cast<uint8_t*>(dev[2]);
+  g.stats = stats ? c->d_df_stats.get() : nullptr;
+  int rc = dispatchVps(c, [&](auto vps_c) {
+    constexpr int VPS = decltype(vps_c)::value;
+    if (ratio == 1) hipLaunchKernelGGL((k_df_gather<VPS, 1>), blocks, dim3(256), 0, c->stream, c->m, g);
+    else if (ratio == 2) hipLaunchKernelGGL((k_df_gather<VPS, 2>), blocks, dim3(256), 0, c->stream, c->m, g);
+    else hipLaunchKernelGGL((k_df_gather<VPS, 4>), blocks, dim3(256), 0, c->stream, c->m, g);
+    HIP_TRY(hipGetLastError());
+    return KHR_OK;
+  });
+  if (rc) return rc;
+  // three in-place passes per grid; a pass along an axis of one cell (or with R = 0) changes nothing and is left out
+  for (int32_t* grid : {g.outer, g.inner}) {
+    if (!grid || R < 1) continue;
+    if (nx > 1) {
+      const int per_wg = std::max(1, kDfTileCells / nx);
+      const long long lines = static_cast<long long>(ny) * nz;
+      hipLaunchKernelGGL((k_df_pass<0>), dim3(static_cast<unsigned>((lines + per_wg - 1) / per_wg)), dim3(256), 0, c->stream, grid, nx, ny, nz, R, per_wg);
+    }
+    if (ny > 1) {
+      const int per_wg = std::max(1, kDfTileCells / (ny * kDfStrip));
+      hipLaunchKernelGGL((k_df_pass<1>), dim3((nx + kDfStrip - 1) / kDfStrip, (nz + per_wg - 1) / per_wg), dim3(256), 0, c->stream, grid, nx, ny, nz, R, per_wg);
+    }
+    if (nz > 1) {
+      const int per_wg = std::max(1, kDfTileCells / (nz * kDfStrip));
+      hipLaunchKernelGGL((k_df_pass<2>), dim3((nx + kDfStrip - 1) / kDfStrip, (ny + per_wg - 1) / per_wg), dim3(256), 0, c->stream, grid, nx, ny, nz, R, per_wg);
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  DfFinish f{};
+  f.n = static_cast<long long>(n);
+  f.outer = g.outer, f.inner = g.inner;
+  f.r2 = R * R;
+  f.cell_size = cell_size, f.max_distance = rq->max_distance;
+  f.distance = static_cast<float*>(dev[0]), f.d2 = static_cast<int32_t*>(dev[1]), f.status = static_cast<uint8_t*>(dev[2]);
+  f.stats = g.stats;
+  if (f.distance || f.d2 || f.status || f.stats) {
+    hipLaunchKernelGGL(k_df_finish, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, c->stream, f);
+    HIP_TRY(hipGetLastError());
+  }
+  unsigned long long h_stats[DFS_COUNT] = {0, 0, 0, 0};
+  if (stats) HIP_TRY(hipMemcpyAsync(h_stats, c->d_df_stats, sizeof(h_stats), hipMemcpyDeviceToHost, c->stream));
+  const bool copy_back = !on_device && stage_bytes > 0;
+  if (copy_back) HIP_TRY(hipMemcpyAsync(c->h_df_stage, c->d_df_stage, stage_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (stats || copy_back) HIP_TRY(hipStreamSynchronize(c->stream));
+  if (copy_back)
+    for (int k = 0; k < 3; ++k)
+      if (host[k]) std::memcpy(host[k], c->h_df_stage + off[k], n * per_cell[k]);
+  if (stats) {
+    stats->n_observed = h_stats[DFS_OBSERVED];
+    stats->n_obstacle = h_stats[DFS_OBSTACLE];
+    stats->n_free = h_stats[DFS_OBSERVED] - h_stats[DFS_OBSTACLE];
+    stats->n_in_range = h_stats[DFS_IN_RANGE];
   }
   return KHR_OK;
 }

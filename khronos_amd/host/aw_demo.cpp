@@ -2,7 +2,7 @@
 // thread drives the reference (spinOnce per InputPacket, finishMapping at shutdown), and prints a JSON
 // summary that tests/test_gpu_host.py compares with the step-wise C-ABI path and the oracle.
 // usage: aw_demo <config.yaml> <width> <height> <frames> [object_label]
-//        aw_demo --slices | --render | --query | --align | --checkpoint | --bench | --rayver ... (below)
+//        aw_demo --slices | --render | --query | --distance | --align | --checkpoint | --bench | --rayver ... (below)
 //   object_label >= 0: the stand-in detector / tracker below; otherwise the plugins named in the config
 #include <execinfo.h>
 #include <csignal>
@@ -624,6 +624,187 @@ static int queryDemo(int argc, char** argv) {
   return agree == frames && frames == N ? 0 : 3;
 }
 
+// ASSUMPTIONS.md A.15 restated on the host over cloneBlock copies (what a planner had to do before khr_distance_field): every
+// allocated block the box overlaps is copied whole, the cells are classified voxel by voxel, and the three windowed passes run
+// line by line.
+static hydra::DistanceField distanceByBlockCopies(const VolumetricMap& map, const hydra::DistanceFieldRequest& rq) {
+  khr_config kc;
+  if (khr_get_config(map.ctx(), &kc) != KHR_OK) throw std::runtime_error(khr_last_error());
+  const int vps = kc.voxels_per_side, sh = vps == 16 ? 4 : 3, ratio = rq.ratio;
+  const float min_weight = rq.min_weight == 0.f ? kc.mesh_min_weight : rq.min_weight;
+  hydra::DistanceField f;
+  f.origin = rq.origin, f.dims = rq.dims;
+  f.cell_size = kc.voxel_size * static_cast<float>(ratio);
+  const int nx = rq.dims[0], ny = rq.dims[1], nz = rq.dims[2];
+  const size_t n = static_cast<size_t>(nx) * ny * nz;
+  constexpr int32_t kFar = KHR_DF_FAR;
+  std::unordered_map<uint64_t, std::unique_ptr<hydra::BlockCopy>> blocks;
+  for (const auto& idx : map.allocatedBlockIndices()) blocks.emplace(QueryByBlockCopies::key(idx[0], idx[1], idx[2]), nullptr);
+  std::vector<int32_t> outer(n), inner(n);
+  f.status.assign(n, 0);
+  for (int z = 0; z < nz; ++z)
+    for (int y = 0; y < ny; ++y)
+      for (int x = 0; x < nx; ++x) {
+        bool observed = false;
+        float value = 0.f;
+        for (int dz = 0; dz < ratio; ++dz)
+          for (int dy = 0; dy < ratio; ++dy)
+            for (int dx = 0; dx < ratio; ++dx) {
+              const int64_t vx = static_cast<int64_t>(rq.origin[0] + x) * ratio + dx, vy = static_cast<int64_t>(rq.origin[1] + y) * ratio + dy,
+                            vz = static_cast<int64_t>(rq.origin[2] + z) * ratio + dz;
+              const int64_t bx = vx >> sh, by = vy >> sh, bz = vz >> sh, K = 1 << 20;
+              if (bx < -K || bx >= K || by < -K || by >= K || bz < -K || bz >= K) continue;
+              auto it = blocks.find(QueryByBlockCopies::key(bx, by, bz));
+              if (it == blocks.end()) continue;
+              if (!it->second)
+                it->second = std::make_unique<hydra::BlockCopy>(map.cloneBlock({static_cast<int32_t>(bx), static_cast<int32_t>(by), static_cast<int32_t>(bz)}));
+              const size_t lin = static_cast<size_t>((vx & (vps - 1)) + vps * ((vy & (vps - 1)) + vps * (vz & (vps - 1))));
+              if (!(it->second->weight[lin] >= min_weight)) continue;
+              const float d = it->second->distance[lin];
+              value = observed ? std::fmin(value, d) : d;
+              observed = true;
+            }
+        const bool obstacle = observed && value <= rq.surface_distance;
+        const size_t at = f.index(x, y, z);
+        outer[at] = (obstacle || (!observed && rq.unknown_is_obstacle)) ? 0 : kFar;
+        inner[at] = (observed && !obstacle) ? 0 : kFar;
+        f.status[at] = static_cast<uint8_t>((observed ? KHR_DF_OBSERVED : 0) | (obstacle ? KHR_DF_OBSTACLE : 0));
+        f.stats.n_observed += observed, f.stats.n_obstacle += obstacle, f.stats.n_free += observed && !obstacle;
+      }
+  const int R = static_cast<int>(std::floor(rq.max_distance / f.cell_size));
+  auto transform = [&](std::vector<int32_t>& g) {
+    std::vector<int64_t> line, res;
+    const size_t stride[3] = {1, static_cast<size_t>(nx), static_cast<size_t>(nx) * ny};
+    const int len[3] = {nx, ny, nz};
+    for (int axis = 0; axis < 3; ++axis) {
+      const int L = len[axis], a1 = (axis + 1) % 3, a2 = (axis + 2) % 3;
+      line.resize(L), res.resize(L);
+      for (int p = 0; p < len[a1]; ++p)
+        for (int q = 0; q < len[a2]; ++q) {
+          const size_t base = stride[a1] * p + stride[a2] * q;
+          for (int i = 0; i < L; ++i) line[i] = g[base + stride[axis] * i];
+          for (int i = 0; i < L; ++i) {
+            int64_t best = line[i];
+            for (int j = std::max(0, i - R); j <= std::min(L - 1, i + R); ++j) best = std::min(best, line[j] + static_cast<int64_t>(i - j) * (i - j));
+            res[i] = std::min<int64_t>(best, kFar);
+          }
+          for (int i = 0; i < L; ++i) g[base + stride[axis] * i] = static_cast<int32_t>(res[i]);
+        }
+    }
+  };
+  transform(outer);
+  if (!rq.positive_only) transform(inner);
+  f.distance.resize(n), f.d2.resize(n);
+  const int64_t r2 = static_cast<int64_t>(R) * R;
+  for (size_t i = 0; i < n; ++i) {
+    const bool in_set = outer[i] == 0, neg = in_set && !rq.positive_only;
+    int32_t mag = in_set ? (rq.positive_only ? 0 : inner[i]) : outer[i];
+    float dist;
+    if (mag <= r2) {
+      dist = f.cell_size * std::sqrt(static_cast<float>(mag));
+      f.status[i] |= KHR_DF_IN_RANGE;
+      ++f.stats.n_in_range;
+    } else {
+      mag = kFar;
+      dist = rq.max_distance;
+    }
+    f.distance[i] = neg ? -dist : dist;
+    f.d2[i] = neg ? -mag : mag;
+  }
+  return f;
+}
+
+// aw_demo --distance <config.yaml> <width> <height> <frames>: a Khronos sink asks, per output, for the distance field of a box around
+// the sensor -- hydra::DistanceFieldConfig from the file's freespace_places -- through VolumetricMap::distanceField
+// (khr_distance_field) and through the cloneBlock loop above, checks the two bit for bit and times both (the device is drained
+// before each).  One JSON line: per-frame means after kWarm frames.
+static int distanceDemo(int argc, char** argv) {
+  if (argc < 6) {
+    std::fprintf(stderr, "usage: aw_demo --distance <config.yaml> <width> <height> <frames>\n");
+    return 2;
+  }
+  std::ifstream in(argv[2]);
+  std::stringstream ss;
+  ss << in.rdbuf();
+  const int W = std::atoi(argv[3]), H = std::atoi(argv[4]), N = std::atoi(argv[5]);
+  constexpr int kWarm = 3;  // frames before the averages (the work grids and the staging grow on the first call)
+  ActiveWindow::Config cfg = ActiveWindow::Config::fromYamlString(ss.str());
+  cfg.max_frame_pixels = static_cast<uint32_t>(W) * H;
+  const hydra::DistanceFieldConfig dfc = hydra::DistanceFieldConfig::fromYaml(khronos_amd::parseYaml(ss.str()));
+  auto out_queue = std::make_shared<ActiveWindow::OutputQueue>();
+  ActiveWindow aw(cfg, out_queue);
+  int frames = 0, agree = 0, timed = 0;
+  double ms_dev = 0, ms_copy = 0;
+  size_t cells = 0;
+  khr_df_stats last_stats{};
+  std::string first_mismatch;
+  using clk = std::chrono::steady_clock;
+  aw.addKhronosSink([&](const FrameData& data, const VolumetricMap& map, const Tracks&) {
+    hydra::DistanceFieldRequest rq(dfc);
+    const float cell = map.config.voxel_size * static_cast<float>(rq.ratio);
+    // the sensor's cell in the middle of a box that reaches the range plus a margin on x and y, half of that on z
+    const int half = std::min(KHR_DF_MAX_DIM / 2, static_cast<int>(std::floor(rq.max_distance / cell)) + 12);
+    const int hd[3] = {half, half, std::max(1, half / 2)};
+    for (int a = 0; a < 3; ++a) {
+      rq.origin[a] = static_cast<int32_t>(std::floor(data.input.world_T_sensor[4 * a + 3] / static_cast<double>(cell))) - hd[a];
+      rq.dims[a] = 2 * hd[a];
+    }
+    khr_sync(map.ctx());
+    const auto t0 = clk::now();
+    const hydra::DistanceField a = map.distanceField(rq);
+    const auto t1 = clk::now();
+    const hydra::DistanceField b = distanceByBlockCopies(map, rq);
+    const auto t2 = clk::now();
+    const char* diff = nullptr;
+    if (!(a.status == b.status)) diff = "status";
+    else if (!(a.d2 == b.d2)) diff = "d2";
+    else if (!sameBits(a.distance, b.distance)) diff = "distance";
+    else if (a.stats.n_observed != b.stats.n_observed || a.stats.n_obstacle != b.stats.n_obstacle || a.stats.n_free != b.stats.n_free ||
+             a.stats.n_in_range != b.stats.n_in_range) diff = "stats";
+    if (!diff) ++agree;
+    else if (first_mismatch.empty()) first_mismatch = "frame " + std::to_string(frames) + ": " + diff + " differs";
+    last_stats = a.stats;
+    cells = a.size();
+    if (frames >= kWarm) {
+      ms_dev += std::chrono::duration<double, std::milli>(t1 - t0).count();
+      ms_copy += std::chrono::duration<double, std::milli>(t2 - t1).count();
+      ++timed;
+    }
+    ++frames;
+  });
+  void* scene = synth_create(1234, 12, 1);
+  const size_t n = static_cast<size_t>(W) * H;
+  std::vector<float> depth(n);
+  std::vector<uint8_t> rgb(n * 3);
+  std::vector<int32_t> label(n);
+  for (int i = 0; i < N; ++i) {
+    hydra::InputPacket pkt;
+    pkt.timestamp_ns = static_cast<uint64_t>(std::llround((1.0 + 0.1 * i) * 1e9));
+    circlePose(0.1 * i, pkt.world_T_body);
+    pkt.sensor = {W, H, W / 2.f, W / 2.f, W / 2.f, H / 2.f, 0.1f, 5.f};
+    synth_render(scene, W, H, pkt.sensor.fx, pkt.sensor.fy, pkt.sensor.cx, pkt.sensor.cy, pkt.world_T_body, 0.1 * i, 5.f, 0.f,
+                 1234u + 7919u * i, depth.data(), rgb.data(), label.data(), 0);
+    pkt.depth = depth.data();
+    pkt.color = rgb.data();
+    pkt.labels = label.data();
+    aw.step(pkt);
+    hydra::ActiveWindowOutput::Ptr popped;
+    while (out_queue->pop(&popped)) {}
+  }
+  aw.finishMapping();
+  synth_destroy(scene);
+  const double d = timed ? static_cast<double>(timed) : 1.0;
+  std::printf("{\"what\": \"the distance field of a box around the sensor (VolumetricMap::distanceField vs a cloneBlock loop), %dx%d, voxel %.4g m, "
+              "ratio %d, max_distance %.4g m, positive_only %d\", \"frames\": %d, \"agree_frames\": %d, \"first_mismatch\": \"%s\", \"timed_frames\": %d, "
+              "\"cells\": %zu, \"last_stats\": {\"n_observed\": %llu, \"n_obstacle\": %llu, \"n_free\": %llu, \"n_in_range\": %llu}, "
+              "\"device_ms\": %.4f, \"block_copy_ms\": %.4f}\n",
+              W, H, static_cast<double>(cfg.volumetric_map.voxel_size), dfc.ratio, static_cast<double>(dfc.max_distance_m), int(dfc.positive_distance_only),
+              frames, agree, first_mismatch.c_str(), timed, cells, static_cast<unsigned long long>(last_stats.n_observed),
+              static_cast<unsigned long long>(last_stats.n_obstacle), static_cast<unsigned long long>(last_stats.n_free),
+              static_cast<unsigned long long>(last_stats.n_in_range), ms_dev / d, ms_copy / d);
+  return agree == frames && frames == N ? 0 : 3;
+}
+
 // 64-bit digest of an image's bytes: sum_i mix(i * L + byte_i) mod 2^64, mix = the splitmix64 step of khr_map_digest
 // (tests/test_gpu_render_view.py restates it in numpy)
 static uint64_t imageDigest(const void* data, size_t bytes) {
@@ -940,6 +1121,14 @@ int main(int argc, char** argv) {
   if (argc >= 2 && std::string(argv[1]) == "--query") {
     try {
       return queryDemo(argc, argv);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "aw_demo: %s\n", e.what());
+      return 1;
+    }
+  }
+  if (argc >= 2 && std::string(argv[1]) == "--distance") {
+    try {
+      return distanceDemo(argc, argv);
     } catch (const std::exception& e) {
       std::fprintf(stderr, "aw_demo: %s\n", e.what());
       return 1;

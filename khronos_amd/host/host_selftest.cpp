@@ -221,6 +221,16 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
+  if (argc > 2 && std::strcmp(argv[1], "--distance-config") == 0) {
+    // hydra::DistanceFieldConfig as it reads a mapper file's freespace_places (tests/test_cpu_distance_field.py)
+    std::ifstream in(argv[2]);
+    std::stringstream ss;
+    ss << in.rdbuf();
+    const hydra::DistanceFieldConfig c = hydra::DistanceFieldConfig::fromYaml(khronos_amd::parseYaml(ss.str()));
+    std::printf("max_distance_m=%.9g min_weight=%.9g positive_distance_only=%d ratio=%d\n", static_cast<double>(c.max_distance_m),
+                static_cast<double>(c.min_weight), c.positive_distance_only ? 1 : 0, c.ratio);
+    return 0;
+  }
   // ---- YAML ----
   if (argc > 1) {
     std::ifstream in(argv[1]);

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/khronos_amd.h"
+#include "mini_yaml.h"
 
 namespace hydra {
 
@@ -300,6 +301,71 @@ struct Alignment {
   }
 };
 
+// The distance-field stage of the reference's mapper configuration (freespace_places of khronos_ros/config/mapper/*.yaml: the
+// active window's TSDF, downsampled by `ratio`, goes into a distance transform with these parameters; the stage itself is
+// un-vendored Hydra).  fromYaml takes the mapper file's root node (freespace_places under `frontend`), or the node that holds
+// freespace_places itself.
+struct DistanceFieldConfig {
+  float max_distance_m = 1.f;
+  float min_weight = 0.f;  // 0 = the mesh's minimum weight
+  bool positive_distance_only = false;
+  int ratio = 1;
+  static DistanceFieldConfig fromYaml(const khronos_amd::YamlNode& root) {
+    DistanceFieldConfig c;
+    const khronos_amd::YamlNode* fp = root.find("freespace_places");
+    if (!fp)
+      if (const khronos_amd::YamlNode* fe = root.find("frontend")) fp = fe->find("freespace_places");
+    if (!fp) return c;
+    if (const khronos_amd::YamlNode* gvd = fp->find("gvd")) {
+      if (gvd->has("max_distance_m")) gvd->read("max_distance_m", c.max_distance_m);
+      if (gvd->has("min_weight")) gvd->read("min_weight", c.min_weight);
+      if (gvd->has("positive_distance_only")) gvd->read("positive_distance_only", c.positive_distance_only);
+    }
+    if (const khronos_amd::YamlNode* ti = fp->find("tsdf_interpolator"))
+      if (ti->has("ratio")) ti->read("ratio", c.ratio);
+    return c;
+  }
+};
+
+// What to compute (VolumetricMap::distanceField): the box in cells of `ratio` voxels, first cell and cells per axis.
+struct DistanceFieldRequest {
+  std::array<int32_t, 3> origin{0, 0, 0}, dims{1, 1, 1};
+  int ratio = 1;
+  float min_weight = 0.f;        // 0 = the mesh's minimum weight
+  float max_distance = 1.f;      // metres
+  float surface_distance = 0.f;  // a cell is an obstacle iff its least observed distance is <= this
+  bool unknown_is_obstacle = false;
+  bool positive_only = false;
+  DistanceFieldRequest() = default;
+  DistanceFieldRequest(const DistanceFieldConfig& c)
+      : ratio(c.ratio), min_weight(c.min_weight), max_distance(c.max_distance_m), positive_only(c.positive_distance_only) {}
+};
+
+// The exact Euclidean distance field of a box of the live map (khr_distance_field; ASSUMPTIONS.md A.15): one entry per cell in
+// the order x + nx * (y + ny * z).  Only the cells of the box take part.
+struct DistanceField {
+  enum Status : uint8_t { kObserved = KHR_DF_OBSERVED, kObstacle = KHR_DF_OBSTACLE, kInRange = KHR_DF_IN_RANGE };
+  std::array<int32_t, 3> origin{0, 0, 0}, dims{0, 0, 0};
+  float cell_size = 0.f;
+  std::vector<float> distance;  // metres; negative inside obstacles unless positive_only; +-max_distance out of range
+  std::vector<int32_t> d2;      // squared cell units; +-KHR_DF_FAR out of range
+  std::vector<uint8_t> status;
+  khr_df_stats stats{};
+  size_t size() const { return status.size(); }
+  size_t index(int x, int y, int z) const { return static_cast<size_t>(x) + static_cast<size_t>(dims[0]) * (static_cast<size_t>(y) + static_cast<size_t>(dims[1]) * static_cast<size_t>(z)); }
+  // the cell a world point lies in, relative to the box's first cell (may lie outside [0, dims))
+  std::array<int32_t, 3> cellOf(float x, float y, float z) const {
+    return {static_cast<int32_t>(std::floor(x / cell_size)) - origin[0], static_cast<int32_t>(std::floor(y / cell_size)) - origin[1],
+            static_cast<int32_t>(std::floor(z / cell_size)) - origin[2]};
+  }
+  bool contains(const std::array<int32_t, 3>& c) const { return c[0] >= 0 && c[0] < dims[0] && c[1] >= 0 && c[1] < dims[1] && c[2] >= 0 && c[2] < dims[2]; }
+  // world position of the centre of the box's cell (x, y, z)
+  std::array<float, 3> centre(int x, int y, int z) const {
+    return {(static_cast<float>(origin[0] + x) + 0.5f) * cell_size, (static_cast<float>(origin[1] + y) + 0.5f) * cell_size,
+            (static_cast<float>(origin[2] + z) + 0.5f) * cell_size};
+  }
+};
+
 // hydra::VolumetricMap role: here a handle on the HBM-resident map of a fusion context.
 class VolumetricMap {
  public:
@@ -432,6 +498,24 @@ class VolumetricMap {
     rq.points = points.data();
     rq.weights = weights.empty() ? nullptr : weights.data();
     return alignRun(rq, opt);
+  }
+  // How far every cell of a box is from the nearest obstacle (khr_distance_field): gathered from the hashed blocks and transformed on
+  // the device, exact.  One call, one host wait, no block copies.  Throws on a bad request.
+  DistanceField distanceField(const DistanceFieldRequest& request) const {
+    khr_df_request rq{};
+    for (int a = 0; a < 3; ++a) rq.origin[a] = request.origin[a], rq.dims[a] = request.dims[a];
+    rq.ratio = request.ratio;
+    rq.min_weight = request.min_weight, rq.max_distance = request.max_distance, rq.surface_distance = request.surface_distance;
+    rq.unknown_is_obstacle = request.unknown_is_obstacle ? 1 : 0, rq.positive_only = request.positive_only ? 1 : 0;
+    DistanceField f;
+    f.origin = request.origin, f.dims = request.dims;
+    f.cell_size = config.voxel_size * static_cast<float>(request.ratio);
+    size_t n = 1;
+    for (int a = 0; a < 3; ++a) n *= request.dims[a] > 0 && request.dims[a] <= KHR_DF_MAX_DIM ? static_cast<size_t>(request.dims[a]) : 0;
+    f.distance.resize(n); f.d2.resize(n); f.status.resize(n);
+    if (khr_distance_field(ctx_, &rq, 0, f.distance.data(), f.d2.data(), f.status.data(), &f.stats) != KHR_OK)
+      throw std::runtime_error(std::string("khr_distance_field: ") + khr_last_error());
+    return f;
   }
   // The map save / load role of hydra::VolumetricMap (un-vendored upstream; the reference's own tree has no counterpart): the live
   // map as one checkpoint file (khr_checkpoint_save: the format is in include/khronos_amd.h) and back into an EMPTY map of the
