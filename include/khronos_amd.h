@@ -353,6 +353,17 @@ int64_t khr_cluster_voxels(khr_ctx* ctx, int slot, int which, float voxel_size, 
  * waits for it and decodes (same output as khr_cluster_voxels). */
 int khr_cluster_voxels_launch(khr_ctx* ctx, int slot, int which, float voxel_size);
 int64_t khr_cluster_voxels_fetch(khr_ctx* ctx, int which, int32_t* ids_out, int64_t* voxels_out, int64_t cap);
+/* Tells the object detector which grid the tracker's voxel sets use (MaxIoUTracker::Config::voxel_size); 0 switches it off
+ * (the default).  When it is on, the pass that writes a frame's final cluster ids into the object image (the end of
+ * khr_detect_objects, or of khr_process_frame with KHR_PF_OBJECTS) also collects the object image's voxel sets at that
+ * size -- one kernel instead of an id remap and a later voxel-set pass over the same pixels.  This happens for a 3D- or
+ * 2D-mode frame with 1 .. 256 connected components (before the size filter); a later khr_cluster_voxels_launch(slot, 1,
+ * the same voxel_size) for that slot then queues nothing and khr_cluster_voxels_fetch(1) returns the sets collected ahead.
+ * Every other request -- another slot or size, which = 0, a frame with more components, without a label image, or whose
+ * object image was replaced since -- runs the stand-alone pass as before, with the same results.  The sets collected ahead
+ * wait in a result set of their own: the sets of the previous khr_cluster_voxels_launch(.., 1, ..) stay fetchable until the
+ * next such launch, whatever the detector does in between. */
+int khr_configure_object_voxel_sets(khr_ctx* ctx, float voxel_size);
 /* replaces: MaxIoUTracker::computeIoUPixels for track_by = pixels (max_iou_tracker.cpp:497-503, 578-600).  A track's
  * last_points are named by the resident frame slot, id image (0 dynamic, 1 object) and cluster id of its last
  * observation (the caller retains the slot).  For up to 32 such references: n_points[r] = number of points

@@ -155,7 +155,7 @@ EXPORTS = [
     "khr_map_slice", "khr_slice_voxel_z", "khr_render_view", "khr_query_points",
     "khr_align_linearize", "khr_align_frame", "khr_distance_field",
     "khr_checkpoint_size", "khr_checkpoint_save", "khr_checkpoint_load", "khr_checkpoint_inspect",
-    "khr_debug_live_resources",
+    "khr_debug_live_resources", "khr_configure_object_voxel_sets",
 ]
 
 _lib = None
@@ -226,6 +226,7 @@ def load_library():
     lib.khr_cluster_voxels_launch.argtypes = [vp, i32, i32, C.c_float]
     lib.khr_cluster_voxels_fetch.argtypes = [vp, i32, vp, vp, C.c_int64]
     lib.khr_cluster_voxels_fetch.restype = C.c_int64
+    lib.khr_configure_object_voxel_sets.argtypes = [vp, C.c_float]
     lib.khr_get_semantic_clusters.argtypes = [vp, i32, C.POINTER(KhrCluster), i32]
     lib.khr_cluster_voxels.argtypes = [vp, i32, i32, C.c_float, vp, vp, C.c_int64]
     lib.khr_cluster_voxels.restype = C.c_int64
@@ -690,6 +691,21 @@ class FusionContext:
         vox = np.zeros((max(n, 1), 3), np.int64)
         n2 = self.lib.khr_cluster_voxels(self.h, slot, which, float(voxel_size), _ptr(ids), _ptr(vox), n)
         self._chk(n2)
+        return ids[:n], vox[:n]
+
+    def configure_object_voxel_sets(self, voxel_size):
+        """the tracker's voxel size: the detector's id remap then also collects the object image's voxel sets (0 = off)."""
+        self._chk(self.lib.khr_configure_object_voxel_sets(self.h, float(voxel_size)))
+
+    def cluster_voxels_launch(self, slot, which, voxel_size):
+        self._chk(self.lib.khr_cluster_voxels_launch(self.h, slot, which, float(voxel_size)))
+
+    def cluster_voxels_fetch(self, which):
+        n = self.lib.khr_cluster_voxels_fetch(self.h, which, None, None, 0)
+        self._chk(n)
+        ids = np.zeros(max(n, 1), np.int32)
+        vox = np.zeros((max(n, 1), 3), np.int64)
+        self._chk(self.lib.khr_cluster_voxels_fetch(self.h, which, _ptr(ids), _ptr(vox), n))
         return ids[:n], vox[:n]
 
     def generate_mesh(self, only_mesh_updated=True, clear_flag=True):

@@ -483,6 +483,43 @@ __global__ __launch_bounds__(256) void k_cluster_voxels(DevFrame f, const int32_
   }
 }
 
+// k_obj_remap_tab and k_cluster_voxels in one pass (khr_configure_object_voxel_sets): the final id goes back to the object image
+// and, for id > 0, straight into the tracker's voxel set -- the image is not read a second time by a second launch
+__global__ __launch_bounds__(256) void k_obj_remap_cluster_voxels(DevFrame f, int32_t* __restrict__ obj, RemapTab tab, float inv, int3 origin,
+                                                                 GvTable t, uint64_t* __restrict__ list, uint32_t* __restrict__ n_list,
+                                                                 uint32_t cap, uint32_t* __restrict__ flags, uint32_t* __restrict__ slots) {
+  __shared__ int32_t s_tab[kRemapTab];
+  s_tab[threadIdx.x] = tab.v[threadIdx.x];
+  __syncthreads();
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool has = false;
+  uint64_t key = 0;
+  if (i < f.W * f.H) {
+    const int32_t prov = obj[i];
+    if (prov) {
+      const int32_t id = s_tab[prov - 1];
+      obj[i] = id;
+      if (id > 0) {
+        if (static_cast<uint32_t>(id) > kGvMaxGroup) {
+          atomicOr(&flags[0], 2u);
+        } else {
+          float pw[3];
+          pixelVertex(f, i, pw);
+          has = gvVoxelKey(pw, inv, origin, static_cast<uint32_t>(id), !(f.range[i] > 0.f), &key);
+          if (!has) atomicOr(&flags[0], 1u);
+        }
+      }
+    }
+  }
+  bool claimed;
+  const uint32_t h = gvInsertWave(t, has, key, &claimed);
+  const uint32_t at = waveAggInc(n_list, claimed);
+  if (claimed && at < cap) {
+    list[at] = key;
+    slots[at] = h;
+  }
+}
+
 
 // ---- MaxIoUTracker, track_by = pixels (max_iou_tracker.cpp:497-503, 578-600) --------------------------------------------------
 // A track's last_points are the world vertices of its last observation's pixels; they stay where they are -- in the id

@@ -116,6 +116,7 @@ struct TimingRec {
 constexpr int kNumTimers = 13;  // 0..7: kernel groups; 8..12: single kernels (k_marching_cubes count / emit, k_tracking_update, k_ever_free, k_snapshot_pack)
 constexpr uint32_t kObjHead = 512;   // cluster records in the first download of the object detector
 constexpr uint32_t kCvHead = 8192;   // (cluster, voxel) keys in the first download of a voxel-set request
+constexpr int kGvReleaseGrid = 64;   // workgroups of k_gv_release_publish: a few thousand slots to free, one returning atomic per workgroup
 constexpr uint32_t kCompCap = 1024, kCompHead = 64;  // motion-cluster components: record capacity / records in the first download
 
 }  // namespace
@@ -141,7 +142,7 @@ struct khr_ctx {
   Event ev_aux, ev_aux_done;
   // batches queued on the auxiliary stream are numbered; aux_seq_done = the latest one the host KNOWS to be complete
   // (a ticket it waited for, an idle stream): a frame slot is only re-ingested when its last batch is
-  uint64_t aux_seq_issued = 0, aux_seq_done = 0, obj_seq = 0, cv_seq[2] = {0, 0};
+  uint64_t aux_seq_issued = 0, aux_seq_done = 0, obj_seq = 0, cv_seq[3] = {0, 0, 0};  // (cv_seq: per result set, see d_cv_n)
   std::vector<DevBuf<uint8_t>> allocs;  // every buffer that lives as long as the context (devAlloc); the raw pointers below without
                                         // an owner type, DevMap m, MeshBuffers mesh[] and the frame slots' planes are views into these
   std::vector<FrameSlot> slots;
@@ -357,18 +358,24 @@ struct khr_ctx {
   uint32_t* d_gv_owners = nullptr;  // table slots claimed by the current request (work list + table reset)
   uint32_t* d_gv_done = nullptr;    // completion counter of k_gv_release_publish
   bool gv_clean = false;            // the (group, voxel) table is empty (every request gives it back empty)
-  bool gv_counters_clean[3] = {false, false, false};  // request counters zeroed by their last k_publish: detect, voxels 0 / 1
+  bool gv_counters_clean[4] = {false, false, false, false};  // request counters zeroed by their last k_publish: detect, voxel result sets 0 / 1 / 2
   PinnedBuf<uint8_t> h_obj_head;   // pinned: {roots, flags, -, -} + the cluster records (first download kObjHead of them)
   Event ev_obj;
   int obj_pending_slot = -1;       // objectsLaunch issued, objectsFinish outstanding
-  // asynchronous per-cluster voxel sets, one request per id image (0 dynamic, 1 object)
-  uint32_t* d_cv_n[2] = {nullptr, nullptr};    // views (see d_gv_n)
-  uint64_t* d_cv_keys[2] = {nullptr, nullptr};
-  PinnedBuf<uint8_t> h_cv[2];  // pinned: {count, flags, -, -} + keys
-  Event ev_cv[2];
+  // asynchronous per-cluster voxel sets, one request per id image (0 dynamic, 1 object).  Three result sets: set 0 belongs to the
+  // dynamic image; the object image's requests use sets 1 and 2 in turn -- the set cv_set_obj is the one khr_cluster_voxels_fetch(1)
+  // reads, the other one takes the voxel sets that objectsFinish queues ahead of the request (khr_configure_object_voxel_sets)
+  // while the previous frame's may still be waiting for their fetch
+  uint32_t* d_cv_n[3] = {nullptr, nullptr, nullptr};    // views (see d_gv_n)
+  uint64_t* d_cv_keys[3] = {nullptr, nullptr, nullptr};
+  PinnedBuf<uint8_t> h_cv[3];  // pinned: {count, flags, -, -} + keys
+  Event ev_cv[3];
   int cv_pending_slot[2] = {-1, -1};
-  uint32_t obj_ticket = 0, cv_ticket[2] = {0, 0};  // h_pinned[4] / [5], [6]
-  int3 cv_origin[2]{};
+  uint32_t obj_ticket = 0, cv_ticket[3] = {0, 0, 0};  // h_pinned[4] / [5], [6], [12]
+  int3 cv_origin[3]{};
+  int cv_set_obj = 1;
+  float obj_cv_size = 0.f;   // khr_configure_object_voxel_sets: the tracker's voxel size (0 = off)
+  int obj_cv_slot = -1;      // objectsFinish queued the slot's voxel sets at obj_cv_size into the set 3 - cv_set_obj (-1 = nothing queued)
   // mesh
   MeshBuffers mesh[2]{};
   int mesh_cur = 0;
@@ -1207,6 +1214,7 @@ int khr_upload_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fram
   s.has_color = frame->color != nullptr;
   s.has_label = frame->label != nullptr;
   s.has_obj = false;
+  if (c->obj_cv_slot == slot) c->obj_cv_slot = -1;
   s.objects_done = false;
   s.clusters.clear();
   s.sem_clusters.clear();
@@ -1276,6 +1284,7 @@ int khr_set_frame_image(khr_ctx* c, int slot, int which, const int32_t* image, i
     HIP_TRY(hipMemsetAsync(dst, 0, n * sizeof(int32_t), c->stream));
   }
   if (which == 1) s.has_obj = image != nullptr;
+  if (which == 1 && c->obj_cv_slot == slot) c->obj_cv_slot = -1;  // (voxel sets queued for the image this one replaces)
   if (which == 0) s.dyn_clean = image == nullptr;
   if (which == 0) s.dynw_valid = false;  // (an installed image brings no list multiplicities: its summaries count every pixel once)
   if (which == 1) {  // an object image written here is read by kernels of the auxiliary stream (voxel sets)
@@ -1938,6 +1947,7 @@ int khr_tick_ingest(khr_ctx* c, const khr_sensor* sensor, const khr_frame* frame
       s.has_color = fr.color != nullptr;
       s.has_label = fr.label != nullptr;
       s.has_obj = false;
+      if (c->obj_cv_slot == slot) c->obj_cv_slot = -1;
       s.objects_done = false;
       s.clusters.clear();
       s.sem_clusters.clear();
@@ -2059,6 +2069,7 @@ int khr_tick_adopt(khr_ctx* c, const khr_sensor* sensor, const khr_converted_fra
       s.has_color = fr.rgba != nullptr;
       s.has_label = fr.label != nullptr;
       s.has_obj = false;
+      if (c->obj_cv_slot == slots_out[base + k]) c->obj_cv_slot = -1;
       s.objects_done = false;
       s.clusters.clear();
       s.sem_clusters.clear();
@@ -3111,7 +3122,7 @@ static int ensureGv(khr_ctx* c) {
     c->d_obj_acc = head ? reinterpret_cast<ObjAcc*>(head + 16) : nullptr;
   }
   KHR_CHAIN(devAlloc(c, &c->d_obj_final, c->obj_root_cap, false));
-  for (int w = 0; w < 2; ++w) {
+  for (int w = 0; w < 3; ++w) {
     uint8_t* head = nullptr;
     KHR_CHAIN(devAlloc(c, &head, 16 + sizeof(uint64_t) * npx));
     c->d_cv_n[w] = reinterpret_cast<uint32_t*>(head);
@@ -3167,6 +3178,7 @@ static int objectsLaunch(khr_ctx* c, int slot) {
   s.has_obj = true;
   s.aux_seq = c->obj_seq = ++c->aux_seq_issued;
   c->obj_pending_slot = -1;
+  if (c->obj_cv_slot == slot) c->obj_cv_slot = -1;  // (the slot's object image is about to be rewritten)
   const int n_labels = static_cast<int>(c->obj_labels.size());
   if (!s.has_label || n_labels == 0) {
     HIP_TRY(hipMemsetAsync(s.obj, 0, sizeof(int32_t) * n, c->aux_stream));
@@ -3206,8 +3218,8 @@ static int objectsLaunch(khr_ctx* c, int slot) {
   HIP_TRY(hipGetLastError());
   if (++c->obj_ticket == 0) ++c->obj_ticket;
   if (oc.use_3d) {
-    hipLaunchKernelGGL(k_gv_release_publish, dim3(256), dim3(256), 0, c->aux_stream, c->d_gv_owners, c->d_gv_n + 2, c->d_gv_keys, c->d_gv_done,
-                       c->d_gv_n, reinterpret_cast<uint32_t*>(c->h_obj_head.dev()), static_cast<uint32_t>(sizeof(ObjAcc) / 4), kObjHead,
+    hipLaunchKernelGGL(k_gv_release_publish, dim3(kGvReleaseGrid), dim3(256), 0, c->aux_stream, c->d_gv_owners, c->d_gv_n + 2, c->d_gv_keys,
+                       c->d_gv_done, c->d_gv_n, reinterpret_cast<uint32_t*>(c->h_obj_head.dev()), static_cast<uint32_t>(sizeof(ObjAcc) / 4), kObjHead,
                        c->h_pinned.dev() + 4, c->obj_ticket, c->d_gv_n);
     c->gv_clean = true;
   } else {
@@ -3217,6 +3229,22 @@ static int objectsLaunch(khr_ctx* c, int slot) {
   HIP_TRY(hipGetLastError());
   c->gv_counters_clean[0] = oc.use_3d != 0;  // (the 2D path resets them itself)
   c->obj_pending_slot = slot;
+  return KHR_OK;
+}
+
+// ticket word of a voxel result set in h_pinned
+static int cvTicketWord(int set) { return set == 2 ? 12 : 5 + set; }
+
+// tail of a voxel-set request: the table is given back empty, the result set's head goes to pinned memory
+static int cvReleasePublish(khr_ctx* c, int set) {
+  c->gv_clean = true;
+  if (++c->cv_ticket[set] == 0) ++c->cv_ticket[set];
+  hipLaunchKernelGGL(k_gv_release_publish, dim3(kGvReleaseGrid), dim3(256), 0, c->aux_stream, c->d_gv_owners, c->d_cv_n[set], c->d_gv_keys,
+                     c->d_gv_done, c->d_cv_n[set], reinterpret_cast<uint32_t*>(c->h_cv[set].dev()), 2u,
+                     static_cast<uint32_t>(std::min<size_t>(kCvHead, c->cfg.max_frame_pixels)), c->h_pinned.dev() + cvTicketWord(set),
+                     c->cv_ticket[set], c->d_cv_n[set]);
+  HIP_TRY(hipGetLastError());
+  c->gv_counters_clean[1 + set] = true;
   return KHR_OK;
 }
 
@@ -3283,7 +3311,29 @@ static int objectsFinish(khr_ctx* c, int slot) {
   if (R <= static_cast<uint32_t>(kRemapTab)) {  // the usual case: the table rides in the kernel arguments
     RemapTab tab{};
     std::memcpy(tab.v, fin.data(), sizeof(int32_t) * R);
-    hipLaunchKernelGGL(k_obj_remap_tab, dim3(gridFor(n)), dim3(256), 0, c->aux_stream, s.obj, n, tab);
+    if (c->obj_cv_size > 0.f) {
+      // the tracker's voxel sets of this object image in the same pass, into the result set that no fetch is reading; a
+      // khr_cluster_voxels_launch(slot, 1, obj_cv_size) adopts it
+      const int set = 3 - c->cv_set_obj;
+      const DevFrame f = makeDevFrame(c, s);
+      const float inv = 1.f / c->obj_cv_size;
+      s.aux_seq = c->cv_seq[set] = ++c->aux_seq_issued;
+      c->cv_origin[set] = windowOrigin(f, inv);
+      GvTable t{c->d_gv_keys, c->gv_mask};
+      const uint32_t tsize = c->gv_mask + 1;
+      if (!c->gv_clean) hipLaunchKernelGGL(k_gv_clear, dim3(gridFor(tsize / 2)), dim3(256), 0, c->aux_stream, c->d_gv_keys, tsize, c->d_cv_n[set]);
+      else if (!c->gv_counters_clean[1 + set]) HIP_TRY(hipMemsetAsync(c->d_cv_n[set], 0, sizeof(uint32_t) * 4, c->aux_stream));
+      c->gv_clean = false;
+      c->gv_counters_clean[1 + set] = false;
+      hipLaunchKernelGGL(k_obj_remap_cluster_voxels, dim3(gridFor(n)), dim3(256), 0, c->aux_stream, f, s.obj, tab, inv, c->cv_origin[set], t,
+                         c->d_cv_keys[set], c->d_cv_n[set], static_cast<uint32_t>(c->cfg.max_frame_pixels), c->d_cv_n[set] + 1, c->d_gv_owners);
+      HIP_TRY(hipGetLastError());
+      const int rcp = cvReleasePublish(c, set);
+      if (rcp) return rcp;
+      c->obj_cv_slot = slot;
+    } else {
+      hipLaunchKernelGGL(k_obj_remap_tab, dim3(gridFor(n)), dim3(256), 0, c->aux_stream, s.obj, n, tab);
+    }
   } else {
     std::memcpy(c->h_obj_head, fin.data(), sizeof(int32_t) * R);
     HIP_TRY(hipMemcpyAsync(c->d_obj_final, c->h_obj_head, sizeof(int32_t) * R, hipMemcpyHostToDevice, c->aux_stream));
@@ -3331,6 +3381,14 @@ int khr_get_semantic_clusters(khr_ctx* c, int slot, khr_cluster* out, int cap) {
   return n;
 }
 
+int khr_configure_object_voxel_sets(khr_ctx* c, float voxel_size) {
+  if (!c) return fail(KHR_EINVAL, "null ctx");
+  if (!(voxel_size >= 0.f) || !std::isfinite(voxel_size)) return fail(KHR_EINVAL, "voxel_size must be >= 0 (0 = off)");
+  if (voxel_size != c->obj_cv_size) c->obj_cv_slot = -1;  // (sets queued ahead at the old size are not adopted)
+  c->obj_cv_size = voxel_size;
+  return KHR_OK;
+}
+
 int khr_cluster_voxels_launch(khr_ctx* c, int slot, int which, float voxel_size) {
   if (!c || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad slot");
   if (!(voxel_size > 0.f) || (which != 0 && which != 1)) return fail(KHR_EINVAL, "bad argument");
@@ -3339,10 +3397,17 @@ int khr_cluster_voxels_launch(khr_ctx* c, int slot, int which, float voxel_size)
   if (rc) return rc;
   FrameSlot& s = c->slots[slot];
   c->cv_pending_slot[which] = slot;
-  uint32_t* hc = reinterpret_cast<uint32_t*>(c->h_cv[which].get());
+  if (which == 1 && c->obj_cv_slot == slot && c->obj_cv_size == voxel_size && s.has_obj) {
+    // objectsFinish queued exactly this request with the id remap: its result set becomes the one the fetch reads
+    c->cv_set_obj = 3 - c->cv_set_obj;
+    c->obj_cv_slot = -1;
+    return KHR_OK;
+  }
+  const int set = which == 0 ? 0 : c->cv_set_obj;
+  uint32_t* hc = reinterpret_cast<uint32_t*>(c->h_cv[set].get());
   if (which == 1 && !s.has_obj) {  // no object image: nothing to look at
     hc[0] = hc[1] = 0;
-    c->cv_ticket[which] = c->h_pinned[5 + which];  // nothing in flight: the fetch sees the current ticket
+    c->cv_ticket[set] = c->h_pinned[cvTicketWord(set)];  // nothing in flight: the fetch sees the current ticket
     return KHR_OK;
   }
   const int n = s.sensor.width * s.sensor.height;
@@ -3352,48 +3417,41 @@ int khr_cluster_voxels_launch(khr_ctx* c, int slot, int which, float voxel_size)
     rc = auxAfterMain(c);
     if (rc) return rc;
   }
-  s.aux_seq = c->cv_seq[which] = ++c->aux_seq_issued;
-  c->cv_origin[which] = windowOrigin(f, inv);
+  s.aux_seq = c->cv_seq[set] = ++c->aux_seq_issued;
+  c->cv_origin[set] = windowOrigin(f, inv);
   GvTable t{c->d_gv_keys, c->gv_mask};
   const uint32_t tsize = c->gv_mask + 1;
-  if (!c->gv_clean) hipLaunchKernelGGL(k_gv_clear, dim3(gridFor(tsize / 2)), dim3(256), 0, c->aux_stream, c->d_gv_keys, tsize, c->d_cv_n[which]);
-  else if (!c->gv_counters_clean[1 + which]) HIP_TRY(hipMemsetAsync(c->d_cv_n[which], 0, sizeof(uint32_t) * 4, c->aux_stream));
+  if (!c->gv_clean) hipLaunchKernelGGL(k_gv_clear, dim3(gridFor(tsize / 2)), dim3(256), 0, c->aux_stream, c->d_gv_keys, tsize, c->d_cv_n[set]);
+  else if (!c->gv_counters_clean[1 + set]) HIP_TRY(hipMemsetAsync(c->d_cv_n[set], 0, sizeof(uint32_t) * 4, c->aux_stream));
   c->gv_clean = false;
-  c->gv_counters_clean[1 + which] = false;
-  hipLaunchKernelGGL(k_cluster_voxels, dim3(gridFor(n)), dim3(256), 0, c->aux_stream, f, which == 0 ? s.dyn : s.obj, inv, c->cv_origin[which], t,
-                     c->d_cv_keys[which], c->d_cv_n[which], static_cast<uint32_t>(c->cfg.max_frame_pixels), c->d_cv_n[which] + 1,
+  c->gv_counters_clean[1 + set] = false;
+  hipLaunchKernelGGL(k_cluster_voxels, dim3(gridFor(n)), dim3(256), 0, c->aux_stream, f, which == 0 ? s.dyn : s.obj, inv, c->cv_origin[set], t,
+                     c->d_cv_keys[set], c->d_cv_n[set], static_cast<uint32_t>(c->cfg.max_frame_pixels), c->d_cv_n[set] + 1,
                      c->d_gv_owners);
-  c->gv_clean = true;
   HIP_TRY(hipGetLastError());
-  if (++c->cv_ticket[which] == 0) ++c->cv_ticket[which];
-  hipLaunchKernelGGL(k_gv_release_publish, dim3(256), dim3(256), 0, c->aux_stream, c->d_gv_owners, c->d_cv_n[which], c->d_gv_keys, c->d_gv_done,
-                     c->d_cv_n[which], reinterpret_cast<uint32_t*>(c->h_cv[which].dev()), 2u,
-                     static_cast<uint32_t>(std::min<size_t>(kCvHead, c->cfg.max_frame_pixels)), c->h_pinned.dev() + 5 + which, c->cv_ticket[which],
-                     c->d_cv_n[which]);
-  HIP_TRY(hipGetLastError());
-  c->gv_counters_clean[1 + which] = true;
-  return KHR_OK;
+  return cvReleasePublish(c, set);
 }
 
 int64_t khr_cluster_voxels_fetch(khr_ctx* c, int which, int32_t* ids_out, int64_t* voxels_out, int64_t cap) {
   if (!c || (which != 0 && which != 1) || cap < 0 || (cap > 0 && (!ids_out || !voxels_out))) return fail(KHR_EINVAL, "bad argument");
   if (c->cv_pending_slot[which] < 0) return fail(KHR_ESTATE, "khr_cluster_voxels_launch has not been called");
+  const int set = which == 0 ? 0 : c->cv_set_obj;
   {
-    const int rcw = waitTicket(c, 5 + which, c->cv_ticket[which], "the cluster voxel sets", c->aux_stream);
-    if (!rcw) c->aux_seq_done = std::max(c->aux_seq_done, c->cv_seq[which]);
+    const int rcw = waitTicket(c, cvTicketWord(set), c->cv_ticket[set], "the cluster voxel sets", c->aux_stream);
+    if (!rcw) c->aux_seq_done = std::max(c->aux_seq_done, c->cv_seq[set]);
     if (rcw) return rcw;
   }
-  const uint32_t* cnt = reinterpret_cast<const uint32_t*>(c->h_cv[which].get());
+  const uint32_t* cnt = reinterpret_cast<const uint32_t*>(c->h_cv[set].get());
   if (cnt[1] & 1u) return fail(KHR_EINVAL, "cluster voxels: a measured point lies more than %d voxels from the sensor", kGvWindow);
   if (cnt[1] & 2u) return fail(KHR_EINVAL, "cluster voxels: cluster id above %u", kGvMaxGroup);
   const uint32_t N = cnt[0];
   if (N == 0) return 0;
   if (N > kCvHead) {
-    HIP_TRY(hipMemcpyAsync(c->h_cv[which], c->d_cv_n[which], 16 + sizeof(uint64_t) * N, hipMemcpyDeviceToHost, c->aux_stream));
+    HIP_TRY(hipMemcpyAsync(c->h_cv[set], c->d_cv_n[set], 16 + sizeof(uint64_t) * N, hipMemcpyDeviceToHost, c->aux_stream));
     HIP_TRY(hipStreamSynchronize(c->aux_stream));
   }
-  const uint64_t* keys = reinterpret_cast<const uint64_t*>(c->h_cv[which] + 16);
-  const int3 origin = c->cv_origin[which];
+  const uint64_t* keys = reinterpret_cast<const uint64_t*>(c->h_cv[set] + 16);
+  const int3 origin = c->cv_origin[set];
   struct E { int32_t id; int64_t v[3]; };
   std::vector<E> e(N);
   for (uint32_t i = 0; i < N; ++i) {
@@ -3514,6 +3572,7 @@ int khr_forward_instances(khr_ctx* c, int slot, float max_range, const int32_t* 
   HIP_TRY(hipMemcpyAsync(&flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   s.has_obj = true;
+  if (c->obj_cv_slot == slot) c->obj_cv_slot = -1;
   s.objects_done = true;
   s.sem_clusters.clear();
   if (flags & 1u) return fail(KHR_EINVAL, "an instance id of the label image is outside 1..%d", max_id);

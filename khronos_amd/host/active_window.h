@@ -268,6 +268,7 @@ class MaxIoUTracker : public Tracker {
   int current_track_id_ = 0;
   mutable std::vector<int32_t> scratch_ids_;
   mutable std::vector<int64_t> scratch_voxels_;
+  mutable khr_ctx* voxel_sets_ctx_ = nullptr;  // the context that was told config.voxel_size (khr_configure_object_voxel_sets)
   // track_by = pixels: the frame being associated and, per track (index), the intersections of its re-projected points
   // with every object-image cluster of that frame (khr_pixel_iou)
   const FrameData* current_ = nullptr;

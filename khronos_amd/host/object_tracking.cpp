@@ -260,6 +260,12 @@ void MaxIoUTracker::setupTrackMeasurements(FrameData& data) const {
 // device frame (unit tests) the clusters are used as given.
 void MaxIoUTracker::launchTrackMeasurements(FrameData& data) const {
   if (config.track_by != Config::TrackBy::kVoxels || !data.input.ctx || data.input.slot < 0) return;
+  // the context learns the tracker's grid when the tracker first sees it: from the next frame on the detector collects the
+  // object image's voxel sets with its id remap, and the launch below finds them queued
+  if (voxel_sets_ctx_ != data.input.ctx) {
+    chk(khr_configure_object_voxel_sets(data.input.ctx, config.voxel_size), "khr_configure_object_voxel_sets");
+    voxel_sets_ctx_ = data.input.ctx;
+  }
   if (!data.semantic_clusters.empty())
     chk(khr_cluster_voxels_launch(data.input.ctx, data.input.slot, 1, config.voxel_size), "khr_cluster_voxels_launch");
   if (!data.dynamic_clusters.empty())
