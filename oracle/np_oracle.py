@@ -173,42 +173,84 @@ def voxel_is_free(cfg, last_occ, last_obs, stamp):
     return ((last_occ.astype(np.float64) / 1e9) < (np.float64(stamp) / 1e9 - np.float64(f32(cfg["temporal_buffer"])))) & (last_obs != 0)
 
 
-def ever_free_pass(cfg, blocks, updated, stamp):
-    """blocks: {(bx, by, bz): dict(last_obs, last_occ, flags)} (flat arrays, x fastest; flags bit1 = ever_free);
-    updated: the block indices the integrator touched in this frame.  Sets the ever_free bit where the voxel is free and all
-    `neighbor_connectivity` neighbours are ever-free or free; a neighbour in a block that does not exist fails the test.
-    (The reference reads neighbours' ever_free while other threads set it; the outcome is the same either way because a
-    voxel that becomes ever-free in this pass is free, ASSUMPTIONS.md B.)"""
+def free_or_ever_free(cfg, blocks, stamp):
+    """per block: (free-or-ever-free volume BEFORE the pass as a (z, y, x) cube, voxelIsFree as a flat array)"""
     vps = cfg["voxels_per_side"]
-    offs = _neighbour_offsets(cfg["neighbor_connectivity"])
-    # free-or-ever-free volume of every block BEFORE the pass, as (z, y, x) cubes
     F, free = {}, {}
     for b, d in blocks.items():
         fr = voxel_is_free(cfg, d["last_occ"], d["last_obs"], stamp)
         free[b] = fr
         F[b] = (((d["flags"] & 2) > 0) | fr).reshape(vps, vps, vps)
+    return F, free
+
+
+def padded_neighbourhood(F, b, vps, halo=None, absent=False, others=None):
+    """the (vps + 2)^3 tile (z, y, x) of free-or-ever-free bits around block b.  A neighbour block that is not in F reads its halo
+    record (halo: {block index: flat bool array}, the other ranks' blocks of a sharded map) and `absent` where there is none: the
+    reference's missing block fails the test, absent=True shows what only the missing blocks refuse.  others=True / False
+    overrides the voxels of every neighbour block that IS in F (what only those refuse)."""
+    pad = np.full((vps + 2, vps + 2, vps + 2), bool(absent))
+    for dz in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                nb = (b[0] + dx, b[1] + dy, b[2] + dz)
+                if nb in F:
+                    src = F[nb] if (others is None or nb == tuple(b)) else np.full((vps, vps, vps), bool(others))
+                elif halo is not None and nb in halo:
+                    src = np.asarray(halo[nb], bool).reshape(vps, vps, vps)
+                else:
+                    continue
+                zs = slice(0, 1) if dz == 1 else (slice(vps - 1, vps) if dz == -1 else slice(0, vps))
+                ys = slice(0, 1) if dy == 1 else (slice(vps - 1, vps) if dy == -1 else slice(0, vps))
+                xs = slice(0, 1) if dx == 1 else (slice(vps - 1, vps) if dx == -1 else slice(0, vps))
+                zd = slice(vps + 1, vps + 2) if dz == 1 else (slice(0, 1) if dz == -1 else slice(1, vps + 1))
+                yd = slice(vps + 1, vps + 2) if dy == 1 else (slice(0, 1) if dy == -1 else slice(1, vps + 1))
+                xd = slice(vps + 1, vps + 2) if dx == 1 else (slice(0, 1) if dx == -1 else slice(1, vps + 1))
+                pad[zd, yd, xd] = src[zs, ys, xs]
+    return pad
+
+
+def neighbours_ok(pad, vps, nn):
+    """flat bool array: all nn neighbours of the voxel are set in the padded tile"""
+    ok = np.ones((vps, vps, vps), bool)
+    for (dx, dy, dz) in _neighbour_offsets(nn):
+        ok &= pad[1 + dz:1 + dz + vps, 1 + dy:1 + dy + vps, 1 + dx:1 + dx + vps]
+    return ok.ravel()
+
+
+def ever_free_pass(cfg, blocks, updated, stamp, halo=None):
+    """blocks: {(bx, by, bz): dict(last_obs, last_occ, flags)} (flat arrays, x fastest; flags bit1 = ever_free);
+    updated: the block indices the integrator touched in this frame.  Sets the ever_free bit where the voxel is free and all
+    `neighbor_connectivity` neighbours are ever-free or free; a neighbour in a block that does not exist fails the test unless
+    `halo` (padded_neighbourhood) has a record of that block.
+    (The reference reads neighbours' ever_free while other threads set it; the outcome is the same either way because a
+    voxel that becomes ever-free in this pass is free, ASSUMPTIONS.md B.)"""
+    vps = cfg["voxels_per_side"]
+    F, free = free_or_ever_free(cfg, blocks, stamp)   # BEFORE the pass
     for b in updated:
-        d = blocks[b]
-        pad = np.zeros((vps + 2, vps + 2, vps + 2), bool)  # missing block => False
-        for dz in (-1, 0, 1):
-            for dy in (-1, 0, 1):
-                for dx in (-1, 0, 1):
-                    nb = (b[0] + dx, b[1] + dy, b[2] + dz)
-                    if nb not in F:
-                        continue
-                    src = F[nb]
-                    zs = slice(0, 1) if dz == 1 else (slice(vps - 1, vps) if dz == -1 else slice(0, vps))
-                    ys = slice(0, 1) if dy == 1 else (slice(vps - 1, vps) if dy == -1 else slice(0, vps))
-                    xs = slice(0, 1) if dx == 1 else (slice(vps - 1, vps) if dx == -1 else slice(0, vps))
-                    zd = slice(vps + 1, vps + 2) if dz == 1 else (slice(0, 1) if dz == -1 else slice(1, vps + 1))
-                    yd = slice(vps + 1, vps + 2) if dy == 1 else (slice(0, 1) if dy == -1 else slice(1, vps + 1))
-                    xd = slice(vps + 1, vps + 2) if dx == 1 else (slice(0, 1) if dx == -1 else slice(1, vps + 1))
-                    pad[zd, yd, xd] = src[zs, ys, xs]
-        ok = np.ones((vps, vps, vps), bool)
-        for (dx, dy, dz) in offs:
-            ok &= pad[1 + dz:1 + dz + vps, 1 + dy:1 + dy + vps, 1 + dx:1 + dx + vps]
-        new = free[b].reshape(vps, vps, vps) & ok
-        d["flags"][new.ravel()] |= 2
+        new = free[b] & neighbours_ok(padded_neighbourhood(F, b, vps, halo), vps, cfg["neighbor_connectivity"])
+        blocks[b]["flags"][new] |= 2
+
+
+def tracking_pass(cfg, blocks, stamp, halo=None):
+    """TrackingIntegrator::updateBlocks over a whole map (tracking_integrator.cpp:70-104): the per-voxel pass over EVERY block
+    (tracking_block: last_occupied, active, to_remove; the block's has_active_data, and tracking_updated cleared), then the
+    ever-free pass over the blocks that were tracking-updated.  blocks: {(bx, by, bz): dict(dist, last_obs, last_occ, flags,
+    block_flags)}; block_flags bit 2 = tracking_updated, bit 3 = has_active_data."""
+    updated = [b for b, d in blocks.items() if d["block_flags"] & 4]
+    for d in blocks.values():
+        act = tracking_block(cfg, d["dist"], d["last_obs"], d["last_occ"], d["flags"], stamp)
+        d["block_flags"] = (int(d["block_flags"]) & ~12) | (8 if act else 0)
+    ever_free_pass(cfg, blocks, updated, stamp, halo)
+
+
+def reset_inactive(blocks):
+    """TrackingIntegrator::resetInactive (tracking_integrator.cpp:106-131): drops the blocks without active data and those whose
+    voxels are all to_remove; returns their indices in (x, y, z) order"""
+    gone = sorted(b for b, d in blocks.items() if not (d["block_flags"] & 8) or bool(((d["flags"] & 4) > 0).all()))
+    for b in gone:
+        del blocks[b]
+    return gone
 
 
 # ---- FreeSpaceMotionDetector (free_space_motion_detector.cpp:73-399), second restatement: plain Python sets / dicts ----
