@@ -136,7 +136,7 @@ struct FuseArgs : FuseFrame {
   // tick form of k_fuse2 (khr_tick_integrate): one byte per wave item [slot * items-per-block + item], bit k = the item is on
   // camera k's TSDF list (k_tick_cull); the kernel clears the byte it has consumed.  nullptr: every frame, every item.
   uint8_t* item_mask;
-  // object-extraction form of k_fuse2 (khr_integrate_shared_batch): bit f of words [item * frame_words ..] = frame f may update a voxel of
+  // object-extraction form of k_fuse2 / k_fuse_obj (khr_integrate_shared_batch): bit f of words [item * frame_words ..] = frame f may update a voxel of
   // the item (k_multi_cull); nullptr: every frame
   const uint32_t* frame_bits;
   int frame_words;
@@ -1181,6 +1181,352 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList l
       *reinterpret_cast<float*>(dist_b + lin * 4u) = dreg[k];
       *reinterpret_cast<float*>(wgt_b + lin * 4u) = wreg[k];
       if (a.with_tracking) *reinterpret_cast<uint64_t*>(lobs_b + lin * 8u) = a.frames[lidx[k]].stamp;
+    }
+    if (lane == 0) {
+      if (touched) atomicOr(&a.blk_flags[slot], BLK_UPDATED | BLK_MESH_UPDATED | BLK_TRACKING_UPDATED | (wrote_neg ? BLK_HAS_NEG : 0u));
+      a.blk_band[slot * kBandSlots + (sbi & (kBandSlots - 1))] = static_cast<uint16_t>(min(cnt, 65535u));
+    }
+    item = item_next;
+    desc = d_next;
+  }
+  if (lane == 0) {
+    s_stat[wave][0] = n_upd;
+    s_stat[wave][1] = n_band;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t su = 0u, sb = 0u;
+#pragma unroll
+    for (int w = 0; w < WPW; ++w) {
+      su += s_stat[w][0];
+      sb += s_stat[w][1];
+    }
+    if (su | sb) {
+      a.wg_stats[2 * blockIdx.x] += su;
+      a.wg_stats[2 * blockIdx.x + 1] += sb;
+    }
+  }
+}
+
+// ====================================================================================================================
+// k_fuse_obj: the multi-frame update of the object extractor's mini-map (8^3 blocks, default integrator switches, binary
+// object layer: sem_mode == 1, K == KS == 2, no tracking stamps).  k_fuse2 keeps distance and weight of an item in registers
+// across the frames of a launch but sends every in-band voxel of every frame through an LDS record and fuseBandRecord:
+// colour, flag byte and both likelihoods are reloaded from the map, updated and stored again, and the next frame reloads what
+// was just stored -- a load -> store -> load chain through memory on 17 bytes that never leave the lane that owns them.
+// Here the WHOLE voxel state (distance, weight, colour, the two likelihoods, flag byte, label) is loaded with the item and
+// stored once after its last frame, only where a frame changed it; the band work is lane <-> voxel inside phase 2 (no record
+// list, no second phase, no wave fences), and a frame costs two dependent rounds of image gathers: the range samples, then
+// -- for the lanes inside the band -- dynamic-mask pixel, four colours and object pixel together.  The frame loop touches
+// no map memory at all.  Operations, operands and their order are those of k_fuse2 + fuseBandRecord: results are bit-identical.
+// ====================================================================================================================
+template <bool EXACT, int WPW, int MINW>
+__global__ __launch_bounds__(64 * WPW, MINW) void k_fuse_obj(FuseArgs a, FuseList list) {
+  constexpr int VPS = 8, ZSPLIT = 4;
+  constexpr int NV = VPS * VPS * VPS;
+  constexpr int SL = VPS * VPS;
+  constexpr int ZR = VPS / ZSPLIT;
+  static_assert(SL == 64 && ZR == 2, "one 8 x 8 slice per wave, two slices per item");
+  // a voxel's small state in one register: flag byte | label << 8 | what has to be stored after the last frame
+  constexpr uint32_t S_LABEL = 0x100u, S_TSDF = 0x200u, S_COLOR = 0x400u, S_SEM = 0x800u, S_FLAG = 0x1000u;
+  __shared__ uint32_t s_stat[WPW][2];
+  __shared__ uint32_t s_q;
+  const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  const int lane = static_cast<int>(threadIdx.x & 63);
+  const float den = a.trunc - a.dropoff_eps;
+  const float yden = rcpRefined(den);
+  const uint32_t nc0 = list.counts[0], nc1 = nc0 + list.counts[1], nc2 = nc1 + list.counts[2], n_items = nc2 + list.counts[3];
+  uint32_t n_upd = 0, n_band = 0;
+  if (a.gate != nullptr && *a.gate != 0u) return;
+  if (threadIdx.x == 0) s_q = 0u;
+  __syncthreads();
+  // list positions, queue and descriptors as in k_fuse2
+  const uint32_t first = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  auto pull = [&]() -> uint32_t {
+    uint32_t j = 0u;
+    if (lane == 0) j = atomicAdd(&s_q, 1u);
+    j = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(j)));
+    return first + gridDim.x * j;
+  };
+  const DescK la = (DescK)list.a, lb = (DescK)list.b;
+  auto descOf = [&](uint32_t i) -> uint4 {
+    u4v d;
+    if (i < nc0) d = la[i];
+    else if (i < nc1) d = la[list.cap - 1u - (i - nc0)];
+    else if (i < nc2) d = lb[i - nc1];
+    else d = lb[list.cap - 1u - (i - nc2)];
+    return make_uint4(d.x, d.y, d.z, d.w);
+  };
+  uint32_t item = pull();
+  uint4 desc = make_uint4(0u, 0u, 0u, 0u);
+  if (item < n_items) desc = descOf(item);
+  while (item < n_items) {
+    const uint32_t item_next = pull();
+    uint4 d_next = make_uint4(0u, 0u, 0u, 0u);
+    if (item_next < n_items) d_next = descOf(item_next);
+    const size_t slot = desc.x & 0xffffffu;
+    const int sbi = static_cast<int>(desc.x >> 24);
+    const int bx = static_cast<int>(desc.y), by = static_cast<int>(desc.z), bz = static_cast<int>(desc.w);
+    const int z0 = sbi * ZR;
+    const float ox = static_cast<float>(bx) * a.bs, oy = static_cast<float>(by) * a.bs, oz = static_cast<float>(bz) * a.bs;
+    const int ix = lane % VPS, iy = lane / VPS;
+    const float px = ox + (static_cast<float>(ix) + 0.5f) * a.vs;
+    const float py = oy + (static_cast<float>(iy) + 0.5f) * a.vs;
+    // block bases are wave-uniform, the voxel adds a 32-bit byte offset
+    char* const dist_b = reinterpret_cast<char*>(a.dist + slot * NV);
+    char* const wgt_b = reinterpret_cast<char*>(a.weight + slot * NV);
+    char* const color_b = reinterpret_cast<char*>(a.color + slot * NV);
+    char* const vfl_b = reinterpret_cast<char*>(a.vflags + slot * NV);
+    char* const lab_b = reinterpret_cast<char*>(a.sem_label + slot * NV);
+    char* const lik_b = reinterpret_cast<char*>(a.lik + slot * NV * 2u);  // voxel-major rows of KS = 2 floats
+    bool touched = false, wrote_neg = false;
+    uint32_t cnt = 0;
+    const int n_frames = a.n_frames;
+    // ---- the item's voxel state: one round of loads here, one round of stores behind the last frame ----
+    float dreg[ZR], wreg[ZR];
+    uint32_t creg[ZR], sreg[ZR];
+    float2 lreg[ZR];
+#pragma unroll
+    for (int k = 0; k < ZR; ++k) {
+      const uint32_t lin = static_cast<uint32_t>(lane + (z0 + k) * SL);
+      dreg[k] = *reinterpret_cast<const float*>(dist_b + lin * 4u);
+      wreg[k] = *reinterpret_cast<const float*>(wgt_b + lin * 4u);
+      creg[k] = *reinterpret_cast<const uint32_t*>(color_b + lin * 4u);
+      lreg[k] = *reinterpret_cast<const float2*>(lik_b + lin * 8u);  // (meaningless without VOX_SEM_VALID: replaced by zeros at first use)
+      sreg[k] = *reinterpret_cast<const uint8_t*>(vfl_b + lin);
+    }
+    uint32_t fbits = ~0u;
+    for (int fi = 0; fi < n_frames; ++fi) {
+      if (a.frame_bits != nullptr) {  // (the item's word of 32 frames through the scalar cache: written by the launch before this one)
+        const int gf = fi + a.frame_bit0;
+        if ((gf & 31) == 0 || fi == 0) {
+          const size_t wi = (slot * static_cast<size_t>(ZSPLIT) + static_cast<size_t>(sbi)) * static_cast<size_t>(a.frame_words) + static_cast<size_t>(gf >> 5);
+          fbits = *(const uint32_t __attribute__((address_space(4)))*)(a.frame_bits + wi);
+        }
+        if (((fbits >> (gf & 31)) & 1u) == 0u) {
+          cnt = 0;  // (what the frame would have left: no voxel of the item in its band)
+          continue;
+        }
+      }
+      // the frame's arguments: entry fi of a.frames, read through the scalar cache
+      FuseFrame F;
+      {
+        const uint32_t __attribute__((address_space(4)))* const w = (const uint32_t __attribute__((address_space(4)))*)(a.frames + fi);
+        uint32_t* const d = reinterpret_cast<uint32_t*>(&F);
+#pragma unroll
+        for (int i = 0; i < static_cast<int>(sizeof(FuseFrame) / 4); ++i) d[i] = w[i];
+      }
+      const float Wm1 = static_cast<float>(F.W - 1), Hm1 = static_cast<float>(F.H - 1);
+      const float fxfy = F.fx * F.fy;
+      const char* const range_b = reinterpret_cast<const char*>(F.range);
+      const uint32_t W4 = static_cast<uint32_t>(F.W) * 4u;
+      const bool has_color = F.has_color != 0, do_sem = F.do_sem != 0, use_mask = F.use_mask != 0;
+      float pxy[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) pxy[c] = F.R[3 * c] * px + F.R[3 * c + 1] * py;
+      // ---- phase 1: geometry of the item's voxels, first round of gathers (range samples) ----
+      float uu[ZR], vv[ZR], zz[ZR];
+      f2u ra[ZR], rb[ZR];
+      bool okk[ZR];
+#pragma unroll
+      for (int k = 0; k < ZR; ++k) {
+        const int iz = z0 + k;
+        const float pz = oz + (static_cast<float>(iz) + 0.5f) * a.vs;
+        float pc[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) pc[c] = (pxy[c] + F.R[3 * c + 2] * pz) + F.t[c];
+        bool ok = pc[2] > 0.f;
+        const float voxel_range = pc[2];
+        ok = ok && !(voxel_range < F.min_range || voxel_range > F.max_range);
+        const float yz = rcpRefined(pc[2]);
+        const float u = divExact(pc[0] * F.fx, pc[2], yz) + F.cx;
+        const float v = divExact(pc[1] * F.fy, pc[2], yz) + F.cy;
+        ok = ok && (fminf(fminf(u, v), fminf(Wm1 - u, Hm1 - v)) >= 0.f);
+        const float uc = ok ? u : 0.f, vc = ok ? v : 0.f;
+        const uint32_t u0 = static_cast<uint32_t>(static_cast<int>(uc)), v0 = static_cast<uint32_t>(static_cast<int>(vc));
+        const uint32_t v1 = min(v0 + 1u, static_cast<uint32_t>(F.H - 1));
+        const uint32_t o0 = v0 * W4 + u0 * 4u, o1 = v1 * W4 + u0 * 4u;
+        ra[k] = *reinterpret_cast<const f2u*>(range_b + o0);
+        rb[k] = *reinterpret_cast<const f2u*>(range_b + o1);
+        uu[k] = uc;
+        vv[k] = vc;
+        zz[k] = voxel_range;
+        okk[k] = ok;
+      }
+      // ---- phase 2a: signed distance and band decision of every voxel; second round of gathers, all of them together ----
+      float sdfv[ZR];
+      bool inb[ZR], nearv[ZR];
+      uint32_t c4[ZR][4], objv[ZR], dynv[ZR];
+#pragma unroll
+      for (int k = 0; k < ZR; ++k) {
+        bool ok = okk[k];
+        const float uc = uu[k], vc = vv[k], voxel_range = zz[k];
+        const uint32_t u0 = static_cast<uint32_t>(static_cast<int>(uc)), v0 = static_cast<uint32_t>(static_cast<int>(vc));
+        const uint32_t v1 = min(v0 + 1u, static_cast<uint32_t>(F.H - 1));
+        const float du = __builtin_amdgcn_fractf(uc), dv = __builtin_amdgcn_fractf(vc);
+        const uint32_t o0 = v0 * W4 + u0 * 4u, o1 = v1 * W4 + u0 * 4u;
+        const bool last_col = u0 >= static_cast<uint32_t>(F.W - 1);
+        const float r0 = ra[k].x, r1 = rb[k].x, r2 = last_col ? ra[k].x : ra[k].y, r3 = last_col ? rb[k].x : rb[k].y;
+        const float mn = fminf(fminf(r0, r1), fminf(r2, r3));
+        const float mx = fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
+        const bool use_nearest = mx - mn > a.adaptive_diff;
+        const bool hi_u = du >= 0.5f, hi_v = dv >= 0.5f;
+        const float r_near = hi_u ? (hi_v ? r3 : r2) : (hi_v ? r1 : r0);
+        const float omu = 1.f - du, omv = 1.f - dv;
+        const float w0 = omu * omv, w1 = omu * dv, w2 = du * omv, w3 = du * dv;
+        const float r_bil = ((w0 * r0 + w1 * r1) + w2 * r2) + w3 * r3;
+        const float dist_surface = use_nearest ? r_near : r_bil;
+        ok = ok && (dist_surface >= F.min_range) && !(dist_surface > F.max_range);
+        const float sdf = dist_surface - voxel_range;
+        ok = ok && !(sdf < -a.trunc);
+        const bool in_band = ok && (fabsf(sdf) < a.trunc);
+        okk[k] = ok;
+        inb[k] = in_band;
+        nearv[k] = use_nearest;
+        sdfv[k] = sdf;
+        dynv[k] = 0u;
+        objv[k] = 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) c4[k][j] = 0u;
+        if (in_band) {
+          if (use_mask) {  // the pixel the update kernels test: largest interpolation weight
+            int best;
+            if (use_nearest) {
+              best = (hi_u ? 2 : 0) + (hi_v ? 1 : 0);
+            } else {
+              best = 0;
+              float bw = w0;
+              if (w1 > bw) { bw = w1; best = 1; }
+              if (w2 > bw) { bw = w2; best = 2; }
+              if (w3 > bw) { bw = w3; best = 3; }
+            }
+            const uint32_t uo = ((best & 2) && !last_col) ? 4u : 0u;
+            const uint32_t bo = ((best & 1) ? o1 : o0) + uo;
+            dynv[k] = static_cast<uint32_t>(*reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(F.dyn) + bo));
+          }
+          if (has_color || do_sem) {  // the pixels of fuseBandRecord
+            int px4[4];
+            float bu, bv, w4[4];
+            interpPixels(uc, vc, F.W, F.H, px4, &bu, &bv);
+            const int best = interpWeights(bu, bv, use_nearest, w4);
+            if (has_color) {
+              const char* const rgba_b = reinterpret_cast<const char*>(F.rgba);
+#pragma unroll
+              for (int j = 0; j < 4; ++j) c4[k][j] = *reinterpret_cast<const uint32_t*>(rgba_b + static_cast<uint32_t>(px4[j]) * 4u);
+            }
+            if (do_sem)
+              objv[k] = static_cast<uint32_t>(*reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(F.obj) + static_cast<uint32_t>(px4[best]) * 4u));
+          }
+        }
+      }
+      // ---- phase 2b: dynamic mask, measurement weight, read-modify-write of the registers ----
+      cnt = 0;
+#pragma unroll
+      for (int k = 0; k < ZR; ++k) {
+        bool ok = okk[k], in_band = inb[k];
+        if (use_mask && in_band && dynv[k] != 0u) {
+          ok = false;
+          in_band = false;
+        }
+        if (__builtin_amdgcn_ballot_w64(ok) == 0ull) continue;
+        const float uc = uu[k], vc = vv[k], depth = zz[k], sdf = sdfv[k];
+        const float yz = rcpRefined(depth);
+        const float d_old = dreg[k], w_old = wreg[k];
+        float w;
+        if (EXACT) {
+          const float qd = divExact(a.vs, depth, yz);
+          w = fxfy * (qd * qd);
+          const float z2 = depth * depth;
+          w = divExact(w, z2, rcpRefined(z2));
+          if (sdf < -a.dropoff_eps) w = fmaxf(w * divExact(a.trunc + sdf, den, yden), 0.f);
+        } else {
+          const float qd = a.vs * yz;
+          w = fxfy * (qd * qd);
+          w = w * (yz * yz);
+          if (sdf < -a.dropoff_eps) w = fmaxf(w * ((a.trunc + sdf) * yden), 0.f);
+        }
+        ok = ok && (w > 0.f);
+        in_band = in_band && ok;
+        const float sdf_c = fmaxf(fminf(a.trunc, sdf), -a.trunc);
+        const float tot = w_old + w;
+        float d_new;
+        if (EXACT) {
+          d_new = divExact(d_old * w_old + sdf_c * w, tot, rcpRefined(tot));
+        } else {
+          d_new = __builtin_fmaf(d_old, w_old, sdf_c * w) * __builtin_amdgcn_rcpf(tot);
+        }
+        const float w_new = fminf(tot, a.max_weight);
+        if (ok) {
+          dreg[k] = d_new;
+          wreg[k] = w_new;
+          sreg[k] |= S_TSDF;
+        }
+        const unsigned long long m_ok = __builtin_amdgcn_ballot_w64(ok), m_band = __builtin_amdgcn_ballot_w64(in_band);
+        n_upd += static_cast<uint32_t>(__popcll(m_ok));
+        touched = touched || (m_ok != 0ull);
+        wrote_neg = wrote_neg || (__builtin_amdgcn_ballot_w64(ok && d_new < 0.f) != 0ull);
+        if (m_band == 0ull) continue;
+        n_band += static_cast<uint32_t>(__popcll(m_band));
+        cnt += static_cast<uint32_t>(__popcll(m_band));
+        if (!in_band) continue;
+        // colour / likelihoods / label of an in-band voxel: the body of fuseBandRecord on the lane's registers
+        const float wb = a.blend_pre ? w_old : w_new;  // the blend's voxel weight
+        if (has_color) {
+          int px4[4];
+          float bu, bv, w4[4];
+          interpPixels(uc, vc, F.W, F.H, px4, &bu, &bv);
+          interpWeights(bu, bv, nearv[k], w4);
+          float acc[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const uint32_t c = c4[k][j];
+            acc[0] = acc[0] + w4[j] * static_cast<float>(c & 0xffu);
+            acc[1] = acc[1] + w4[j] * static_cast<float>((c >> 8) & 0xffu);
+            acc[2] = acc[2] + w4[j] * static_cast<float>((c >> 16) & 0xffu);
+          }
+          const float ctot = wb + w;
+          const float ytot = rcpRefined(ctot);
+          const uint32_t co = creg[k];
+          uint32_t out = 0xff000000u;
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) {
+            const float cn = static_cast<float>(toU8(acc[ch]));
+            const float cv = static_cast<float>((co >> (8 * ch)) & 0xffu);
+            out |= static_cast<uint32_t>(toU8(divExact(cv * wb + cn * w, ctot, ytot))) << (8 * ch);
+          }
+          creg[k] = out;
+          sreg[k] |= S_COLOR;
+        }
+        if (do_sem) {
+          const int label = (static_cast<int32_t>(objv[k]) == F.object_id) ? 1 : 0;
+          const bool empty = !(sreg[k] & VOX_SEM_VALID);
+          float l0 = empty ? 0.f : lreg[k].x, l1 = empty ? 0.f : lreg[k].y;
+          l0 += (label == 0) ? 1.f : 0.f;
+          l1 += (label == 1) ? 1.f : 0.f;
+          lreg[k] = make_float2(l0, l1);
+          // arg-max: "k == 0 or strictly greater"
+          const uint32_t bestk = (l1 > l0) ? 1u : 0u;
+          uint32_t s = (sreg[k] & ~S_LABEL) | (bestk ? S_LABEL : 0u) | S_SEM;
+          if (empty) s |= VOX_SEM_VALID | S_FLAG;
+          sreg[k] = s;
+        }
+      }
+    }  // frames
+    // ---- the item's voxel state back to the map, where a frame changed it ----
+#pragma unroll
+    for (int k = 0; k < ZR; ++k) {
+      const uint32_t lin = static_cast<uint32_t>(lane + (z0 + k) * SL);
+      const uint32_t s = sreg[k];
+      if (s & S_TSDF) {
+        *reinterpret_cast<float*>(dist_b + lin * 4u) = dreg[k];
+        *reinterpret_cast<float*>(wgt_b + lin * 4u) = wreg[k];
+      }
+      if (s & S_COLOR) *reinterpret_cast<uint32_t*>(color_b + lin * 4u) = creg[k];
+      if (s & S_SEM) {
+        *reinterpret_cast<float2*>(lik_b + lin * 8u) = lreg[k];
+        *reinterpret_cast<uint32_t*>(lab_b + lin * 4u) = (s & S_LABEL) ? 1u : 0u;
+      }
+      if (s & S_FLAG) *reinterpret_cast<uint8_t*>(vfl_b + lin) = static_cast<uint8_t>(s & 0xffu);
     }
     if (lane == 0) {
       if (touched) atomicOr(&a.blk_flags[slot], BLK_UPDATED | BLK_MESH_UPDATED | BLK_TRACKING_UPDATED | (wrote_neg ? BLK_HAS_NEG : 0u));

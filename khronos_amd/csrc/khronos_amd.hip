@@ -1539,8 +1539,9 @@ static void fillFuseMap(khr_ctx* c, FuseArgs* a) {
   a->blend_pre = c->cfg.color_blend_weight != 0;
 }
 
-// All frames of a batch in ONE launch (k_fuse2): every wave item is walked through the frames in order.  Only for
-// `allocate = false` integrations of 8^3-voxel maps with the default integrator switches (the object extractor's mini-map);
+// The frames of a batch in one launch per kMultiChunk of them (k_fuse_obj for the extractor's binary object map, k_fuse2 otherwise):
+// every wave item is walked through the frames in order.  Only for `allocate = false` integrations of 8^3-voxel maps with the
+// default integrator switches (the object extractor's mini-map);
 // returns 1 when the batch was not taken (the caller then integrates frame by frame).
 static int integrateUpdateMulti(khr_ctx* c, khr_ctx* src, const int* src_slots, const int* object_ids, int n_frames, int use_mask) {
   if (c->cfg.voxels_per_side != 8 || n_frames < 2 || n_frames > kMaxMultiFrames) return 1;
@@ -1640,8 +1641,16 @@ static int integrateUpdateMulti(khr_ctx* c, khr_ctx* src, const int* src_slots, 
       KHR_LAUNCH_TIMED(0, kern, dim3(grid), dim3(64 * WPW), a, list);
     }
   };
-  if (exactArithmetic(c)) go(&k_fuse2<8, 4, true, true, WPW, 4>);
-  else go(&k_fuse2<8, 4, true, false, WPW, 4>);
+  // the extractor's configuration (binary object layer, no tracking stamps) has a kernel of its own that keeps the whole voxel
+  // state in registers across a launch's frames (k_fuse_obj); every other map keeps k_fuse2
+  const bool object_map = c->p.with_semantics && a.sem_mode == 1 && a.K == 2 && a.KS == 2 && !a.with_tracking;
+  if (object_map) {
+    if (exactArithmetic(c)) go(&k_fuse_obj<true, WPW, 4>);
+    else go(&k_fuse_obj<false, WPW, 4>);
+  } else {
+    if (exactArithmetic(c)) go(&k_fuse2<8, 4, true, true, WPW, 4>);
+    else go(&k_fuse2<8, 4, true, false, WPW, 4>);
+  }
   HIP_TRY(hipGetLastError());
   return KHR_OK;
 }
