@@ -15,13 +15,15 @@
 //    (u0, v1)-(u0+1, v1)); distance / weight of the z-step's 64 voxels are loaded with them -- for all 64 lanes since round 4:
 //    the kernel's vector-memory instruction stream is STATIC (see k_fuse), and a lane without an update writes back what it
 //    loaded, so that every distance / weight store is a whole 256-byte segment;
-//  * every DECISION (in front of the camera, in range, in the image, interpolation mode, sdf >= -truncation, inside the
-//    band, dynamic mask, weight > 0) is evaluated with the reference's operations in the reference's order; the
-//    divisions behind them share one refined reciprocal of the voxel depth and use the correctly rounded
-//    rcp-Newton-FMA sequence (what hipcc emits for `/`, minus the scaling steps that are unnecessary for depths in
-//    [min_range, max_range]).  EXACT = false relaxes only VALUES: measurement weight and running average use
-//    contracted FMAs and v_rcp_f32 (relative error ~1e-6, far inside the 1e-4 the path promises);
-//    EXACT = true keeps them bit-identical to the CPU oracle (khr_config.exact_arithmetic, golden tests);
+//  * every VALUE and every DECISION of a voxel's update (in front of the camera, in range, in the image, interpolation mode,
+//    sdf >= -truncation, inside the band, dynamic mask, weight > 0, running average, colour blend) is a function of
+//    khr_fuse_math.h, evaluated with the reference's operations in the reference's order; the divisions behind them share one
+//    refined reciprocal of the voxel depth and use the correctly rounded rcp-Newton-FMA sequence (what hipcc emits for `/`,
+//    minus the scaling steps that are unnecessary for depths in [min_range, max_range]).  The kernels of this file are
+//    SCHEDULES of those functions: what they keep in registers, when they gather, what they store where.  EXACT = false
+//    relaxes only VALUES: measurement weight and running average use contracted FMAs and v_rcp_f32 (relative error ~1e-6, far
+//    inside the 1e-4 the path promises); EXACT = true keeps them bit-identical to the CPU oracle (khr_config.exact_arithmetic,
+//    golden tests);
 //  * in-band voxels (a few per cent) are compacted with a ballot into a per-wave LDS list {voxel, mode, weights, u, v}
 //    and worked off DENSELY by the same wave in 64-record chunks: colour and label lookup lane <-> record, the K
 //    likelihoods as whole 128-byte rows moved by 8 lanes each (fuseBandRows; fuseBandRecord for small frames, the binary
@@ -32,55 +34,9 @@
 //    (hot-address atomics sustain only ~90 ops/us on gfx950); beginIntegrate / khr_get_stats fold them.
 #pragma once
 #include "khr_device.h"
+#include "khr_fuse_math.h"  // the arithmetic of one voxel's update: every value and decision below comes from there
 
 namespace khr {
-
-__device__ inline void interpPixels(float u, float v, int W, int H, int* px, float* du, float* dv) {
-  const int u0 = static_cast<int>(floorf(u)), v0 = static_cast<int>(floorf(v));
-  const int u1 = min(u0 + 1, W - 1), v1 = min(v0 + 1, H - 1);
-  *du = u - static_cast<float>(u0);
-  *dv = v - static_cast<float>(v0);
-  px[0] = v0 * W + u0;
-  px[1] = v1 * W + u0;
-  px[2] = v0 * W + u1;
-  px[3] = v1 * W + u1;
-}
-
-__device__ inline int interpWeights(float du, float dv, bool use_nearest, float* w4) {
-  int best;
-  if (use_nearest) {
-    const int nearest = (du >= 0.5f ? 2 : 0) + (dv >= 0.5f ? 1 : 0);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) w4[k] = (k == nearest) ? 1.f : 0.f;
-    best = nearest;
-  } else {
-    w4[0] = (1.f - du) * (1.f - dv);
-    w4[1] = (1.f - du) * dv;
-    w4[2] = du * (1.f - dv);
-    w4[3] = du * dv;
-    best = 0;
-#pragma unroll
-    for (int k = 1; k < 4; ++k)
-      if (w4[k] > w4[best]) best = k;
-  }
-  return best;
-}
-
-// y ~ 1 / b: v_rcp_f32 (1 ulp) + one Newton step.  For normal b this is the reciprocal hipcc's IEEE division uses.
-__device__ inline float rcpRefined(float b) {
-  const float y = __builtin_amdgcn_rcpf(b);
-  const float e = __builtin_fmaf(-b, y, 1.f);
-  return __builtin_fmaf(e, y, y);
-}
-// correctly rounded a / b from y = rcpRefined(b): the quotient / residual steps of hipcc's expansion of an IEEE f32
-// division (v_div_scale / v_div_fmas / v_div_fixup only matter for operands near the ends of the exponent range)
-__device__ inline float divExact(float a, float b, float y) {
-  float q = a * y;
-  float r = __builtin_fmaf(-b, q, a);
-  q = __builtin_fmaf(r, y, q);
-  r = __builtin_fmaf(-b, q, a);
-  return __builtin_fmaf(r, y, q);
-}
 
 typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));  // two adjacent pixels, 4-byte aligned
 
@@ -145,6 +101,83 @@ struct FuseArgs : FuseFrame {
 
 constexpr int kRecCap = 256;        // in-band records a wave collects before it works them off (one 4-z chunk of a patch)
 
+typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+typedef const u4v __attribute__((address_space(4))) * DescK;
+
+// ---- plumbing the update kernels share ---------------------------------------------------------------------------------
+// Workgroup b owns the list positions first, first + grid, ... and its waves take them from an LDS counter, whoever asks first.
+// XCD-aware share: workgroup b runs on XCD b % 8 (round-robin dispatch), so its first position is
+// (b % 8) * (grid / 8) + b / 8: list positions that are neighbours -- the items of one block, blocks that are neighbours
+// in the visible list -- land on workgroups of the SAME XCD and share its L2 for the image rows and voxel lines they
+// have in common.  (grid is a multiple of 8.)
+__device__ __forceinline__ uint32_t firstListPos() { return (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3); }
+// next position of the workgroup's share; wave-uniform result
+__device__ __forceinline__ uint32_t pullListPos(uint32_t* s_q, int lane, uint32_t first) {
+  uint32_t j = 0u;
+  if (lane == 0) j = atomicAdd(s_q, 1u);
+  j = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(j)));
+  return first + gridDim.x * j;
+}
+// descriptor of item i in deal order: class 0, 1, 2, 3 (FuseList; nc0 .. nc2 = the running class counts), through the scalar
+// cache (the list was written by the previous kernel; scalar loads return on lgkmcnt and are not ordered behind the wave's
+// vector stores).  k_fuse has a form of its own that keeps the list out of its scalar registers.
+__device__ __forceinline__ uint4 descOf(const FuseList& list, uint32_t nc0, uint32_t nc1, uint32_t nc2, uint32_t i) {
+  const DescK la = (DescK)list.a, lb = (DescK)list.b;
+  u4v d;
+  if (i < nc0) d = la[i];
+  else if (i < nc1) d = la[list.cap - 1u - (i - nc0)];
+  else if (i < nc2) d = lb[i - nc1];
+  else d = lb[list.cap - 1u - (i - nc2)];
+  return make_uint4(d.x, d.y, d.z, d.w);
+}
+// a frame's arguments from device memory (an entry of FuseArgs::frames), read through the scalar cache
+__device__ __forceinline__ FuseFrame loadFuseFrame(const FuseFrame* p) {
+  FuseFrame F;
+  const uint32_t __attribute__((address_space(4)))* const w = (const uint32_t __attribute__((address_space(4)))*)p;
+  uint32_t* const d = reinterpret_cast<uint32_t*>(&F);
+#pragma unroll
+  for (int i = 0; i < static_cast<int>(sizeof(FuseFrame) / 4); ++i) d[i] = w[i];
+  return F;
+}
+// can frame fi of the launch update a voxel of the item (FuseArgs::frame_bits, k_multi_cull)?  item = slot * items per block +
+// item of the block; fbits carries the item's current word of 32 frames (through the scalar cache: written by the launch before this one)
+__device__ __forceinline__ bool frameMayTouch(const FuseArgs& a, size_t item, int fi, uint32_t& fbits) {
+  if (a.frame_bits == nullptr) return true;
+  const int gf = fi + a.frame_bit0;
+  if ((gf & 31) == 0 || fi == 0)
+    fbits = *(const uint32_t __attribute__((address_space(4)))*)(a.frame_bits + item * static_cast<size_t>(a.frame_words) + static_cast<size_t>(gf >> 5));
+  return ((fbits >> (gf & 31)) & 1u) != 0u;
+}
+// what a multi-frame item leaves behind: its block's flags and its in-band count at the last frame (next update's cost class)
+__device__ __forceinline__ void multiItemEpilogue(const FuseArgs& a, size_t slot, int sbi, int lane, bool touched, bool wrote_neg, uint32_t cnt) {
+  if (lane == 0) {
+    if (touched) atomicOr(&a.blk_flags[slot], BLK_UPDATED | BLK_MESH_UPDATED | BLK_TRACKING_UPDATED | (wrote_neg ? BLK_HAS_NEG : 0u));
+    a.blk_band[slot * kBandSlots + (sbi & (kBandSlots - 1))] = static_cast<uint16_t>(min(cnt, 65535u));
+  }
+}
+// statistics: one read-modify-write per workgroup on its own slot (folded by beginIntegrate / khr_get_stats)
+template <int WPW>
+__device__ __forceinline__ void statsEpilogue(uint32_t (&s_stat)[WPW][2], int wave, int lane, uint32_t n_upd, uint32_t n_band, uint32_t* wg_stats) {
+  if (lane == 0) {
+    s_stat[wave][0] = n_upd;
+    s_stat[wave][1] = n_band;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t su = 0u, sb = 0u;
+#pragma unroll
+    for (int w = 0; w < WPW; ++w) {
+      su += s_stat[w][0];
+      sb += s_stat[w][1];
+    }
+    if (su | sb) {
+      wg_stats[2 * blockIdx.x] += su;
+      wg_stats[2 * blockIdx.x + 1] += sb;
+    }
+  }
+}
+
+
 // colour / label / likelihood update of one in-band voxel (the body of updateVoxel for |sdf| < truncation)
 // `a` points into the kernel-argument segment: the fields only this phase needs (image / layer pointers, label
 // parameters) are scalar loads issued here, instead of ~40 SGPRs kept alive through the voxel loop.
@@ -193,26 +226,7 @@ __device__ inline void fuseBandRecord(FuseArgsK ka, FuseFrameK kf, size_t slot, 
         l4[j] = j < K / 4 ? *reinterpret_cast<const float4*>(lik_b + lik_o + static_cast<uint32_t>(j) * 16u) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   }
-  if (has_color) {
-    float acc[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint32_t c = c4[k];
-      acc[0] = acc[0] + w4[k] * static_cast<float>(c & 0xffu);
-      acc[1] = acc[1] + w4[k] * static_cast<float>((c >> 8) & 0xffu);
-      acc[2] = acc[2] + w4[k] * static_cast<float>((c >> 16) & 0xffu);
-    }
-    const float tot = w_new + w;
-    const float ytot = rcpRefined(tot);
-    uint32_t out = 0xff000000u;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      const float cn = static_cast<float>(toU8(acc[ch]));
-      const float cv = static_cast<float>((co >> (8 * ch)) & 0xffu);
-      out |= static_cast<uint32_t>(toU8(divExact(cv * w_new + cn * w, tot, ytot))) << (8 * ch);
-    }
-    *reinterpret_cast<uint32_t*>(color_b + lin * 4u) = out;
-  }
+  if (has_color) *reinterpret_cast<uint32_t*>(color_b + lin * 4u) = blendColor(c4, w4, co, w_new, w);
   if (!do_sem || label < 0 || label >= K) return;
   const bool empty = !(fl & VOX_SEM_VALID);
   const float add_hit = (a.sem_mode == 1) ? 1.f : a.log_match, add_miss = (a.sem_mode == 1) ? 0.f : a.log_nomatch;
@@ -347,24 +361,7 @@ __device__ __forceinline__ void fuseBandRows(FuseArgsK ka, FuseFrameK kf, size_t
     // ---- part A: colour ----
     {
       const uint32_t c4[4] = {ca.x, cb.x, last_col ? ca.x : ca.y, last_col ? cb.x : cb.y};
-      float acc[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const uint32_t c = c4[k];
-        acc[0] = acc[0] + w4[k] * static_cast<float>(c & 0xffu);
-        acc[1] = acc[1] + w4[k] * static_cast<float>((c >> 8) & 0xffu);
-        acc[2] = acc[2] + w4[k] * static_cast<float>((c >> 16) & 0xffu);
-      }
-      const float tot = w_new + w;
-      const float ytot = rcpRefined(tot);
-      uint32_t out = 0xff000000u;
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        const float cn = static_cast<float>(toU8(acc[ch]));
-        const float cv = static_cast<float>((co >> (8 * ch)) & 0xffu);
-        out |= static_cast<uint32_t>(toU8(divExact(cv * w_new + cn * w, tot, ytot))) << (8 * ch);
-      }
-      *reinterpret_cast<uint32_t*>(color_b + lin * 4u) = out;
+      *reinterpret_cast<uint32_t*>(color_b + lin * 4u) = blendColor(c4, w4, co, w_new, w);
     }
     const bool upd = label >= 0 && label < K;
     const bool empty = !(fl & VOX_SEM_VALID);
@@ -491,9 +488,6 @@ struct FuseItem {
   f2u ra[ZR], rb[ZR];
 };
 
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-typedef const u4v __attribute__((address_space(4))) * DescK;
-
 template <int VPS, int ZSPLIT, bool DEFCFG, bool EXACT, int WPW>
 __global__ __launch_bounds__(64 * WPW) void k_fuse(FuseArgs a, FuseList list) {  // isa:kernel setup
   constexpr int NV = VPS * VPS * VPS;
@@ -527,19 +521,10 @@ __global__ __launch_bounds__(64 * WPW) void k_fuse(FuseArgs a, FuseList list) { 
   // the wave's sink line: target of the stores that must be issued but have nothing to write (see above)
   char* const sink_b = reinterpret_cast<char*>(a.sink) + (static_cast<size_t>(blockIdx.x) * WPW + static_cast<size_t>(wave)) * 256u;
   const bool trk = a.with_tracking != 0;
-  // next item of this workgroup's share (positions blockIdx.x, blockIdx.x + gridDim.x, ...: every workgroup gets the same
-  // mix of the cost classes), handed to whichever of its waves asks first; wave-uniform result
-  // XCD-aware share: workgroup b runs on XCD b % 8 (round-robin dispatch), so its first position is
-  // (b % 8) * (grid / 8) + b / 8: list positions that are neighbours -- the items of one block, blocks that are neighbours
-  // in the visible list -- land on workgroups of the SAME XCD and share its L2 for the image rows and voxel lines they
-  // have in common.  (grid is a multiple of 8.)
-  const uint32_t first = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  auto pull = [&]() -> uint32_t {
-    uint32_t j = 0u;
-    if (lane == 0) j = atomicAdd(&s_q, 1u);
-    j = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(j)));
-    return first + gridDim.x * j;
-  };
+  // next item of this workgroup's share (every workgroup gets the same mix of the cost classes), handed to whichever of its
+  // waves asks first
+  const uint32_t first = firstListPos();
+  auto pull = [&]() -> uint32_t { return pullListPos(&s_q, lane, first); };
   // descriptor of item i in deal order: class 0, 1, 2, 3 (FuseList), through the scalar cache (the list was written by the
   // previous kernel; scalar loads return on lgkmcnt and are not ordered behind the wave's vector stores)
   // The list's pointers and class boundaries are read from the kernel-argument segment / the counter words each time (scalar
@@ -588,37 +573,20 @@ __global__ __launch_bounds__(64 * WPW) void k_fuse(FuseArgs a, FuseList list) { 
     const char* const wgt_b = reinterpret_cast<const char*>(a.weight + it.slot * NV);
 #pragma unroll
     for (int k = 0; k < ZR; ++k) {
-      const int iz = it.z0 + k;  // isa:p1 voxel transform + range validity
+      const int iz = it.z0 + k;  // isa:p1 voxel transform + range validity + projection
       const uint32_t lin = static_cast<uint32_t>(it.lin_xy + iz * SL);
       const float pz = it.oz + (static_cast<float>(iz) + 0.5f) * a.vs;
-      float pc[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) pc[c] = (pxy[c] + a.R[3 * c + 2] * pz) + a.t[c];
-      bool ok = pc[2] > 0.f;
-      const float voxel_range = range_mode == 0 ? pc[2] : sqrtf((pc[0] * pc[0] + pc[1] * pc[1]) + pc[2] * pc[2]);
-      ok = ok && !(voxel_range < a.min_range || voxel_range > a.max_range);
-      const float yz = rcpRefined(pc[2]);  // isa:p1 projection (rcp + 2 exact divisions + in-image test)
-      const float u = divExact(pc[0] * a.fx, pc[2], yz) + a.cx;
-      const float v = divExact(pc[1] * a.fy, pc[2], yz) + a.cy;
-      // ceil(u) >= W || floor(u) < 0  <=>  u > W - 1 || u < 0  (W - 1 is an integer-valued float); x - y >= 0 <=> x >= y
-      // holds exactly in IEEE arithmetic, so the four tests are one min3 / min / compare
-      ok = ok && (fminf(fminf(u, v), fminf(Wm1 - u, Hm1 - v)) >= 0.f);
-      // invalid lanes gather pixel (0, 0); valid lanes have 0 <= u <= W - 1, so floor == truncation  // isa:p1 pixel addresses + range gathers
-      const float uc = ok ? u : 0.f, vc = ok ? v : 0.f;
-      const uint32_t u0 = static_cast<uint32_t>(static_cast<int>(uc)), v0 = static_cast<uint32_t>(static_cast<int>(vc));
-      const uint32_t v1 = min(v0 + 1u, static_cast<uint32_t>(a.H - 1));
-      // byte offsets of (u0, v0), (u0, v1).  24-bit multiplies (rows and row pitch are far below 2^24): the full 32-bit
-      // multiply-add only exists as v_mad_u64_u32, whose 64-bit addend drags an unrelated register into the instruction --
-      // when that register is the target of a load in flight, the compiler has to wait for it (seen in the ISA: vmcnt(2))
-      const uint32_t o0 = __umul24(v0, W4) + u0 * 4u, o1 = __umul24(v1, W4) + u0 * 4u;
-      it.ra[k] = *reinterpret_cast<const f2u*>(range_b + o0);  // (u0, v0), (u0 + 1, v0)
-      it.rb[k] = *reinterpret_cast<const f2u*>(range_b + o1);  // (u0, v1), (u0 + 1, v1)
+      const VoxelProj p = projectVoxel(a, pxy, pz, Wm1, Hm1, range_mode);  // (one isa phase: transform, validity, rcp + 2 exact divisions, in-image test)
+      // invalid lanes gather pixel (0, 0); the 24-bit multiplies of pairOffsets<true> keep a load in flight out of the address  // isa:p1 pixel addresses + range gathers
+      const PairOffsets o = pairOffsets<true>(p.uc, p.vc, a.H, W4);
+      it.ra[k] = *reinterpret_cast<const f2u*>(range_b + o.o0);  // (u0, v0), (u0 + 1, v0)
+      it.rb[k] = *reinterpret_cast<const f2u*>(range_b + o.o1);  // (u0, v1), (u0 + 1, v1)
       it.d[k] = *reinterpret_cast<const float*>(dist_b + lin * 4u);  // isa:p1 distance / weight loads + item state
       it.w[k] = *reinterpret_cast<const float*>(wgt_b + lin * 4u);
-      it.u[k] = uc;
-      it.v[k] = vc;
-      it.z[k] = ok ? voxel_range : -1.f;
-      it.yz[k] = yz;
+      it.u[k] = p.uc;
+      it.v[k] = p.vc;
+      it.z[k] = p.ok ? p.range : -1.f;
+      it.yz[k] = p.yz;
     }
   };
 
@@ -653,78 +621,25 @@ __global__ __launch_bounds__(64 * WPW) void k_fuse(FuseArgs a, FuseList list) { 
         const float pz = cur.oz + (static_cast<float>(iz) + 0.5f) * a.vs;
         depth = (cur.pxy2 + a.R[8] * pz) + a.t[2];
       }
-      const uint32_t u0 = static_cast<uint32_t>(static_cast<int>(uc)), v0 = static_cast<uint32_t>(static_cast<int>(vc));
-      const uint32_t v1 = min(v0 + 1u, static_cast<uint32_t>(a.H - 1));
-      const float du = __builtin_amdgcn_fractf(uc), dv = __builtin_amdgcn_fractf(vc);  // x - floor(x), exact for x >= 0
-      const uint32_t o0 = v0 * W4 + u0 * 4u, o1 = v1 * W4 + u0 * 4u;
-      // pixel order of the reference: (u0,v0) (u0,v1) (u1,v0) (u1,v1) with u1 = min(u0 + 1, W - 1)
-      const bool last_col = u0 >= static_cast<uint32_t>(a.W - 1);
-      const float r0 = cur.ra[k].x, r1 = cur.rb[k].x, r2 = last_col ? cur.ra[k].x : cur.ra[k].y, r3 = last_col ? cur.rb[k].x : cur.rb[k].y;
-      bool use_nearest = interp == 0;
-      if (interp == 2) {
-        const float mn = fminf(fminf(r0, r1), fminf(r2, r3));
-        const float mx = fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
-        use_nearest = use_nearest || (mx - mn > a.adaptive_diff);
-      }
-      const bool hi_u = du >= 0.5f, hi_v = dv >= 0.5f;
-      const float r_near = hi_u ? (hi_v ? r3 : r2) : (hi_v ? r1 : r0);
-      const float omu = 1.f - du, omv = 1.f - dv;
-      const float w0 = omu * omv, w1 = omu * dv, w2 = du * omv, w3 = du * dv;
-      const float r_bil = ((w0 * r0 + w1 * r1) + w2 * r2) + w3 * r3;
-      const float dist_surface = use_nearest ? r_near : r_bil;
-      ok = ok && (dist_surface >= a.min_range) && !(dist_surface > a.max_range);
-      const float sdf = dist_surface - voxel_range;
-      ok = ok && !(sdf < -a.trunc);
-      bool in_band = ok && (fabsf(sdf) < a.trunc);
+      const SurfaceSample s = sampleSurface(ok, cur.ra[k].x, cur.ra[k].y, cur.rb[k].x, cur.rb[k].y, uc, vc, a.W, interp, a.adaptive_diff, voxel_range,
+                                            a.min_range, a.max_range, a.trunc);
+      const float sdf = s.sdf;
+      const bool use_nearest = s.use_nearest;
+      ok = s.ok;
+      bool in_band = s.in_band;
       if (__builtin_expect(a.use_mask && __builtin_amdgcn_ballot_w64(in_band) != 0ull, 0)) {  // isa:p2 dynamic mask
-        // interpolateID(mask): pixel of the largest weight (first maximum)
-        int best;
-        if (use_nearest) {
-          best = (hi_u ? 2 : 0) + (hi_v ? 1 : 0);
-        } else {
-          best = 0;
-          float bw = w0;
-          if (w1 > bw) { bw = w1; best = 1; }
-          if (w2 > bw) { bw = w2; best = 2; }
-          if (w3 > bw) { bw = w3; best = 3; }
-        }
-        const uint32_t uo = ((best & 2) && !last_col) ? 4u : 0u;
-        const uint32_t bo = ((best & 1) ? o1 : o0) + uo;
-        if (in_band && *reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(a.dyn) + bo) != 0) {
+        const PairOffsets o = pairOffsets<false>(uc, vc, a.H, W4);
+        if (in_band && *reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(a.dyn) + maskPixelOffset(s, o.o0, o.o1)) != 0) {
           ok = false;
           in_band = false;
         }
       }
       if (__builtin_amdgcn_ballot_w64(ok) != 0ull) {
-      // measurement weight (computeWeight): fx fy vs^2 / z^4, linear drop-off behind the surface  // isa:p2 measurement weight
-      float w;
-      if (EXACT) {
-        const float qd = divExact(a.vs, depth, yz);
-        w = fxfy * (qd * qd);
-        if (!const_weight) {
-          const float z2 = depth * depth;
-          w = divExact(w, z2, rcpRefined(z2));
-        }
-        if (use_dropoff && sdf < -a.dropoff_eps) w = fmaxf(w * divExact(a.trunc + sdf, den, yden), 0.f);
-      } else {
-        const float qd = a.vs * yz;
-        w = fxfy * (qd * qd);
-        if (!const_weight) w = w * (yz * yz);
-        if (use_dropoff && sdf < -a.dropoff_eps) w = fmaxf(w * ((a.trunc + sdf) * yden), 0.f);
-      }
-      // w > 0 is the same decision in both modes: the factors are positive normal numbers far from underflow, so
-      // the product is zero exactly when trunc + sdf == 0
+      const float w = measurementWeight<EXACT>(a.vs, fxfy, depth, yz, sdf, a.trunc, a.dropoff_eps, den, yden, use_dropoff, const_weight);  // isa:p2 measurement weight
       ok = ok && (w > 0.f);
       in_band = in_band && ok;
-      const float sdf_c = fmaxf(fminf(a.trunc, sdf), -a.trunc);  // isa:p2 running average
-      const float tot = w_old + w;
-      float d_new;
-      if (EXACT) {
-        d_new = divExact(d_old * w_old + sdf_c * w, tot, rcpRefined(tot));
-      } else {
-        d_new = __builtin_fmaf(d_old, w_old, sdf_c * w) * __builtin_amdgcn_rcpf(tot);
-      }
-      const float w_new = fminf(tot, a.max_weight);
+      const VoxelAverage avg = runningAverage<EXACT>(d_old, w_old, sdf, w, a.trunc, a.max_weight);  // isa:p2 running average
+      const float d_new = avg.d_new, w_new = avg.w_new;
       if (ok) {
         d_out = d_new;
         w_out = w_new;
@@ -847,24 +762,7 @@ __global__ __launch_bounds__(64 * WPW) void k_fuse(FuseArgs a, FuseList list) { 
       }
     }
   }
-  // statistics: one read-modify-write per workgroup on its own slot (folded by beginIntegrate / khr_get_stats)  // isa:kernel epilogue
-  if (lane == 0) {
-    s_stat[wave][0] = n_upd;
-    s_stat[wave][1] = n_band;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t su = 0u, sb2 = 0u;
-#pragma unroll
-    for (int w = 0; w < WPW; ++w) {
-      su += s_stat[w][0];
-      sb2 += s_stat[w][1];
-    }
-    if (su | sb2) {
-      a.wg_stats[2 * blockIdx.x] += su;
-      a.wg_stats[2 * blockIdx.x + 1] += sb2;
-    }
-  }
+  statsEpilogue<WPW>(s_stat, wave, lane, n_upd, n_band, a.wg_stats);  // isa:kernel epilogue
 }
 
 // fold k_fuse's item records into the block flags (one thread per pool slot): a block some item of which was touched becomes
@@ -894,7 +792,9 @@ __global__ __launch_bounds__(256) void k_fuse_fold(uint32_t* __restrict__ blk_fl
 // the wave takes its next item -- the updates of a voxel by consecutive frames are order dependent, those of different items
 // are not.  One launch then replaces one launch per frame (MeshObjectExtractor re-integrates every buffered frame of a track,
 // mesh_object_extractor.cpp:239-243: 27 launches of ~18 us for a few hundred blocks each).
-template <int VPS, int ZSPLIT, bool DEFCFG, bool EXACT, int WPW, int MINW>
+// The reference's default switches only (z-depth range, adaptive interpolation, weight drop-off, no constant weight): its
+// callers (integrateUpdateMulti, tickUnion) take it for those and integrate frame by frame with k_fuse otherwise.
+template <int VPS, int ZSPLIT, bool EXACT, int WPW, int MINW>
 __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList list) {
   constexpr int NV = VPS * VPS * VPS;
   constexpr int SL = VPS * VPS;
@@ -907,10 +807,6 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList l
   __shared__ uint32_t s_q;
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
   const int lane = static_cast<int>(threadIdx.x & 63);
-  const int range_mode = DEFCFG ? 0 : a.range_mode;
-  const int interp = DEFCFG ? 2 : a.interp;
-  const bool use_dropoff = DEFCFG ? true : (a.use_dropoff != 0);
-  const bool const_weight = DEFCFG ? false : (a.const_weight != 0);
   const float den = a.trunc - a.dropoff_eps;
   const float yden = rcpRefined(den);
   const uint32_t nc0 = list.counts[0], nc1 = nc0 + list.counts[1], nc2 = nc1 + list.counts[2], n_items = nc2 + list.counts[3];
@@ -918,34 +814,17 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList l
   if (a.gate != nullptr && *a.gate != 0u) return;  // speculative launch, and the frame has motion seeds
   if (threadIdx.x == 0) s_q = 0u;
   __syncthreads();
-  // workgroup b owns the list positions first, first + grid, ... (XCD-aware share as k_fuse); its waves take them from an LDS
-  // counter.  (Tried here and dropped, with numbers in DESIGN.md section 6: queue heads in global memory with work
+  // (Tried here and dropped, with numbers in DESIGN.md section 6: queue heads in global memory with work
   // stealing between workgroups -- 20 k returning global atomics per launch cost 30 us even on 256 different words --
   // and an oversubscribed, non-persistent grid -- a second round of workgroups costs ~15 us of dispatch.)
-  const uint32_t first = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  auto pull = [&]() -> uint32_t {
-    uint32_t j = 0u;
-    if (lane == 0) j = atomicAdd(&s_q, 1u);
-    j = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(j)));
-    return first + gridDim.x * j;
-  };
-  // descriptor of item i in deal order, through the scalar cache (the list was written by the previous kernel)
-  const DescK la = (DescK)list.a, lb = (DescK)list.b;
-  auto descOf = [&](uint32_t i) -> uint4 {
-    u4v d;
-    if (i < nc0) d = la[i];
-    else if (i < nc1) d = la[list.cap - 1u - (i - nc0)];
-    else if (i < nc2) d = lb[i - nc1];
-    else d = lb[list.cap - 1u - (i - nc2)];
-    return make_uint4(d.x, d.y, d.z, d.w);
-  };
-  uint32_t item = pull();
+  const uint32_t first = firstListPos();
+  uint32_t item = pullListPos(&s_q, lane, first);
   uint4 desc = make_uint4(0u, 0u, 0u, 0u);
-  if (item < n_items) desc = descOf(item);
+  if (item < n_items) desc = descOf(list, nc0, nc1, nc2, item);
   while (item < n_items) {
-    const uint32_t item_next = pull();
+    const uint32_t item_next = pullListPos(&s_q, lane, first);
     uint4 d_next = make_uint4(0u, 0u, 0u, 0u);
-    if (item_next < n_items) d_next = descOf(item_next);
+    if (item_next < n_items) d_next = descOf(list, nc0, nc1, nc2, item_next);
     // ---- phase 1: geometry of the item's ZR voxels per lane; all their loads issued ----
     const size_t slot = desc.x & 0xffffffu;
     const int sbi = static_cast<int>(desc.x >> 24);
@@ -960,6 +839,7 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList l
     char* const dist_b = reinterpret_cast<char*>(a.dist + slot * NV);
     char* const wgt_b = reinterpret_cast<char*>(a.weight + slot * NV);
     char* const lobs_b = reinterpret_cast<char*>(a.last_obs + slot * NV);
+    const size_t mi = slot * static_cast<size_t>(PATCHES * ZSPLIT) + static_cast<size_t>(sbi);  // the item's index in the per-item arrays
     bool touched = false, wrote_neg = false;
     uint32_t cnt = 0;
     const int n_frames = a.n_frames;
@@ -977,7 +857,6 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList l
     }
     uint32_t frame_mask = ~0u;
     if (a.item_mask != nullptr) {  // which cameras listed the item (their culling is conservative: the others cannot touch it)
-      const size_t mi = slot * static_cast<size_t>(PATCHES * ZSPLIT) + static_cast<size_t>(sbi);
       const uint32_t word = *(const uint32_t __attribute__((address_space(4)))*)(a.item_mask + (mi & ~static_cast<size_t>(3)));
       frame_mask = (word >> (8u * static_cast<uint32_t>(mi & 3))) & 0xffu;
       // the byte is cleared only once the scalar load has RETURNED (scalar loads and vector stores reach the L2 on
@@ -988,25 +867,11 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList l
     uint32_t fbits = ~0u;
     for (int fi = 0; fi < n_frames; ++fi) {
     if (((frame_mask >> fi) & 1u) == 0u) continue;
-    if (a.frame_bits != nullptr) {  // (the item's word of 32 frames through the scalar cache: written by the launch before this one)
-      const int gf = fi + a.frame_bit0;
-      if ((gf & 31) == 0 || fi == 0) {
-        const size_t wi = (slot * static_cast<size_t>(PATCHES * ZSPLIT) + static_cast<size_t>(sbi)) * static_cast<size_t>(a.frame_words) + static_cast<size_t>(gf >> 5);
-        fbits = *(const uint32_t __attribute__((address_space(4)))*)(a.frame_bits + wi);
-      }
-      if (((fbits >> (gf & 31)) & 1u) == 0u) {
-        cnt = 0;  // (what the frame would have left: no voxel of the item in its band)
-        continue;
-      }
+    if (!frameMayTouch(a, mi, fi, fbits)) {
+      cnt = 0;  // (what the frame would have left: no voxel of the item in its band)
+      continue;
     }
-    // the frame's arguments: entry fi of a.frames, read through the scalar cache
-    FuseFrame F;
-    {
-      const uint32_t __attribute__((address_space(4)))* const w = (const uint32_t __attribute__((address_space(4)))*)(a.frames + fi);
-      uint32_t* const d = reinterpret_cast<uint32_t*>(&F);
-#pragma unroll
-      for (int i = 0; i < static_cast<int>(sizeof(FuseFrame) / 4); ++i) d[i] = w[i];
-    }
+    const FuseFrame F = loadFuseFrame(a.frames + fi);
     const float Wm1 = static_cast<float>(F.W - 1), Hm1 = static_cast<float>(F.H - 1);
     const float fxfy = F.fx * F.fy;
     const char* const range_b = reinterpret_cast<const char*>(F.range);
@@ -1014,137 +879,61 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList l
     float pxy[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) pxy[c] = F.R[3 * c] * px + F.R[3 * c + 1] * py;
-    float uu[ZR], vv[ZR], zz[ZR], yzz[ZR], dd[ZR], ww[ZR];
+    VoxelProj pr[ZR];
+    float dd[ZR], ww[ZR];
     f2u ra[ZR], rb[ZR];
-    bool okk[ZR];
 #pragma unroll
     for (int k = 0; k < ZR; ++k) {
-      const int iz = z0 + k;
-      const float pz = oz + (static_cast<float>(iz) + 0.5f) * a.vs;
-      float pc[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) pc[c] = (pxy[c] + F.R[3 * c + 2] * pz) + F.t[c];
-      bool ok = pc[2] > 0.f;
-      const float voxel_range = range_mode == 0 ? pc[2] : sqrtf((pc[0] * pc[0] + pc[1] * pc[1]) + pc[2] * pc[2]);
-      ok = ok && !(voxel_range < F.min_range || voxel_range > F.max_range);
-      const float yz = rcpRefined(pc[2]);
-      const float u = divExact(pc[0] * F.fx, pc[2], yz) + F.cx;
-      const float v = divExact(pc[1] * F.fy, pc[2], yz) + F.cy;
-      ok = ok && (fminf(fminf(u, v), fminf(Wm1 - u, Hm1 - v)) >= 0.f);
-      const float uc = ok ? u : 0.f, vc = ok ? v : 0.f;
-      const uint32_t u0 = static_cast<uint32_t>(static_cast<int>(uc)), v0 = static_cast<uint32_t>(static_cast<int>(vc));
-      const uint32_t v1 = min(v0 + 1u, static_cast<uint32_t>(F.H - 1));
-      const uint32_t o0 = v0 * W4 + u0 * 4u, o1 = v1 * W4 + u0 * 4u;
-      ra[k] = *reinterpret_cast<const f2u*>(range_b + o0);
-      rb[k] = *reinterpret_cast<const f2u*>(range_b + o1);
+      const float pz = oz + (static_cast<float>(z0 + k) + 0.5f) * a.vs;
+      pr[k] = projectVoxel(F, pxy, pz, Wm1, Hm1, 0);
+      const PairOffsets o = pairOffsets<false>(pr[k].uc, pr[k].vc, F.H, W4);
+      ra[k] = *reinterpret_cast<const f2u*>(range_b + o.o0);
+      rb[k] = *reinterpret_cast<const f2u*>(range_b + o.o1);
       dd[k] = dreg[k];
       ww[k] = wreg[k];
-      uu[k] = uc;
-      vv[k] = vc;
-      zz[k] = voxel_range;
-      yzz[k] = yz;
-      okk[k] = ok;
     }
     // ---- phase 2: measurement, decisions, read-modify-write ----
     cnt = 0;
 #pragma unroll
     for (int k = 0; k < ZR; ++k) {
-      bool ok = okk[k];
+      bool ok = pr[k].ok;
       if (__builtin_amdgcn_ballot_w64(ok) == 0ull) continue;
-      const int iz = z0 + k;
-      const uint32_t lin = static_cast<uint32_t>(lin_xy + iz * SL);
-      const float uc = uu[k], vc = vv[k], voxel_range = zz[k], yz = yzz[k];
-      float depth = voxel_range;
-      if (range_mode != 0) {
-        const float pz = oz + (static_cast<float>(iz) + 0.5f) * a.vs;
-        depth = (pxy[2] + F.R[8] * pz) + F.t[2];
-      }
-      const uint32_t u0 = static_cast<uint32_t>(static_cast<int>(uc)), v0 = static_cast<uint32_t>(static_cast<int>(vc));
-      const uint32_t v1 = min(v0 + 1u, static_cast<uint32_t>(F.H - 1));
-      const float du = __builtin_amdgcn_fractf(uc), dv = __builtin_amdgcn_fractf(vc);
-      const uint32_t o0 = v0 * W4 + u0 * 4u, o1 = v1 * W4 + u0 * 4u;
+      const uint32_t lin = static_cast<uint32_t>(lin_xy + (z0 + k) * SL);
+      const float uc = pr[k].uc, vc = pr[k].vc, depth = pr[k].range;
       const float d_old = dd[k], w_old = ww[k];
-      const bool last_col = u0 >= static_cast<uint32_t>(F.W - 1);
-      const float r0 = ra[k].x, r1 = rb[k].x, r2 = last_col ? ra[k].x : ra[k].y, r3 = last_col ? rb[k].x : rb[k].y;
-      bool use_nearest = interp == 0;
-      if (interp == 2) {
-        const float mn = fminf(fminf(r0, r1), fminf(r2, r3));
-        const float mx = fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
-        use_nearest = use_nearest || (mx - mn > a.adaptive_diff);
-      }
-      const bool hi_u = du >= 0.5f, hi_v = dv >= 0.5f;
-      const float r_near = hi_u ? (hi_v ? r3 : r2) : (hi_v ? r1 : r0);
-      const float omu = 1.f - du, omv = 1.f - dv;
-      const float w0 = omu * omv, w1 = omu * dv, w2 = du * omv, w3 = du * dv;
-      const float r_bil = ((w0 * r0 + w1 * r1) + w2 * r2) + w3 * r3;
-      const float dist_surface = use_nearest ? r_near : r_bil;
-      ok = ok && (dist_surface >= F.min_range) && !(dist_surface > F.max_range);
-      const float sdf = dist_surface - voxel_range;
-      ok = ok && !(sdf < -a.trunc);
-      bool in_band = ok && (fabsf(sdf) < a.trunc);
+      const SurfaceSample s = sampleSurface(ok, ra[k].x, ra[k].y, rb[k].x, rb[k].y, uc, vc, F.W, 2, a.adaptive_diff, depth, F.min_range, F.max_range, a.trunc);
+      ok = s.ok;
+      bool in_band = s.in_band;
       if (__builtin_expect(F.use_mask && __builtin_amdgcn_ballot_w64(in_band) != 0ull, 0)) {
-        int best;
-        if (use_nearest) {
-          best = (hi_u ? 2 : 0) + (hi_v ? 1 : 0);
-        } else {
-          best = 0;
-          float bw = w0;
-          if (w1 > bw) { bw = w1; best = 1; }
-          if (w2 > bw) { bw = w2; best = 2; }
-          if (w3 > bw) { bw = w3; best = 3; }
-        }
-        const uint32_t uo = ((best & 2) && !last_col) ? 4u : 0u;
-        const uint32_t bo = ((best & 1) ? o1 : o0) + uo;
-        if (in_band && *reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(F.dyn) + bo) != 0) {
+        const PairOffsets o = pairOffsets<false>(uc, vc, F.H, W4);
+        if (in_band && *reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(F.dyn) + maskPixelOffset(s, o.o0, o.o1)) != 0) {
           ok = false;
           in_band = false;
         }
       }
       if (__builtin_amdgcn_ballot_w64(ok) == 0ull) continue;
-      float w;
-      if (EXACT) {
-        const float qd = divExact(a.vs, depth, yz);
-        w = fxfy * (qd * qd);
-        if (!const_weight) {
-          const float z2 = depth * depth;
-          w = divExact(w, z2, rcpRefined(z2));
-        }
-        if (use_dropoff && sdf < -a.dropoff_eps) w = fmaxf(w * divExact(a.trunc + sdf, den, yden), 0.f);
-      } else {
-        const float qd = a.vs * yz;
-        w = fxfy * (qd * qd);
-        if (!const_weight) w = w * (yz * yz);
-        if (use_dropoff && sdf < -a.dropoff_eps) w = fmaxf(w * ((a.trunc + sdf) * yden), 0.f);
-      }
+      const float w = measurementWeight<EXACT>(a.vs, fxfy, depth, pr[k].yz, s.sdf, a.trunc, a.dropoff_eps, den, yden, true, false);
       ok = ok && (w > 0.f);
       in_band = in_band && ok;
-      const float sdf_c = fmaxf(fminf(a.trunc, sdf), -a.trunc);
-      const float tot = w_old + w;
-      float d_new;
-      if (EXACT) {
-        d_new = divExact(d_old * w_old + sdf_c * w, tot, rcpRefined(tot));
-      } else {
-        d_new = __builtin_fmaf(d_old, w_old, sdf_c * w) * __builtin_amdgcn_rcpf(tot);
-      }
-      const float w_new = fminf(tot, a.max_weight);
+      const VoxelAverage avg = runningAverage<EXACT>(d_old, w_old, s.sdf, w, a.trunc, a.max_weight);
       if (ok) {
-        dreg[k] = d_new;
-        wreg[k] = w_new;
+        dreg[k] = avg.d_new;
+        wreg[k] = avg.w_new;
         lidx[k] = fi;
       }
       const unsigned long long m_ok = __builtin_amdgcn_ballot_w64(ok), m_band = __builtin_amdgcn_ballot_w64(in_band);
       n_upd += static_cast<uint32_t>(__popcll(m_ok));
       touched = touched || (m_ok != 0ull);
-      wrote_neg = wrote_neg || (__builtin_amdgcn_ballot_w64(ok && d_new < 0.f) != 0ull);
+      wrote_neg = wrote_neg || (__builtin_amdgcn_ballot_w64(ok && avg.d_new < 0.f) != 0ull);
       if (m_band) {
         n_band += static_cast<uint32_t>(__popcll(m_band));
         if (in_band) {
           const uint32_t pos = cnt + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m_band >> 32),
                                                               __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m_band), 0u));
           uint32_t* const rec = &s_rec[wave][0][pos];
-          rec[0] = lin | (use_nearest ? 0x10000u : 0u);
+          rec[0] = lin | (s.use_nearest ? 0x10000u : 0u);
           rec[CAP] = __float_as_uint(w);
-          rec[2 * CAP] = __float_as_uint(a.blend_pre ? w_old : w_new);
+          rec[2 * CAP] = __float_as_uint(a.blend_pre ? w_old : avg.w_new);
           rec[3 * CAP] = __float_as_uint(uc);
           rec[4 * CAP] = __float_as_uint(vc);
         }
@@ -1182,30 +971,11 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList l
       *reinterpret_cast<float*>(wgt_b + lin * 4u) = wreg[k];
       if (a.with_tracking) *reinterpret_cast<uint64_t*>(lobs_b + lin * 8u) = a.frames[lidx[k]].stamp;
     }
-    if (lane == 0) {
-      if (touched) atomicOr(&a.blk_flags[slot], BLK_UPDATED | BLK_MESH_UPDATED | BLK_TRACKING_UPDATED | (wrote_neg ? BLK_HAS_NEG : 0u));
-      a.blk_band[slot * kBandSlots + (sbi & (kBandSlots - 1))] = static_cast<uint16_t>(min(cnt, 65535u));
-    }
+    multiItemEpilogue(a, slot, sbi, lane, touched, wrote_neg, cnt);
     item = item_next;
     desc = d_next;
   }
-  if (lane == 0) {
-    s_stat[wave][0] = n_upd;
-    s_stat[wave][1] = n_band;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t su = 0u, sb = 0u;
-#pragma unroll
-    for (int w = 0; w < WPW; ++w) {
-      su += s_stat[w][0];
-      sb += s_stat[w][1];
-    }
-    if (su | sb) {
-      a.wg_stats[2 * blockIdx.x] += su;
-      a.wg_stats[2 * blockIdx.x + 1] += sb;
-    }
-  }
+  statsEpilogue<WPW>(s_stat, wave, lane, n_upd, n_band, a.wg_stats);
 }
 
 // ====================================================================================================================
@@ -1218,7 +988,8 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList l
 // stored once after its last frame, only where a frame changed it; the band work is lane <-> voxel inside phase 2 (no record
 // list, no second phase, no wave fences), and a frame costs two dependent rounds of image gathers: the range samples, then
 // -- for the lanes inside the band -- dynamic-mask pixel, four colours and object pixel together.  The frame loop touches
-// no map memory at all.  Operations, operands and their order are those of k_fuse2 + fuseBandRecord: results are bit-identical.
+// no map memory at all.  The values and decisions are the functions of khr_fuse_math.h that k_fuse2 and fuseBandRecord call;
+// what is written out here is the binary layer's two-entry likelihood row (fuseBandRecord's row loop for K = 2, sem_mode 1).
 // ====================================================================================================================
 template <bool EXACT, int WPW, int MINW>
 __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse_obj(FuseArgs a, FuseList list) {
@@ -1240,30 +1011,14 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse_obj(FuseArgs a, FuseLis
   if (a.gate != nullptr && *a.gate != 0u) return;
   if (threadIdx.x == 0) s_q = 0u;
   __syncthreads();
-  // list positions, queue and descriptors as in k_fuse2
-  const uint32_t first = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  auto pull = [&]() -> uint32_t {
-    uint32_t j = 0u;
-    if (lane == 0) j = atomicAdd(&s_q, 1u);
-    j = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(j)));
-    return first + gridDim.x * j;
-  };
-  const DescK la = (DescK)list.a, lb = (DescK)list.b;
-  auto descOf = [&](uint32_t i) -> uint4 {
-    u4v d;
-    if (i < nc0) d = la[i];
-    else if (i < nc1) d = la[list.cap - 1u - (i - nc0)];
-    else if (i < nc2) d = lb[i - nc1];
-    else d = lb[list.cap - 1u - (i - nc2)];
-    return make_uint4(d.x, d.y, d.z, d.w);
-  };
-  uint32_t item = pull();
+  const uint32_t first = firstListPos();
+  uint32_t item = pullListPos(&s_q, lane, first);
   uint4 desc = make_uint4(0u, 0u, 0u, 0u);
-  if (item < n_items) desc = descOf(item);
+  if (item < n_items) desc = descOf(list, nc0, nc1, nc2, item);
   while (item < n_items) {
-    const uint32_t item_next = pull();
+    const uint32_t item_next = pullListPos(&s_q, lane, first);
     uint4 d_next = make_uint4(0u, 0u, 0u, 0u);
-    if (item_next < n_items) d_next = descOf(item_next);
+    if (item_next < n_items) d_next = descOf(list, nc0, nc1, nc2, item_next);
     const size_t slot = desc.x & 0xffffffu;
     const int sbi = static_cast<int>(desc.x >> 24);
     const int bx = static_cast<int>(desc.y), by = static_cast<int>(desc.z), bz = static_cast<int>(desc.w);
@@ -1297,25 +1052,11 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse_obj(FuseArgs a, FuseLis
     }
     uint32_t fbits = ~0u;
     for (int fi = 0; fi < n_frames; ++fi) {
-      if (a.frame_bits != nullptr) {  // (the item's word of 32 frames through the scalar cache: written by the launch before this one)
-        const int gf = fi + a.frame_bit0;
-        if ((gf & 31) == 0 || fi == 0) {
-          const size_t wi = (slot * static_cast<size_t>(ZSPLIT) + static_cast<size_t>(sbi)) * static_cast<size_t>(a.frame_words) + static_cast<size_t>(gf >> 5);
-          fbits = *(const uint32_t __attribute__((address_space(4)))*)(a.frame_bits + wi);
-        }
-        if (((fbits >> (gf & 31)) & 1u) == 0u) {
-          cnt = 0;  // (what the frame would have left: no voxel of the item in its band)
-          continue;
-        }
+      if (!frameMayTouch(a, slot * static_cast<size_t>(ZSPLIT) + static_cast<size_t>(sbi), fi, fbits)) {
+        cnt = 0;  // (what the frame would have left: no voxel of the item in its band)
+        continue;
       }
-      // the frame's arguments: entry fi of a.frames, read through the scalar cache
-      FuseFrame F;
-      {
-        const uint32_t __attribute__((address_space(4)))* const w = (const uint32_t __attribute__((address_space(4)))*)(a.frames + fi);
-        uint32_t* const d = reinterpret_cast<uint32_t*>(&F);
-#pragma unroll
-        for (int i = 0; i < static_cast<int>(sizeof(FuseFrame) / 4); ++i) d[i] = w[i];
-      }
+      const FuseFrame F = loadFuseFrame(a.frames + fi);
       const float Wm1 = static_cast<float>(F.W - 1), Hm1 = static_cast<float>(F.H - 1);
       const float fxfy = F.fx * F.fy;
       const char* const range_b = reinterpret_cast<const char*>(F.range);
@@ -1330,28 +1071,15 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse_obj(FuseArgs a, FuseLis
       bool okk[ZR];
 #pragma unroll
       for (int k = 0; k < ZR; ++k) {
-        const int iz = z0 + k;
-        const float pz = oz + (static_cast<float>(iz) + 0.5f) * a.vs;
-        float pc[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) pc[c] = (pxy[c] + F.R[3 * c + 2] * pz) + F.t[c];
-        bool ok = pc[2] > 0.f;
-        const float voxel_range = pc[2];
-        ok = ok && !(voxel_range < F.min_range || voxel_range > F.max_range);
-        const float yz = rcpRefined(pc[2]);
-        const float u = divExact(pc[0] * F.fx, pc[2], yz) + F.cx;
-        const float v = divExact(pc[1] * F.fy, pc[2], yz) + F.cy;
-        ok = ok && (fminf(fminf(u, v), fminf(Wm1 - u, Hm1 - v)) >= 0.f);
-        const float uc = ok ? u : 0.f, vc = ok ? v : 0.f;
-        const uint32_t u0 = static_cast<uint32_t>(static_cast<int>(uc)), v0 = static_cast<uint32_t>(static_cast<int>(vc));
-        const uint32_t v1 = min(v0 + 1u, static_cast<uint32_t>(F.H - 1));
-        const uint32_t o0 = v0 * W4 + u0 * 4u, o1 = v1 * W4 + u0 * 4u;
-        ra[k] = *reinterpret_cast<const f2u*>(range_b + o0);
-        rb[k] = *reinterpret_cast<const f2u*>(range_b + o1);
-        uu[k] = uc;
-        vv[k] = vc;
-        zz[k] = voxel_range;
-        okk[k] = ok;
+        const float pz = oz + (static_cast<float>(z0 + k) + 0.5f) * a.vs;
+        const VoxelProj p = projectVoxel(F, pxy, pz, Wm1, Hm1, 0);
+        const PairOffsets o = pairOffsets<false>(p.uc, p.vc, F.H, W4);
+        ra[k] = *reinterpret_cast<const f2u*>(range_b + o.o0);
+        rb[k] = *reinterpret_cast<const f2u*>(range_b + o.o1);
+        uu[k] = p.uc;
+        vv[k] = p.vc;
+        zz[k] = p.range;
+        okk[k] = p.ok;
       }
       // ---- phase 2a: signed distance and band decision of every voxel; second round of gathers, all of them together ----
       float sdfv[ZR];
@@ -1359,56 +1087,26 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse_obj(FuseArgs a, FuseLis
       uint32_t c4[ZR][4], objv[ZR], dynv[ZR];
 #pragma unroll
       for (int k = 0; k < ZR; ++k) {
-        bool ok = okk[k];
-        const float uc = uu[k], vc = vv[k], voxel_range = zz[k];
-        const uint32_t u0 = static_cast<uint32_t>(static_cast<int>(uc)), v0 = static_cast<uint32_t>(static_cast<int>(vc));
-        const uint32_t v1 = min(v0 + 1u, static_cast<uint32_t>(F.H - 1));
-        const float du = __builtin_amdgcn_fractf(uc), dv = __builtin_amdgcn_fractf(vc);
-        const uint32_t o0 = v0 * W4 + u0 * 4u, o1 = v1 * W4 + u0 * 4u;
-        const bool last_col = u0 >= static_cast<uint32_t>(F.W - 1);
-        const float r0 = ra[k].x, r1 = rb[k].x, r2 = last_col ? ra[k].x : ra[k].y, r3 = last_col ? rb[k].x : rb[k].y;
-        const float mn = fminf(fminf(r0, r1), fminf(r2, r3));
-        const float mx = fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
-        const bool use_nearest = mx - mn > a.adaptive_diff;
-        const bool hi_u = du >= 0.5f, hi_v = dv >= 0.5f;
-        const float r_near = hi_u ? (hi_v ? r3 : r2) : (hi_v ? r1 : r0);
-        const float omu = 1.f - du, omv = 1.f - dv;
-        const float w0 = omu * omv, w1 = omu * dv, w2 = du * omv, w3 = du * dv;
-        const float r_bil = ((w0 * r0 + w1 * r1) + w2 * r2) + w3 * r3;
-        const float dist_surface = use_nearest ? r_near : r_bil;
-        ok = ok && (dist_surface >= F.min_range) && !(dist_surface > F.max_range);
-        const float sdf = dist_surface - voxel_range;
-        ok = ok && !(sdf < -a.trunc);
-        const bool in_band = ok && (fabsf(sdf) < a.trunc);
-        okk[k] = ok;
-        inb[k] = in_band;
-        nearv[k] = use_nearest;
-        sdfv[k] = sdf;
+        const float uc = uu[k], vc = vv[k];
+        const SurfaceSample s = sampleSurface(okk[k], ra[k].x, ra[k].y, rb[k].x, rb[k].y, uc, vc, F.W, 2, a.adaptive_diff, zz[k], F.min_range, F.max_range, a.trunc);
+        okk[k] = s.ok;
+        inb[k] = s.in_band;
+        nearv[k] = s.use_nearest;
+        sdfv[k] = s.sdf;
         dynv[k] = 0u;
         objv[k] = 0u;
 #pragma unroll
         for (int j = 0; j < 4; ++j) c4[k][j] = 0u;
-        if (in_band) {
-          if (use_mask) {  // the pixel the update kernels test: largest interpolation weight
-            int best;
-            if (use_nearest) {
-              best = (hi_u ? 2 : 0) + (hi_v ? 1 : 0);
-            } else {
-              best = 0;
-              float bw = w0;
-              if (w1 > bw) { bw = w1; best = 1; }
-              if (w2 > bw) { bw = w2; best = 2; }
-              if (w3 > bw) { bw = w3; best = 3; }
-            }
-            const uint32_t uo = ((best & 2) && !last_col) ? 4u : 0u;
-            const uint32_t bo = ((best & 1) ? o1 : o0) + uo;
-            dynv[k] = static_cast<uint32_t>(*reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(F.dyn) + bo));
+        if (s.in_band) {
+          if (use_mask) {
+            const PairOffsets o = pairOffsets<false>(uc, vc, F.H, W4);
+            dynv[k] = static_cast<uint32_t>(*reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(F.dyn) + maskPixelOffset(s, o.o0, o.o1)));
           }
           if (has_color || do_sem) {  // the pixels of fuseBandRecord
             int px4[4];
             float bu, bv, w4[4];
             interpPixels(uc, vc, F.W, F.H, px4, &bu, &bv);
-            const int best = interpWeights(bu, bv, use_nearest, w4);
+            const int best = interpWeights(bu, bv, s.use_nearest, w4);
             if (has_color) {
               const char* const rgba_b = reinterpret_cast<const char*>(F.rgba);
 #pragma unroll
@@ -1430,71 +1128,32 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse_obj(FuseArgs a, FuseLis
         }
         if (__builtin_amdgcn_ballot_w64(ok) == 0ull) continue;
         const float uc = uu[k], vc = vv[k], depth = zz[k], sdf = sdfv[k];
-        const float yz = rcpRefined(depth);
         const float d_old = dreg[k], w_old = wreg[k];
-        float w;
-        if (EXACT) {
-          const float qd = divExact(a.vs, depth, yz);
-          w = fxfy * (qd * qd);
-          const float z2 = depth * depth;
-          w = divExact(w, z2, rcpRefined(z2));
-          if (sdf < -a.dropoff_eps) w = fmaxf(w * divExact(a.trunc + sdf, den, yden), 0.f);
-        } else {
-          const float qd = a.vs * yz;
-          w = fxfy * (qd * qd);
-          w = w * (yz * yz);
-          if (sdf < -a.dropoff_eps) w = fmaxf(w * ((a.trunc + sdf) * yden), 0.f);
-        }
+        // (the refined reciprocal of the depth is computed again: it is not carried across the second round of gathers)
+        const float w = measurementWeight<EXACT>(a.vs, fxfy, depth, rcpRefined(depth), sdf, a.trunc, a.dropoff_eps, den, yden, true, false);
         ok = ok && (w > 0.f);
         in_band = in_band && ok;
-        const float sdf_c = fmaxf(fminf(a.trunc, sdf), -a.trunc);
-        const float tot = w_old + w;
-        float d_new;
-        if (EXACT) {
-          d_new = divExact(d_old * w_old + sdf_c * w, tot, rcpRefined(tot));
-        } else {
-          d_new = __builtin_fmaf(d_old, w_old, sdf_c * w) * __builtin_amdgcn_rcpf(tot);
-        }
-        const float w_new = fminf(tot, a.max_weight);
+        const VoxelAverage avg = runningAverage<EXACT>(d_old, w_old, sdf, w, a.trunc, a.max_weight);
         if (ok) {
-          dreg[k] = d_new;
-          wreg[k] = w_new;
+          dreg[k] = avg.d_new;
+          wreg[k] = avg.w_new;
           sreg[k] |= S_TSDF;
         }
         const unsigned long long m_ok = __builtin_amdgcn_ballot_w64(ok), m_band = __builtin_amdgcn_ballot_w64(in_band);
         n_upd += static_cast<uint32_t>(__popcll(m_ok));
         touched = touched || (m_ok != 0ull);
-        wrote_neg = wrote_neg || (__builtin_amdgcn_ballot_w64(ok && d_new < 0.f) != 0ull);
+        wrote_neg = wrote_neg || (__builtin_amdgcn_ballot_w64(ok && avg.d_new < 0.f) != 0ull);
         if (m_band == 0ull) continue;
         n_band += static_cast<uint32_t>(__popcll(m_band));
         cnt += static_cast<uint32_t>(__popcll(m_band));
         if (!in_band) continue;
-        // colour / likelihoods / label of an in-band voxel: the body of fuseBandRecord on the lane's registers
-        const float wb = a.blend_pre ? w_old : w_new;  // the blend's voxel weight
+        // colour / likelihoods / label of an in-band voxel, on the lane's registers
         if (has_color) {
           int px4[4];
           float bu, bv, w4[4];
           interpPixels(uc, vc, F.W, F.H, px4, &bu, &bv);
           interpWeights(bu, bv, nearv[k], w4);
-          float acc[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const uint32_t c = c4[k][j];
-            acc[0] = acc[0] + w4[j] * static_cast<float>(c & 0xffu);
-            acc[1] = acc[1] + w4[j] * static_cast<float>((c >> 8) & 0xffu);
-            acc[2] = acc[2] + w4[j] * static_cast<float>((c >> 16) & 0xffu);
-          }
-          const float ctot = wb + w;
-          const float ytot = rcpRefined(ctot);
-          const uint32_t co = creg[k];
-          uint32_t out = 0xff000000u;
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch) {
-            const float cn = static_cast<float>(toU8(acc[ch]));
-            const float cv = static_cast<float>((co >> (8 * ch)) & 0xffu);
-            out |= static_cast<uint32_t>(toU8(divExact(cv * wb + cn * w, ctot, ytot))) << (8 * ch);
-          }
-          creg[k] = out;
+          creg[k] = blendColor(c4[k], w4, creg[k], a.blend_pre ? w_old : avg.w_new, w);
           sreg[k] |= S_COLOR;
         }
         if (do_sem) {
@@ -1528,30 +1187,11 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse_obj(FuseArgs a, FuseLis
       }
       if (s & S_FLAG) *reinterpret_cast<uint8_t*>(vfl_b + lin) = static_cast<uint8_t>(s & 0xffu);
     }
-    if (lane == 0) {
-      if (touched) atomicOr(&a.blk_flags[slot], BLK_UPDATED | BLK_MESH_UPDATED | BLK_TRACKING_UPDATED | (wrote_neg ? BLK_HAS_NEG : 0u));
-      a.blk_band[slot * kBandSlots + (sbi & (kBandSlots - 1))] = static_cast<uint16_t>(min(cnt, 65535u));
-    }
+    multiItemEpilogue(a, slot, sbi, lane, touched, wrote_neg, cnt);
     item = item_next;
     desc = d_next;
   }
-  if (lane == 0) {
-    s_stat[wave][0] = n_upd;
-    s_stat[wave][1] = n_band;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t su = 0u, sb = 0u;
-#pragma unroll
-    for (int w = 0; w < WPW; ++w) {
-      su += s_stat[w][0];
-      sb += s_stat[w][1];
-    }
-    if (su | sb) {
-      a.wg_stats[2 * blockIdx.x] += su;
-      a.wg_stats[2 * blockIdx.x + 1] += sb;
-    }
-  }
+  statsEpilogue<WPW>(s_stat, wave, lane, n_upd, n_band, a.wg_stats);
 }
 
 // per-camera update arguments of a tick -> device memory (they travel as kernel arguments: no host staging, no host wait)

@@ -1608,25 +1608,8 @@ static int integrateUpdateMulti(khr_ctx* c, khr_ctx* src, const int* src_slots, 
   constexpr int WPW = 8;
   auto go = [&](auto kern) {
     // one workgroup per WPW items is enough (c->explicit_blocks bounds the map), at most what is resident
-    // (the occupancy query is a driver call of tens of microseconds: once per instantiation, not once per extracted object)
-    static std::map<std::pair<int, const void*>, std::pair<int, int>> per_cu_of;  // (device, kernel) -> resident workgroups per CU, CUs
-    static std::mutex per_cu_mu;
-    int per_cu = 0, cus = 256;
-    {
-      std::lock_guard<std::mutex> lock(per_cu_mu);
-      const std::pair<int, const void*> key{c->device, reinterpret_cast<const void*>(kern)};
-      auto it = per_cu_of.find(key);
-      if (it != per_cu_of.end()) {
-        per_cu = it->second.first;
-        cus = it->second.second;
-      } else {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * WPW, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-        per_cu_of[key] = {per_cu, cus};
-      }
-    }
-    int grid = std::min(kUpdateStatSlots, per_cu * cus) / 8 * 8;
+    // (fuse2Grid: the occupancy query is a driver call of tens of microseconds, once per instantiation, not once per extracted object)
+    int grid = fuse2Grid(c, reinterpret_cast<const void*>(kern), WPW);
     if (c->explicit_blocks > 0) {
       const uint64_t items = c->explicit_blocks * c->wpb;
       grid = std::max(8, static_cast<int>(std::min<uint64_t>(static_cast<uint64_t>(grid), (items + WPW - 1) / WPW) + 7) / 8 * 8);
@@ -1648,8 +1631,8 @@ static int integrateUpdateMulti(khr_ctx* c, khr_ctx* src, const int* src_slots, 
     if (exactArithmetic(c)) go(&k_fuse_obj<true, WPW, 4>);
     else go(&k_fuse_obj<false, WPW, 4>);
   } else {
-    if (exactArithmetic(c)) go(&k_fuse2<8, 4, true, true, WPW, 4>);
-    else go(&k_fuse2<8, 4, true, false, WPW, 4>);
+    if (exactArithmetic(c)) go(&k_fuse2<8, 4, true, WPW, 4>);
+    else go(&k_fuse2<8, 4, false, WPW, 4>);
   }
   HIP_TRY(hipGetLastError());
   return KHR_OK;
@@ -2162,12 +2145,12 @@ static int tickUpdateUnion(khr_ctx* c, const int* slots, const DevFrame* frames,
     KHR_LAUNCH_TIMED(0, kern, dim3(grid), dim3(64 * wpw), a, list);
   };
   if (c->cfg.voxels_per_side == 8) {
-    if (exactArithmetic(c)) go(&k_fuse2<8, 4, true, true, 8, 4>, 8);
-    else go(&k_fuse2<8, 4, true, false, 8, 4>, 8);
+    if (exactArithmetic(c)) go(&k_fuse2<8, 4, true, 8, 4>, 8);
+    else go(&k_fuse2<8, 4, false, 8, 4>, 8);
   } else if (c->fuse_zsplit == 8) {
-    go(&k_fuse2<16, 8, true, true, 16, 4>, 16);
+    go(&k_fuse2<16, 8, true, 16, 4>, 16);
   } else {
-    go(&k_fuse2<16, 4, true, true, 16, 4>, 16);
+    go(&k_fuse2<16, 4, true, 16, 4>, 16);
   }
   c->tick_mask_dirty = false;
   HIP_TRY(hipGetLastError());

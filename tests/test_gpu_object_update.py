@@ -2,7 +2,8 @@
 likelihoods, flag byte, label -- stays in registers across the frames of a launch, chunks of kMultiChunk = 7 frames per launch).
 Two 8^3 object contexts over the same allocated box: one takes khr_integrate_shared_batch, the other one khr_integrate_shared call
 per frame (the single-frame kernel, which test_gpu_parity holds to the oracle).  Everything is compared bit for bit: map digests,
-prune counts, mesh arrays, update counters.
+voxel layers, prune counts, mesh arrays, update counters.  A second map configuration (LABEL_MAP: tracking stamps, four labels read
+from the label image) is not the extractor's: its batch takes k_fuse2<8, 4, ..> with LDS records and fuseBandRecord.
 
 The box is the part of the scene's back wall (label 3 at pixel (160, 120) of frame 0: the plane y = 3 m) the first frames look at,
 324 blocks of 32 cm; the objects in front of it give the object image its misses, the turning camera new voxels in every frame."""
@@ -42,22 +43,30 @@ def window():
     win.close()
 
 
-def _mini(exact, blend):
-    c = FusionContext(default_config(voxels_per_side=8, voxel_size=0.04, truncation_distance=0.08, with_semantics=1, with_tracking=0,
-                                     semantic_mode=1, num_labels=2, max_blocks=512, max_frame_pixels=W * H,
-                                     exact_arithmetic=exact, color_blend_weight=blend))
+OBJECT_MAP = dict(with_tracking=0, semantic_mode=1, num_labels=2)  # the extractor's configuration: the batch takes k_fuse_obj
+LABEL_MAP = dict(with_tracking=1, semantic_mode=0, num_labels=4)   # any other 8^3 map: the batch takes k_fuse2<8, 4, ..>
+
+
+def _mini(exact, blend, layout):
+    c = FusionContext(default_config(voxels_per_side=8, voxel_size=0.04, truncation_distance=0.08, with_semantics=1,
+                                     max_blocks=512, max_frame_pixels=W * H, exact_arithmetic=exact, color_blend_weight=blend, **layout))
     c.allocate_blocks(BOX)
     return c
 
 
+LAYERS = ("distance", "weight", "color", "flags", "sem_label", "likelihoods", "last_observed")
+
+
 def _layers(ctx):
-    bl = [ctx.download_block(idx) for idx in ctx.block_indices()]
-    return {k: np.stack([b[k] for b in bl]) for k in ("flags", "likelihoods", "color", "weight")}
+    order = ctx.block_indices()
+    order = order[np.lexsort(order.T)]
+    bl = [ctx.download_block(idx) for idx in order]
+    return {k: np.stack([b[k] for b in bl]) for k in LAYERS}
 
 
-def _run(win, slots, ids, exact=1, blend=0, use_mask=False):
+def _run(win, slots, ids, exact=1, blend=0, use_mask=False, layout=OBJECT_MAP):
     """the batch context against the frame-by-frame one; returns the batch context's digest"""
-    a, b = _mini(exact, blend), _mini(exact, blend)
+    a, b = _mini(exact, blend, layout), _mini(exact, blend, layout)
     try:
         a.integrate_shared_batch(win, slots, ids, use_mask=use_mask)
         sem_frames = [i for i in range(len(slots)) if ids is not None and ids[i] >= 0]
@@ -72,14 +81,24 @@ def _run(win, slots, ids, exact=1, blend=0, use_mask=False):
         la = _layers(a)
         valid = (la["flags"] & VOX_SEM_VALID) != 0
         assert (la["weight"] > 0).any() and (la["color"][..., :3] != 0).any()
+        sa, sb = a.stats(), b.stats()
+        assert sa["cum_updated_voxels"] == sb["cum_updated_voxels"] > 0
+        if layout is LABEL_MAP:
+            # the voxel layers themselves, last_observed with them (likelihoods and label where the voxel holds any); labels of the
+            # label image and stamps of more than one frame have arrived: a voxel the later frames no longer see keeps its stamp
+            lb = _layers(b)
+            for k in LAYERS:
+                on = valid if k in ("likelihoods", "sem_label") else np.ones_like(valid)
+                x, y = (np.moveaxis(l[k], 1, -1) if k == "likelihoods" else l[k] for l in (la, lb))
+                assert np.array_equal(x[on], y[on]), k
+            assert valid.any() and len(np.unique(la["last_observed"][la["weight"] > 0])) >= 2
+            return da
         if len(sem_frames) >= 2:
             # state carried over at least two frames, and voxels whose first label arrived in a later frame of the launch
             assert (la["likelihoods"].sum(axis=1)[valid] >= 2).any()
             assert valid_first.any() and (valid & ~valid_first).any()
         else:
             assert not sem_frames and not valid.any()
-        sa, sb = a.stats(), b.stats()
-        assert sa["cum_updated_voxels"] == sb["cum_updated_voxels"] > 0
         # the mesh of the updated map (every case has a surface), the prune counts, and the mesh of what the prune keeps (nothing where
         # the object layer saw misses only or was never written)
         for pruned in (False, True):
@@ -106,6 +125,13 @@ def test_batch_equals_frame_by_frame(window, n, exact, blend):
     """under, at and across kMultiChunk = 7 (8 and 15 end in a one-frame chunk), both arithmetic modes, both blend weights"""
     win, slots = window
     _run(win, slots[:n], [3] * n, exact=exact, blend=blend)
+
+
+@pytest.mark.parametrize("exact", [1, 0])
+def test_label_map_batch_equals_frame_by_frame(window, exact):
+    """a map with tracking stamps and four labels, all N_MAX frames (three launches): k_fuse2<8, 4, ..> on the batch path"""
+    win, slots = window
+    _run(win, slots, None, exact=exact, layout=LABEL_MAP)
 
 
 def test_frames_without_object_id_in_the_middle(window):

@@ -7,8 +7,9 @@
     python tools/isa_breakdown.py /tmp/khr_dev_g.s [--kernel SUBSTRING] [--phases-file khr_kernels_fuse.h]
 
 Phases are source-line ranges of khronos_amd/csrc/khr_kernels_fuse.h, found by the marker comments `// isa:<phase>` in the kernel
-(every line from a marker to the next one belongs to that phase); instructions from other files (khr_device.h helpers, HIP
-headers) are attributed to the phase of the last kernel-file line seen before them (inlined callees).  Static counts: the item
+(every line from a marker to the next one belongs to that phase); instructions of inlined callees -- other files (khr_fuse_math.h,
+khr_device.h, HIP headers) and the helpers defined in the kernel file ahead of its first marker -- go to the phase of their call
+site, read from the inlined-at chain the assembler prints behind each `.loc`.  Static counts: the item
 loop is straight-line code with the ZR z-steps unrolled, so (loop-body count) / ZR is the per-z-step figure the PMC counter
 SQ_INSTS_VALU integrates dynamically."""
 import argparse
@@ -48,7 +49,7 @@ def classify(op):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("asm")
-    ap.add_argument("--kernel", default="k_fuseILi16ELi4ELb1ELb1ELi12ELb0E")
+    ap.add_argument("--kernel", default="k_fuseILi16ELi4ELb1ELb1ELi12EEE")
     ap.add_argument("--source", default="khronos_amd/csrc/khr_kernels_fuse.h")
     ap.add_argument("--file-name", default="khr_kernels_fuse.h")
     a = ap.parse_args()
@@ -91,10 +92,16 @@ def main():
             continue
         m = re.match(r"\s*\.loc\s+(\d+)\s+(\d+)", ln)
         if m:
-            # helper functions defined above the first marker (rcpRefined, divExact, interpPixels ...) and everything from
-            # other files are inlined callees: they stay with the phase of the call site
-            if files.get(int(m.group(1))) == a.file_name and int(m.group(2)) >= marks[0][0]:
-                cur_phase = phase_of(int(m.group(2)))
+            # helper functions defined above the first marker (the shared plumbing) and everything from other files (khr_fuse_math.h,
+            # khr_device.h, HIP headers) are inlined callees: they go to the phase of the call site, which the assembler comment of
+            # the .loc names (`callee.h:L:C @[ caller.h:L:C @[ ... ] ]`): the innermost frame that lies behind the first marker
+            frames = re.findall(r"([^\s\[\]@;]+):(\d+):\d+", ln.split(";", 1)[1]) if ";" in ln else []
+            if not frames:
+                frames = [(files.get(int(m.group(1)), ""), m.group(2))]
+            for f, l in frames:
+                if f.endswith(a.file_name) and int(l) >= marks[0][0]:
+                    cur_phase = phase_of(int(l))
+                    break
             continue
         m = re.match(r"\s+([a-z_0-9]+)\s", ln)
         if not m or ln.lstrip().startswith((".", ";")):
