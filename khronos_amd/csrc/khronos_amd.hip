@@ -168,7 +168,7 @@ struct khr_ctx {
   unsigned long long* d_dbg = nullptr;
   unsigned long long* d_digest = nullptr;  // khr_map_digest accumulators
   uint32_t* d_wg_stats = nullptr;
-  bool defer_fold = false, fold_pending = false;  // k_fuse's item records: folded by the next k_tracking_select instead of k_fuse_fold
+  bool fold_pending = false;  // k_fuse's item records: folded by the next k_tracking_select instead of k_fuse_fold
   int stream_priority = 0;  // +1 the active window's streams (highest), -1 an object mini-map's (lowest), 0 default (env KHR_STREAM_PRIORITY=0)
   unsigned char* d_fuse_sink = nullptr;  // k_fuse: one 256-byte sink line per wave (kUpdateStatSlots workgroups x 16 waves)
   DevBuf<uint32_t> d_pix_scratch;  // khr_pixel_iou: mask image + counters (allocated on first use)
@@ -211,10 +211,8 @@ struct khr_ctx {
   };
   std::shared_ptr<FramePool> frame_pool = std::make_shared<FramePool>();
   khr_snapshot* pending_snapshot = nullptr;  // taken inside khr_process_frame(KHR_PF_SNAPSHOT)
-  hipStream_t snap_stream_override = nullptr;  // view (set around khr_snapshot_updated by khr_process_frame)
   Event ev_snap_fork, ev_snap_join;
   Event ev_mc_fork, ev_mc_join;
-  bool fork_after_select = false;            // trackingPhase records ev_mc_fork behind k_tracking_select
   // upper bound of the blocks an explicitly allocated map holds (khr_allocate_blocks since the last khr_reset_map; 0 =
   // unknown): the update kernel of an `allocate = false` integration (object mini-maps) sizes its persistent grid from it
   // instead of filling the chip with workgroups that find no item
@@ -251,7 +249,7 @@ struct khr_ctx {
   uint32_t seed_ticket = 0;
   bool seed_publish_pending = false;
   bool seed_by_ticket = false;   // motionFinish waits for the ticket (k_motion_pixels) instead of ev_seed (key import)
-  bool begin_in_ingest = false, begun = false;  // khr_process_frame folds k_begin_integrate into k_frame_ingest
+  bool begun = false;            // the frame's ingest kernel did k_begin_integrate's work (khr_process_frame, main-stream ingest)
   uint32_t fetch_ticket = 0;                     // khr_fetch_mesh: completion ticket the gather kernel publishes
   bool fetch_pending = false;                    // khr_fetch_mesh_launch issued, khr_fetch_mesh outstanding
   uint32_t* d_fetch_done = nullptr;              //   + its workgroup completion counter (device)
@@ -265,7 +263,6 @@ struct khr_ctx {
   PinnedBuf<void> h_up;                          // upload staging (khr_allocate_blocks: page-locked, read by the kernel in place)
   Event ev_ingest;                               // khr_process_frame: this frame's main-stream ingest is queued
   Event ev_up;                                   // the last upload out of h_up has been consumed
-  hipStream_t ingest_stream = nullptr;           // view, khr_process_frame: ingest on the auxiliary stream (set around khr_upload_frame)
   // frames handed over with khr_ingest_ahead[_host], oldest first, waiting for their khr_process_frame calls.  Up to kMaxAhead: a
   // frontend that hands frame i + 1 over BEFORE it calls khr_process_frame for frame i keeps the copy engine busy across the
   // host's wait inside that call (round 5: with one entry the host-to-device copy of a 720p frame, ~205 us, started only after
@@ -275,10 +272,8 @@ struct khr_ctx {
   Event ev_ahead[2];      // conversion of the entry finished (auxiliary stream)
   Event ev_ahead_h2d[2];  // host planes of the entry have arrived (host-to-device stream)
   int ahead_ev_next = 0;
-  Event* h2d_ev_target = nullptr;  // view (set around khr_upload_frame: which event the pinned copy records)
   Event ev_h2d;                    // the pinned copy's own event (h2d_stream)
   bool h2d_pending = false;    // a copy out of caller memory is queued: the caller's buffers are released by the next call / khr_sync
-  bool host_input_pinned = false;  // (set around khr_upload_frame by the callers that were told the memory is page-locked)
   uint64_t h2d_bytes = 0;      // bytes queued through the pinned path (statistics)
   int ef_parity = 0, ef_cur = 0;  // which of C_N_EF / C_N_EF2 the next / the latest tracking pass fills
   Event ev_seed;
@@ -326,8 +321,6 @@ struct khr_ctx {
   bool md_seed_run = false;         // the frame detected last had motion seeds: the next frame's chain is queued ahead of its seed count
   uint32_t md_prev_seed_px = 0;     // ... sized from that frame's seed pixels
   uint64_t n_md_prelaunched = 0, n_md_prelaunch_repeats = 0;
-  bool md_defer_summary = false;    // clusterSummaryLaunch only notes the request (md_summary_pending = largest id)
-  int md_summary_pending = -1;
   uint32_t md_last_seeds = 0;       // seed voxels of the previous seed frame (predicts which component path is needed)
   uint32_t* d_md_edges = nullptr;     // seed-seed edge list of the latest seed frame (k_md_adjacency -> k_md_comp_lds)
   uint32_t* d_md_scratch4 = nullptr;  // 4 words k_publish may zero
@@ -453,18 +446,20 @@ struct ScopedTimer {
   khr_ctx* c;
   int which;
   Event a, b;
+  hipStream_t st;  // the stream the bracketed launches go to
   bool on = false;
-  ScopedTimer(khr_ctx* ctx, int w) : c(ctx), which(w) {
+  ScopedTimer(khr_ctx* ctx, int w, hipStream_t stream = nullptr)  // (nullptr: the context's)
+      : c(ctx), which(w), st(stream ? stream : static_cast<hipStream_t>(ctx->stream)) {
     on = w >= 0 && ((c->timing >> w) & 1u);
     if (on) {
       a = takeEvent(c);
       b = takeEvent(c);
-      hipEventRecord(a, c->stream);
+      hipEventRecord(a, st);
     }
   }
   ~ScopedTimer() {
     if (on) {
-      hipEventRecord(b, c->stream);
+      hipEventRecord(b, st);
       c->pending.push_back({which, std::move(a), std::move(b)});
     }
   }
@@ -1191,35 +1186,66 @@ static int acquireSlot(khr_ctx* c) {
   return slot;
 }
 
-int khr_upload_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* frame, int on_device) {
-  if (!c || !sensor || !frame || !frame->depth) return fail(KHR_EINVAL, "null argument");
+// is `slot` a frame of this context that can be read?
+static bool validSlot(const khr_ctx* c, int slot) {
+  return slot >= 0 && slot < static_cast<int>(c->slots.size()) && c->slots[slot].valid;
+}
+
+static int checkSensor(const khr_ctx* c, const khr_sensor* sensor) {
   const size_t n = static_cast<size_t>(sensor->width) * sensor->height;
   if (sensor->width < 2 || sensor->height < 2 || n > c->cfg.max_frame_pixels)
     return fail(KHR_EINVAL, "frame %dx%d exceeds max_frame_pixels=%u", sensor->width, sensor->height, c->cfg.max_frame_pixels);
   if (!(sensor->fx > 0.f) || !(sensor->fy > 0.f) || !(sensor->max_range > sensor->min_range))
     return fail(KHR_EINVAL, "bad intrinsics / range");
-  HIP_TRY(hipSetDevice(c->device));
-  // next slot of the ring that nobody holds (khr_retain_slot): buffered frames and frames a detached extraction still reads
-  // stay intact however far the stream has advanced
-  const int slot = acquireSlot(c);
-  if (slot < 0) return slot;
+  return KHR_OK;
+}
+
+// a ring slot becomes a new frame: nothing of its previous occupant is left (`meta` without its plane pointers)
+static FrameSlot& newFrameSlot(khr_ctx* c, int slot, const khr_sensor& sensor, const khr_frame& meta, bool has_color, bool has_label,
+                               bool valid) {
   FrameSlot& s = c->slots[slot];
-  const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  s.valid = false;  // until the ingest is queued: an error below leaves a slot nobody can integrate, not the previous occupant
-  s.sensor = *sensor;
-  s.meta = *frame;
+  s.valid = valid;
+  s.sensor = sensor;
+  s.meta = meta;
   s.meta.depth = nullptr;
   s.meta.color = nullptr;
   s.meta.label = nullptr;
-  s.has_color = frame->color != nullptr;
-  s.has_label = frame->label != nullptr;
+  s.has_color = has_color;
+  s.has_label = has_label;
   s.has_obj = false;
   if (c->obj_cv_slot == slot) c->obj_cv_slot = -1;
   s.objects_done = false;
   s.clusters.clear();
   s.sem_clusters.clear();
-  const bool pinned = !on_device && c->host_input_pinned;
-  hipStream_t ist = ((on_device || pinned) && c->ingest_stream) ? c->ingest_stream : c->stream;
+  s.tw = (sensor.width + kTile - 1) / kTile;
+  s.th = (sensor.height + kTile - 1) / kTile;
+  s.dyn_clean = true, s.dynw_valid = false;
+  return s;
+}
+
+// what the caller of an ingest chooses for its frame (khr_upload_frame: the defaults)
+struct IngestOpts {
+  hipStream_t stream = nullptr;  // where the ingest kernel runs, for device and page-locked inputs (nullptr: the main stream)
+  bool pinned = false;           // host buffers are page-locked: their copies go to the host-to-device stream, no host wait
+  Event* h2d_event = nullptr;    // the event those copies record (nullptr: c->ev_h2d, and the context notes h2d_pending)
+  bool begin = false;            // the ingest kernel also does k_begin_integrate's work
+};
+
+static int uploadFrame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* frame, int on_device, const IngestOpts& opts) {
+  if (!c || !sensor || !frame || !frame->depth) return fail(KHR_EINVAL, "null argument");
+  KHR_TRY(checkSensor(c, sensor));
+  const size_t n = static_cast<size_t>(sensor->width) * sensor->height;
+  HIP_TRY(hipSetDevice(c->device));
+  // next slot of the ring that nobody holds (khr_retain_slot): buffered frames and frames a detached extraction still reads
+  // stay intact however far the stream has advanced
+  const int slot = acquireSlot(c);
+  if (slot < 0) return slot;
+  const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  // not valid until the ingest is queued: an error below leaves a slot nobody can integrate, not the previous occupant
+  FrameSlot& s = newFrameSlot(c, slot, *sensor, *frame, frame->color != nullptr, frame->label != nullptr, false);
+  const bool pinned = !on_device && opts.pinned;
+  hipStream_t ist = ((on_device || pinned) && opts.stream) ? opts.stream : static_cast<hipStream_t>(c->stream);
+  Event& evh = opts.h2d_event ? *opts.h2d_event : c->ev_h2d;
   ScopedTimer tm(c, ist == c->stream ? 6 : -1);
   const float* depth_src = frame->depth;
   const uint8_t* rgb_src = frame->color;
@@ -1232,7 +1258,7 @@ int khr_upload_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fram
     hipStream_t cs = c->stream;
     if (pinned) {
       if (!c->h2d_stream) KHR_TRY(createStream(c, c->h2d_stream));
-      KHR_TRY((c->h2d_ev_target ? *c->h2d_ev_target : c->ev_h2d).ensure());
+      KHR_TRY(evh.ensure());
       cs = c->h2d_stream;
       if (ist == c->stream) {  // main-stream ingest: the slot's previous readers are ordered in front of it, so must the copy be
         KHR_TRY(c->ev_ingest.ensure());
@@ -1251,29 +1277,28 @@ int khr_upload_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fram
       label_src = s.label;
     }
     if (pinned) {
-      const Event& evh = c->h2d_ev_target ? *c->h2d_ev_target : c->ev_h2d;
       HIP_TRY(hipEventRecord(evh, cs));
       HIP_TRY(hipStreamWaitEvent(ist, evh, 0));
-      if (!c->h2d_ev_target) c->h2d_pending = true;
+      if (!opts.h2d_event) c->h2d_pending = true;
       c->h2d_bytes += n * (4u + (frame->color ? 3u : 0u) + (frame->label ? 4u : 0u));
     }
   }
-  s.tw = (sensor->width + kTile - 1) / kTile;
-  s.th = (sensor->height + kTile - 1) / kTile;
   hipLaunchKernelGGL(k_frame_ingest, dim3(s.tw * s.th), dim3(256), 0, ist, depth_src, rgb_src, label_src, s.depth,
                      s.range, s.rgba, s.label, s.dyn, s.tile_max, s.tw, sensor->width, sensor->height, sensor->fx, sensor->fy,
-                     sensor->cx, sensor->cy, c->p.range_mode, c->m, c->p.nvox, c->d_wg_stats, c->begin_in_ingest ? 1 : 0);
+                     sensor->cx, sensor->cy, c->p.range_mode, c->m, c->p.nvox, c->d_wg_stats, opts.begin ? 1 : 0);
   HIP_TRY(hipGetLastError());
-  c->begun = c->begin_in_ingest;
-  c->begin_in_ingest = false;
+  c->begun = opts.begin;
   if (!on_device && !pinned) HIP_TRY(hipStreamSynchronize(c->stream));  // caller buffers may be reused after return
   s.valid = true;
-  s.dyn_clean = true, s.dynw_valid = false;
   return slot;
 }
 
+int khr_upload_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* frame, int on_device) {
+  return uploadFrame(c, sensor, frame, on_device, IngestOpts{});
+}
+
 int khr_set_frame_image(khr_ctx* c, int slot, int which, const int32_t* image, int on_device) {
-  if (!c || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad slot");
+  if (!c || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad slot");
   FrameSlot& s = c->slots[slot];
   const size_t n = static_cast<size_t>(s.sensor.width) * s.sensor.height;
   int32_t* dst = which == 0 ? s.dyn : s.obj;
@@ -1295,7 +1320,7 @@ int khr_set_frame_image(khr_ctx* c, int slot, int which, const int32_t* image, i
 }
 
 int khr_download_frame(khr_ctx* c, int slot, float* range, float* vertex_map, int32_t* dynamic_image) {
-  if (!c || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad slot");
+  if (!c || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad slot");
   FrameSlot& s = c->slots[slot];
   const size_t n = static_cast<size_t>(s.sensor.width) * s.sensor.height;
   if (range) HIP_TRY(hipMemcpyAsync(range, s.vRange(), n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -1322,7 +1347,7 @@ struct khr_frame_copy {
 };
 
 int khr_frame_copy_create(khr_ctx* c, int slot, khr_frame_copy** out) {
-  if (!c || !out || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad argument");
+  if (!c || !out || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad argument");
   HIP_TRY(hipSetDevice(c->device));
   FrameSlot& s = c->slots[slot];
   const size_t n = static_cast<size_t>(s.sensor.width) * s.sensor.height, n_pad = (n + 3) / 4 * 4;
@@ -1399,7 +1424,7 @@ void khr_frame_copy_release(khr_frame_copy* fc) {
 }
 
 int khr_copy_frame_image(khr_ctx* c, int slot, int which, void* device_dst) {
-  if (!c || !device_dst || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad argument");
+  if (!c || !device_dst || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad argument");
   if (which != 0 && which != 1) return fail(KHR_EINVAL, "which must be 0 (dynamic) or 1 (object)");
   HIP_TRY(hipSetDevice(c->device));
   FrameSlot& s = c->slots[slot];
@@ -1417,7 +1442,7 @@ int khr_copy_frame_image(khr_ctx* c, int slot, int which, void* device_dst) {
 }
 
 int khr_download_frame_image(khr_ctx* c, int slot, int which, int32_t* image) {
-  if (!c || !image || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad argument");
+  if (!c || !image || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad argument");
   if (which != 0 && which != 1) return fail(KHR_EINVAL, "which must be 0 (dynamic) or 1 (object)");
   FrameSlot& s = c->slots[slot];
   const size_t n = static_cast<size_t>(s.sensor.width) * s.sensor.height;
@@ -1638,8 +1663,9 @@ static int integrateUpdateMulti(khr_ctx* c, khr_ctx* src, const int* src_slots, 
   return KHR_OK;
 }
 
+// defer_fold: the items' records are left to the next k_tracking_select (c->fold_pending) instead of a k_fuse_fold launch
 static int integrateUpdate(khr_ctx* c, FrameSlot& s, const DevFrame& f, int allocate_blocks, int use_mask,
-                           int object_id, const UpdateLists* lists = nullptr, const uint32_t* gate = nullptr) {
+                           int object_id, bool defer_fold, const UpdateLists* lists = nullptr, const uint32_t* gate = nullptr) {
   DevMap& m = c->m;
   FuseList list{c->d_work4, c->d_work4 + c->item_cap, c->item_cap, &m.counters[C_N_ITEMS0]};
   if (lists) list = lists->list;
@@ -1667,7 +1693,7 @@ static int integrateUpdate(khr_ctx* c, FrameSlot& s, const DevFrame& f, int allo
         KHR_LAUNCH_TIMED(0, kern, dim3(grid), dim3(64 * wpw), a, list);
         // the items' {touched, negative} bits -> block flags (k_fuse writes one record per item instead of an atomic); left to
         // k_tracking_select when the tracking pass follows directly (khr_process_frame)
-        if (c->defer_fold) c->fold_pending = true;
+        if (defer_fold) c->fold_pending = true;
         else hipLaunchKernelGGL(k_fuse_fold, dim3((c->m.capacity + 255) / 256), dim3(256), 0, c->stream, m.blk_flags, m.blk_band,
                                 &m.counters[C_MAX_SLOT], gate);
       };
@@ -1699,7 +1725,7 @@ static int integrateUpdate(khr_ctx* c, FrameSlot& s, const DevFrame& f, int allo
 }
 
 int khr_integrate(khr_ctx* c, int slot, int allocate_blocks, int use_mask, int object_id) {
-  if (!c || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad slot");
+  if (!c || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad slot");
   HIP_TRY(hipSetDevice(c->device));
   FrameSlot& s = c->slots[slot];
   const DevFrame f = makeDevFrame(c, s);
@@ -1709,12 +1735,11 @@ int khr_integrate(khr_ctx* c, int slot, int allocate_blocks, int use_mask, int o
   }
   int rc = integrateAlloc(c, s, f, allocate_blocks);
   if (rc) return rc;
-  return integrateUpdate(c, s, f, allocate_blocks, use_mask, object_id);
+  return integrateUpdate(c, s, f, allocate_blocks, use_mask, object_id, false);
 }
 
 int khr_integrate_shared(khr_ctx* c, khr_ctx* src, int src_slot, int allocate_blocks, int use_mask, int object_id) {
-  if (!c || !src || src_slot < 0 || src_slot >= static_cast<int>(src->slots.size()) || !src->slots[src_slot].valid)
-    return fail(KHR_EINVAL, "bad source slot");
+  if (!c || !src || !validSlot(src, src_slot)) return fail(KHR_EINVAL, "bad source slot");
   if (c->device != src->device) return fail(KHR_EINVAL, "contexts live on different devices");
   HIP_TRY(hipSetDevice(c->device));
   // the frame must be complete: either the caller declared the dependency on the device (khr_depend_on) or the host waits
@@ -1726,15 +1751,14 @@ int khr_integrate_shared(khr_ctx* c, khr_ctx* src, int src_slot, int allocate_bl
   const DevFrame f = makeDevFrame(src, s);
   int rc = integrateAlloc(c, s, f, allocate_blocks);
   if (rc) return rc;
-  return integrateUpdate(c, s, f, allocate_blocks, use_mask, object_id);
+  return integrateUpdate(c, s, f, allocate_blocks, use_mask, object_id, false);
 }
 
 int khr_integrate_shared_batch(khr_ctx* c, khr_ctx* src, const int* src_slots, const int* object_ids, int n_frames,
                                int allocate_blocks, int use_mask) {
   if (!c || !src || !src_slots || n_frames < 0) return fail(KHR_EINVAL, "bad argument");
   for (int i = 0; i < n_frames; ++i)
-    if (src_slots[i] < 0 || src_slots[i] >= static_cast<int>(src->slots.size()) || !src->slots[src_slots[i]].valid)
-      return fail(KHR_EINVAL, "bad source slot");
+    if (!validSlot(src, src_slots[i])) return fail(KHR_EINVAL, "bad source slot");
   if (c->device != src->device) return fail(KHR_EINVAL, "contexts live on different devices");
   if (n_frames == 0) return KHR_OK;
   if (allocate_blocks) {  // the frustum differs per frame: nothing to share
@@ -1764,7 +1788,7 @@ int khr_integrate_shared_batch(khr_ctx* c, khr_ctx* src, const int* src_slots, c
   for (int i = 0; i < n_frames; ++i) {
     FrameSlot& s = src->slots[src_slots[i]];
     const DevFrame f = makeDevFrame(src, s);
-    const int rc = integrateUpdate(c, s, f, 0, use_mask, object_ids ? object_ids[i] : -1);
+    const int rc = integrateUpdate(c, s, f, 0, use_mask, object_ids ? object_ids[i] : -1, false);
     if (rc) return rc;
   }
   // (statistics: cum_integrate_calls counts this batch once; the voxel counts cover all its frames)
@@ -1785,7 +1809,8 @@ static uint64_t stampThreshold(double T) {
   return hi;
 }
 
-static int trackingPhase(khr_ctx* c, uint64_t stamp, int phase) {
+// fork_event: recorded behind k_tracking_select (nullptr: none)
+static int trackingPhase(khr_ctx* c, uint64_t stamp, int phase, hipEvent_t fork_event = nullptr) {
   DevMap& m = c->m;
   const double now = static_cast<double>(stamp) / 1e9;
   const uint64_t lim_active = stampThreshold(now - c->p.temporal_window);
@@ -1807,7 +1832,7 @@ static int trackingPhase(khr_ctx* c, uint64_t stamp, int phase) {
                          c->d_trk_proc, c->d_ef, cnt, cnt_next, c->fold_pending ? m.blk_band : nullptr);
       c->fold_pending = false;
       // (khr_process_frame at output cadence: marching cubes start here, beside the rest of the tracking pass)
-      if (c->fork_after_select) HIP_TRY(hipEventRecord(c->ev_mc_fork, c->stream));
+      if (fork_event) HIP_TRY(hipEventRecord(fork_event, c->stream));
       KHR_LAUNCH_TIMED(10, (k_tracking_update<V, (V == 16 ? 4 : 1)>), dim3(V == 16 ? 4096 : 1024), dim3(256), m, c->p, stamp,
                        c->last_track_stamp, lim_active, lim_free, c->d_trk_proc, cnt);
       c->last_track_stamp = stamp;
@@ -1903,60 +1928,30 @@ struct TickSlotsGuard {  // an error after the acquisition leaves the tick's slo
   ~TickSlotsGuard() { if (armed) for (int i = 0; i < n; ++i) c->slots[slots[i]].valid = false; }
 };
 
-int khr_tick_ingest(khr_ctx* c, const khr_sensor* sensor, const khr_frame* frames, int n_frames, int count_seeds,
-                    int* slots_out, uint32_t* n_seed_pixels, int64_t* seed_counts_device) {
+// the arguments khr_tick_ingest and khr_tick_adopt share
+static int tickArgs(const khr_ctx* c, const khr_sensor* sensor, const void* frames, int n_frames, const int* slots_out) {
   if (!c || !sensor || !frames || !slots_out || n_frames < 1) return fail(KHR_EINVAL, "bad argument");
-  const size_t n = static_cast<size_t>(sensor->width) * sensor->height;
-  if (sensor->width < 2 || sensor->height < 2 || n > c->cfg.max_frame_pixels)
-    return fail(KHR_EINVAL, "frame %dx%d exceeds max_frame_pixels=%u", sensor->width, sensor->height, c->cfg.max_frame_pixels);
-  if (!(sensor->fx > 0.f) || !(sensor->fy > 0.f) || !(sensor->max_range > sensor->min_range))
-    return fail(KHR_EINVAL, "bad intrinsics / range");
+  KHR_TRY(checkSensor(c, sensor));
   if (static_cast<size_t>(n_frames) > c->slots.size()) return fail(KHR_EINVAL, "more frames than frame slots (num_frame_slots)");
-  for (int i = 0; i < n_frames; ++i)
-    if (!frames[i].depth) return fail(KHR_EINVAL, "frame %d has no depth image", i);
+  return KHR_OK;
+}
+
+// ... and what they do: the tick's slots, and per batch of up to kMaxTick frames `batch(base, nb, count_seeds)` -- which turns the
+// slots slots_out[base .. base + nb) into the batch's frames and queues their kernel -- followed by the seed counts' publish
+static int tickFrames(khr_ctx* c, int n_frames, int count_seeds, int* slots_out, uint32_t* n_seed_pixels, int64_t* seed_counts_device,
+                      const std::function<void(int, int, int)>& batch) {
   HIP_TRY(hipSetDevice(c->device));
   int rc = ensureTick(c);
   if (rc) return rc;
   count_seeds = count_seeds && c->cfg.with_tracking;
   c->tick_seed_host.assign(n_frames, 0u);
   c->tick_seed_collected = 0;
-  const int tw = (sensor->width + kTile - 1) / kTile, th = (sensor->height + kTile - 1) / kTile;
   ScopedTimer tm(c, 6);
   if ((rc = acquireTickSlots(c, n_frames, slots_out))) return rc;
   TickSlotsGuard undo{c, slots_out, n_frames};
   for (int base = 0; base < n_frames; base += kMaxTick) {
     const int nb = std::min(kMaxTick, n_frames - base);
-    TickIngest t{};
-    for (int k = 0; k < nb; ++k) {
-      const khr_frame& fr = frames[base + k];
-      const int slot = slots_out[base + k];
-      FrameSlot& s = c->slots[slot];
-      s.sensor = *sensor;
-      s.meta = fr;
-      s.meta.depth = nullptr;
-      s.meta.color = nullptr;
-      s.meta.label = nullptr;
-      s.has_color = fr.color != nullptr;
-      s.has_label = fr.label != nullptr;
-      s.has_obj = false;
-      if (c->obj_cv_slot == slot) c->obj_cv_slot = -1;
-      s.objects_done = false;
-      s.clusters.clear();
-      s.sem_clusters.clear();
-      s.tw = tw;
-      s.th = th;
-      s.valid = true;
-      s.dyn_clean = true, s.dynw_valid = false;
-      t.depth_in[k] = fr.depth; t.rgb_in[k] = fr.color; t.label_in[k] = fr.label;
-      t.depth[k] = s.depth; t.range[k] = s.range; t.rgba[k] = s.rgba; t.label[k] = s.label; t.dyn[k] = s.dyn;
-      t.tile_max[k] = s.tile_max;
-      float R[9], tt[3];
-      makePose(fr.world_T_sensor, R, tt, t.Rw[k], t.tw[k]);
-      t.min_z_world[k] = static_cast<float>(fr.world_T_sensor[11] + static_cast<double>(c->cfg.md_min_z_coordinate));
-    }
-    hipLaunchKernelGGL(k_tick_ingest, dim3(tw * th, nb), dim3(256), 0, c->stream, t, tw, sensor->width, sensor->height, sensor->fx,
-                       sensor->fy, sensor->cx, sensor->cy, c->p.range_mode, c->m, c->p, c->cfg.md_max_range, count_seeds ? 1 : 0,
-                       c->d_tick_seeds);
+    batch(base, nb, count_seeds);
     if (count_seeds) {
       ++c->tick_ticket;
       if (c->tick_ticket == 0) ++c->tick_ticket;
@@ -1979,9 +1974,33 @@ int khr_tick_ingest(khr_ctx* c, const khr_sensor* sensor, const khr_frame* frame
   if (!count_seeds && n_seed_pixels) std::memset(n_seed_pixels, 0, sizeof(uint32_t) * n_frames);
   if (!count_seeds && seed_counts_device) HIP_TRY(hipMemsetAsync(seed_counts_device, 0, sizeof(int64_t) * n_frames, c->stream));
   c->begun = false;
-  c->begin_in_ingest = false;
   undo.armed = false;
   return KHR_OK;
+}
+
+int khr_tick_ingest(khr_ctx* c, const khr_sensor* sensor, const khr_frame* frames, int n_frames, int count_seeds,
+                    int* slots_out, uint32_t* n_seed_pixels, int64_t* seed_counts_device) {
+  KHR_TRY(tickArgs(c, sensor, frames, n_frames, slots_out));
+  for (int i = 0; i < n_frames; ++i)
+    if (!frames[i].depth) return fail(KHR_EINVAL, "frame %d has no depth image", i);
+  return tickFrames(c, n_frames, count_seeds, slots_out, n_seed_pixels, seed_counts_device, [&](int base, int nb, int seeds) {
+    TickIngest t{};
+    int tw = 0, th = 0;
+    for (int k = 0; k < nb; ++k) {
+      const khr_frame& fr = frames[base + k];
+      FrameSlot& s = newFrameSlot(c, slots_out[base + k], *sensor, fr, fr.color != nullptr, fr.label != nullptr, true);
+      tw = s.tw, th = s.th;
+      t.depth_in[k] = fr.depth; t.rgb_in[k] = fr.color; t.label_in[k] = fr.label;
+      t.depth[k] = s.depth; t.range[k] = s.range; t.rgba[k] = s.rgba; t.label[k] = s.label; t.dyn[k] = s.dyn;
+      t.tile_max[k] = s.tile_max;
+      float R[9], tt[3];
+      makePose(fr.world_T_sensor, R, tt, t.Rw[k], t.tw[k]);
+      t.min_z_world[k] = static_cast<float>(fr.world_T_sensor[11] + static_cast<double>(c->cfg.md_min_z_coordinate));
+    }
+    hipLaunchKernelGGL(k_tick_ingest, dim3(tw * th, nb), dim3(256), 0, c->stream, t, tw, sensor->width, sensor->height, sensor->fx,
+                       sensor->fy, sensor->cx, sensor->cy, c->p.range_mode, c->m, c->p, c->cfg.md_max_range, seeds ? 1 : 0,
+                       c->d_tick_seeds);
+  });
 }
 
 // ---- sender-side ingest: converted planes travel, not raw frames -------------------------------------------------------
@@ -2009,7 +2028,7 @@ int khr_converted_views(const khr_sensor* sensor, const void* packed_device, int
 }
 
 int khr_export_converted(khr_ctx* c, int slot, void* packed_device, int with_depth) {
-  if (!c || !packed_device || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad slot");
+  if (!c || !packed_device || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad slot");
   HIP_TRY(hipSetDevice(c->device));
   const FrameSlot& s = c->slots[slot];
   const uint32_t n = static_cast<uint32_t>(s.sensor.width) * static_cast<uint32_t>(s.sensor.height);
@@ -2022,53 +2041,25 @@ int khr_export_converted(khr_ctx* c, int slot, void* packed_device, int with_dep
 
 int khr_tick_adopt(khr_ctx* c, const khr_sensor* sensor, const khr_converted_frame* frames, int n_frames, int count_seeds,
                    int* slots_out, uint32_t* n_seed_pixels, int64_t* seed_counts_device) {
-  if (!c || !sensor || !frames || !slots_out || n_frames < 1) return fail(KHR_EINVAL, "bad argument");
-  const size_t n = static_cast<size_t>(sensor->width) * sensor->height;
-  if (sensor->width < 2 || sensor->height < 2 || n > c->cfg.max_frame_pixels)
-    return fail(KHR_EINVAL, "frame %dx%d exceeds max_frame_pixels=%u", sensor->width, sensor->height, c->cfg.max_frame_pixels);
-  if (!(sensor->fx > 0.f) || !(sensor->fy > 0.f) || !(sensor->max_range > sensor->min_range))
-    return fail(KHR_EINVAL, "bad intrinsics / range");
-  if (static_cast<size_t>(n_frames) > c->slots.size()) return fail(KHR_EINVAL, "more frames than frame slots (num_frame_slots)");
+  KHR_TRY(tickArgs(c, sensor, frames, n_frames, slots_out));
   for (int i = 0; i < n_frames; ++i) {
     if (!frames[i].range || !frames[i].tile_max) return fail(KHR_EINVAL, "frame %d has no range image / range tiles", i);
     if (!frames[i].depth && c->p.range_mode != 0)
       return fail(KHR_EINVAL, "frame %d has no depth plane (only with range_mode 0 is depth == range where it is read)", i);
   }
-  HIP_TRY(hipSetDevice(c->device));
-  int rc = ensureTick(c);
-  if (rc) return rc;
-  count_seeds = count_seeds && c->cfg.with_tracking;
-  c->tick_seed_host.assign(n_frames, 0u);
-  c->tick_seed_collected = 0;
-  const int tw = (sensor->width + kTile - 1) / kTile, th = (sensor->height + kTile - 1) / kTile;
-  ScopedTimer tm(c, 6);
   // slots adopted by an EARLIER tick refer to planes in a receive buffer the caller is about to reuse: they
   // stop being readable here, instead of silently mixing the new tick's planes with the old tick's meta data
   for (FrameSlot& old : c->slots)
     if (old.x_range != nullptr) old.valid = false;
-  if ((rc = acquireTickSlots(c, n_frames, slots_out))) return rc;
-  TickSlotsGuard undo{c, slots_out, n_frames};
-  for (int base = 0; base < n_frames; base += kMaxTick) {
-    const int nb = std::min(kMaxTick, n_frames - base);
+  const size_t n = static_cast<size_t>(sensor->width) * sensor->height;
+  return tickFrames(c, n_frames, count_seeds, slots_out, n_seed_pixels, seed_counts_device, [&](int base, int nb, int seeds) {
     TickAdopt t{};
     for (int k = 0; k < nb; ++k) {
       const khr_converted_frame& fr = frames[base + k];
-      FrameSlot& s = c->slots[slots_out[base + k]];
-      s.sensor = *sensor;
-      s.meta = khr_frame{};
-      s.meta.timestamp_ns = fr.timestamp_ns;
-      std::memcpy(s.meta.world_T_sensor, fr.world_T_sensor, sizeof(s.meta.world_T_sensor));
-      s.has_color = fr.rgba != nullptr;
-      s.has_label = fr.label != nullptr;
-      s.has_obj = false;
-      if (c->obj_cv_slot == slots_out[base + k]) c->obj_cv_slot = -1;
-      s.objects_done = false;
-      s.clusters.clear();
-      s.sem_clusters.clear();
-      s.tw = tw;
-      s.th = th;
-      s.valid = true;
-      s.dyn_clean = true, s.dynw_valid = false;
+      khr_frame meta{};
+      meta.timestamp_ns = fr.timestamp_ns;
+      std::memcpy(meta.world_T_sensor, fr.world_T_sensor, sizeof(meta.world_T_sensor));
+      FrameSlot& s = newFrameSlot(c, slots_out[base + k], *sensor, meta, fr.rgba != nullptr, fr.label != nullptr, true);
       s.x_range = fr.range;
       s.x_depth = fr.depth ? fr.depth : fr.range;
       s.x_rgba = fr.rgba;
@@ -2082,29 +2073,8 @@ int khr_tick_adopt(khr_ctx* c, const khr_sensor* sensor, const khr_converted_fra
       t.min_z_world[k] = static_cast<float>(fr.world_T_sensor[11] + static_cast<double>(c->cfg.md_min_z_coordinate));
     }
     hipLaunchKernelGGL(k_tick_adopt, dim3(gridFor(n), nb), dim3(256), 0, c->stream, t, sensor->width, sensor->height, sensor->fx,
-                       sensor->fy, sensor->cx, sensor->cy, c->m, c->p, c->cfg.md_max_range, count_seeds ? 1 : 0, c->d_tick_seeds);
-    if (count_seeds) {
-      ++c->tick_ticket;
-      if (c->tick_ticket == 0) ++c->tick_ticket;
-      hipLaunchKernelGGL(k_tick_publish, dim3(1), dim3(64), 0, c->stream, c->d_tick_seeds, nb, c->h_tick.dev(), c->h_tick.dev() + 32,
-                         c->tick_ticket, seed_counts_device ? reinterpret_cast<long long*>(seed_counts_device) + base : nullptr);
-    }
-    HIP_TRY(hipGetLastError());
-    if (count_seeds && (n_seed_pixels || n_frames > kMaxTick)) {
-      rc = waitWord(c, &c->h_tick[32], c->tick_ticket, "tick seed counts");
-      if (rc) return rc;
-      for (int k = 0; k < nb; ++k) c->tick_seed_host[base + k] = c->h_tick[k];
-      c->tick_seed_collected = base + nb;
-    }
-  }
-  c->tick_seed_n = count_seeds ? n_frames : 0;
-  if (count_seeds && n_seed_pixels) std::memcpy(n_seed_pixels, c->tick_seed_host.data(), sizeof(uint32_t) * n_frames);
-  if (!count_seeds && n_seed_pixels) std::memset(n_seed_pixels, 0, sizeof(uint32_t) * n_frames);
-  if (!count_seeds && seed_counts_device) HIP_TRY(hipMemsetAsync(seed_counts_device, 0, sizeof(int64_t) * n_frames, c->stream));
-  c->begun = false;
-  c->begin_in_ingest = false;
-  undo.armed = false;
-  return KHR_OK;
+                       sensor->fy, sensor->cx, sensor->cy, c->m, c->p, c->cfg.md_max_range, seeds ? 1 : 0, c->d_tick_seeds);
+  });
 }
 
 int khr_tick_seed_counts(khr_ctx* c, uint32_t* n_seed_pixels, int n_frames) {
@@ -2162,7 +2132,7 @@ int khr_tick_integrate(khr_ctx* c, const int* slots, int n_frames, int use_mask,
   if (phases & 1) phases |= 12;  // bit 0 = allocation (bit 2) + initialisation / culling (bit 3)
   if ((phases & 14) != 14 && n_frames > kMaxTick) return fail(KHR_EINVAL, "split phases take at most %d frames", kMaxTick);
   for (int i = 0; i < n_frames; ++i) {
-    if (slots[i] < 0 || slots[i] >= static_cast<int>(c->slots.size()) || !c->slots[slots[i]].valid) return fail(KHR_EINVAL, "bad slot");
+    if (!validSlot(c, slots[i])) return fail(KHR_EINVAL, "bad slot");
     const khr_sensor &a = c->slots[slots[i]].sensor, &b = c->slots[slots[0]].sensor;
     if (a.width != b.width || a.height != b.height) return fail(KHR_EINVAL, "the frames of a tick must come from sensors of one image size");
   }
@@ -2241,7 +2211,7 @@ int khr_tick_integrate(khr_ctx* c, const int* slots, int n_frames, int use_mask,
       UpdateLists lists;
       lists.list = FuseList{c->d_tick_work4 + static_cast<size_t>(2 * k) * c->item_cap, c->d_tick_work4 + static_cast<size_t>(2 * k + 1) * c->item_cap,
                             c->item_cap, &c->d_tick_counts[2 * kMaxTick + 4 * k]};
-      rc = integrateUpdate(c, s, t.f[k], 1, use_mask, object_id, &lists);
+      rc = integrateUpdate(c, s, t.f[k], 1, use_mask, object_id, false, &lists);
       if (rc) return rc;
     }
     if (phases & 2) c->motion_ignore_epoch = 0;
@@ -2439,10 +2409,6 @@ static int waitTicket(khr_ctx* c, int word, uint32_t ticket, const char* what, h
 // per-cluster summaries (pixel count, AABB, vertex sum) of the freshly painted dynamic image, queued behind the paint pass
 // and published to pinned memory; khr_get_dynamic_clusters only has to wait for the ticket
 static int clusterSummaryLaunch(khr_ctx* c, FrameSlot& s, int max_id) {
-  if (c->md_defer_summary) {  // khr_process_frame queues the update kernels first: nothing on the frame's critical path reads the summaries
-    c->md_summary_pending = max_id;
-    return KHR_OK;
-  }
   const int tiles = ((s.sensor.width + kAccTile - 1) / kAccTile) * ((s.sensor.height + kAccTile - 1) / kAccTile);
   hipLaunchKernelGGL(k_cluster_summary, dim3(tiles), dim3(1024), 0, c->stream, makeDevFrame(c, s), s.dyn, c->d_md_acc,
                      s.dynw_valid ? static_cast<const uint8_t*>(s.dynw) : nullptr);
@@ -2454,8 +2420,16 @@ static int clusterSummaryLaunch(khr_ctx* c, FrameSlot& s, int max_id) {
   return KHR_OK;
 }
 
-static int motionFinish(khr_ctx* c, FrameSlot& s) {
+// deferred_summary: nullptr = the clusters' summaries are queued behind the paint pass; otherwise the caller queues them
+// (clusterSummaryLaunch) and receives the largest cluster id here, or -1 when there is nothing to summarise
+static int motionFinish(khr_ctx* c, FrameSlot& s, int* deferred_summary = nullptr) {
+  if (deferred_summary) *deferred_summary = -1;
   if (!c->cfg.with_tracking) return 0;
+  auto summary = [&](int max_id) {
+    if (!deferred_summary) return clusterSummaryLaunch(c, s, max_id);
+    *deferred_summary = max_id;
+    return static_cast<int>(KHR_OK);
+  };
   const int n = s.sensor.width * s.sensor.height;
   static const bool md_timing = std::getenv("KHR_MD_TIMING") != nullptr;
   auto t0 = std::chrono::steady_clock::now();
@@ -2684,7 +2658,7 @@ static int motionFinish(khr_ctx* c, FrameSlot& s) {
       s.dynw_valid = true;
       HIP_TRY(hipGetLastError());
       {
-        const int rcs = clusterSummaryLaunch(c, s, kept.back().first);
+        const int rcs = summary(kept.back().first);
         if (rcs) return rcs;
       }
       s.clusters.resize(kept.size());
@@ -2900,7 +2874,7 @@ static int motionFinish(khr_ctx* c, FrameSlot& s) {
     s.dynw_valid = true;
     HIP_TRY(hipGetLastError());
     {
-      const int rcs = clusterSummaryLaunch(c, s, kept.back().first);
+      const int rcs = summary(kept.back().first);
       if (rcs) return rcs;
     }
     s.clusters.resize(kept.size());
@@ -2916,7 +2890,7 @@ static int motionFinish(khr_ctx* c, FrameSlot& s) {
 }
 
 int khr_detect_motion(khr_ctx* c, int slot) {
-  if (!c || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad slot");
+  if (!c || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad slot");
   HIP_TRY(hipSetDevice(c->device));
   FrameSlot& s = c->slots[slot];
   int rc = motionLaunch(c, s, false);
@@ -2925,7 +2899,7 @@ int khr_detect_motion(khr_ctx* c, int slot) {
 }
 
 int khr_motion_keys(khr_ctx* c, int slot, void* keys_out, int on_device, uint32_t* n_seed_pixels) {
-  if (!c || !keys_out || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad argument");
+  if (!c || !keys_out || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad argument");
   HIP_TRY(hipSetDevice(c->device));
   FrameSlot& s = c->slots[slot];
   const int n = s.sensor.width * s.sensor.height;
@@ -2955,7 +2929,7 @@ int khr_motion_keys(khr_ctx* c, int slot, void* keys_out, int on_device, uint32_
 }
 
 int khr_detect_motion_from_keys(khr_ctx* c, int slot, const void* keys, int on_device) {
-  if (!c || !keys || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad argument");
+  if (!c || !keys || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad argument");
   HIP_TRY(hipSetDevice(c->device));
   FrameSlot& s = c->slots[slot];
   const int n = s.sensor.width * s.sensor.height;
@@ -2979,7 +2953,7 @@ int khr_detect_motion_from_keys(khr_ctx* c, int slot, const void* keys, int on_d
 size_t khr_motion_bits_bytes(int64_t n_pixels) { return n_pixels > 0 ? 16u * static_cast<size_t>((n_pixels + 63) / 64) : 0u; }
 
 int khr_motion_bits(khr_ctx* c, int slot, void* bits_device) {
-  if (!c || !bits_device || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad argument");
+  if (!c || !bits_device || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad argument");
   HIP_TRY(hipSetDevice(c->device));
   FrameSlot& s = c->slots[slot];
   const int n = s.sensor.width * s.sensor.height;
@@ -2994,7 +2968,7 @@ int khr_motion_bits(khr_ctx* c, int slot, void* bits_device) {
 }
 
 int khr_detect_motion_from_bits(khr_ctx* c, int slot, const void* bits_device) {
-  if (!c || !bits_device || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad argument");
+  if (!c || !bits_device || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad argument");
   HIP_TRY(hipSetDevice(c->device));
   FrameSlot& s = c->slots[slot];
   const int n = s.sensor.width * s.sensor.height;
@@ -3011,7 +2985,7 @@ int khr_detect_motion_from_bits(khr_ctx* c, int slot, const void* bits_device) {
 }
 
 int khr_dynamic_pack_bytes(khr_ctx* c, int slot, void* dst_device) {
-  if (!c || !dst_device || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad argument");
+  if (!c || !dst_device || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad argument");
   HIP_TRY(hipSetDevice(c->device));
   FrameSlot& s = c->slots[slot];
   const int n4 = (s.sensor.width * s.sensor.height + 3) / 4;  // (the slot's images are allocated for max_frame_pixels, a multiple of 4 or padded)
@@ -3021,7 +2995,7 @@ int khr_dynamic_pack_bytes(khr_ctx* c, int slot, void* dst_device) {
 }
 
 int khr_dynamic_unpack_bytes(khr_ctx* c, int slot, const void* src_device) {
-  if (!c || !src_device || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad argument");
+  if (!c || !src_device || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad argument");
   HIP_TRY(hipSetDevice(c->device));
   FrameSlot& s = c->slots[slot];
   const int n4 = (s.sensor.width * s.sensor.height + 3) / 4;
@@ -3037,8 +3011,7 @@ int khr_dynamic_unpack_bytes(khr_ctx* c, int slot, const void* src_device) {
 // object half keeps, and its adopted twin in the all-gather buffer, which the tick paints).  Stream-ordered device copy.
 int khr_mirror_dynamic(khr_ctx* c, int src, int dst) {
   if (!c) return fail(KHR_EINVAL, "null ctx");
-  const int ns = static_cast<int>(c->slots.size());
-  if (src < 0 || dst < 0 || src >= ns || dst >= ns || !c->slots[src].valid || !c->slots[dst].valid) return fail(KHR_EINVAL, "bad slot");
+  if (!validSlot(c, src) || !validSlot(c, dst)) return fail(KHR_EINVAL, "bad slot");
   if (src == dst) return KHR_OK;
   FrameSlot& a = c->slots[src];
   FrameSlot& b = c->slots[dst];
@@ -3057,7 +3030,7 @@ int khr_mirror_dynamic(khr_ctx* c, int src, int dst) {
 
 int khr_get_dynamic_clusters(khr_ctx* c, int slot, khr_cluster* out, int cap) {
   if (!c || cap < 0 || (!out && cap > 0)) return fail(KHR_EINVAL, "bad argument");
-  if (slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad slot");
+  if (!validSlot(c, slot)) return fail(KHR_EINVAL, "bad slot");
   const int n = static_cast<int>(c->slots[slot].clusters.size());
   if (n == 0) return 0;
   // the summaries (the tracker's bounding boxes, max_iou_tracker.cpp:466-476) were queued behind the paint pass and
@@ -3336,7 +3309,7 @@ static int objectsFinish(khr_ctx* c, int slot) {
 }
 
 int khr_detect_objects(khr_ctx* c, int slot) {
-  if (!c || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad slot");
+  if (!c || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad slot");
   if (!c->obj_configured) return fail(KHR_ESTATE, "khr_configure_object_detector has not been called");
   HIP_TRY(hipSetDevice(c->device));
   FrameSlot& s = c->slots[slot];
@@ -3353,7 +3326,7 @@ int khr_detect_objects(khr_ctx* c, int slot) {
 // nothing is awaited; khr_detect_objects(slot) later only collects the result.  Lets a caller that has other device work to
 // queue first (the sharded tick) overlap it with the detection of its own camera's frame.
 int khr_detect_objects_launch(khr_ctx* c, int slot) {
-  if (!c || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad slot");
+  if (!c || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad slot");
   if (!c->obj_configured) return KHR_ESTATE;  // (no detector configured: not an error here, nothing to launch)
   HIP_TRY(hipSetDevice(c->device));
   FrameSlot& s = c->slots[slot];
@@ -3365,7 +3338,7 @@ int khr_detect_objects_launch(khr_ctx* c, int slot) {
 
 int khr_get_semantic_clusters(khr_ctx* c, int slot, khr_cluster* out, int cap) {
   if (!c || cap < 0 || (!out && cap > 0)) return fail(KHR_EINVAL, "bad argument");
-  if (slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad slot");
+  if (!validSlot(c, slot)) return fail(KHR_EINVAL, "bad slot");
   const FrameSlot& s = c->slots[slot];
   if (!s.objects_done) return fail(KHR_ESTATE, "khr_detect_objects has not run for this frame");
   const int n = static_cast<int>(s.sem_clusters.size());
@@ -3382,7 +3355,7 @@ int khr_configure_object_voxel_sets(khr_ctx* c, float voxel_size) {
 }
 
 int khr_cluster_voxels_launch(khr_ctx* c, int slot, int which, float voxel_size) {
-  if (!c || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad slot");
+  if (!c || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad slot");
   if (!(voxel_size > 0.f) || (which != 0 && which != 1)) return fail(KHR_EINVAL, "bad argument");
   HIP_TRY(hipSetDevice(c->device));
   int rc = ensureGv(c);
@@ -3480,7 +3453,7 @@ int64_t khr_cluster_voxels(khr_ctx* c, int slot, int which, float voxel_size, in
 }
 
 int khr_pixel_iou(khr_ctx* c, int slot, const khr_pixel_ref* refs, int n_refs, int max_id, uint32_t* n_points, uint32_t* inter) {
-  if (!c || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad slot");
+  if (!c || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad slot");
   if (n_refs < 0 || n_refs > kPixRefs || (n_refs > 0 && (!refs || !n_points || !inter)) || max_id < 1 || max_id > 65535)
     return fail(KHR_EINVAL, "bad argument (at most %d references per call)", kPixRefs);
   if (n_refs == 0) return KHR_OK;
@@ -3510,8 +3483,7 @@ int khr_pixel_iou(khr_ctx* c, int slot, const khr_pixel_ref* refs, int n_refs, i
   for (int a = 0; a < n_refs; ++a) {
     if (done[a]) continue;
     const khr_pixel_ref& ra = refs[a];
-    if (ra.slot < 0 || ra.slot >= static_cast<int>(c->slots.size()) || !c->slots[ra.slot].valid || (ra.which != 0 && ra.which != 1))
-      return fail(KHR_EINVAL, "bad reference %d", a);
+    if (!validSlot(c, ra.slot) || (ra.which != 0 && ra.which != 1)) return fail(KHR_EINVAL, "bad reference %d", a);
     FrameSlot& src = c->slots[ra.slot];
     if (src.sensor.width != cur.sensor.width || src.sensor.height != cur.sensor.height)
       return fail(KHR_EINVAL, "reference frames must have the current frame's image size");
@@ -3538,7 +3510,7 @@ int khr_pixel_iou(khr_ctx* c, int slot, const khr_pixel_ref* refs, int n_refs, i
 
 int khr_forward_instances(khr_ctx* c, int slot, float max_range, const int32_t* background_ids, int n_background, int max_id,
                           khr_cluster* out) {
-  if (!c || slot < 0 || slot >= static_cast<int>(c->slots.size()) || !c->slots[slot].valid) return fail(KHR_EINVAL, "bad slot");
+  if (!c || !validSlot(c, slot)) return fail(KHR_EINVAL, "bad slot");
   if (!out || max_id < 1 || max_id > 65535 || n_background < 0 || (n_background > 0 && !background_ids)) return fail(KHR_EINVAL, "bad argument");
   FrameSlot& s = c->slots[slot];
   if (!s.has_label) return fail(KHR_ESTATE, "the frame has no label image to forward");
@@ -3589,14 +3561,14 @@ int khr_forward_instances(khr_ctx* c, int slot, float max_range, const int32_t* 
   return present;
 }
 
-int khr_generate_mesh(khr_ctx* c, int only_mesh_updated, int clear_flag) {
-  if (!c) return fail(KHR_EINVAL, "null ctx");
+// marching cubes on stream `st`: the context's (khr_generate_mesh), or khr_process_frame's mesh stream beside the tracking pass
+static int generateMesh(khr_ctx* c, hipStream_t st, int only_mesh_updated, int clear_flag) {
   HIP_TRY(hipSetDevice(c->device));
   DevMap& m = c->m;
   const size_t cap = m.capacity;
-  ScopedTimer tm(c, 5);
-  HIP_TRY(hipMemsetAsync(c->d_mesh_nwork, 0, sizeof(uint32_t), c->stream));
-  hipLaunchKernelGGL(k_mesh_prepare, dim3(gridFor(cap + 1)), dim3(256), 0, c->stream, m, only_mesh_updated ? BLK_MESH_UPDATED : 0u,
+  ScopedTimer tm(c, 5, st);
+  HIP_TRY(hipMemsetAsync(c->d_mesh_nwork, 0, sizeof(uint32_t), st));
+  hipLaunchKernelGGL(k_mesh_prepare, dim3(gridFor(cap + 1)), dim3(256), 0, st, m, only_mesh_updated ? BLK_MESH_UPDATED : 0u,
                      c->d_work, c->d_mesh_nwork, c->d_regen, c->d_mesh_count, c->d_mesh_old_off);
   MeshBuffers src = c->mesh[c->mesh_cur], dst = c->mesh[c->mesh_cur ^ 1];
   RemoteMeshHalo rmh{};
@@ -3613,16 +3585,16 @@ int khr_generate_mesh(khr_ctx* c, int only_mesh_updated, int clear_flag) {
   const uint32_t maxv = static_cast<uint32_t>(std::min<uint64_t>(c->cfg.max_mesh_vertices, 0xfffffff0ull));
   int rc = dispatchVps(c, [&](auto vps) {
     constexpr int V = decltype(vps)::value;
-    KHR_LAUNCH_TIMED(8, (k_marching_cubes<V, false>), dim3(kStreamGrid), dim3(256), m, c->p, c->d_work,
+    KHR_LAUNCH_TIMED_ON(8, st, (k_marching_cubes<V, false>), dim3(kStreamGrid), dim3(256), m, c->p, c->d_work,
                      c->d_mesh_nwork, c->d_mesh_count, c->d_mesh_offset, dst, clear_flag, maxv, rmh, 0xffffffffu,
                      static_cast<const uint8_t*>(nullptr), MeshBuffers{}, static_cast<const uint32_t*>(nullptr));
     size_t tb = c->cub_temp_bytes;
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_cub_temp, tb, c->d_mesh_count, c->d_mesh_offset,
-                                             static_cast<int>(cap + 1), c->stream));
+                                             static_cast<int>(cap + 1), st));
     // no host round trip: the capacity check happens on the device (C_MESH_OVERFLOW), totals are read lazily
     // emit pass + the copy of the kept blocks' vertices in ONE launch (the trailing kMoveWgs workgroups copy)
     constexpr uint32_t kMoveWgs = 1024;
-    KHR_LAUNCH_TIMED(9, (k_marching_cubes<V, true>), dim3(kStreamGrid + kMoveWgs), dim3(256), m, c->p, c->d_work,
+    KHR_LAUNCH_TIMED_ON(9, st, (k_marching_cubes<V, true>), dim3(kStreamGrid + kMoveWgs), dim3(256), m, c->p, c->d_work,
                      c->d_mesh_nwork, c->d_mesh_count, c->d_mesh_offset, dst, clear_flag, maxv, rmh, static_cast<uint32_t>(kStreamGrid),
                      static_cast<const uint8_t*>(c->d_regen), src, static_cast<const uint32_t*>(c->d_mesh_old_off));
     return KHR_OK;
@@ -3632,6 +3604,11 @@ int khr_generate_mesh(khr_ctx* c, int only_mesh_updated, int clear_flag) {
   c->mesh_stale = true;
   HIP_TRY(hipGetLastError());
   return KHR_OK;
+}
+
+int khr_generate_mesh(khr_ctx* c, int only_mesh_updated, int clear_flag) {
+  if (!c) return fail(KHR_EINVAL, "null ctx");
+  return generateMesh(c, c->stream, only_mesh_updated, clear_flag);
 }
 
 // archival kernels; no host round trip: the hash table / free list rebuild is conditional on the device
@@ -4036,7 +4013,6 @@ static int ingestAhead(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fr
   const int evi = c->ahead_ev_next;
   for (const auto& e : c->ahead_q)
     if (e.ev == evi) return fail(KHR_ESTATE, "look-ahead event ring out of step");
-  c->begin_in_ingest = false;
   // a host frame is converted on the host-to-device stream itself, right behind its planes: on the auxiliary stream the conversion
   // -- which waits ~205 us for a 720p frame's planes -- would sit in front of the CURRENT frame's object-detector kernels, whose
   // results the host waits for at the end of khr_process_frame (seen in the rocprofv3 timeline: main stream idle for 250 us)
@@ -4045,13 +4021,11 @@ static int ingestAhead(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fr
     if (!c->h2d_stream) KHR_TRY(createStream(c, c->h2d_stream));
     conv_stream = c->h2d_stream;
   }
-  c->ingest_stream = conv_stream;
-  c->host_input_pinned = !on_device;
-  c->h2d_ev_target = &c->ev_ahead_h2d[evi];
-  const int slot = khr_upload_frame(c, sensor, frame, on_device);
-  c->h2d_ev_target = nullptr;
-  c->host_input_pinned = false;
-  c->ingest_stream = nullptr;
+  IngestOpts opts;
+  opts.stream = conv_stream;
+  opts.pinned = !on_device;
+  opts.h2d_event = &c->ev_ahead_h2d[evi];
+  const int slot = uploadFrame(c, sensor, frame, on_device, opts);
   if (slot < 0) return slot;
   auto undo = [&](int rc) {  // nothing published yet: the slot simply is not a frame
     c->slots[slot].valid = false;
@@ -4093,6 +4067,11 @@ int khr_ingest_cancel(khr_ctx* c) {
   return KHR_OK;
 }
 
+static int snapshotUpdated(khr_ctx* c, hipStream_t st, uint32_t fields, int64_t cap_blocks, khr_snapshot** out);  // (with the snapshots, below)
+
+// One call per frame.  What it chooses for its own frame -- the ingest's stream, the deferred fold, the deferred cluster summaries, the
+// mesh kernels' fork point and stream, the snapshot's stream -- goes to the functions the step-wise entry points use as arguments; the
+// context only keeps what lives between calls.
 int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* frame, int on_device, uint32_t flags,
                       int* n_clusters) {
   if (!c) return fail(KHR_EINVAL, "null ctx");
@@ -4126,7 +4105,6 @@ int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fra
     khr_ctx* c;
     bool ok = false;
     ~Leave() {
-      c->defer_fold = false;
       if (!ok && c->fold_pending) {  // an error between the update launch and the tracking pass: fold now, nobody else will
         hipLaunchKernelGGL(k_fuse_fold, dim3((c->m.capacity + 255) / 256), dim3(256), 0, c->stream, c->m.blk_flags, c->m.blk_band,
                            &c->m.counters[C_MAX_SLOT], static_cast<const uint32_t*>(nullptr));
@@ -4156,14 +4134,12 @@ int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fra
     if (e.host) leave.own_h2d = c->ev_ahead_h2d[e.ev];
     c->slot_leases[slot].fetch_sub(1, std::memory_order_acq_rel);  // (the look-ahead's own lease)
   } else {
-    c->begin_in_ingest = !early;
     c->last_ingest_on_aux = early;
-    c->ingest_stream = early ? c->aux_stream : nullptr;
-    c->host_input_pinned = pinned_in;
-    slot = khr_upload_frame(c, sensor, frame, on_device);
-    c->host_input_pinned = false;
-    c->ingest_stream = nullptr;
-    c->begin_in_ingest = false;
+    IngestOpts opts;
+    opts.stream = early ? static_cast<hipStream_t>(c->aux_stream) : nullptr;
+    opts.pinned = pinned_in;
+    opts.begin = !early;  // (main-stream ingest: k_begin_integrate folded into it)
+    slot = uploadFrame(c, sensor, frame, on_device, opts);
     if (slot < 0) return slot;
   }
   c->last_frame_slot = slot;
@@ -4208,11 +4184,12 @@ int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fra
   bool speculated = false;
   size_t spec_timer = static_cast<size_t>(-1), spec_end = 0;
   // the update kernel's item records are folded into the block flags by the tracking pass's first kernel when it follows directly
-  c->defer_fold = (flags & KHR_PF_TRACKING) && c->cfg.with_tracking;  // (reset below, before the tracking pass)
+  const bool tracking = (flags & KHR_PF_TRACKING) && c->cfg.with_tracking;
+  const bool defer_fold = tracking;  // (`leave` folds if an error exit comes between the update launch and the tracking pass)
   // (not behind a seed frame: the frame is expected to have seeds, its clustering chain is queued ahead of the count instead)
   if (motion && c->cfg.with_tracking && !(c->md_seed_run && std::getenv("KHR_MD_NO_PRELAUNCH") == nullptr)) {
     const size_t n_pending = c->pending.size();
-    rc = integrateUpdate(c, s, f, 1, 0, -1, nullptr, &c->m.counters[C_N_SEEDS]);
+    rc = integrateUpdate(c, s, f, 1, 0, -1, defer_fold, nullptr, &c->m.counters[C_N_SEEDS]);
     if (rc) return rc;
     if (c->pending.size() > n_pending) spec_timer = n_pending;  // (first of the launch's timer samples)
     spec_end = c->pending.size();
@@ -4220,11 +4197,9 @@ int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fra
   }
   // (3) host looks at the seed count (clusters only exist when there are seeds)
   bool have_seeds = false;
+  int summary_pending = -1;  // largest id of the dynamic clusters whose summaries are queued behind the update kernels
   if (motion) {
-    c->md_defer_summary = true;
-    c->md_summary_pending = -1;
-    const int nc = motionFinish(c, s);
-    c->md_defer_summary = false;
+    const int nc = motionFinish(c, s, &summary_pending);
     if (nc < 0) return nc;
     if (n_clusters) *n_clusters = nc;
     have_seeds = c->cfg.with_tracking && c->h_pinned[0] != 0;
@@ -4234,37 +4209,30 @@ int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fra
   if (speculated && have_seeds && spec_timer != static_cast<size_t>(-1))  // the gated launches did nothing: not samples
     for (size_t i = spec_timer; i < spec_end && i < c->pending.size(); ++i) c->pending[i].which = -1;
   if (!speculated || have_seeds) {
-    rc = integrateUpdate(c, s, f, 1, motion ? 1 : 0, -1);
+    rc = integrateUpdate(c, s, f, 1, motion ? 1 : 0, -1, defer_fold);
     if (rc) return rc;
   }
-  if (c->md_summary_pending >= 0) {  // the dynamic clusters' summaries, behind the update kernels
-    const int pend = c->md_summary_pending;
-    c->md_summary_pending = -1;
-    if ((rc = clusterSummaryLaunch(c, s, pend))) return rc;
-  }
-  c->defer_fold = false;  // (from here on the tracking pass folds; `leave` covers the error exits above)
+  // the dynamic clusters' summaries: nothing on the frame's critical path reads them
+  if (summary_pending >= 0 && (rc = clusterSummaryLaunch(c, s, summary_pending))) return rc;
   // Output frames: marching cubes read distance / weight / colour / label / stamps, which the tracking pass does not touch
   // (it writes voxel flags, last_occupied, free bits and -- atomically -- block flags): the mesh kernels are forked onto
   // their own stream behind k_tracking_select (which has folded the update's block flags) and joined before archival.
-  const bool mc_fork = (flags & KHR_PF_OUTPUT) && (flags & KHR_PF_TRACKING) && c->cfg.with_tracking;
+  const bool mc_fork = (flags & KHR_PF_OUTPUT) && tracking;
   if (mc_fork) {
     if (!c->mc_stream) KHR_TRY(createStream(c, c->mc_stream));
     KHR_TRY(c->ev_mc_fork.ensure());
     KHR_TRY(c->ev_mc_join.ensure());
-    c->fork_after_select = true;
   }
-  rc = (flags & KHR_PF_TRACKING) ? khr_update_tracking(c, frame->timestamp_ns) : KHR_OK;
-  c->fork_after_select = false;
-  if (rc) return rc;
+  if (tracking) {  // (khr_update_tracking, with the mesh kernels' fork point behind k_tracking_select)
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = trackingPhase(c, frame->timestamp_ns, 3, mc_fork ? static_cast<hipEvent_t>(c->ev_mc_fork) : nullptr))) return rc;
+  }
   // output frames: which blocks the archival below will drop is decided now (the tracking pass has set the block flags it looks at);
   // their list goes to the host at once, the archival itself has to wait for the mesh kernels and the snapshot
   const bool early_list = (flags & KHR_PF_OUTPUT) && c->cfg.with_tracking;
   if (mc_fork) {
     HIP_TRY(hipStreamWaitEvent(c->mc_stream, c->ev_mc_fork, 0));
-    std::swap(c->stream, c->mc_stream);  // (khr_generate_mesh queues everything on the context's stream; both owners stay members)
-    rc = khr_generate_mesh(c, 1, 1);
-    std::swap(c->stream, c->mc_stream);
-    if (rc) return rc;
+    if ((rc = generateMesh(c, c->mc_stream, 1, 1))) return rc;
     HIP_TRY(hipEventRecord(c->ev_mc_join, c->mc_stream));
   }
   HT("pf_update_launched");
@@ -4283,16 +4251,13 @@ int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fra
       HIP_TRY(hipEventRecord(c->ev_snap_fork, c->stream));
       HIP_TRY(hipStreamWaitEvent(c->snap_stream, c->ev_snap_fork, 0));
       const int64_t snap_cap = c->cfg.max_snapshot_blocks ? c->cfg.max_snapshot_blocks : 8192;  // (100 KB per block)
-      c->snap_stream_override = c->snap_stream;
-      rc = khr_snapshot_updated(c, KHR_SNAP_ALL, snap_cap, &c->pending_snapshot);
-      c->snap_stream_override = nullptr;
-      if (rc) return rc;
+      if ((rc = snapshotUpdated(c, c->snap_stream, KHR_SNAP_ALL, snap_cap, &c->pending_snapshot))) return rc;
       HIP_TRY(hipEventRecord(c->ev_snap_join, c->snap_stream));
     }
     // (the list kernel on the main stream BEHIND the fork points: it runs beside the mesh kernels and the snapshot, not in front of them)
     if (early_list && (rc = removedPublishLaunch(c))) return rc;
     if (mc_fork) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_mc_join, 0));
-    else if ((rc = khr_generate_mesh(c, 1, 1))) return rc;
+    else if ((rc = generateMesh(c, c->stream, 1, 1))) return rc;
     if (snap) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_snap_join, 0));
     if (c->cfg.with_tracking) {
       if ((rc = resetInactiveLaunch(c, early_list, BLK_UPDATED))) return rc;  // (archival + the flag clearing of :169-171 in one pass)
@@ -5735,8 +5700,9 @@ int khr_reserve_snapshots(khr_ctx* c, uint32_t fields, int64_t cap_blocks, int n
   return KHR_OK;
 }
 
-int khr_snapshot_updated(khr_ctx* c, uint32_t fields, int64_t cap_blocks, khr_snapshot** out) {
-  if (!c || !out || !(fields & KHR_SNAP_EVERYTHING)) return fail(KHR_EINVAL, "bad argument");
+// the snapshot's kernels on stream `st`: the context's (khr_snapshot_updated), or khr_process_frame's snapshot stream
+static int snapshotUpdated(khr_ctx* c, hipStream_t st, uint32_t fields, int64_t cap_blocks, khr_snapshot** out) {
+  if (!out || !(fields & KHR_SNAP_EVERYTHING)) return fail(KHR_EINVAL, "bad argument");
   *out = nullptr;
   HIP_TRY(hipSetDevice(c->device));
   const bool trk = c->cfg.with_tracking, sem = c->cfg.with_semantics;
@@ -5782,7 +5748,6 @@ int khr_snapshot_updated(khr_ctx* c, uint32_t fields, int64_t cap_blocks, khr_sn
   snap->o.K = c->p.K;
   snap->o.KS = c->p.KS;
   snap->o.track_stamp = c->last_track_stamp;
-  hipStream_t st = c->snap_stream_override ? c->snap_stream_override : c->stream;
   hipError_t e = hipMemsetAsync(snap->d_count, 0, 4, st);
   int rc_ev = KHR_OK;
   if (e == hipSuccess) {
@@ -5805,6 +5770,11 @@ int khr_snapshot_updated(khr_ctx* c, uint32_t fields, int64_t cap_blocks, khr_sn
   }
   *out = snap.release();
   return KHR_OK;
+}
+
+int khr_snapshot_updated(khr_ctx* c, uint32_t fields, int64_t cap_blocks, khr_snapshot** out) {
+  if (!c) return fail(KHR_EINVAL, "bad argument");
+  return snapshotUpdated(c, c->stream, fields, cap_blocks, out);
 }
 
 int khr_take_snapshot(khr_ctx* c, khr_snapshot** out) {

@@ -431,6 +431,97 @@ def test_a_rejected_hand_over_does_not_wedge_the_context():
             a.free()
 
 
+def test_stepwise_calls_after_fused_calls():
+    """khr_process_frame and the step-by-step calls mixed on ONE context: whatever the fused call chooses for its own frame (ingest
+    stream, deferred fold, deferred cluster summaries, the mesh and snapshot streams) must not reach the step-wise call behind it,
+    nor the other way round.  Frames with i % 3 == 1 are step-wise, the others fused, so that both forms get output frames (every
+    fourth) and each form follows the other; 16 frames, because the scene's motion detector first fires at frame 13 (step-wise), then at
+    14 and 15 (fused, 15 with output): the clusters' summaries are read back in both forms.  Frame 5 is a fused call that FAILS behind its ingest (KHR_PF_OBJECTS without a
+    configured detector): the frame is lost, the oracle skips it, and the calls behind it still match.  A second context is fed
+    identically, except that it takes the fused output frames' snapshot step by step (khr_snapshot_updated between the tracking pass
+    and the archival): both snapshots list the same blocks."""
+    from common import DeviceArray
+    from khronos_amd.capi import KhronosAmdError
+    cfg, ctx, ora, s, sen, osen = make_pair(width=160, height=120, temporal_window=0.75, num_frame_slots=4)
+    ctx2 = type(ctx)(cfg)
+    held = []
+    base = ctx.PF_MOTION | ctx.PF_TRACKING | ctx.PF_INPUT_READY
+
+    def device_frame(c, fr):
+        f = c.make_frame(fr["stamp"], fr["pose"], 0)
+        dev = [DeviceArray(np.ascontiguousarray(fr[k])) for k in ("depth", "rgb", "label")]
+        held.append(dev)
+        f.depth, f.color, f.label = (d.data_ptr() for d in dev)
+        return f
+
+    def stepwise(c, fr, out_now):
+        slot = c.upload_frame(sen, fr["stamp"], fr["pose"], fr["depth"], fr["rgb"], fr["label"])
+        nc = c.detect_motion(slot)
+        c.integrate(slot, allocate_blocks=True, use_mask=True)
+        c.update_tracking(fr["stamp"])
+        removed = None
+        if out_now:
+            c.generate_mesh(True, True)
+            removed = c.reset_inactive()
+            c.clear_updated()
+        return slot, nc, removed
+
+    fired = {True: 0, False: 0}  # clusters found in fused / in step-wise frames
+    n_snap = 0
+    for i in range(16):
+        fr = s.render(i)
+        out_now = i % 4 == 3
+        fused = i % 3 != 1
+        if i == 5:  # fails behind the ingest: the frame is in its slot, nothing of it in the map
+            for c in (ctx, ctx2):
+                with pytest.raises(KhronosAmdError, match="KHR_PF_OBJECTS"):
+                    c.process_frame(sen, device_frame(c, fr), on_device=True, flags=base | c.PF_OBJECTS)
+            continue
+        if fused:
+            flags = base | ((ctx.PF_OUTPUT | ctx.PF_SNAPSHOT) if out_now else 0)
+            slot, nc = ctx.process_frame(sen, device_frame(ctx, fr), on_device=True, flags=flags)
+            removed = ctx.last_removed() if out_now else None
+            _, nc2 = ctx2.process_frame(sen, device_frame(ctx2, fr), on_device=True, flags=base)
+            if out_now:
+                snap, snap2 = ctx.take_snapshot(), ctx2.snapshot_updated()
+                assert snap is not None
+                ind, ind2 = snap.download()["indices"], snap2.download()["indices"]
+                snap.release()
+                snap2.release()
+                assert len(ind) > 0 and np.array_equal(ind, ind2), i
+                n_snap += 1
+                ctx2.generate_mesh(True, True)
+                assert np.array_equal(ctx2.reset_inactive(), removed), i
+                ctx2.clear_updated()
+        else:
+            slot, nc, removed = stepwise(ctx, fr, out_now)
+            _, nc2, removed2 = stepwise(ctx2, fr, out_now)
+            assert removed is None or np.array_equal(removed, removed2), i
+        n_o, dyn_o, _ = ora.detect_motion(osen, fr["stamp"], fr["pose"], fr["depth"])
+        assert nc == n_o and nc2 == n_o, (i, nc, nc2, n_o)
+        fired[fused] += nc
+        for k in ctx.dynamic_clusters(slot):
+            assert k["num_pixels_painted"] == int((dyn_o == k["id"]).sum()) > 0, (i, k["id"])
+        ora.integrate(osen, fr["stamp"], fr["pose"], fr["depth"], fr["rgb"], fr["label"], mask=dyn_o)
+        ora.update_tracking(fr["stamp"])
+        if out_now:
+            ora.generate_mesh(True, True)
+            ro = ora.reset_inactive()
+            ora.clear_updated()
+            assert np.array_equal(removed, ro), i
+            gm, om = ctx.download_mesh(), ora.mesh()
+            assert gm["points"].shape == om["points"].shape, i
+            assert np.abs(gm["points"] - om["points"]).max() <= TOL if len(om["points"]) else True
+    assert fired[True] > 0 and fired[False] > 0 and n_snap == 3
+    compare_maps(ctx, ora, max_blocks=60)
+    compare_maps(ctx2, ora, max_blocks=60)
+    ctx.sync()
+    ctx2.sync()
+    for dev in held:
+        for d in dev:
+            d.free()
+
+
 def test_two_shards_with_halo_exchange_equal_unsharded():
     """hash-range sharding + halo records: tracking / ever-free of 2 shards == the unsharded map, and the HIP
     halo records are bit-identical to the oracle's."""
