@@ -2,7 +2,7 @@
 // map housekeeping kernels.  gfx950, wave64.
 #pragma once
 #include <cstring>
-
+#include "khr_md_host.h"  // CompAcc
 #include "khr_device.h"
 
 namespace khr {
@@ -386,12 +386,12 @@ __global__ __launch_bounds__(256) void k_md_adjacency(const uint64_t* __restrict
 // is an order-free reduction: the first seed in the canonical (x, y, z) order (= the position of the cluster in the
 // reference's visiting order, ASSUMPTIONS.md C.1), the length of the cluster's pixel list (seed pixels + the pixels
 // of every adjacent boundary voxel once per adjacent seed, :255-265) and the voxel bounding box (merge pre-test).
-struct CompAcc {
-  unsigned long long n_pixels;
-  unsigned long long min_key;  // canonical-order key of the first seed
-  int32_t lo[3], hi[3];
-  uint32_t root, pad;
-};
+// The record is CompAcc of khr_md_host.h (the host reads it there, without HIP):
+//   n_pixels    length of the pixel list
+//   min_key     canonical-order key of the first seed (canonKey below)
+//   lo, hi      voxel bounding box
+//   root, pad   scratch while the components form; in the downloaded records the overlap row (k_md_comp_overlap)
+static_assert(sizeof(CompAcc) == 48, "CompAcc travels to the host as 12 words (k_publish)");
 __device__ inline unsigned long long canonKey(uint64_t packed) {
   int x, y, z;
   unpackKey(packed, &x, &y, &z);

@@ -307,7 +307,6 @@ struct khr_ctx {
   uint64_t seed_wait_late_us = 0, seed_wait_late_frame = 0, seed_wait_late_state = 0;
   bool last_ingest_on_aux = false;
   uint64_t n_md_device_merges = 0, n_md_host_walks = 0;  // seed frames whose clusters were merged from the device's overlap rows / walked on the host
-  std::vector<int32_t> h_md_bnd_deg;
   ClusterAcc* d_md_acc = nullptr;  // [256], index = cluster id
   // device components of the seed graph: head = {S, B, R, 0} followed by the component records
   uint32_t *d_md_parent = nullptr, *d_md_rootidx = nullptr;
@@ -324,12 +323,8 @@ struct khr_ctx {
   uint32_t md_last_seeds = 0;       // seed voxels of the previous seed frame (predicts which component path is needed)
   uint32_t* d_md_edges = nullptr;     // seed-seed edge list of the latest seed frame (k_md_adjacency -> k_md_comp_lds)
   uint32_t* d_md_scratch4 = nullptr;  // 4 words k_publish may zero
-  std::vector<uint64_t> h_md_seed_keys, h_md_bnd_keys;
-  std::vector<uint32_t> h_md_seed_counts, h_md_bnd_counts, h_md_adj;
-  PinnedBuf<uint32_t> h_md_walk;     // page-locked block the host walk's lists travel through (kernels read / write it: no copy engine)
+  PinnedBuf<uint32_t> h_md_walk;     // page-locked block the host walk's lists and final ids travel through (kernels read / write it: no copy engine)
   Event ev_md_walk_up;               // the last upload out of it has been consumed
-  std::vector<int32_t> h_md_seed_final, h_md_bnd_final;
-  std::vector<ClusterAcc> h_md_acc;
   PinnedBuf<ClusterAcc> h_md_acc_pinned;   // summaries of the latest seed frame (k_publish_cluster_acc), ticket h_pinned[7]
   uint32_t md_acc_ticket = 0;
   int md_acc_slot = -1;                    // the frame slot the published summaries belong to
@@ -1038,9 +1033,8 @@ int khr_create(const khr_config* cfg, khr_ctx** out) {
     KHR_CHAIN(devAlloc(c, &c->d_md_bnd_deg, c->md_list_cap, false));
     KHR_CHAIN(devAlloc(c, &c->d_md_bnd_mask, c->md_list_cap, false));
     KHR_CHAIN(devAlloc(c, &c->d_md_adj, static_cast<size_t>(c->md_list_cap) * 26, false));
-    {  // the host walk's page-locked block, for 16 k seed voxels to begin with (grown on demand: a growth is a hipHostMalloc inside a frame)
-      KHR_CHAIN(c->h_md_walk.alloc(std::min<size_t>(c->md_list_cap, 16384) * (3 + 26 + 3) + 16));
-    }
+    // the host walk's page-locked block (lists + final ids), for 16 k seed voxels to begin with (grown on demand: a growth is a hipHostMalloc inside a frame)
+    KHR_CHAIN(c->h_md_walk.alloc(std::min<size_t>(c->md_list_cap, 16384) * (3 + 26 + 3 + 3) + 16));
     // (not zeroed: devAlloc's memset is queued on the context's NON-BLOCKING stream, and the synchronous copy of the reduction
     //  identities below runs on the null stream -- nothing orders the two, and a memset that lands second leaves zeros, i.e.
     //  boxes clamped at 0 for the first seed frame's clusters.  Found by tests/test_gpu_ref_pin.py.)
@@ -2420,116 +2414,114 @@ static int clusterSummaryLaunch(khr_ctx* c, FrameSlot& s, int max_id) {
   return KHR_OK;
 }
 
-// deferred_summary: nullptr = the clusters' summaries are queued behind the paint pass; otherwise the caller queues them
-// (clusterSummaryLaunch) and receives the largest cluster id here, or -1 when there is nothing to summarise
-static int motionFinish(khr_ctx* c, FrameSlot& s, int* deferred_summary = nullptr) {
-  if (deferred_summary) *deferred_summary = -1;
-  if (!c->cfg.with_tracking) return 0;
-  auto summary = [&](int max_id) {
-    if (!deferred_summary) return clusterSummaryLaunch(c, s, max_id);
-    *deferred_summary = max_id;
-    return static_cast<int>(KHR_OK);
-  };
-  const int n = s.sensor.width * s.sensor.height;
-  static const bool md_timing = std::getenv("KHR_MD_TIMING") != nullptr;
-  auto t0 = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!md_timing) return;
-    const auto t1 = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[md] %s %.1f us\n", what, std::chrono::duration<double, std::micro>(t1 - t0).count());
-    t0 = t1;
-  };
-  // ---- device: seed / boundary voxel tables, compact lists, seed adjacency ------------------------
-  const int nn = c->cfg.md_neighbor_connectivity;
-  // Table size for THIS frame.  The allocation covers the worst case (every pixel its own voxel: 2 M slots at 720p), and the
-  // clear and the two compaction passes walk the whole table; a seed frame has ~20 pixels per seed voxel, so the
-  // optimistic size is 2 slots per seed PIXEL (the seed table can then never fill up).  The near / boundary tables
-  // (<= nn entries per seed voxel) may: the near table switches itself to direct mode on the device, a full boundary
-  // table raises the overflow flag and the frame is repeated with the full-size tables.  Likewise the lock-free
-  // component kernels (for more than 12 k seed voxels) are only queued when the previous seed frame came close to
-  // needing them; a frame that needs them unexpectedly is repeated.
+// ---- motion detector: the frame finish, the one place where host and device meet on the frame path; stages as motionFinish calls
+// them.  What the host decides (cluster order, merge groups, size filter, ids, the seed-graph walk) is in khr_md_host.h, free of HIP.
+// Test and A/B hooks, read once per call: tests flip them inside one process (KHR_MD_HOST_WALK / KHR_MD_LDS_MAX: khr_create).
+struct MdHooks {
+  bool no_device_merge, no_predict, no_prelaunch;
+  uint32_t table_log2, prelaunch_px;  // 0 = not set
+};
+static MdHooks mdHooks() {
+  static const bool no_device_merge = std::getenv("KHR_MD_NO_DEVICE_MERGE") != nullptr;  // the host walk decides the merges (once per process)
+  MdHooks h{};
+  h.no_device_merge = no_device_merge;
+  h.no_predict = std::getenv("KHR_MD_NO_PREDICT") != nullptr;      // the lock-free component kernels only after a repeat
+  h.no_prelaunch = std::getenv("KHR_MD_NO_PRELAUNCH") != nullptr;  // no chain queued ahead of the seed count
+  if (const char* e = std::getenv("KHR_MD_TABLE_LOG2")) h.table_log2 = static_cast<uint32_t>(std::min(30, std::max(4, std::atoi(e))));  // forces the repeat
+  if (const char* e = std::getenv("KHR_MD_PRELAUNCH_PX")) h.prelaunch_px = static_cast<uint32_t>(std::max(1, std::atoi(e)));  // a bound that is exceeded
+  return h;
+}
+
+// A frame that follows a seed frame gets its chain queued BEFORE the host has seen its seed count (mdRunChain), and
+// khr_process_frame, which expects seeds then, does not speculate the update kernel: both ask here.
+static bool mdQueuesAhead(const khr_ctx* c, const MdHooks& hooks) { return c->md_seed_run && c->seed_by_ticket && !hooks.no_prelaunch; }
+
+// Table size (as a mask) for a seed-pixel count.  The allocation covers the worst case (every pixel its own voxel: 2 M slots at 720p),
+// and the clear and the two compaction passes walk the whole table; a seed frame has ~20 pixels per seed voxel, so the optimistic size
+// is 2 slots per seed PIXEL (the seed table can then never fill up).  The near / boundary tables (<= nn entries per seed voxel) may: the
+// near table switches itself to direct mode on the device, a full boundary table raises the overflow flag and the frame is repeated.
+static uint32_t mdMaskFor(const khr_ctx* c, const MdHooks& hooks, uint32_t seed_pixels) {
+  uint32_t ts = 1u << 14;
+  while (ts < 2ull * std::max<uint32_t>(seed_pixels, 1u) && ts - 1 < c->md_mask) ts <<= 1;
+  if (hooks.table_log2) ts = 1u << hooks.table_log2;
+  return std::min(ts - 1, c->md_mask);
+}
+
+struct MdTables { VoxTable seeds, bnd, near; };  // the views of the voxel tables a chain worked on
+struct MdHead { uint32_t S, B, R, overflow; };   // seed voxels, boundary voxels, components, "a table filled up"
+// the chain up to the component records, sized for `seed_pixels` seed pixels (the kernels take the counts themselves from device
+// memory); *t = the table views it used.  device_merge: also mergeClusters' overlap rows (0 < separation <= 2 voxels: the voxel
+// pairs mergeClusters tests are within each other's 27-neighbourhood -- the device can answer)
+static int mdLaunchChain(khr_ctx* c, int n, uint32_t seed_pixels, uint32_t mask, bool global_components, bool device_merge, MdTables* t) {
   const uint32_t cap = c->md_list_cap;
+  const int nn = c->cfg.md_neighbor_connectivity;
   CompAcc* d_comp_out = reinterpret_cast<CompAcc*>(reinterpret_cast<uint8_t*>(c->d_md_n) + 16);
-  auto maskFor = [&](uint32_t seed_pixels) {
-    uint32_t ts = 1u << 14;
-    while (ts < 2ull * std::max<uint32_t>(seed_pixels, 1u) && ts - 1 < c->md_mask) ts <<= 1;
-    if (const char* e = std::getenv("KHR_MD_TABLE_LOG2")) ts = 1u << std::min(30, std::max(4, std::atoi(e)));  // test hook: forces the repeat
-    return std::min(ts - 1, c->md_mask);
-  };
+  const uint32_t seed_px = std::min<uint32_t>(seed_pixels, cap);  // #seed voxels <= #seed pixels
+  const size_t tsize = static_cast<size_t>(mask) + 1;
+  const VoxTable seeds = t->seeds = VoxTable{c->d_md_keys, c->d_md_counts, c->d_md_ids, mask};
+  const VoxTable bnd = t->bnd = VoxTable{c->d_md_keys + tsize, c->d_md_counts + tsize, c->d_md_ids + tsize, mask};
+  const VoxTable near = t->near = VoxTable{c->d_md_keys + 2 * tsize, c->d_md_counts + 2 * tsize, c->d_md_ids + 2 * tsize, mask};
+  int32_t* const d_box = reinterpret_cast<int32_t*>(c->d_md_scratch4) + 8;  // [0..5] seed voxel box, [6] direct mode, [7] edge count
+  hipLaunchKernelGGL(k_md_clear, dim3(1024), dim3(256), 0, c->stream, c->d_md_keys, c->d_md_counts, static_cast<uint32_t>(tsize), c->d_md_n, d_box);
+  hipLaunchKernelGGL(k_md_seed_insert, dim3(gridFor(n)), dim3(256), 0, c->stream, c->d_keys, n, seeds, c->d_md_n + 3);
+  hipLaunchKernelGGL(k_md_compact, dim3(gridFor(tsize)), dim3(256), 0, c->stream, seeds, c->d_md_seed_keys, c->d_md_seed_counts, c->d_md_n, cap, nullptr);
+  // (whether the `near` table can hold nn entries per seed voxel is decided on the device, which knows the voxel count)
+  hipLaunchKernelGGL(k_md_near_insert, dim3(256), dim3(256), 0, c->stream, c->d_md_seed_keys, c->d_md_n, cap, nn, near, c->d_md_n + 3, d_box);
+  hipLaunchKernelGGL(k_md_boundary_insert, dim3(gridFor(n)), dim3(256), 0, c->stream, c->d_keys, n, near, bnd, seeds, nn, 0, d_box, c->d_md_n + 3);
+  hipLaunchKernelGGL(k_md_compact, dim3(gridFor(tsize)), dim3(256), 0, c->stream, bnd, c->d_md_bnd_keys, c->d_md_bnd_counts,
+                     c->d_md_n + 1, cap, c->d_md_bnd_final, c->d_md_bnd_deg, c->d_md_bnd_mask);
+  uint32_t* const d_n_edges = c->d_md_scratch4 + 15;
+  hipLaunchKernelGGL(k_md_adjacency, dim3(1024), dim3(256), 0, c->stream, c->d_md_seed_keys, c->d_md_n, seeds, bnd, nn, cap,
+                     c->d_md_adj, c->d_md_edges, cap, d_n_edges);  // (room for `cap` edges)
+  // connected components of the seed graph + their order-free summaries, on the device
+  hipLaunchKernelGGL(k_md_comp_lds, dim3(1), dim3(1024), 0, c->stream, c->d_md_adj, c->d_md_n, cap, nn, c->d_md_parent, c->d_md_comp_acc,
+                     c->md_lds_max, c->d_md_edges, cap, d_n_edges, (c->p.dbg & 16) ? c->d_dbg : nullptr);
+  if (global_components) {
+    hipLaunchKernelGGL(k_md_comp_init, dim3(64), dim3(256), 0, c->stream, c->d_md_adj, c->d_md_n, cap, nn, c->d_md_parent, c->d_md_comp_acc,
+                       c->md_lds_max);
+    hipLaunchKernelGGL(k_md_comp_jump, dim3(64), dim3(256), 0, c->stream, c->d_md_n, cap, c->d_md_parent, c->md_lds_max);
+    hipLaunchKernelGGL(k_md_comp_union, dim3(1024), dim3(256), 0, c->stream, c->d_md_adj, c->d_md_n, cap, nn, c->d_md_parent, c->md_lds_max);
+  }
+  hipLaunchKernelGGL(k_md_comp_reduce, dim3(gridFor(seed_px)), dim3(256), 0, c->stream, c->d_md_seed_keys, c->d_md_seed_counts,
+                     c->d_md_bnd_keys, c->d_md_bnd_counts, c->d_md_adj, c->d_md_n, cap, nn, c->d_md_parent, c->d_md_comp_acc);
+  hipLaunchKernelGGL(k_md_comp_roots, dim3(gridFor(seed_px)), dim3(256), 0, c->stream, c->d_md_n, cap, c->d_md_parent, c->d_md_comp_acc,
+                     c->d_md_rootidx, c->d_md_n + 2, d_comp_out, kCompCap);
+  // mergeClusters' overlap rows (<= 64 components, separation <= 2 voxels; both kernels leave at once when there is one component)
+  if (device_merge) {
+    hipLaunchKernelGGL(k_md_bnd_comps, dim3(256), dim3(256), 0, c->stream, c->d_md_bnd_keys, c->d_md_n, cap, nn, seeds, c->d_md_parent,
+                       c->d_md_rootidx, c->d_md_bnd_mask);
+    hipLaunchKernelGGL(k_md_comp_overlap, dim3(512), dim3(256), 0, c->stream, c->d_md_seed_keys, c->d_md_bnd_keys, c->d_md_n, cap,
+                       c->cfg.md_min_separation_distance > 1.f ? 1 : 0, seeds, bnd, c->d_md_parent, c->d_md_rootidx, c->d_md_bnd_mask, d_comp_out);
+  }
+  HIP_TRY(hipGetLastError());
+  // counters + the first component records -> pinned memory by a one-workgroup kernel, the host spins on the ticket
+  if (++c->md_head_ticket == 0) ++c->md_head_ticket;
+  hipLaunchKernelGGL(k_publish, dim3(1), dim3(1024), 0, c->stream, c->d_md_n, reinterpret_cast<uint32_t*>(c->h_md_head.dev()),
+                     static_cast<uint32_t>(sizeof(CompAcc) / 4), kCompHead, c->h_pinned.dev() + 8, c->md_head_ticket, c->d_md_scratch4);
+  HIP_TRY(hipGetLastError());
+  return KHR_OK;
+}
+
+// Runs the chain until the head counts are on the host: 1 = *head and *t are this frame's, 0 = the frame has no seeds, < 0 = error.
+// Seed frames come in runs (something moves through the view for a while): a frame behind a seed frame has its chain queued
+// before the wait for its seed count, sized for twice the previous frame's seed pixels.  The kernels then sit in the stream's queue
+// behind the allocation / culling pass instead of arriving one by one after the count's trip to the host (78 us of idle main
+// stream in front of the chain and 5 - 15 us between its seventeen launches, profiles/r06_kernel_trace_frames.txt).  A frame without
+// seeds runs that chain on empty lists; more seed pixels than the bound: the chain is repeated with this frame's own sizes.  At
+// most two more repeats follow: a table filled up, or more seed voxels than the LDS kernel takes (the lock-free component kernels
+// are only queued when the previous seed frame came close to needing them).
+static int mdRunChain(khr_ctx* c, FrameSlot& s, const MdHooks& hooks, bool device_merge, MdTables* t, MdHead* head) {
+  const int n = s.sensor.width * s.sensor.height;
   bool with_global = c->md_host_walk || 2u * c->md_last_seeds > c->md_lds_max || c->md_lds_max < kCompLds;
-  if (std::getenv("KHR_MD_NO_PREDICT")) with_global = false;  // test hook: the lock-free path only after a repeat
-  VoxTable seeds{}, bnd{}, near{};
-  // (0 < separation <= 2 voxels: the voxel pairs mergeClusters tests are within each other's 27-neighbourhood -- the device can answer)
-  static const bool no_device_merge = std::getenv("KHR_MD_NO_DEVICE_MERGE") != nullptr;  // A/B and test hook: the host walk decides
-  const bool device_merge = !no_device_merge && !c->md_host_walk && c->cfg.md_min_separation_distance > 0.f && c->cfg.md_min_separation_distance <= 2.f;
-  // the chain up to the component records, sized for `seed_pixels` seed pixels (the kernels take the counts themselves from device memory)
-  auto launchChain = [&](uint32_t seed_pixels, uint32_t mask, bool global_components) {
-    const uint32_t seed_px = std::min<uint32_t>(seed_pixels, cap);  // #seed voxels <= #seed pixels
-    const size_t tsize = static_cast<size_t>(mask) + 1;
-    seeds = VoxTable{c->d_md_keys, c->d_md_counts, c->d_md_ids, mask};
-    bnd = VoxTable{c->d_md_keys + tsize, c->d_md_counts + tsize, c->d_md_ids + tsize, mask};
-    near = VoxTable{c->d_md_keys + 2 * tsize, c->d_md_counts + 2 * tsize, c->d_md_ids + 2 * tsize, mask};
-    int32_t* const d_box = reinterpret_cast<int32_t*>(c->d_md_scratch4) + 8;  // [0..5] seed voxel box, [6] direct mode, [7] edge count
-    hipLaunchKernelGGL(k_md_clear, dim3(1024), dim3(256), 0, c->stream, c->d_md_keys, c->d_md_counts, static_cast<uint32_t>(tsize), c->d_md_n, d_box);
-    hipLaunchKernelGGL(k_md_seed_insert, dim3(gridFor(n)), dim3(256), 0, c->stream, c->d_keys, n, seeds, c->d_md_n + 3);
-    hipLaunchKernelGGL(k_md_compact, dim3(gridFor(tsize)), dim3(256), 0, c->stream, seeds, c->d_md_seed_keys,
-                       c->d_md_seed_counts, c->d_md_n, cap, nullptr);
-    // (whether the `near` table can hold nn entries per seed voxel is decided on the device, which knows the voxel count)
-    hipLaunchKernelGGL(k_md_near_insert, dim3(256), dim3(256), 0, c->stream, c->d_md_seed_keys, c->d_md_n, cap, nn, near, c->d_md_n + 3, d_box);
-    hipLaunchKernelGGL(k_md_boundary_insert, dim3(gridFor(n)), dim3(256), 0, c->stream, c->d_keys, n, near, bnd, seeds, nn, 0, d_box,
-                       c->d_md_n + 3);
-    hipLaunchKernelGGL(k_md_compact, dim3(gridFor(tsize)), dim3(256), 0, c->stream, bnd, c->d_md_bnd_keys, c->d_md_bnd_counts,
-                       c->d_md_n + 1, cap, c->d_md_bnd_final, c->d_md_bnd_deg, c->d_md_bnd_mask);
-    const uint32_t edge_cap = cap;
-    uint32_t* const d_n_edges = c->d_md_scratch4 + 15;
-    hipLaunchKernelGGL(k_md_adjacency, dim3(1024), dim3(256), 0, c->stream, c->d_md_seed_keys, c->d_md_n, seeds, bnd, nn, cap,
-                       c->d_md_adj, c->d_md_edges, edge_cap, d_n_edges);
-    // connected components of the seed graph + their order-free summaries, on the device
-    hipLaunchKernelGGL(k_md_comp_lds, dim3(1), dim3(1024), 0, c->stream, c->d_md_adj, c->d_md_n, cap, nn, c->d_md_parent, c->d_md_comp_acc,
-                       c->md_lds_max, c->d_md_edges, edge_cap, d_n_edges, (c->p.dbg & 16) ? c->d_dbg : nullptr);
-    if (global_components) {
-      hipLaunchKernelGGL(k_md_comp_init, dim3(64), dim3(256), 0, c->stream, c->d_md_adj, c->d_md_n, cap, nn, c->d_md_parent, c->d_md_comp_acc,
-                         c->md_lds_max);
-      hipLaunchKernelGGL(k_md_comp_jump, dim3(64), dim3(256), 0, c->stream, c->d_md_n, cap, c->d_md_parent, c->md_lds_max);
-      hipLaunchKernelGGL(k_md_comp_union, dim3(1024), dim3(256), 0, c->stream, c->d_md_adj, c->d_md_n, cap, nn, c->d_md_parent, c->md_lds_max);
-    }
-    hipLaunchKernelGGL(k_md_comp_reduce, dim3(gridFor(seed_px)), dim3(256), 0, c->stream, c->d_md_seed_keys, c->d_md_seed_counts,
-                       c->d_md_bnd_keys, c->d_md_bnd_counts, c->d_md_adj, c->d_md_n, cap, nn, c->d_md_parent, c->d_md_comp_acc);
-    hipLaunchKernelGGL(k_md_comp_roots, dim3(gridFor(seed_px)), dim3(256), 0, c->stream, c->d_md_n, cap, c->d_md_parent, c->d_md_comp_acc,
-                       c->d_md_rootidx, c->d_md_n + 2, d_comp_out, kCompCap);
-    // mergeClusters' overlap rows (<= 64 components, separation <= 2 voxels; both kernels leave at once when there is one component)
-    if (device_merge) {
-      hipLaunchKernelGGL(k_md_bnd_comps, dim3(256), dim3(256), 0, c->stream, c->d_md_bnd_keys, c->d_md_n, cap, nn, seeds, c->d_md_parent,
-                         c->d_md_rootidx, c->d_md_bnd_mask);
-      hipLaunchKernelGGL(k_md_comp_overlap, dim3(512), dim3(256), 0, c->stream, c->d_md_seed_keys, c->d_md_bnd_keys, c->d_md_n, cap,
-                         c->cfg.md_min_separation_distance > 1.f ? 1 : 0, seeds, bnd, c->d_md_parent, c->d_md_rootidx, c->d_md_bnd_mask, d_comp_out);
-    }
-    HIP_TRY(hipGetLastError());
-    // counters + the first component records -> pinned memory by a one-workgroup kernel, the host spins on the ticket
-    if (++c->md_head_ticket == 0) ++c->md_head_ticket;
-    hipLaunchKernelGGL(k_publish, dim3(1), dim3(1024), 0, c->stream, c->d_md_n, reinterpret_cast<uint32_t*>(c->h_md_head.dev()),
-                       static_cast<uint32_t>(sizeof(CompAcc) / 4), kCompHead, c->h_pinned.dev() + 8, c->md_head_ticket, c->d_md_scratch4);
-    HIP_TRY(hipGetLastError());
-    return KHR_OK;
-  };
-  // (round 6) Seed frames come in runs (something moves through the view for a while): a frame that follows a seed frame gets its
-  // chain queued BEFORE the host has seen its seed count, sized for twice the previous frame's seed pixels.  The kernels then sit in
-  // the stream's queue behind the allocation / culling pass instead of arriving one by one after the count's trip to the host (78 us
-  // of idle main stream in front of the chain and 5 - 15 us between its seventeen launches, profiles/r06_kernel_trace_frames.txt).
-  // A frame without seeds runs the chain on empty lists (its records are never looked at); more seed pixels than the bound, or a
-  // table that filled up: the chain is repeated with this frame's own sizes, as before.
-  const bool no_prelaunch = std::getenv("KHR_MD_NO_PRELAUNCH") != nullptr;  // (A/B and test hook; looked at per frame: tests flip it inside one process)
+  if (hooks.no_predict) with_global = false;
   uint32_t pre_px = 0, pre_mask = 0;
-  if (c->md_seed_run && c->seed_by_ticket && !no_prelaunch) {
-    pre_px = std::min<uint32_t>(cap, std::max<uint32_t>(4096u, 2u * c->md_prev_seed_px));
-    if (const char* e = std::getenv("KHR_MD_PRELAUNCH_PX")) pre_px = static_cast<uint32_t>(std::max(1, std::atoi(e)));  // test hook: a bound that is exceeded
-    pre_mask = maskFor(pre_px);
-    const int rcl = launchChain(pre_px, pre_mask, with_global);
-    if (rcl) return rcl;
+  if (mdQueuesAhead(c, hooks)) {
+    pre_px = hooks.prelaunch_px ? hooks.prelaunch_px : std::min<uint32_t>(c->md_list_cap, std::max<uint32_t>(4096u, 2u * c->md_prev_seed_px));
+    pre_mask = mdMaskFor(c, hooks, pre_px);
+    KHR_TRY(mdLaunchChain(c, n, pre_px, pre_mask, with_global, device_merge, t));
     ++c->n_md_prelaunched;
   }
-  { const int rcw = waitSeedCount(c); if (rcw) return rcw; }
-  lap("wait seed count");
+  KHR_TRY(waitSeedCount(c));
   s.clusters.clear();
   c->md_seed_run = c->h_pinned[0] != 0;
   if (c->h_pinned[0] == 0) return 0;
@@ -2537,356 +2529,138 @@ static int motionFinish(khr_ctx* c, FrameSlot& s, int* deferred_summary = nullpt
   s.dyn_clean = false;  // clusters may be painted from here on
   bool chain_queued = pre_px != 0 && c->h_pinned[0] <= pre_px;
   if (pre_px != 0 && !chain_queued) ++c->n_md_prelaunch_repeats;
-  uint32_t mask = chain_queued ? pre_mask : maskFor(c->h_pinned[0]);
+  uint32_t mask = chain_queued ? pre_mask : mdMaskFor(c, hooks, c->h_pinned[0]);
   const uint32_t* cnt = reinterpret_cast<const uint32_t*>(c->h_md_head.get());
   for (int attempt = 0;; ++attempt) {
-    if (!chain_queued) {
-      const int rcl = launchChain(c->h_pinned[0], mask, with_global);
-      if (rcl) return rcl;
-    }
+    if (!chain_queued) KHR_TRY(mdLaunchChain(c, n, c->h_pinned[0], mask, with_global, device_merge, t));
     chain_queued = false;
-    {
-      const int rcw = waitTicket(c, 8, c->md_head_ticket, "the motion detector's component records");
-      if (rcw) return rcw;
-    }
-    if (attempt < 2) {
-      if (cnt[3] && mask < c->md_mask) {  // a table filled up: once more with the worst-case size
-        mask = c->md_mask;
-        continue;
-      }
-      if (cnt[0] > c->md_lds_max && !with_global) {  // more seed voxels than the single-workgroup kernel takes
-        with_global = true;
-        continue;
-      }
-    }
-    break;
+    KHR_TRY(waitTicket(c, 8, c->md_head_ticket, "the motion detector's component records"));
+    const bool table_full = cnt[3] && mask < c->md_mask;                                    // once more with the worst-case size
+    const bool lds_short = !table_full && cnt[0] > c->md_lds_max && !with_global;  // more seed voxels than the single-workgroup kernel takes
+    if (attempt == 2 || !(table_full || lds_short)) break;
+    if (table_full) mask = c->md_mask;
+    else with_global = true;
   }
-  c->md_last_seeds = cnt[0];
-  lap("tables + adjacency + components + head sync");
-  const uint32_t S = cnt[0], B = cnt[1], R = cnt[2];
-  if (cnt[3]) return fail(KHR_ENOMEM, "motion detector: neighbour table overflow (%u seed voxels)", S);
-  if (S > cap || B > cap) return fail(KHR_ENOMEM, "motion detector: %u seed / %u boundary voxels exceed the list capacity %u", S, B, cap);
-  if (R <= kCompCap && !c->md_host_walk) {
-    if (R > kCompHead) {
-      HIP_TRY(hipMemcpyAsync(c->h_md_head, c->d_md_n, 16 + sizeof(CompAcc) * R, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    const CompAcc* comp = reinterpret_cast<const CompAcc*>(c->h_md_head + 16);
-    // cluster order = order in which the walk meets the first seed of each component (ASSUMPTIONS.md C.1)
-    std::vector<uint32_t> order(R);
-    for (uint32_t i = 0; i < R; ++i) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return comp[a].min_key < comp[b].min_key; });
-    // mergeClusters (:274-355) can only join clusters whose voxel boxes come closer than min_separation_distance:
-    // the box gap is a lower bound of every pairwise voxel distance.  If no pair qualifies, nothing merges and the
-    // clusters are the components; otherwise the exact voxel-pair test runs on the host path below.
-    const float sep = c->cfg.md_min_separation_distance;
-    bool may_merge = false;
-    for (uint32_t i = 0; i < R && !may_merge; ++i)
-      for (uint32_t j = i + 1; j < R; ++j) {
-        int64_t gap2 = 0;
-        for (int d = 0; d < 3; ++d) {
-          const int64_t gp = std::max<int64_t>(0, std::max<int64_t>(static_cast<int64_t>(comp[i].lo[d]) - comp[j].hi[d],
-                                                                       static_cast<int64_t>(comp[j].lo[d]) - comp[i].hi[d]));
-          gap2 += gp * gp;
-        }
-        if (static_cast<float>(static_cast<int64_t>(std::sqrt(static_cast<double>(gap2)))) < sep) {
-          may_merge = true;
-          break;
-        }
-      }
-    // mergeClusters (:274-331) from the device's overlap rows: the clusters that end up together are the connected components of
-    // the overlap graph (getConnectedClusters recurses), the merged cluster stays at the position of its first member (`current`
-    // only ever absorbs later clusters) and its pixel list is the concatenation of the members' (:351-355)
-    std::vector<uint32_t> group(R);
-    for (uint32_t i = 0; i < R; ++i) group[i] = i;
-    const bool merge_here = may_merge && device_merge && R <= 64;
-    if (merge_here) {
-      std::function<uint32_t(uint32_t)> find = [&](uint32_t x) { return group[x] == x ? x : (group[x] = find(group[x])); };
-      for (uint32_t i = 0; i < R; ++i) {
-        unsigned long long row = (static_cast<unsigned long long>(comp[i].pad) << 32) | comp[i].root;
-        row &= ~(1ull << i);
-        while (row) {
-          const uint32_t j = static_cast<uint32_t>(__builtin_ctzll(row));
-          row &= row - 1ull;
-          if (j < R) group[find(i)] = find(j);
-        }
-      }
-      for (uint32_t i = 0; i < R; ++i) group[i] = find(i);
-      ++c->n_md_device_merges;
-    }
-    if (!may_merge || merge_here) {
-      c->stats.n_seeds = S;
-      // applyClusterLevelFilters (:365-379) + ids of writeClustersToData (:381-399)
-      int32_t* fin = reinterpret_cast<int32_t*>(c->h_md_head.get());  // the records are no longer needed once ids are taken
-      std::vector<std::pair<int, uint64_t>> kept;
-      std::vector<int32_t> tmp(R, 0);
-      std::vector<uint64_t> gpx(R, 0);
-      std::vector<int32_t> gid(R, -1);  // per group representative: -1 not met yet, 0 filtered out, > 0 the cluster's id
-      for (uint32_t r = 0; r < R; ++r) gpx[group[r]] += comp[r].n_pixels;
-      int id = 1;
-      for (uint32_t r : order) {
-        const uint32_t g = group[r];
-        if (gid[g] < 0) {  // the group's first member in cluster order: its position is the merged cluster's
-          const int size = static_cast<int>(gpx[g]);
-          if (size < c->cfg.md_min_cluster_size || size > c->cfg.md_max_cluster_size) {
-            gid[g] = 0;
-          } else {
-            gid[g] = id;
-            kept.emplace_back(id, gpx[g]);
-            if (id < 255) ++id;
-          }
-        }
-        tmp[r] = gid[g];
-      }
-      lap("component order + filter");
-      if (kept.empty()) return 0;
-      CompFinals inl{};
-      const int32_t* fin_dev = nullptr;
-      if (R <= static_cast<uint32_t>(kCompInline)) {  // the ids travel in the kernel arguments
-        for (uint32_t i = 0; i < R; ++i) inl.id[i] = tmp[i];
-      } else {
-        std::memcpy(fin, tmp.data(), sizeof(int32_t) * R);
-        HIP_TRY(hipMemcpyAsync(c->d_md_comp_final, fin, sizeof(int32_t) * R, hipMemcpyHostToDevice, c->stream));
-        fin_dev = c->d_md_comp_final;
-      }
-      // (the boundary voxels' final ids were zeroed by the compaction pass)
-      hipLaunchKernelGGL(k_md_comp_finals, dim3(1024), dim3(256), 0, c->stream, c->d_md_adj, c->d_md_n, cap, nn, c->d_md_parent,
-                         c->d_md_rootidx, fin_dev, inl, c->d_md_seed_final, c->d_md_bnd_final, c->d_md_bnd_deg);
-      hipLaunchKernelGGL(k_md_paint, dim3(gridFor(n)), dim3(256), 0, c->stream, c->d_keys, n, seeds, bnd, c->d_md_seed_final,
-                         c->d_md_bnd_final, s.dyn, c->d_md_bnd_deg, s.dynw);
-      s.dyn_clean = false;
-      s.dynw_valid = true;
-      HIP_TRY(hipGetLastError());
-      {
-        const int rcs = summary(kept.back().first);
-        if (rcs) return rcs;
-      }
-      s.clusters.resize(kept.size());
-      for (size_t i = 0; i < kept.size(); ++i) {
-        s.clusters[i] = khr_cluster{};
-        s.clusters[i].id = kept[i].first;
-        s.clusters[i].num_pixels_listed = kept[i].second;
-        s.clusters[i].semantic_id = -1;
-      }
-      lap("finals + paint launch");
-      return static_cast<int>(kept.size());
-    }
+  *head = MdHead{cnt[0], cnt[1], cnt[2], cnt[3]};
+  c->md_last_seeds = head->S;
+  if (head->overflow) return fail(KHR_ENOMEM, "motion detector: neighbour table overflow (%u seed voxels)", head->S);
+  if (head->S > c->md_list_cap || head->B > c->md_list_cap)
+    return fail(KHR_ENOMEM, "motion detector: %u seed / %u boundary voxels exceed the list capacity %u", head->S, head->B, c->md_list_cap);
+  return 1;
+}
+
+// Shared tail of both finishes, behind the final ids on the device: the paint pass, the clusters' summaries (queued here, or left
+// to the caller with the largest id in *deferred_summary) and the slot's cluster list.  Returns the number of clusters.
+static int mdPaintAndList(khr_ctx* c, FrameSlot& s, const MdTables& t, const mdh::Kept& kept, int* deferred_summary) {
+  const int n = s.sensor.width * s.sensor.height;
+  hipLaunchKernelGGL(k_md_paint, dim3(gridFor(n)), dim3(256), 0, c->stream, c->d_keys, n, t.seeds, t.bnd, c->d_md_seed_final,
+                     c->d_md_bnd_final, s.dyn, c->d_md_bnd_deg, s.dynw);
+  s.dyn_clean = false, s.dynw_valid = true;
+  HIP_TRY(hipGetLastError());
+  if (deferred_summary) *deferred_summary = kept.back().first;
+  else KHR_TRY(clusterSummaryLaunch(c, s, kept.back().first));
+  s.clusters.assign(kept.size(), khr_cluster{});
+  for (size_t i = 0; i < kept.size(); ++i) {
+    s.clusters[i].id = kept[i].first;
+    s.clusters[i].num_pixels_listed = kept[i].second;
+    s.clusters[i].semantic_id = -1;
   }
-  c->stats.n_seeds = S;
-  ++c->n_md_host_walks;
-  std::vector<uint64_t>& sk = c->h_md_seed_keys;
-  std::vector<uint64_t>& bk = c->h_md_bnd_keys;
-  std::vector<uint32_t>&sc = c->h_md_seed_counts, &bc = c->h_md_bnd_counts, &adj = c->h_md_adj;
-  sk.resize(S); sc.resize(S); adj.resize(static_cast<size_t>(S) * nn); bk.resize(B); bc.resize(B);
-  // The lists reach the host through a page-locked block that a kernel writes (and the finals go back the same way): copies
-  // into these pageable vectors went through the copy engines, where -- with a consumer downloading an output's 90 - 190 MB at
-  // the same time -- this frame's few kilobytes waited 7 ms (profiles/r05_host_consumer_40.txt).
-  const size_t w_sk = 2 * static_cast<size_t>(S), w_sc = S, w_adj = static_cast<size_t>(S) * nn, w_bk = 2 * static_cast<size_t>(B), w_bc = B;
-  const size_t walk_words = w_sk + w_sc + w_adj + w_bk + w_bc + 16;
+  return static_cast<int>(kept.size());
+}
+
+// Finish from the records: the clusters are the components, or (merge_here) the groups the device's overlap rows connect.  The
+// host only numbers them; the ids go back inline or by a copy, and k_md_comp_finals spreads them over the listed voxels.
+static int mdFinishFromRecords(khr_ctx* c, FrameSlot& s, const MdTables& t, const CompAcc* comp, uint32_t R, bool merge_here, int* deferred_summary) {
+  const std::vector<uint32_t> order = mdh::clusterOrder(comp, R);
+  const std::vector<uint32_t> group = merge_here ? mdh::groupsFromRows(comp, R) : mdh::Groups(R).labels();
+  std::vector<int32_t> ids;
+  const mdh::Kept kept = mdh::numberClusters(order.data(), group.data(), R, [&](uint32_t r) { return comp[r].n_pixels; },
+                                             c->cfg.md_min_cluster_size, c->cfg.md_max_cluster_size, &ids);
+  if (kept.empty()) return 0;
+  CompFinals inl{};
+  const int32_t* fin_dev = nullptr;
+  if (R <= static_cast<uint32_t>(kCompInline)) {  // the ids travel in the kernel arguments
+    std::copy(ids.begin(), ids.end(), inl.id);
+  } else {
+    int32_t* fin = reinterpret_cast<int32_t*>(c->h_md_head.get());  // the records are no longer needed once ids are taken
+    std::copy(ids.begin(), ids.end(), fin);
+    HIP_TRY(hipMemcpyAsync(c->d_md_comp_final, fin, sizeof(int32_t) * R, hipMemcpyHostToDevice, c->stream));
+    fin_dev = c->d_md_comp_final;
+  }
+  // (the boundary voxels' final ids were zeroed by the compaction pass)
+  hipLaunchKernelGGL(k_md_comp_finals, dim3(1024), dim3(256), 0, c->stream, c->d_md_adj, c->d_md_n, c->md_list_cap, c->cfg.md_neighbor_connectivity,
+                     c->d_md_parent, c->d_md_rootidx, fin_dev, inl, c->d_md_seed_final, c->d_md_bnd_final, c->d_md_bnd_deg);
+  return mdPaintAndList(c, s, t, kept, deferred_summary);
+}
+
+static void mdCopyWords(khr_ctx* c, const void* src, void* dst, size_t words) {
+  if (words) hipLaunchKernelGGL(k_copy_words, dim3(static_cast<unsigned>((words + 255) / 256)), dim3(256), 0, c->stream,
+                                static_cast<const uint32_t*>(src), static_cast<uint32_t*>(dst), static_cast<uint32_t>(words));
+}
+
+// Finish by the host walk.  The lists come down and the final ids go up through a page-locked block that kernels write and read:
+// copies through the copy engines -- with a consumer downloading an output's 90 - 190 MB at the same time -- made this frame's
+// few kilobytes wait 7 ms (profiles/r05_host_consumer_40.txt).  The walk reads the lists where they land and writes its results
+// behind them in the same block, so nothing is copied on the host; the 64-bit lists come first to keep them aligned.
+static int mdFinishByWalk(khr_ctx* c, FrameSlot& s, const MdTables& t, const MdHead& head, int* deferred_summary) {
+  const size_t S = head.S, B = head.B, nn = static_cast<size_t>(c->cfg.md_neighbor_connectivity);
+  const size_t o_sk = 0, o_bk = o_sk + 2 * S, o_sc = o_bk + 2 * B, o_adj = o_sc + S, o_bc = o_adj + S * nn;  // lists, in words
+  const size_t o_sf = o_bc + B, o_bf = o_sf + S, o_bd = o_bf + B, walk_words = o_bd + B + 16;                // results
   if (c->ev_md_walk_up) HIP_TRY(hipEventSynchronize(c->ev_md_walk_up));  // (the previous seed frame's upload reads the block)
   if (walk_words > c->h_md_walk.count()) {
     const size_t want = std::max<size_t>(2 * walk_words, 1u << 18);
     if (c->h_md_walk.reserve(want)) return fail(KHR_ENOMEM, "page-locked block of the motion detector's host walk (%zu bytes)", want * 4);
   }
   KHR_TRY(c->ev_md_walk_up.ensure());
-  uint32_t* const walk_dev = c->h_md_walk.dev();
-  {
-    size_t o = 0;
-    auto down = [&](const void* src, size_t words) {
-      if (words) hipLaunchKernelGGL(k_copy_words, dim3(static_cast<unsigned>((words + 255) / 256)), dim3(256), 0, c->stream,
-                                    static_cast<const uint32_t*>(src), walk_dev + o, static_cast<uint32_t>(words));
-      o += words;
-    };
-    down(c->d_md_seed_keys, w_sk);
-    down(c->d_md_seed_counts, w_sc);
-    down(c->d_md_adj, w_adj);
-    down(c->d_md_bnd_keys, w_bk);
-    down(c->d_md_bnd_counts, w_bc);
-    HIP_TRY(hipGetLastError());
-  }
+  uint32_t *const w = c->h_md_walk, *const w_dev = c->h_md_walk.dev();
+  mdCopyWords(c, c->d_md_seed_keys, w_dev + o_sk, 2 * S);
+  mdCopyWords(c, c->d_md_bnd_keys, w_dev + o_bk, 2 * B);
+  mdCopyWords(c, c->d_md_seed_counts, w_dev + o_sc, S);
+  mdCopyWords(c, c->d_md_adj, w_dev + o_adj, S * nn);
+  mdCopyWords(c, c->d_md_bnd_counts, w_dev + o_bc, B);
+  HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
-  {
-    const uint32_t* w = c->h_md_walk;
-    std::memcpy(sk.data(), w, w_sk * 4); w += w_sk;
-    std::memcpy(sc.data(), w, w_sc * 4); w += w_sc;
-    std::memcpy(adj.data(), w, w_adj * 4); w += w_adj;
-    if (B) {
-      std::memcpy(bk.data(), w, w_bk * 4); w += w_bk;
-      std::memcpy(bc.data(), w, w_bc * 4);
-    }
-  }
+  const mdh::WalkLists lists{reinterpret_cast<const uint64_t*>(w + o_sk), reinterpret_cast<const uint64_t*>(w + o_bk), w + o_sc, w + o_bc, w + o_adj,
+                             head.S, head.B, static_cast<int>(nn)};
+  const mdh::Kept kept = mdh::walkClusters(lists, c->cfg.md_min_separation_distance, c->cfg.md_min_cluster_size, c->cfg.md_max_cluster_size,
+                                        reinterpret_cast<int32_t*>(w + o_sf), reinterpret_cast<int32_t*>(w + o_bf), reinterpret_cast<int32_t*>(w + o_bd));
+  if (kept.empty()) return 0;
+  mdCopyWords(c, w_dev + o_sf, c->d_md_seed_final, S);
+  mdCopyWords(c, w_dev + o_bf, c->d_md_bnd_final, B);
+  mdCopyWords(c, w_dev + o_bd, c->d_md_bnd_deg, B);
+  HIP_TRY(hipEventRecord(c->ev_md_walk_up, c->stream));
+  return mdPaintAndList(c, s, t, kept, deferred_summary);
+}
 
-  lap("list download");
-  // ---- host: the seed-graph walk on compact ids (sequential in the reference too) ---------------
-  struct G { int64_t x, y, z; };
-  auto unpack = [](uint64_t k) {
-    int x, y, z;
-    unpackKey(k, &x, &y, &z);
-    return G{x, y, z};
-  };
-  // canonical seed order: ascending (x, y, z) (ASSUMPTIONS.md C.1)
-  std::vector<uint32_t> order(S);
-  std::vector<G> sg(S);
-  for (uint32_t i = 0; i < S; ++i) {
-    order[i] = i;
-    sg[i] = unpack(sk[i]);
-  }
-  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-    const G &ga = sg[a], &gb = sg[b];
-    return ga.x != gb.x ? ga.x < gb.x : (ga.y != gb.y ? ga.y < gb.y : ga.z < gb.z);
-  });
-  struct Cluster {
-    uint64_t n_pixels = 0;        // with the duplicates the reference produces (:255-265)
-    std::vector<uint32_t> seeds;  // seed ids
-    std::vector<uint32_t> bnds;   // boundary ids (unique)
-    int64_t lo[3], hi[3];
-  };
-  std::vector<Cluster> clusters;
-  std::vector<uint8_t> closed(S, 0);
-  // clusterDynamicVoxels (free_space_motion_detector.cpp:205-272)
-  std::vector<uint32_t> stack;
-  for (uint32_t s0 : order) {
-    if (closed[s0]) continue;
-    stack.assign(1, s0);
-    Cluster cl;
-    while (!stack.empty()) {
-      const uint32_t r = stack.back();
-      stack.pop_back();
-      if (closed[r]) continue;
-      closed[r] = 1;
-      cl.n_pixels += sc[r];
-      cl.seeds.push_back(r);
-      for (int k = 0; k < nn; ++k) {
-        const uint32_t a = adj[static_cast<size_t>(r) * nn + k];
-        if (a == 0xffffffffu) continue;
-        if (a & 0x80000000u) {
-          stack.push_back(a & 0x7fffffffu);
-        } else {
-          cl.n_pixels += bc[a];  // appended once per adjacent expanded seed
-          cl.bnds.push_back(a);
-        }
-      }
-    }
-    std::sort(cl.bnds.begin(), cl.bnds.end());
-    cl.bnds.erase(std::unique(cl.bnds.begin(), cl.bnds.end()), cl.bnds.end());
-    clusters.push_back(std::move(cl));
-  }
-  lap("graph walk");
-  const size_t nc = clusters.size();
-  std::vector<std::vector<G>> vox(nc);
-  for (size_t i = 0; i < nc; ++i) {
-    Cluster& cl = clusters[i];
-    for (int d = 0; d < 3; ++d) { cl.lo[d] = INT64_MAX; cl.hi[d] = INT64_MIN; }
-    for (uint32_t r : cl.seeds) vox[i].push_back(sg[r]);
-    for (uint32_t r : cl.bnds) vox[i].push_back(unpack(bk[r]));
-    for (const G& g : vox[i]) {
-      const int64_t v[3] = {g.x, g.y, g.z};
-      for (int d = 0; d < 3; ++d) { cl.lo[d] = std::min(cl.lo[d], v[d]); cl.hi[d] = std::max(cl.hi[d], v[d]); }
-    }
-  }
-  // mergeClusters (:274-355); (p1 - p2).norm() on int64 vectors truncates to integer (ASSUMPTIONS.md C.2)
+// The clusters of a frame whose seed pixels are being counted; returns their number.  deferred_summary: nullptr = the clusters'
+// summaries are queued behind the paint pass; otherwise the caller queues them (clusterSummaryLaunch) and receives the largest
+// cluster id here, or -1 when there is nothing to summarise
+static int motionFinish(khr_ctx* c, FrameSlot& s, int* deferred_summary = nullptr) {
+  if (deferred_summary) *deferred_summary = -1;
+  if (!c->cfg.with_tracking) return 0;
+  const MdHooks hooks = mdHooks();
   const float sep = c->cfg.md_min_separation_distance;
-  auto overlapTest = [&](size_t i, size_t j) {
-    // exact bounding-box rejection: a lower bound of every pairwise squared distance
-    int64_t gap2 = 0;
-    for (int d = 0; d < 3; ++d) {
-      const int64_t gp = std::max<int64_t>(0, std::max(clusters[i].lo[d] - clusters[j].hi[d], clusters[j].lo[d] - clusters[i].hi[d]));
-      gap2 += gp * gp;
+  const bool device_merge = !hooks.no_device_merge && !c->md_host_walk && sep > 0.f && sep <= 2.f;
+  MdTables t{};
+  MdHead head{};
+  const int rc = mdRunChain(c, s, hooks, device_merge, &t, &head);
+  if (rc <= 0) return rc;
+  c->stats.n_seeds = head.S;
+  if (head.R <= kCompCap && !c->md_host_walk) {
+    if (head.R > kCompHead) {  // (the first kCompHead records came with the head counts)
+      HIP_TRY(hipMemcpyAsync(c->h_md_head, c->d_md_n, 16 + sizeof(CompAcc) * head.R, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    if (!(static_cast<float>(static_cast<int64_t>(std::sqrt(static_cast<double>(gap2)))) < sep)) return false;
-    for (const G& a : vox[i])
-      for (const G& b : vox[j]) {
-        const int64_t dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
-        const int64_t n2 = dx * dx + dy * dy + dz * dz;
-        if (static_cast<float>(static_cast<int64_t>(std::sqrt(static_cast<double>(n2)))) < sep) return true;
-      }
-    return false;
-  };
-  std::vector<uint8_t> overlap(nc * nc, 0);
-  for (size_t i = 0; i < nc; ++i)
-    for (size_t j = i + 1; j < nc; ++j) overlap[i * nc + j] = overlap[j * nc + i] = overlapTest(i, j);
-  std::vector<uint8_t> merged(nc, 0), keep(nc, 0);
-  std::function<void(size_t, std::vector<size_t>&)> connected = [&](size_t ci, std::vector<size_t>& outv) {
-    for (size_t i = 0; i < nc; ++i) {
-      if (merged[i]) continue;
-      if (overlap[ci * nc + i]) {
-        merged[i] = 1;
-        outv.push_back(i);
-        connected(i, outv);
-      }
-    }
-  };
-  for (size_t cur = 0; cur < nc; ++cur) {
-    if (merged[cur]) continue;
-    std::vector<size_t> idx;
-    connected(cur, idx);
-    for (size_t i : idx) {
-      if (i == cur) continue;
-      clusters[cur].n_pixels += clusters[i].n_pixels;
-      clusters[cur].seeds.insert(clusters[cur].seeds.end(), clusters[i].seeds.begin(), clusters[i].seeds.end());
-      clusters[cur].bnds.insert(clusters[cur].bnds.end(), clusters[i].bnds.begin(), clusters[i].bnds.end());
-    }
-    keep[cur] = 1;
+    const CompAcc* comp = reinterpret_cast<const CompAcc*>(c->h_md_head + 16);
+    // no two boxes closer than the separation: the clusters are the components.  Otherwise the device's overlap rows say who
+    // merges (they exist for up to 64 components), or the exact voxel-pair test runs in the host walk below
+    const bool may_merge = mdh::mayMerge(comp, head.R, sep);
+    const bool merge_here = may_merge && device_merge && head.R <= 64;
+    if (merge_here) ++c->n_md_device_merges;
+    if (!may_merge || merge_here) return mdFinishFromRecords(c, s, t, comp, head.R, merge_here, deferred_summary);
   }
-  lap("merge");
-  // applyClusterLevelFilters (:365-379) + writeClustersToData (:381-399): later clusters overwrite earlier ones
-  std::vector<int32_t>&seed_final = c->h_md_seed_final, &bnd_final = c->h_md_bnd_final, &bnd_deg = c->h_md_bnd_deg;
-  seed_final.assign(S, 0);
-  bnd_final.assign(std::max<uint32_t>(B, 1), 0);
-  bnd_deg.assign(std::max<uint32_t>(B, 1), 0);  // per boundary voxel: how many seeds of kept clusters list it (:255-265)
-  int id = 1, n_out = 0;
-  std::vector<std::pair<int, uint64_t>> kept;  // (id, pixel list length incl. duplicates)
-  for (size_t ci = 0; ci < nc; ++ci) {
-    if (!keep[ci]) continue;
-    const int size = static_cast<int>(clusters[ci].n_pixels);
-    if (size < c->cfg.md_min_cluster_size || size > c->cfg.md_max_cluster_size) continue;
-    kept.emplace_back(id, clusters[ci].n_pixels);
-    for (uint32_t r : clusters[ci].seeds) {
-      seed_final[r] = id;
-      for (int k = 0; k < nn; ++k) {
-        const uint32_t a = adj[static_cast<size_t>(r) * nn + k];
-        if (a != 0xffffffffu && !(a & 0x80000000u)) ++bnd_deg[a];
-      }
-    }
-    for (uint32_t r : clusters[ci].bnds) bnd_final[r] = id;
-    if (id < 255) ++id;
-    ++n_out;
-  }
-  if (n_out > 0) {
-    // the host vectors are context members, so the asynchronous upload may outlive this call
-    {
-      uint32_t* w = c->h_md_walk;  // (S + 2 B words: the block holds more than that, sized above)
-      std::memcpy(w, seed_final.data(), sizeof(int32_t) * S);
-      if (B) std::memcpy(w + S, bnd_final.data(), sizeof(int32_t) * B);
-      if (B) std::memcpy(w + S + B, bnd_deg.data(), sizeof(int32_t) * B);
-      auto up = [&](void* dst, size_t off, size_t words) {
-        if (words) hipLaunchKernelGGL(k_copy_words, dim3(static_cast<unsigned>((words + 255) / 256)), dim3(256), 0, c->stream,
-                                      static_cast<const uint32_t*>(walk_dev + off), static_cast<uint32_t*>(dst), static_cast<uint32_t>(words));
-      };
-      up(c->d_md_seed_final, 0, S);
-      up(c->d_md_bnd_final, S, B);
-      up(c->d_md_bnd_deg, static_cast<size_t>(S) + B, B);
-      HIP_TRY(hipEventRecord(c->ev_md_walk_up, c->stream));
-    }
-    hipLaunchKernelGGL(k_md_paint, dim3(gridFor(n)), dim3(256), 0, c->stream, c->d_keys, n, seeds, bnd, c->d_md_seed_final,
-                       c->d_md_bnd_final, s.dyn, c->d_md_bnd_deg, s.dynw);
-    s.dyn_clean = false;
-    s.dynw_valid = true;
-    HIP_TRY(hipGetLastError());
-    {
-      const int rcs = summary(kept.back().first);
-      if (rcs) return rcs;
-    }
-    s.clusters.resize(kept.size());
-    for (size_t i = 0; i < kept.size(); ++i) {
-      s.clusters[i] = khr_cluster{};
-      s.clusters[i].id = kept[i].first;
-      s.clusters[i].num_pixels_listed = kept[i].second;
-      s.clusters[i].semantic_id = -1;
-    }
-  }
-  lap("filter + paint launch");
-  return n_out;
+  ++c->n_md_host_walks;
+  return mdFinishByWalk(c, s, t, head, deferred_summary);
 }
 
 int khr_detect_motion(khr_ctx* c, int slot) {
@@ -4187,7 +3961,7 @@ int khr_process_frame(khr_ctx* c, const khr_sensor* sensor, const khr_frame* fra
   const bool tracking = (flags & KHR_PF_TRACKING) && c->cfg.with_tracking;
   const bool defer_fold = tracking;  // (`leave` folds if an error exit comes between the update launch and the tracking pass)
   // (not behind a seed frame: the frame is expected to have seeds, its clustering chain is queued ahead of the count instead)
-  if (motion && c->cfg.with_tracking && !(c->md_seed_run && std::getenv("KHR_MD_NO_PRELAUNCH") == nullptr)) {
+  if (motion && c->cfg.with_tracking && !mdQueuesAhead(c, mdHooks())) {
     const size_t n_pending = c->pending.size();
     rc = integrateUpdate(c, s, f, 1, 0, -1, defer_fold, nullptr, &c->m.counters[C_N_SEEDS]);
     if (rc) return rc;

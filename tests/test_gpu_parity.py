@@ -729,7 +729,9 @@ def test_compact_mesh_halo_equals_unsharded(world, vps):
 def test_motion_clustering_from_key_images(mode, monkeypatch):
     """the clustering half of the motion detector on hand-made voxel-key images (no map involved): duplicate boundary
     counts, truncated-norm merging, 300 clusters (ids saturate at 255), 1500 components (more than the device record
-    capacity: host path), shared boundary voxels with zero separation — device vs oracle, every clustering mode."""
+    capacity: host path), shared boundary voxels with zero separation — device vs oracle, every clustering mode.  Each case
+    also pins which finish the frame took (khr_stats.n_md_device_merges / n_md_host_walks): the component records alone, the
+    records with the device's overlap rows (a merge among at most 64 components), or the host walk."""
     from test_cpu_motion_kat import _image, key
     if mode == "host":
         monkeypatch.setenv("KHR_MD_HOST_WALK", "1")
@@ -737,29 +739,46 @@ def test_motion_clustering_from_key_images(mode, monkeypatch):
         monkeypatch.setenv("KHR_MD_LDS_MAX", "0")
     W, H = 128, 64
     rng = np.random.default_rng(8)
+    # (runs, config, expected rise of (n_md_device_merges, n_md_host_walks) in the modes that do not force the walk; None = not pinned)
     cases = []
-    cases.append(([(key(0, 0, 0, True), 3), (key(1, 0, 0, True), 3), (key(0, 1, 0), 5)], dict(md_min_cluster_size=16, md_min_separation_distance=0.5)))
-    cases.append(([(key(0, 0, 0, True), 4), (key(2, 2, 2, True), 4)], dict(md_min_cluster_size=1, md_min_separation_distance=3.2)))
-    cases.append(([(key(4 * i, 0, 0, True), 3) for i in range(300)], dict(md_min_cluster_size=1, md_min_separation_distance=1.0)))
-    cases.append(([(key(3 * (i % 40), 3 * (i // 40), 7, True), 2) for i in range(1500)], dict(md_min_cluster_size=1, md_min_separation_distance=1.0)))
-    cases.append(([(key(0, 0, 0, True), 3), (key(2, 0, 0, True), 3), (key(1, 0, 0), 5)], dict(md_min_cluster_size=1, md_min_separation_distance=0.0)))
+    cases.append(([(key(0, 0, 0, True), 3), (key(1, 0, 0, True), 3), (key(0, 1, 0), 5)], dict(md_min_cluster_size=16, md_min_separation_distance=0.5), (0, 0)))
+    cases.append(([(key(0, 0, 0, True), 4), (key(2, 2, 2, True), 4)], dict(md_min_cluster_size=1, md_min_separation_distance=3.2), (0, 1)))
+    cases.append(([(key(4 * i, 0, 0, True), 3) for i in range(300)], dict(md_min_cluster_size=1, md_min_separation_distance=1.0), (0, 0)))
+    cases.append(([(key(3 * (i % 40), 3 * (i // 40), 7, True), 2) for i in range(1500)], dict(md_min_cluster_size=1, md_min_separation_distance=1.0), (0, 1)))
+    cases.append(([(key(0, 0, 0, True), 3), (key(2, 0, 0, True), 3), (key(1, 0, 0), 5)], dict(md_min_cluster_size=1, md_min_separation_distance=0.0), (0, 0)))
     # random blobs: seeds and occupied voxels scattered in a 12^3 cube, 1..6 pixels each
     vox = rng.integers(0, 12, (400, 3))
     vox = np.unique(vox, axis=0)
     runs = [(key(int(v[0]), int(v[1]), int(v[2]), bool(rng.uniform() < 0.35)), int(rng.integers(1, 7))) for v in vox]
-    cases.append((runs, dict(md_min_cluster_size=4, md_min_separation_distance=1.0)))
-    cases.append((runs, dict(md_min_cluster_size=1, md_min_separation_distance=2.5, md_neighbor_connectivity=6)))
-    for runs, kw in cases:
+    cases.append((runs, dict(md_min_cluster_size=4, md_min_separation_distance=1.0), None))
+    cases.append((runs, dict(md_min_cluster_size=1, md_min_separation_distance=2.5, md_neighbor_connectivity=6), None))
+    # two seeds that are not adjacent but share a boundary voxel (their components are at distance 0 and merge) among isolated seeds:
+    # 12 components merge from the device's overlap rows, 102 are more than the rows hold and fall through from the records to the walk
+    pair = [(key(0, 0, 0, True), 3), (key(2, 0, 0, True), 3), (key(1, 0, 0), 5)]
+    for n_iso, path in ((10, (1, 0)), (100, (0, 1))):
+        cases.append((pair + [(key(4 * i, 8, 0, True), 3) for i in range(n_iso)], dict(md_min_cluster_size=1, md_min_separation_distance=1.0), path))
+    for runs, kw, path in cases:
         cfg, ctx, ora, s, sen, osen = make_pair(width=W, height=H, **kw)
         img, _ = _image(W, H, runs)
         # a frame slot to paint into (its content is irrelevant: the keys are given)
         fr = s.render(0)
         slot = ctx.upload_frame(sen, fr["stamp"], fr["pose"], fr["depth"], fr["rgb"], fr["label"])
+        st0 = ctx.stats()
         n_g = ctx.detect_motion_from_keys(slot, img)
+        st1 = ctx.stats()
+        taken = (st1["n_md_device_merges"] - st0["n_md_device_merges"], st1["n_md_host_walks"] - st0["n_md_host_walks"])
+        if mode == "host":
+            assert taken == (0, 1), (kw, taken)  # (every case has seeds)
+        elif path is not None:
+            assert taken == path, (kw, taken)
+        else:
+            assert taken[0] + taken[1] <= 1, (kw, taken)
         n_o, dyn_o, _ = ora.detect_motion_from_keys(img)
         dyn_g = ctx.download_frame(slot, (H, W), range_image=False, dynamic_image=True)[2]
         assert n_g == n_o, (kw, n_g, n_o)
         assert np.array_equal(dyn_g, dyn_o), kw
+        if runs[:3] == pair and len(runs) > 3:  # the pair among isolated seeds
+            assert n_o == len(runs) - 2 and [int(x) for x in dyn_o.ravel()[[0, 3, 6, 11, 14]]] == [1, 1, 1, 2, 3]
         cl = ctx.dynamic_clusters(slot)
         assert len(cl) == n_g
         for c in cl[:50]:
