@@ -1779,9 +1779,12 @@ __global__ __launch_bounds__(256) void k_rehash(DevMap m) {
   if (is_free) m.free_slots[idx] = s;
 }
 
-// khr_reset_map: back to the freshly created state (no block, empty hash, identity free list, zero counters / statistics)
-__global__ __launch_bounds__(256) void k_reset_map(DevMap m) {
+// khr_reset_map: back to the freshly created state (no block, empty hash, identity free list, zero counters / statistics).
+// wg_stats: the update kernels' per-workgroup partial sums of the last call (2 * kUpdateStatSlots words), which the next call would
+// otherwise fold into the zeroed totals -- the first object's last batch counted as the second object's
+__global__ __launch_bounds__(256) void k_reset_map(DevMap m, uint32_t* __restrict__ wg_stats) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  for (uint32_t j = i; j < 2u * kUpdateStatSlots; j += gridDim.x * blockDim.x) wg_stats[j] = 0u;
   if (i <= m.ht_mask) m.ht_keys[i] = kEmptyKey;
   if (i < m.capacity) {
     m.blk_flags[i] = 0u;

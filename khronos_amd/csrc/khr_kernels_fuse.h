@@ -1279,31 +1279,36 @@ __global__ __launch_bounds__(256) void k_multi_cull(const uint32_t* __restrict__
 // (>= 3/4, >= 1/2, >= 1/4 of the batch, fewer), heaviest class first.  k_fuse2 deals list position p to workgroup p mod
 // grid, and a workgroup's waves take its positions in order: every workgroup starts on its long items and fills up with the short
 // ones (the launch is as long as its slowest wave -- before: two items of 28 frames each, a dependent round trip or two per frame,
-// while most items see half the frames or none).  One thread per item, one returning atomic per class and workgroup.
+// while most items see half the frames or none).  One thread per item and pass, one returning atomic per class, workgroup and pass.
+// The host sizes the grid from the explicitly allocated blocks, the items are those of every slot in use (C_MAX_SLOT: blocks of an
+// allocating integration or of a loaded checkpoint count too): the grid strides over them, once in the extractor's call sequence.
 __global__ __launch_bounds__(1024) void k_multi_order(const uint32_t* __restrict__ blk_flags, const int4* __restrict__ blk_index, const uint32_t* __restrict__ n_slots_ptr,
                                                      const uint32_t* __restrict__ bits, int n_words, int n_frames, uint32_t wpb, uint32_t live_flag,
                                                      FuseList out) {
   __shared__ uint32_t s_cnt[4], s_off[4];
-  const uint32_t n_items = *n_slots_ptr * wpb;
-  if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0u;
-  __syncthreads();
-  const uint32_t it = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t n = 0u, cls = 0u, pos = 0u;
-  if (it < n_items && (blk_flags[it / wpb] & live_flag))
-    for (int w = 0; w < n_words; ++w) n += static_cast<uint32_t>(__popc(bits[static_cast<size_t>(it) * n_words + w]));
-  if (n) {
-    const uint32_t q = 4u * n, f = static_cast<uint32_t>(n_frames);
-    cls = q >= 3u * f ? 0u : (q >= 2u * f ? 1u : (q >= f ? 2u : 3u));
-    pos = atomicAdd(&s_cnt[cls], 1u);
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) s_off[threadIdx.x] = s_cnt[threadIdx.x] ? atomicAdd(&out.counts[threadIdx.x], s_cnt[threadIdx.x]) : 0u;
-  __syncthreads();
-  if (n) {
-    const uint32_t slot = it / wpb;
-    const int4 bi = blk_index[slot];
-    *fuseDescPtr(out, cls, s_off[cls] + pos) =
-        make_uint4(slot | ((it % wpb) << 24), static_cast<uint32_t>(bi.x), static_cast<uint32_t>(bi.y), static_cast<uint32_t>(bi.z));
+  const uint32_t n_items = *n_slots_ptr * wpb;  // (a slot has 24 bits in an item's descriptor: no overflow here or in the loop)
+  // the loop bound is the same for every thread of a workgroup: the barriers inside are reached by all of them
+  for (uint32_t it0 = blockIdx.x * blockDim.x; it0 < n_items; it0 += gridDim.x * blockDim.x) {
+    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t it = it0 + threadIdx.x;
+    uint32_t n = 0u, cls = 0u, pos = 0u;
+    if (it < n_items && (blk_flags[it / wpb] & live_flag))
+      for (int w = 0; w < n_words; ++w) n += static_cast<uint32_t>(__popc(bits[static_cast<size_t>(it) * n_words + w]));
+    if (n) {
+      const uint32_t q = 4u * n, f = static_cast<uint32_t>(n_frames);
+      cls = q >= 3u * f ? 0u : (q >= 2u * f ? 1u : (q >= f ? 2u : 3u));
+      pos = atomicAdd(&s_cnt[cls], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) s_off[threadIdx.x] = s_cnt[threadIdx.x] ? atomicAdd(&out.counts[threadIdx.x], s_cnt[threadIdx.x]) : 0u;
+    __syncthreads();
+    if (n) {
+      const uint32_t slot = it / wpb;
+      const int4 bi = blk_index[slot];
+      *fuseDescPtr(out, cls, s_off[cls] + pos) =
+          make_uint4(slot | ((it % wpb) << 24), static_cast<uint32_t>(bi.x), static_cast<uint32_t>(bi.y), static_cast<uint32_t>(bi.z));
+    }
   }
 }
 

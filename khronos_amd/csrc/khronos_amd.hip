@@ -820,7 +820,7 @@ int khr_reset_map(khr_ctx* c, float voxel_size, float truncation_distance) {
   c->cfg.truncation_distance = truncation_distance;
   deriveMetricParams(c->cfg, c->p);
   const size_t n = std::max<size_t>(static_cast<size_t>(c->m.ht_mask) + 1, c->m.capacity);
-  hipLaunchKernelGGL(k_reset_map, dim3(gridFor(n)), dim3(256), 0, c->stream, c->m);
+  hipLaunchKernelGGL(k_reset_map, dim3(gridFor(n)), dim3(256), 0, c->stream, c->m, c->d_wg_stats);
   HIP_TRY(hipGetLastError());
   c->mesh_cur = 0;
   c->mesh_total = 0;
@@ -5112,7 +5112,7 @@ int ckptEnsureStage(khr_ctx* c, const CkptShape& sh, uint32_t cb, bool bounce) {
 // back to the empty map on the device and in the host mirrors (the failure exit of a load, and its first step)
 int ckptClearMap(khr_ctx* c) {
   const size_t n = std::max<size_t>(static_cast<size_t>(c->m.ht_mask) + 1, c->m.capacity);
-  hipLaunchKernelGGL(k_reset_map, dim3(gridFor(n)), dim3(256), 0, c->stream, c->m);
+  hipLaunchKernelGGL(k_reset_map, dim3(gridFor(n)), dim3(256), 0, c->stream, c->m, c->d_wg_stats);
   HIP_TRY(hipGetLastError());
   c->mesh_cur = 0;
   c->mesh_total = 0;
