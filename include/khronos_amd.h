@@ -818,6 +818,35 @@ int64_t khr_fetch_mesh(khr_ctx* ctx, khr_mesh_view* out);
 int khr_fetch_mesh_into(khr_ctx* ctx, float* points, uint8_t* colors_rgba, uint32_t* labels, uint64_t* first_seen, uint64_t* stamps);
 int64_t khr_download_mesh(khr_ctx* ctx, float* points, uint8_t* colors_rgba, uint32_t* labels,
                           uint64_t* first_seen, uint64_t* stamps, int64_t cap);
+/* The same mesh as an INDEXED mesh, welded on the device (ASSUMPTIONS.md A.16).  The soup S is the mesh exactly as
+ * khr_download_mesh / khr_fetch_mesh hand it out (sorted block order, face f = vertices 3f, 3f + 1, 3f + 2).  The cell of a vertex
+ * at `resolution` r (metres) is floorf(p / r) per axis, p / r the IEEE float32 quotient; the representative of a cell is the soup
+ * vertex with the least soup index in it; the welded vertices are the representatives in ascending soup index, each with the
+ * position, colour, label, first_seen and stamp of its representative bit for bit (nothing is averaged); soup_to_vertex[i] is the
+ * welded index of the representative of i's cell; face f becomes soup_to_vertex[3f .. 3f + 2] and is dropped iff two of the three
+ * are equal -- the kept faces keep soup order and winding, duplicates stay.  n_faces + n_degenerate_faces = n_soup_vertices / 3.
+ * With r = voxel_size the voxel centres (on which two of a vertex's three coordinates lie) sit mid-cell; with r = voxel_size / 2
+ * they sit on cell boundaries, where one-ulp differences between the cubes that share an edge split a vertex.
+ *
+ * khr_weld_mesh welds the mesh of the last khr_generate_mesh in stream order on the context's stream and waits for the counts
+ * (at most two host waits: the mesh total if it is not current, and the counts).  The result is a copy in buffers the context
+ * owns: it stays valid across later frames and khr_generate_mesh calls, until the next khr_weld_mesh, khr_reset_map,
+ * khr_checkpoint_load or khr_destroy.  The map and the mesh are only read.  `stats` may be NULL.  An empty mesh is KHR_OK with
+ * all-zero statistics.  KHR_EINVAL: resolution not finite or <= 0, or a vertex whose cell index lies outside [-2^20, 2^20) (the
+ * resolution is too fine for the extent of the map; found on the device); KHR_ENOMEM: the mesh is in the overflow state of
+ * khr_generate_mesh; KHR_ESTATE: world_size > 1 (indices are rank-local and the seams between shards would stay open: a sharded
+ * consumer welds after it has gathered).  A failed weld discards an earlier result.
+ *
+ * khr_weld_mesh_into copies the result of the last successful weld (KHR_ESTATE without one); any pointer may be NULL; it may be
+ * called several times.  on_device == 0: host arrays, filled when the call returns.  on_device != 0: device arrays, copied
+ * device-to-device in stream order, nothing is awaited.  points 3 floats, colors_rgba 4 bytes, labels / first_seen / stamps one
+ * word per welded vertex, faces 3 indices per kept face, soup_to_vertex one index per soup vertex. */
+typedef struct khr_weld_stats {
+  uint64_t n_soup_vertices, n_vertices, n_faces, n_degenerate_faces;
+} khr_weld_stats;
+int khr_weld_mesh(khr_ctx* ctx, float resolution, khr_weld_stats* stats);
+int khr_weld_mesh_into(khr_ctx* ctx, int on_device, float* points, uint8_t* colors_rgba, uint32_t* labels, uint64_t* first_seen,
+                       uint64_t* stamps, uint32_t* faces, uint32_t* soup_to_vertex);
 
 /* ---- tick path: the camera frames of ONE tick batched (sharded multi-camera runs) ------------------------------------
  * In a hash-range sharded run every rank sees every camera frame, so the per-camera work of a

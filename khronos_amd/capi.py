@@ -57,6 +57,10 @@ class KhrQueryStats(C.Structure):
 KHR_QP_VALUE, KHR_QP_GRADIENT, KHR_QP_VOXEL = 1, 2, 4
 
 
+class KhrWeldStats(C.Structure):
+    _fields_ = [("n_soup_vertices", C.c_uint64), ("n_vertices", C.c_uint64), ("n_faces", C.c_uint64), ("n_degenerate_faces", C.c_uint64)]
+
+
 class KhrDfRequest(C.Structure):
     _fields_ = [("origin", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("ratio", C.c_int32), ("min_weight", C.c_float),
                 ("max_distance", C.c_float), ("surface_distance", C.c_float), ("unknown_is_obstacle", C.c_int32),
@@ -156,6 +160,7 @@ EXPORTS = [
     "khr_align_linearize", "khr_align_frame", "khr_distance_field",
     "khr_checkpoint_size", "khr_checkpoint_save", "khr_checkpoint_load", "khr_checkpoint_inspect",
     "khr_debug_live_resources", "khr_configure_object_voxel_sets",
+    "khr_weld_mesh", "khr_weld_mesh_into",
 ]
 
 _lib = None
@@ -282,6 +287,8 @@ def load_library():
     lib.khr_fetch_mesh.argtypes = [vp, vp]
     lib.khr_fetch_mesh.restype = i64
     lib.khr_fetch_mesh_into.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.khr_weld_mesh.argtypes = [vp, C.c_float, C.POINTER(KhrWeldStats)]
+    lib.khr_weld_mesh_into.argtypes = [vp, i32] + [vp] * 7
     lib.khr_debug_read.argtypes = [vp, vp, i64]
     lib.khr_debug_live_resources.argtypes = [C.POINTER(i64)]
     lib.khr_tick_ingest.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
@@ -1207,6 +1214,42 @@ class FusionContext:
         if n:
             self._chk(self.lib.khr_fetch_mesh_into(self.h, _ptr(pts), _ptr(col), _ptr(lab), _ptr(fs), _ptr(st)))
         return {"points": pts, "colors": col, "labels": lab, "first_seen": fs, "stamps": st}
+
+    WELD_FIELDS = (("points", np.float32, (3,), "v"), ("colors", np.uint8, (4,), "v"), ("labels", np.uint32, (), "v"),
+                   ("first_seen", np.uint64, (), "v"), ("stamps", np.uint64, (), "v"), ("faces", np.uint32, (3,), "f"),
+                   ("soup_to_vertex", np.uint32, (), "s"))
+
+    def weld_mesh_into(self, out, on_device=False):
+        """khr_weld_mesh_into: the result of the last weld into caller buffers (`out`: WELD_FIELDS name -> contiguous array, or an
+        integer device pointer with on_device; absent / None = not copied).  Returns the return code without raising."""
+        ptrs = []
+        for name, _, _, _ in self.WELD_FIELDS:
+            a = out.get(name)
+            ptrs.append(None if a is None else (C.c_void_p(int(a)) if on_device else _ptr(a)))
+        return self.lib.khr_weld_mesh_into(self.h, int(on_device), *ptrs)
+
+    def weld_mesh(self, resolution, device=False):
+        """The mesh of the last generate_mesh as an indexed mesh, welded on the device at `resolution` metres (khr_weld_mesh,
+        ASSUMPTIONS.md A.16).  Returns a dict: points (n, 3) float32, colors (n, 4) uint8, labels (n,) uint32, first_seen / stamps
+        (n,) uint64 of the welded vertices, faces (m, 3) uint32, soup_to_vertex (n_soup,) uint32, and stats (n_soup_vertices,
+        n_vertices, n_faces, n_degenerate_faces).  device=True: torch tensors on the context's device (int32 / int64 stand in for the
+        unsigned types), copied device to device and complete when the call returns."""
+        st = KhrWeldStats()
+        self._chk(self.lib.khr_weld_mesh(self.h, float(resolution), C.byref(st)))
+        stats = {k: int(getattr(st, k)) for k, _ in KhrWeldStats._fields_}
+        n = {"v": stats["n_vertices"], "f": stats["n_faces"], "s": stats["n_soup_vertices"]}
+        if device:
+            import torch
+            dev = torch.device("cuda", self.cfg.device)
+            tdt = {np.float32: torch.float32, np.uint8: torch.uint8, np.uint32: torch.int32, np.uint64: torch.int64}
+            out = {k: torch.empty((n[w],) + sh, dtype=tdt[dt], device=dev) for k, dt, sh, w in self.WELD_FIELDS}
+            self._chk(self.weld_mesh_into({k: t.data_ptr() for k, t in out.items()}, on_device=True))
+            self.sync()  # (the copies ran on the context's stream: complete before torch reads the tensors on its own)
+        else:
+            out = {k: np.zeros((n[w],) + sh, dt) for k, dt, sh, w in self.WELD_FIELDS}
+            self._chk(self.weld_mesh_into(out))
+        out["stats"] = stats
+        return out
 
     def fetch_mesh_reuse(self, bufs):
         """fetch_mesh() into arrays the caller keeps (a consumer that takes one mesh per output must not pay page faults on 20 MB of

@@ -40,6 +40,7 @@
 #include "khr_kernels_distance.h"
 #include "khr_kernels_align.h"
 #include "khr_kernels_checkpoint.h"
+#include "khr_kernels_weld.h"
 
 using namespace khr;
 
@@ -415,6 +416,13 @@ struct khr_ctx {
   DevBuf<uint32_t> d_ckpt_slots[2];
   DevBuf<uint32_t> d_ckpt_err;
   Event ev_ckpt_filled[2], ev_ckpt_drained[2];
+  // welded mesh (khr_weld_mesh): the work area (block bases, per-vertex words, the cell table), the scans' temporary storage and
+  // the result, each grown to the largest mesh so far; the counts come back through a page-locked block of their own
+  DevBuf<uint8_t> d_weld_work, d_weld_cub, d_weld_out;
+  PinnedBuf<uint32_t> h_weld;
+  WeldOut weld_out{};       // views into d_weld_out
+  khr_weld_stats weld_stats{};
+  bool weld_valid = false;  // a weld succeeded and nothing has discarded its result
   // timing
   uint32_t timing = 0;  // bit i = timer i enabled
   std::vector<TimingRec> pending;
@@ -825,6 +833,7 @@ int khr_reset_map(khr_ctx* c, float voxel_size, float truncation_distance) {
   c->mesh_cur = 0;
   c->mesh_total = 0;
   c->mesh_stale = false;
+  c->weld_valid = false;
   c->host_index_valid = false, ++c->map_gen;
   c->explicit_blocks = 0;
   c->last_removed = 0;
@@ -5239,6 +5248,7 @@ int khr_checkpoint_save(khr_ctx* c, void* buffer, uint64_t cap_bytes, uint64_t* 
 int khr_checkpoint_load(khr_ctx* c, const void* buffer, uint64_t n_bytes, int64_t* n_kept) {
   if (!c || !buffer) return fail(KHR_EINVAL, "null argument");
   if (n_kept) *n_kept = 0;
+  c->weld_valid = false;  // (khr_weld_mesh: the welded mesh belongs to the map before the load)
   khr_checkpoint_header h;
   int rc = khr_checkpoint_inspect(buffer, n_bytes, &h);
   if (rc) return rc;
@@ -5925,6 +5935,133 @@ int khr_fetch_mesh_into(khr_ctx* c, float* points, uint8_t* colors_rgba, uint32_
     for (std::thread& th : pool) th.join();
   }
   HT("fetch_copied");
+  return KHR_OK;
+}
+
+// ---- welded mesh (khr_kernels_weld.h, ASSUMPTIONS.md A.16) ----------------------------------------------------------------
+int khr_weld_mesh(khr_ctx* c, float resolution, khr_weld_stats* stats) {
+  if (!c) return fail(KHR_EINVAL, "null ctx");
+  if (stats) *stats = khr_weld_stats{};
+  c->weld_valid = false;  // (a failed weld discards the earlier result)
+  c->weld_stats = khr_weld_stats{};
+  if (!std::isfinite(resolution) || !(resolution > 0.f)) return fail(KHR_EINVAL, "khr_weld_mesh: resolution must be finite and > 0");
+  if (c->cfg.world_size > 1)
+    return fail(KHR_ESTATE, "khr_weld_mesh needs the whole mesh: world_size is %d (indices are rank-local; weld after the gather)", c->cfg.world_size);
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = refreshMeshTotals(c);  // (host wait 1, only when the total is not current; KHR_ENOMEM in the overflow state)
+  if (rc) return rc;
+  // the extent of the vertex buffer: vertices of blocks archived since the meshing included, so an upper bound of the soup
+  const uint64_t n_cap64 = c->mesh_total;
+  if (n_cap64 == 0) {
+    c->weld_valid = true;
+    return KHR_OK;
+  }
+  if (n_cap64 > (1ull << 30)) return fail(KHR_ENOMEM, "khr_weld_mesh: %llu vertices, at most 2^30", static_cast<unsigned long long>(n_cap64));
+  const uint32_t n_cap = static_cast<uint32_t>(n_cap64), cap = c->m.capacity, nf_cap = n_cap / 3u;
+  if ((rc = ensureSortKeys(c))) return rc;
+  uint32_t tsize = 4;
+  while (tsize < 2u * n_cap) tsize <<= 1;
+  // the three areas; a growth waits for whatever still reads the old block (a device-to-device copy of the last result)
+  auto al = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
+  size_t o = 0;
+  auto carve = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
+  const size_t w_cnt = carve(4ull * (cap + 1)), w_base = carve(4ull * (cap + 1)), w_off = carve(4ull * cap), w_src = carve(4ull * n_cap),
+               w_hs = carve(4ull * n_cap), w_rep = carve(4ull * (n_cap + 1)), w_widx = carve(4ull * (n_cap + 1)), w_keep = carve(4ull * (nf_cap + 1)),
+               w_fidx = carve(4ull * (nf_cap + 1)), w_keys = carve(8ull * tsize), w_vals = carve(4ull * tsize), w_head = carve(4ull * kWeldHeadWords);
+  const size_t work_bytes = o;
+  o = 0;
+  const size_t o_p = carve(12ull * n_cap), o_c = carve(4ull * n_cap), o_l = carve(4ull * n_cap), o_s = carve(8ull * n_cap),
+               o_f = carve(12ull * (nf_cap + 1)), o_v = carve(4ull * n_cap);
+  const size_t out_bytes = o;
+  const int scan_len = static_cast<int>(std::max(n_cap, cap) + 1u);
+  size_t cub_bytes = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, static_cast<uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), scan_len, c->stream));
+  cub_bytes = std::max<size_t>(cub_bytes, 256);
+  if (work_bytes > c->d_weld_work.count() || out_bytes > c->d_weld_out.count() || cub_bytes > c->d_weld_cub.count()) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->d_weld_work.reserve(work_bytes) || c->d_weld_out.reserve(out_bytes) || c->d_weld_cub.reserve(cub_bytes))
+      return fail(KHR_ENOMEM, "khr_weld_mesh: buffers for %u vertices (%zu bytes)", n_cap, work_bytes + out_bytes + cub_bytes);
+  }
+  if (!c->h_weld && c->h_weld.alloc(kWeldHeadWords)) return fail(KHR_ENOMEM, "khr_weld_mesh: page-locked counts");
+  uint8_t* const wb = c->d_weld_work;
+  WeldWork w{};
+  w.blk_count = reinterpret_cast<uint32_t*>(wb + w_cnt), w.blk_base = reinterpret_cast<uint32_t*>(wb + w_base);
+  w.blk_off = reinterpret_cast<uint32_t*>(wb + w_off), w.src = reinterpret_cast<uint32_t*>(wb + w_src);
+  w.hslot = reinterpret_cast<uint32_t*>(wb + w_hs), w.is_rep = reinterpret_cast<uint32_t*>(wb + w_rep);
+  w.widx = reinterpret_cast<uint32_t*>(wb + w_widx), w.keep = reinterpret_cast<uint32_t*>(wb + w_keep);
+  w.fidx = reinterpret_cast<uint32_t*>(wb + w_fidx), w.keys = reinterpret_cast<uint64_t*>(wb + w_keys);
+  w.vals = reinterpret_cast<uint32_t*>(wb + w_vals), w.head = reinterpret_cast<uint32_t*>(wb + w_head);
+  w.mask = tsize - 1u, w.n_cap = n_cap;
+  w.max_vertices = static_cast<uint32_t>(std::min<uint64_t>(c->cfg.max_mesh_vertices, 0xfffffff0ull));
+  uint8_t* const ob = c->d_weld_out;
+  WeldOut& out = c->weld_out;
+  out.points = reinterpret_cast<float*>(ob + o_p), out.colors = reinterpret_cast<uint32_t*>(ob + o_c);
+  out.labels = reinterpret_cast<uint32_t*>(ob + o_l), out.stamps = reinterpret_cast<uint64_t*>(ob + o_s);
+  out.faces = reinterpret_cast<uint32_t*>(ob + o_f), out.soup_to_vertex = reinterpret_cast<uint32_t*>(ob + o_v);
+  const MeshBuffers mb = c->mesh[c->mesh_cur];
+  hipStream_t st = c->stream;
+  // KHR_WELD_MERGE=0: every lane inserts for itself (A/B switch of the wave-level key merge, results identical)
+  const char* const env = std::getenv("KHR_WELD_MERGE");
+  const bool merge = !(env && env[0] == '0');
+  hipLaunchKernelGGL(k_weld_clear, dim3(std::min(gridFor(tsize / 2), 2048)), dim3(256), 0, st, w);
+  // the live blocks in sorted (x, y, z) order, as the checkpoint stream orders them
+  HIP_TRY(hipMemsetAsync(c->d_slice_count, 0, sizeof(uint32_t), st));
+  hipLaunchKernelGGL(k_ckpt_select, dim3(std::min(gridFor(cap), 1024)), dim3(256), 0, st, c->m, c->d_slice_count, c->d_slice_keys);
+  HIP_TRY(hipGetLastError());
+  if ((rc = sortKeys(c))) return rc;
+  hipLaunchKernelGGL(k_weld_block_counts, dim3(gridFor(static_cast<size_t>(cap) + 1)), dim3(256), 0, st, c->m, c->d_slice_keys, c->d_slice_count, w);
+  size_t tb = c->d_weld_cub.count();
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_weld_cub.get(), tb, w.blk_count, w.blk_base, static_cast<int>(cap + 1u), st));
+  if (merge) hipLaunchKernelGGL((k_weld_insert<true>), dim3(gridFor(n_cap)), dim3(256), 0, st, c->m, mb, resolution, w);
+  else hipLaunchKernelGGL((k_weld_insert<false>), dim3(gridFor(n_cap)), dim3(256), 0, st, c->m, mb, resolution, w);
+  hipLaunchKernelGGL(k_weld_resolve, dim3(gridFor(static_cast<size_t>(n_cap) + 1)), dim3(256), 0, st, cap, w);
+  tb = c->d_weld_cub.count();
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_weld_cub.get(), tb, w.is_rep, w.widx, static_cast<int>(n_cap + 1u), st));
+  hipLaunchKernelGGL(k_weld_vertices, dim3(gridFor(n_cap)), dim3(256), 0, st, cap, mb, w, out);
+  hipLaunchKernelGGL(k_weld_face_flags, dim3(gridFor(static_cast<size_t>(nf_cap) + 1)), dim3(256), 0, st, cap, w, out);
+  tb = c->d_weld_cub.count();
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_weld_cub.get(), tb, w.keep, w.fidx, static_cast<int>(nf_cap + 1u), st));
+  hipLaunchKernelGGL(k_weld_faces, dim3(gridFor(static_cast<size_t>(nf_cap) + 1)), dim3(256), 0, st, cap, w, out);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(c->h_weld.get(), w.head, sizeof(uint32_t) * kWeldHeadWords, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));  // (host wait 2: the counts)
+  const uint32_t* h = c->h_weld;
+  if (h[0] & kWeldErrBounds) return fail(KHR_ESTATE, "khr_weld_mesh: the mesh descriptors do not match the vertex buffer (%u vertices)", n_cap);
+  if (h[0] & kWeldErrRange)
+    return fail(KHR_EINVAL, "khr_weld_mesh: a vertex lies outside the cell range [-2^20, 2^20) at resolution %g: too fine for the extent of the map",
+                static_cast<double>(resolution));
+  khr_weld_stats s{};
+  s.n_soup_vertices = h[1], s.n_vertices = h[2], s.n_faces = h[3];
+  s.n_degenerate_faces = s.n_soup_vertices / 3 - s.n_faces;
+  c->weld_stats = s;
+  c->weld_valid = true;
+  if (stats) *stats = s;
+  return KHR_OK;
+}
+
+int khr_weld_mesh_into(khr_ctx* c, int on_device, float* points, uint8_t* colors_rgba, uint32_t* labels, uint64_t* first_seen, uint64_t* stamps,
+                       uint32_t* faces, uint32_t* soup_to_vertex) {
+  if (!c) return fail(KHR_EINVAL, "null ctx");
+  if (!c->weld_valid) return fail(KHR_ESTATE, "no successful khr_weld_mesh before khr_weld_mesh_into");
+  const khr_weld_stats& s = c->weld_stats;
+  if (s.n_soup_vertices == 0) return KHR_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const WeldOut& o = c->weld_out;
+  const size_t nv = s.n_vertices, nf = s.n_faces, ns = s.n_soup_vertices;
+  hipError_t e = hipSuccess;
+  auto field = [&](void* dst, const void* src, size_t bytes) {
+    if (e == hipSuccess && dst && bytes) e = hipMemcpyAsync(dst, src, bytes, kind, c->stream);
+  };
+  field(points, o.points, 12 * nv);
+  field(colors_rgba, o.colors, 4 * nv);
+  field(labels, o.labels, 4 * nv);
+  field(first_seen, o.stamps, 8 * nv);
+  field(stamps, o.stamps, 8 * nv);
+  field(faces, o.faces, 12 * nf);
+  field(soup_to_vertex, o.soup_to_vertex, 4 * ns);
+  if (e != hipSuccess) return fail(KHR_EDEVICE, "khr_weld_mesh_into: copy failed: %s", hipGetErrorString(e));
+  if (!on_device) HIP_TRY(hipStreamSynchronize(c->stream));
   return KHR_OK;
 }
 

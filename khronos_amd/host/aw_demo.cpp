@@ -2,7 +2,7 @@
 // thread drives the reference (spinOnce per InputPacket, finishMapping at shutdown), and prints a JSON
 // summary that tests/test_gpu_host.py compares with the step-wise C-ABI path and the oracle.
 // usage: aw_demo <config.yaml> <width> <height> <frames> [object_label]
-//        aw_demo --slices | --render | --query | --distance | --align | --checkpoint | --bench | --rayver ... (below)
+//        aw_demo --slices | --render | --query | --distance | --align | --weld | --checkpoint | --bench | --rayver ... (below)
 //   object_label >= 0: the stand-in detector / tracker below; otherwise the plugins named in the config
 #include <execinfo.h>
 #include <csignal>
@@ -1099,9 +1099,148 @@ static void onSegv(int sig) {  // a crash must not look like an empty result: pr
   _exit(128 + sig);
 }
 
+// the weld of ASSUMPTIONS.md A.16 on one host thread: first-come over the soup, one unordered_map of cells.  false: a vertex out of range
+static bool hostWeld(const hydra::Mesh& soup, float r, hydra::IndexedMesh* out) {
+  const size_t n = soup.numVertices();
+  std::unordered_map<uint64_t, uint32_t> index;
+  index.reserve(n / 4 + 16);
+  out->soup_to_vertex.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    uint64_t key = 0;
+    for (int a = 0; a < 3; ++a) {
+      const float p = soup.points[3 * i + a], c = std::floor(p / r);
+      if (!std::isfinite(p) || !(c >= -1048576.f && c < 1048576.f)) return false;
+      key |= static_cast<uint64_t>(static_cast<uint32_t>(static_cast<int>(c) + (1 << 20)) & 0x1fffffu) << (21 * a);
+    }
+    const auto it = index.emplace(key, static_cast<uint32_t>(out->labels.size()));
+    if (it.second) {
+      out->points.insert(out->points.end(), &soup.points[3 * i], &soup.points[3 * i] + 3);
+      out->colors.insert(out->colors.end(), &soup.colors[4 * i], &soup.colors[4 * i] + 4);
+      out->labels.push_back(soup.labels[i]);
+      out->first_seen_stamps.push_back(soup.first_seen_stamps[i]);
+      out->stamps.push_back(soup.stamps[i]);
+    }
+    out->soup_to_vertex[i] = it.first->second;
+  }
+  for (size_t f = 0; f + 2 < n; f += 3) {
+    const uint32_t a = out->soup_to_vertex[f], b = out->soup_to_vertex[f + 1], c = out->soup_to_vertex[f + 2];
+    if (a != b && b != c && a != c) out->faces.insert(out->faces.end(), {a, b, c});
+  }
+  out->stats.n_soup_vertices = n;
+  out->stats.n_vertices = out->labels.size();
+  out->stats.n_faces = out->faces.size() / 3;
+  out->stats.n_degenerate_faces = n / 3 - out->stats.n_faces;
+  return true;
+}
+
+static double medianOf(std::vector<double> v) {
+  if (v.empty()) return 0.0;
+  std::sort(v.begin(), v.end());
+  return v.size() % 2 ? v[v.size() / 2] : 0.5 * (v[v.size() / 2 - 1] + v[v.size() / 2]);
+}
+
+// aw_demo --weld <config.yaml> <width> <height> <frames> [resolution] [repeats]: drives the synthetic stream through an ActiveWindow and
+// then takes the window's mesh (the last output's) twice: as an indexed mesh welded on the device (VolumetricMap::weldedMesh:
+// khr_weld_mesh + khr_weld_mesh_into) and as the soup (khr_fetch_mesh + khr_fetch_mesh_into) welded here by the same definition.
+// One JSON line: the counts, whether the two are equal array for array, the median wall-clock time of both ways over `repeats`
+// (device drained before each), and the bytes that cross to the host.  resolution 0 / absent: the voxel size.
+static int weldDemo(int argc, char** argv) {
+  if (argc < 6) {
+    std::fprintf(stderr, "usage: aw_demo --weld <config.yaml> <width> <height> <frames> [resolution] [repeats]\n");
+    return 2;
+  }
+  std::ifstream in(argv[2]);
+  std::stringstream ss;
+  ss << in.rdbuf();
+  const int W = std::atoi(argv[3]), H = std::atoi(argv[4]), N = std::atoi(argv[5]);
+  ActiveWindow::Config cfg = ActiveWindow::Config::fromYamlString(ss.str());
+  cfg.max_frame_pixels = static_cast<uint32_t>(W) * H;
+  float r = argc > 6 ? static_cast<float>(std::atof(argv[6])) : 0.f;
+  if (!(r > 0.f)) r = cfg.volumetric_map.voxel_size;
+  const int reps = std::max(1, argc > 7 ? std::atoi(argv[7]) : 5);
+  auto out_queue = std::make_shared<ActiveWindow::OutputQueue>();
+  ActiveWindow aw(cfg, out_queue);
+  void* scene = synth_create(1234, 12, 1);
+  const size_t n = static_cast<size_t>(W) * H;
+  std::vector<float> depth(n);
+  std::vector<uint8_t> rgb(n * 3);
+  std::vector<int32_t> label(n);
+  for (int i = 0; i < N; ++i) {
+    hydra::InputPacket pkt;
+    pkt.timestamp_ns = static_cast<uint64_t>(std::llround((1.0 + 0.1 * i) * 1e9));
+    circlePose(0.1 * i, pkt.world_T_body);
+    pkt.sensor = {W, H, W / 2.f, W / 2.f, W / 2.f, H / 2.f, 0.1f, 5.f};
+    synth_render(scene, W, H, pkt.sensor.fx, pkt.sensor.fy, pkt.sensor.cx, pkt.sensor.cy, pkt.world_T_body, 0.1 * i, 5.f, 0.f,
+                 1234u + 7919u * i, depth.data(), rgb.data(), label.data(), 0);
+    pkt.depth = depth.data();
+    pkt.color = rgb.data();
+    pkt.labels = label.data();
+    aw.step(pkt);
+    hydra::ActiveWindowOutput::Ptr popped;
+    while (out_queue->pop(&popped)) {}
+  }
+  synth_destroy(scene);
+  const VolumetricMap& map = aw.getMap();
+  using clk = std::chrono::steady_clock;
+  auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+  hydra::IndexedMesh dev, host;
+  hydra::Mesh soup;
+  std::vector<double> t_dev, t_fetch, t_weld;
+  bool in_range = true;
+  for (int k = 0; k < reps + 1; ++k) {  // (the first round grows the buffers of both ways and is not timed)
+    khr_sync(map.ctx());
+    const auto t0 = clk::now();
+    dev = map.weldedMesh(r);
+    const auto t1 = clk::now();
+    khr_sync(map.ctx());
+    const auto t2 = clk::now();
+    khr_mesh_view view{};
+    const int64_t nv = khr_fetch_mesh(map.ctx(), &view);
+    if (nv < 0) throw std::runtime_error(std::string("khr_fetch_mesh: ") + khr_last_error());
+    soup.points.resize(3 * nv); soup.colors.resize(4 * nv); soup.labels.resize(nv); soup.first_seen_stamps.resize(nv); soup.stamps.resize(nv);
+    if (nv && khr_fetch_mesh_into(map.ctx(), soup.points.data(), soup.colors.data(), soup.labels.data(), soup.first_seen_stamps.data(),
+                                  soup.stamps.data()) != KHR_OK)
+      throw std::runtime_error(std::string("khr_fetch_mesh_into: ") + khr_last_error());
+    const auto t3 = clk::now();
+    host = hydra::IndexedMesh();
+    in_range = hostWeld(soup, r, &host);
+    const auto t4 = clk::now();
+    if (k > 0) t_dev.push_back(ms(t0, t1)), t_fetch.push_back(ms(t2, t3)), t_weld.push_back(ms(t3, t4));
+  }
+  aw.finishMapping();
+  const char* diff = nullptr;
+  if (!in_range) diff = "the host weld found a vertex out of range";
+  else if (dev.stats.n_soup_vertices != host.stats.n_soup_vertices || dev.stats.n_vertices != host.stats.n_vertices ||
+           dev.stats.n_faces != host.stats.n_faces || dev.stats.n_degenerate_faces != host.stats.n_degenerate_faces) diff = "stats";
+  else if (!sameBits(dev.points, host.points)) diff = "points";
+  else if (dev.colors != host.colors) diff = "colors";
+  else if (dev.labels != host.labels) diff = "labels";
+  else if (dev.first_seen_stamps != host.first_seen_stamps) diff = "first_seen";
+  else if (dev.stamps != host.stamps) diff = "stamps";
+  else if (dev.faces != host.faces) diff = "faces";
+  else if (dev.soup_to_vertex != host.soup_to_vertex) diff = "soup_to_vertex";
+  const unsigned long long ns = dev.stats.n_soup_vertices, nv = dev.stats.n_vertices, nf = dev.stats.n_faces;
+  std::printf("{\"what\": \"the window's mesh as an indexed mesh: VolumetricMap::weldedMesh (device) vs khr_fetch_mesh + a one-thread host weld, %dx%d, "
+              "voxel %.4g m\", \"frames\": %d, \"resolution\": %.9g, \"repeats\": %d, \"n_soup_vertices\": %llu, \"n_vertices\": %llu, \"n_faces\": %llu, "
+              "\"n_degenerate_faces\": %llu, \"equal\": %s, \"first_mismatch\": \"%s\", \"device_weld_ms\": %.4f, \"fetch_ms\": %.4f, "
+              "\"host_weld_ms\": %.4f, \"soup_bytes\": %llu, \"indexed_bytes\": %llu, \"soup_to_vertex_bytes\": %llu}\n",
+              W, H, static_cast<double>(cfg.volumetric_map.voxel_size), N, static_cast<double>(r), reps, ns, nv, nf,
+              static_cast<unsigned long long>(dev.stats.n_degenerate_faces), diff ? "false" : "true", diff ? diff : "", medianOf(t_dev),
+              medianOf(t_fetch), medianOf(t_weld), 36ull * ns, 36ull * nv + 12ull * nf, 4ull * ns);
+  return diff ? 3 : 0;
+}
+
 int main(int argc, char** argv) {
   std::signal(SIGSEGV, onSegv);
   std::signal(SIGABRT, onSegv);
+  if (argc >= 2 && std::string(argv[1]) == "--weld") {
+    try {
+      return weldDemo(argc, argv);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "aw_demo: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc >= 3 && std::string(argv[1]) == "--rayver") {
     try {
       return rayverDemo(argv[2]);

@@ -366,6 +366,8 @@ struct DistanceField {
   }
 };
 
+struct IndexedMesh;  // (below, behind Mesh)
+
 // hydra::VolumetricMap role: here a handle on the HBM-resident map of a fusion context.
 class VolumetricMap {
  public:
@@ -525,6 +527,10 @@ class VolumetricMap {
   // checkpoint.  (Defined in active_window.cpp.)
   size_t save(const std::string& path) const;
   size_t load(const std::string& path);
+  // The mesh of the last meshing as an indexed mesh: one vertex per cell of a grid of `resolution` metres, the role of the
+  // frontend's voxel-grid mesh compression (khr_weld_mesh, ASSUMPTIONS.md A.16).  Welded on the device; the indexed mesh alone
+  // crosses to the host.  Throws std::runtime_error with khr_last_error's text.  (Defined below, behind IndexedMesh.)
+  IndexedMesh weldedMesh(float resolution) const;
 
  private:
   static khr_align_request alignRequest(const double* prior, const AlignOptions& opt) {
@@ -563,6 +569,28 @@ struct Mesh {
   std::vector<uint64_t> first_seen_stamps, stamps;
   size_t numVertices() const { return labels.size(); }
 };
+
+// a Mesh with explicit faces (VolumetricMap::weldedMesh): 3 vertex indices per face; soup_to_vertex maps every vertex of the
+// triangle soup the mesh was welded from to its welded vertex
+struct IndexedMesh : Mesh {
+  std::vector<uint32_t> faces;
+  std::vector<uint32_t> soup_to_vertex;
+  khr_weld_stats stats{};
+  size_t numFaces() const { return faces.size() / 3; }
+};
+
+inline IndexedMesh VolumetricMap::weldedMesh(float resolution) const {
+  IndexedMesh m;
+  if (khr_weld_mesh(ctx_, resolution, &m.stats) != KHR_OK) throw std::runtime_error(std::string("khr_weld_mesh: ") + khr_last_error());
+  const size_t nv = m.stats.n_vertices;
+  m.points.resize(3 * nv); m.colors.resize(4 * nv); m.labels.resize(nv); m.first_seen_stamps.resize(nv); m.stamps.resize(nv);
+  m.faces.resize(3 * m.stats.n_faces);
+  m.soup_to_vertex.resize(m.stats.n_soup_vertices);
+  if (khr_weld_mesh_into(ctx_, 0, m.points.data(), m.colors.data(), m.labels.data(), m.first_seen_stamps.data(), m.stamps.data(), m.faces.data(),
+                         m.soup_to_vertex.data()) != KHR_OK)
+    throw std::runtime_error(std::string("khr_weld_mesh_into: ") + khr_last_error());
+  return m;
+}
 
 struct BoundingBox {
   float min[3] = {0, 0, 0}, max[3] = {0, 0, 0};
