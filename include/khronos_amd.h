@@ -848,6 +848,41 @@ int khr_weld_mesh(khr_ctx* ctx, float resolution, khr_weld_stats* stats);
 int khr_weld_mesh_into(khr_ctx* ctx, int on_device, float* points, uint8_t* colors_rgba, uint32_t* labels, uint64_t* first_seen,
                        uint64_t* stamps, uint32_t* faces, uint32_t* soup_to_vertex);
 
+/* ---- another map fused into the live map (ASSUMPTIONS.md A.17) -------------------------------------------------------
+ * khr_merge_map fuses the map of `src` into the map of `dst` on the device: a side context that holds yesterday's checkpoint, a
+ * stretch of map under a corrected pose, another robot's window.  KHR_MERGE_ALIGNED moves voxels to voxels under an integer voxel
+ * offset, nothing is interpolated; KHR_MERGE_RESAMPLE samples the source at the destination's voxel centres under a rigid
+ * transform, the sample being exactly what khr_query_points(src, p, min_weight) returns at the transformed centre.  A destination
+ * voxel changes only where its source sample is valid: an unobserved one (weight 0, or a block the merge creates) takes the
+ * source's values unchanged, an observed one the weighted mean of the distances and colours, the capped weight sum, the later
+ * stamps, and the tracking and semantic rules of A.17.  A block with at least one valid sample is touched: it gains
+ * KHR_BLK_UPDATED | MESH_UPDATED | TRACKING_UPDATED, so the next output meshes and snapshots it as after an integration.  A
+ * merged-in block whose stamps lie outside the temporal window is archived by the next khr_reset_inactive like any other.
+ *
+ * `src` is only read.  dst's stream is ordered behind everything queued on src's stream by an event, and src's later work behind
+ * the merge's kernels by another, so src may be used or destroyed as soon as the call returns; there is one host wait, for
+ * the counts that decide the errors and fill `stats` (may be NULL).  The frame ring, the mesh layer, the detectors' state and the
+ * cumulative khr_stats counters of dst are not touched.  Every error leaves dst bit for bit as it was (khr_map_digest).
+ * KHR_EINVAL: NULL arguments or src == dst; contexts on different devices; a difference in voxel_size, voxels_per_side,
+ * truncation_distance, with_semantics, with_tracking, num_labels or semantic_mode (the text names the field); an unknown mode; a
+ * negative or non-finite min_weight; ALIGNED: |offset| >= 2^30; RESAMPLE: a non-finite pose, a last row other than 0 0 0 1, a
+ * rotation R with max |R^T R - I| > 1e-5 or det R < 0; a touched destination block outside the 21-bit key range (found on the
+ * device before anything is written).  KHR_ESTATE: world_size > 1 on either side.  KHR_ENOMEM: the new blocks do not fit dst's
+ * pool (the text gives the number needed and the number free).  An empty src, or a merge that touches nothing, is KHR_OK.
+ * n_candidate_blocks counts the distinct destination blocks inside the key range that some live source block can reach. */
+#define KHR_MERGE_ALIGNED 0
+#define KHR_MERGE_RESAMPLE 1
+typedef struct khr_merge_request {
+  int32_t mode;
+  int32_t voxel_offset[3]; /* ALIGNED: destination global voxel g receives source global voxel g - voxel_offset */
+  double dst_T_src[16];    /* RESAMPLE: row-major 4x4, rigid */
+  float min_weight;        /* a source voxel counts as observed iff weight >= this; 0 = the DESTINATION's mesh_min_weight */
+} khr_merge_request;
+typedef struct khr_merge_stats {
+  uint64_t n_src_blocks, n_candidate_blocks, n_touched_blocks, n_new_blocks, n_added_voxels, n_merged_voxels;
+} khr_merge_stats;
+int khr_merge_map(khr_ctx* dst, khr_ctx* src, const khr_merge_request* request, khr_merge_stats* stats);
+
 /* ---- tick path: the camera frames of ONE tick batched (sharded multi-camera runs) ------------------------------------
  * In a hash-range sharded run every rank sees every camera frame, so the per-camera work of a
  * rank is what does not shrink with the rank count.  These two calls are khr_upload_frame / khr_integrate for n_frames

@@ -61,6 +61,18 @@ class KhrWeldStats(C.Structure):
     _fields_ = [("n_soup_vertices", C.c_uint64), ("n_vertices", C.c_uint64), ("n_faces", C.c_uint64), ("n_degenerate_faces", C.c_uint64)]
 
 
+KHR_MERGE_ALIGNED, KHR_MERGE_RESAMPLE = 0, 1
+
+
+class KhrMergeRequest(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("voxel_offset", C.c_int32 * 3), ("dst_T_src", C.c_double * 16), ("min_weight", C.c_float)]
+
+
+class KhrMergeStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_src_blocks", "n_candidate_blocks", "n_touched_blocks", "n_new_blocks", "n_added_voxels",
+                                          "n_merged_voxels")]
+
+
 class KhrDfRequest(C.Structure):
     _fields_ = [("origin", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("ratio", C.c_int32), ("min_weight", C.c_float),
                 ("max_distance", C.c_float), ("surface_distance", C.c_float), ("unknown_is_obstacle", C.c_int32),
@@ -160,7 +172,7 @@ EXPORTS = [
     "khr_align_linearize", "khr_align_frame", "khr_distance_field",
     "khr_checkpoint_size", "khr_checkpoint_save", "khr_checkpoint_load", "khr_checkpoint_inspect",
     "khr_debug_live_resources", "khr_configure_object_voxel_sets",
-    "khr_weld_mesh", "khr_weld_mesh_into",
+    "khr_weld_mesh", "khr_weld_mesh_into", "khr_merge_map",
 ]
 
 _lib = None
@@ -289,6 +301,7 @@ def load_library():
     lib.khr_fetch_mesh_into.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.khr_weld_mesh.argtypes = [vp, C.c_float, C.POINTER(KhrWeldStats)]
     lib.khr_weld_mesh_into.argtypes = [vp, i32] + [vp] * 7
+    lib.khr_merge_map.argtypes = [vp, vp, C.POINTER(KhrMergeRequest), C.POINTER(KhrMergeStats)]
     lib.khr_debug_read.argtypes = [vp, vp, i64]
     lib.khr_debug_live_resources.argtypes = [C.POINTER(i64)]
     lib.khr_tick_ingest.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
@@ -1250,6 +1263,31 @@ class FusionContext:
             self._chk(self.weld_mesh_into(out))
         out["stats"] = stats
         return out
+
+    @staticmethod
+    def merge_request(mode, voxel_offset=(0, 0, 0), pose=None, min_weight=0.0):
+        """khr_merge_request: mode KHR_MERGE_ALIGNED with an integer voxel offset, or KHR_MERGE_RESAMPLE with `pose` = dst_T_src
+        (4x4, rigid); min_weight 0 = the destination's mesh_min_weight"""
+        rq = KhrMergeRequest()
+        rq.mode = int(mode)
+        rq.voxel_offset[:] = [int(v) for v in voxel_offset]
+        rq.dst_T_src[:] = np.asarray(np.eye(4) if pose is None else pose, np.float64).reshape(16).tolist()
+        rq.min_weight = float(min_weight)
+        return rq
+
+    def merge_map_rc(self, src, request):
+        """khr_merge_map without raising: (return code, statistics dict)"""
+        st = KhrMergeStats()
+        rc = self.lib.khr_merge_map(self.h, src.h if src is not None else None, C.byref(request) if request is not None else None, C.byref(st))
+        return rc, {k: int(getattr(st, k)) for k, _ in KhrMergeStats._fields_}
+
+    def merge_map(self, src, mode=KHR_MERGE_ALIGNED, voxel_offset=(0, 0, 0), pose=None, min_weight=0.0, request=None):
+        """Fuse the map of the context `src` into this one on the device (khr_merge_map, ASSUMPTIONS.md A.17); `src` is only
+        read.  Returns the statistics as a dict."""
+        rq = request if request is not None else self.merge_request(mode, voxel_offset, pose, min_weight)
+        rc, st = self.merge_map_rc(src, rq)
+        self._chk(rc)
+        return st
 
     def fetch_mesh_reuse(self, bufs):
         """fetch_mesh() into arrays the caller keeps (a consumer that takes one mesh per output must not pay page faults on 20 MB of

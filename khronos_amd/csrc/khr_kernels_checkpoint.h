@@ -253,8 +253,10 @@ __global__ __launch_bounds__(256) void k_ckpt_unpack(DevMap m, DevParams p, cons
 //                                that is not ever-free
 //   blk_band                     per wave item, the voxels with weight > 0 inside the truncation band: an estimate of what
 //                                k_fuse reports; only the culling pass's cost class reads it, the results do not depend on it
+// list != nullptr: only the slots list[0, *n_list) (khr_merge_map: the blocks a merge has rewritten) instead of every live block
 template <int VPS>
-__global__ __launch_bounds__(256) void k_ckpt_rebuild(DevMap m, DevParams p, uint32_t wpb) {
+__global__ __launch_bounds__(256) void k_ckpt_rebuild(DevMap m, DevParams p, uint32_t wpb, const uint32_t* __restrict__ list = nullptr,
+                                                     const uint32_t* __restrict__ n_list = nullptr) {
   constexpr int NV = VPS * VPS * VPS, NG = NV / 64, PATCHES = VPS * VPS / 64;
   __shared__ uint32_t s_band[kBandSlots];
   __shared__ unsigned long long s_min[2][4];
@@ -262,7 +264,10 @@ __global__ __launch_bounds__(256) void k_ckpt_rebuild(DevMap m, DevParams p, uin
   const uint32_t n_slots = min(m.counters[C_MAX_SLOT], m.capacity);
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t zr = max(1u, static_cast<uint32_t>(VPS) / max(1u, wpb / PATCHES));  // z steps per wave item (cullBlocks)
-  for (uint32_t s = blockIdx.x; s < n_slots; s += gridDim.x) {
+  const uint32_t n_items = list ? *n_list : n_slots;
+  for (uint32_t it = blockIdx.x; it < n_items; it += gridDim.x) {
+    const uint32_t s = list ? list[it] : it;
+    if (s >= n_slots) continue;  // (uniform)
     const uint32_t fl = m.blk_flags[s];
     if (!(fl & BLK_LIVE)) continue;  // (uniform)
     if (threadIdx.x < kBandSlots) s_band[threadIdx.x] = 0u;

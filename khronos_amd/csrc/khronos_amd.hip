@@ -41,6 +41,7 @@
 #include "khr_kernels_align.h"
 #include "khr_kernels_checkpoint.h"
 #include "khr_kernels_weld.h"
+#include "khr_kernels_merge.h"
 
 using namespace khr;
 
@@ -423,6 +424,15 @@ struct khr_ctx {
   WeldOut weld_out{};       // views into d_weld_out
   khr_weld_stats weld_stats{};
   bool weld_valid = false;  // a weld succeeded and nothing has discarded its result
+  // map merges (khr_merge_map, this context as the destination): the candidate set, the candidate list, its per-candidate words
+  // (slot, hit, touched list), each grown to the largest merge so far; the counters with their page-locked mirror; the event that
+  // orders this context's stream behind the source's
+  DevBuf<uint64_t> d_merge_set;
+  DevBuf<int4> d_merge_cand;
+  DevBuf<uint32_t> d_merge_words;
+  DevBuf<uint32_t> d_merge_ctr;
+  PinnedBuf<uint32_t> h_merge;
+  Event ev_merge;
   // timing
   uint32_t timing = 0;  // bit i = timer i enabled
   std::vector<TimingRec> pending;
@@ -6062,6 +6072,169 @@ int khr_weld_mesh_into(khr_ctx* c, int on_device, float* points, uint8_t* colors
   field(soup_to_vertex, o.soup_to_vertex, 4 * ns);
   if (e != hipSuccess) return fail(KHR_EDEVICE, "khr_weld_mesh_into: copy failed: %s", hipGetErrorString(e));
   if (!on_device) HIP_TRY(hipStreamSynchronize(c->stream));
+  return KHR_OK;
+}
+
+// ---- another map fused into the live map (khr_merge_map; ASSUMPTIONS.md A.17, device side: khr_kernels_merge.h) ----------------
+int khr_merge_map(khr_ctx* c, khr_ctx* src, const khr_merge_request* rq, khr_merge_stats* stats) {
+  if (stats) *stats = khr_merge_stats{};
+  if (!c || !src || !rq) return fail(KHR_EINVAL, "khr_merge_map: null argument");
+  if (src == c) return fail(KHR_EINVAL, "khr_merge_map: src and dst are the same context");
+  if (c->device != src->device) return fail(KHR_EINVAL, "khr_merge_map: the contexts live on different devices (%d and %d)", src->device, c->device);
+  {
+    const khr_checkpoint_header hs = ckptHeaderFor(src->cfg, 0), hd = ckptHeaderFor(c->cfg, 0);
+#define KHR_MERGE_FIELD(name, fmt, cast)                                                                                          \
+  if (hs.name != hd.name)                                                                                                         \
+    return fail(KHR_EINVAL, "khr_merge_map: " #name " is " fmt " in the source and " fmt " in the destination", static_cast<cast>(hs.name), \
+                static_cast<cast>(hd.name));
+    KHR_MERGE_FIELD(voxel_size, "%.9g", double)
+    KHR_MERGE_FIELD(voxels_per_side, "%d", int)
+    KHR_MERGE_FIELD(truncation_distance, "%.9g", double)
+    KHR_MERGE_FIELD(with_semantics, "%d", int)
+    KHR_MERGE_FIELD(with_tracking, "%d", int)
+    KHR_MERGE_FIELD(num_labels, "%d", int)
+    KHR_MERGE_FIELD(semantic_mode, "%d", int)
+#undef KHR_MERGE_FIELD
+  }
+  if (rq->mode != KHR_MERGE_ALIGNED && rq->mode != KHR_MERGE_RESAMPLE) return fail(KHR_EINVAL, "khr_merge_map: unknown mode %d", rq->mode);
+  if (!std::isfinite(rq->min_weight) || rq->min_weight < 0.f) return fail(KHR_EINVAL, "khr_merge_map: min_weight must be finite and >= 0");
+  if (c->cfg.world_size > 1 || src->cfg.world_size > 1)
+    return fail(KHR_ESTATE, "khr_merge_map needs whole maps: world_size is %d in the source and %d in the destination", src->cfg.world_size,
+                c->cfg.world_size);
+  MergeArgs X{};
+  X.mode = rq->mode;
+  X.min_weight = rq->min_weight > 0.f ? rq->min_weight : c->p.mesh_min_weight;
+  X.ks_src = src->p.KS;
+  X.src_stamp = src->last_track_stamp;
+  X.dst_stamp = c->last_track_stamp;
+  if (rq->mode == KHR_MERGE_ALIGNED) {
+    for (int a = 0; a < 3; ++a) {
+      const int64_t o = rq->voxel_offset[a];
+      if (o <= -(1ll << 30) || o >= (1ll << 30)) return fail(KHR_EINVAL, "khr_merge_map: voxel_offset[%d] = %lld, |offset| must be below 2^30", a, static_cast<long long>(o));
+      X.off[a] = rq->voxel_offset[a];
+    }
+  } else {
+    const double* T = rq->dst_T_src;
+    for (int i = 0; i < 16; ++i)
+      if (!std::isfinite(T[i])) return fail(KHR_EINVAL, "khr_merge_map: dst_T_src is not finite");
+    if (T[12] != 0.0 || T[13] != 0.0 || T[14] != 0.0 || T[15] != 1.0) return fail(KHR_EINVAL, "khr_merge_map: the last row of dst_T_src is not 0 0 0 1");
+    double worst = 0.0;
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        double s = 0.0;
+        for (int k = 0; k < 3; ++k) s += T[4 * k + i] * T[4 * k + j];
+        worst = std::max(worst, std::fabs(s - (i == j ? 1.0 : 0.0)));
+      }
+    if (worst > 1e-5) return fail(KHR_EINVAL, "khr_merge_map: dst_T_src is not rigid: max |R^T R - I| = %.3g", worst);
+    const double det = T[0] * (T[5] * T[10] - T[6] * T[9]) - T[1] * (T[4] * T[10] - T[6] * T[8]) + T[2] * (T[4] * T[9] - T[5] * T[8]);
+    if (det < 0.0) return fail(KHR_EINVAL, "khr_merge_map: dst_T_src is a reflection (det R = %.3g)", det);
+    for (int a = 0; a < 3; ++a) {  // src_T_dst = [R^T | -R^T t] in double, cast once
+      double t = 0.0;
+      for (int k = 0; k < 3; ++k) {
+        X.M[4 * a + k] = static_cast<float>(T[4 * k + a]);
+        t += T[4 * k + a] * T[4 * k + 3];
+        X.F[4 * a + k] = static_cast<float>(T[4 * a + k]);
+      }
+      X.M[4 * a + 3] = static_cast<float>(-t);
+      X.F[4 * a + 3] = static_cast<float>(T[4 * a + 3]);
+    }
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  // scratch, sized by what the source's pool can reach (its block count is not known without a wait)
+  const size_t reach = rq->mode == KHR_MERGE_ALIGNED ? kMergeReachAligned : kMergeReachResample;
+  const size_t cap = reach * static_cast<size_t>(src->m.capacity);
+  if (cap > (1ull << 30)) return fail(KHR_ENOMEM, "khr_merge_map: %zu candidate blocks, at most 2^30", cap);
+  size_t set_n = 64;
+  while (set_n < 2 * cap) set_n <<= 1;
+  if (set_n > c->d_merge_set.count() || cap > c->d_merge_cand.count() || !c->d_merge_ctr || !c->h_merge) {
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (whatever still uses the old blocks)
+    int rc = KHR_OK;
+    KHR_CHAIN(c->d_merge_set.reserve(set_n));
+    KHR_CHAIN(c->d_merge_cand.reserve(cap));
+    KHR_CHAIN(c->d_merge_words.reserve(3 * cap));
+    KHR_CHAIN(c->d_merge_ctr.reserve(16));
+    KHR_CHAIN(c->h_merge.reserve(16));
+    if (rc) return fail(KHR_ENOMEM, "khr_merge_map: scratch for %zu candidate blocks", cap);
+  }
+  KHR_TRY(c->ev_merge.ensure());
+  MergeScratch S{};
+  S.set_keys = c->d_merge_set;
+  S.set_mask = static_cast<uint32_t>(set_n - 1);
+  S.cand = c->d_merge_cand;
+  S.cap = static_cast<uint32_t>(cap);
+  S.cand_slot = c->d_merge_words;
+  S.cand_hit = c->d_merge_words + cap;
+  S.touched = c->d_merge_words + 2 * cap;
+  S.ctr = c->d_merge_ctr;
+  S.ctr64 = reinterpret_cast<unsigned long long*>(c->d_merge_ctr + MC_COUNT);
+  // behind everything queued on the source's stream
+  if (c->stream != src->stream) {
+    HIP_TRY(hipEventRecord(c->ev_merge, src->stream));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_merge, 0));
+  }
+  HIP_TRY(hipMemsetAsync(S.ctr, 0, 16 * sizeof(uint32_t), c->stream));
+  HIP_TRY(hipMemsetAsync(S.set_keys, 0xff, set_n * sizeof(uint64_t), c->stream));
+  int rc = dispatchVps(c, [&](auto vps) {
+    constexpr int V = decltype(vps)::value;
+    hipLaunchKernelGGL((k_merge_candidates<V>), dim3(std::max(1, std::min(gridFor(src->m.capacity), 1024))), dim3(256), 0, c->stream, src->m, c->p, X, S);
+    HIP_TRY(hipGetLastError());
+    const dim3 grid(static_cast<uint32_t>(std::min<size_t>(cap, 8192)));
+    if (X.mode == kMergeAligned) hipLaunchKernelGGL((k_merge_probe<V, kMergeAligned>), grid, dim3(256), 0, c->stream, c->m, src->m, c->p, X, S);
+    else hipLaunchKernelGGL((k_merge_probe<V, kMergeResample>), grid, dim3(256), 0, c->stream, c->m, src->m, c->p, X, S);
+    HIP_TRY(hipGetLastError());
+    return KHR_OK;
+  });
+  if (rc) return rc;
+  // the one host wait: the counts
+  uint32_t* const h = c->h_merge;
+  HIP_TRY(hipMemcpyAsync(h, S.ctr, 12 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(h + 12, &c->m.counters[C_FREE_HEAD], 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  static_assert(C_FREE_HEAD == 0 && C_N_FREE == 1, "the two free-list words are adjacent");
+  uint64_t v64[2];
+  std::memcpy(v64, h + MC_COUNT, sizeof(v64));
+  const uint32_t n_list = std::min<uint32_t>(h[MC_LIST], S.cap), n_touched = h[MC_TOUCHED], n_new = h[MC_NEW];
+  if (h[MC_ERR] & kMergeErrOverflow) return fail(KHR_EDEVICE, "khr_merge_map: the candidate list overflowed (%u entries, room for %u)", h[MC_LIST], S.cap);
+  if (h[MC_ERR] & kMergeErrRange)
+    return fail(KHR_EINVAL, "khr_merge_map: a destination block with a valid sample lies outside the block index range [-2^20, 2^20)");
+  const uint32_t n_free = h[13] - std::min(h[12], h[13]);
+  if (n_new > n_free) return fail(KHR_ENOMEM, "khr_merge_map: the merge needs %u new blocks, the pool (max_blocks %u) has %u free", n_new, c->m.capacity, n_free);
+  khr_merge_stats st{};
+  st.n_src_blocks = h[MC_SRC];
+  st.n_candidate_blocks = h[MC_CAND];
+  st.n_touched_blocks = n_touched;
+  st.n_new_blocks = n_new;
+  st.n_added_voxels = v64[0];
+  st.n_merged_voxels = v64[1];
+  if (n_touched > 0) {
+    hipLaunchKernelGGL(k_merge_insert, dim3(gridFor(n_list)), dim3(256), 0, c->stream, c->m, S);
+    HIP_TRY(hipGetLastError());
+    rc = dispatchVps(c, [&](auto vps) {
+      constexpr int V = decltype(vps)::value;
+      const auto write = [&](auto mode) {  // semantics first: it reads the voxel flags the attributes kernel rewrites
+        constexpr int M = decltype(mode)::value;
+        if (c->p.with_semantics) hipLaunchKernelGGL((k_merge_rows<V, M>), dim3(n_list), dim3(256), 0, c->stream, c->m, src->m, c->p, X, S);
+        hipLaunchKernelGGL((k_merge_attributes<V, M>), dim3(n_list), dim3(256), 0, c->stream, c->m, src->m, c->p, X, S);
+        hipLaunchKernelGGL((k_merge_apply<V, M>), dim3(n_list), dim3(256), 0, c->stream, c->m, src->m, c->p, X, S);
+      };
+      if (X.mode == kMergeAligned) write(std::integral_constant<int, kMergeAligned>());
+      else write(std::integral_constant<int, kMergeResample>());
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL((k_ckpt_rebuild<V>), dim3(n_touched), dim3(256), 0, c->stream, c->m, c->p, c->wpb, static_cast<const uint32_t*>(S.touched),
+                         static_cast<const uint32_t*>(S.ctr + MC_NLIST));
+      HIP_TRY(hipGetLastError());
+      return KHR_OK;
+    });
+    if (rc) return rc;
+    // ... and the source's later work (a frame, a reset, its destruction) behind the kernels that still read it
+    if (c->stream != src->stream) {
+      HIP_TRY(hipEventRecord(c->ev_merge, c->stream));
+      HIP_TRY(hipStreamWaitEvent(src->stream, c->ev_merge, 0));
+    }
+    c->host_index_valid = false, ++c->map_gen;
+    if (c->explicit_blocks > 0) c->explicit_blocks += n_new;
+  }
+  if (stats) *stats = st;
   return KHR_OK;
 }
 

@@ -2,7 +2,7 @@
 // thread drives the reference (spinOnce per InputPacket, finishMapping at shutdown), and prints a JSON
 // summary that tests/test_gpu_host.py compares with the step-wise C-ABI path and the oracle.
 // usage: aw_demo <config.yaml> <width> <height> <frames> [object_label]
-//        aw_demo --slices | --render | --query | --distance | --align | --weld | --checkpoint | --bench | --rayver ... (below)
+//        aw_demo --slices | --render | --query | --distance | --align | --weld | --merge | --checkpoint | --bench | --rayver ... (below)
 //   object_label >= 0: the stand-in detector / tracker below; otherwise the plugins named in the config
 #include <execinfo.h>
 #include <csignal>
@@ -1230,9 +1230,208 @@ static int weldDemo(int argc, char** argv) {
   return diff ? 3 : 0;
 }
 
+// ---- aw_demo --merge ----------------------------------------------------------------------------------------------------------
+// a block of a map on the host: cloneBlock's layers plus the likelihood rows ([k][voxel], zero without a semantic entry)
+struct MergeBlock {
+  hydra::BlockCopy b;
+  std::vector<float> lik;
+};
+using MergeBlocks = std::map<hydra::BlockIndex, MergeBlock>;
+
+static MergeBlocks downloadMap(const VolumetricMap& map, int K) {
+  MergeBlocks out;
+  const size_t n = static_cast<size_t>(map.config.voxels_per_side) * map.config.voxels_per_side * map.config.voxels_per_side;
+  for (const auto& idx : map.allocatedBlockIndices()) {
+    MergeBlock& m = out[idx];
+    m.b = map.cloneBlock(idx);
+    m.lik.assign(n * static_cast<size_t>(K), 0.f);
+    if (K > 0 && khr_download_block(map.ctx(), idx[0], idx[1], idx[2], nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, m.lik.data(),
+                                    nullptr) != KHR_OK)
+      throw std::runtime_error(std::string("khr_download_block: ") + khr_last_error());
+  }
+  return out;
+}
+
+// ASSUMPTIONS.md A.17, ALIGNED with zero offset, one thread: src into dst
+static khr_merge_stats hostMerge(MergeBlocks* dst, const MergeBlocks& src, size_t n, int K, float min_weight, float max_weight) {
+  khr_merge_stats st{};
+  st.n_src_blocks = st.n_candidate_blocks = src.size();
+  for (const auto& kv : src) {
+    const MergeBlock& s = kv.second;
+    bool any = false;
+    for (size_t v = 0; v < n && !any; ++v) any = s.b.weight[v] >= min_weight;
+    if (!any) continue;
+    ++st.n_touched_blocks;
+    auto it = dst->find(kv.first);
+    if (it == dst->end()) {
+      ++st.n_new_blocks;
+      MergeBlock fresh;
+      fresh.b.index = kv.first;
+      fresh.b.distance.assign(n, 0.f); fresh.b.weight.assign(n, 0.f); fresh.b.color.assign(4 * n, 0); fresh.b.last_observed.assign(n, 0);
+      fresh.b.last_occupied.assign(n, 0); fresh.b.flags.assign(n, 0); fresh.b.semantic_label.assign(n, 0);
+      fresh.lik.assign(n * static_cast<size_t>(K), 0.f);
+      it = dst->emplace(kv.first, std::move(fresh)).first;
+    }
+    MergeBlock& d = it->second;
+    bool active = false;
+    for (size_t v = 0; v < n; ++v) {
+      if (s.b.weight[v] >= min_weight) {
+        const float ws = s.b.weight[v], wd = d.b.weight[v];
+        const uint8_t fs = s.b.flags[v], fd = d.b.flags[v];
+        if (wd == 0.f) {
+          ++st.n_added_voxels;
+          d.b.distance[v] = s.b.distance[v];
+          d.b.weight[v] = std::fmin(ws, max_weight);
+          for (int c = 0; c < 4; ++c) d.b.color[4 * v + c] = s.b.color[4 * v + c];
+          d.b.last_observed[v] = s.b.last_observed[v];
+          d.b.last_occupied[v] = s.b.last_occupied[v];
+          d.b.flags[v] = fs;
+          d.b.semantic_label[v] = s.b.semantic_label[v];
+          for (int k = 0; k < K; ++k) d.lik[k * n + v] = (fs & KHR_VOX_SEM_VALID) ? s.lik[k * n + v] : 0.f;
+        } else {
+          ++st.n_merged_voxels;
+          const float sum = wd + ws;
+          d.b.distance[v] = (d.b.distance[v] * wd + s.b.distance[v] * ws) / sum;
+          if (s.b.color[4 * v + 3] != 0) {
+            if (d.b.color[4 * v + 3] == 0) {
+              for (int c = 0; c < 4; ++c) d.b.color[4 * v + c] = s.b.color[4 * v + c];
+            } else {
+              for (int c = 0; c < 3; ++c)
+                d.b.color[4 * v + c] = static_cast<uint8_t>(
+                    std::floor((static_cast<float>(d.b.color[4 * v + c]) * wd + static_cast<float>(s.b.color[4 * v + c]) * ws) / sum + 0.5f));
+              d.b.color[4 * v + 3] = 255;
+            }
+          }
+          d.b.weight[v] = std::fmin(sum, max_weight);
+          d.b.last_observed[v] = std::max(d.b.last_observed[v], s.b.last_observed[v]);
+          d.b.last_occupied[v] = std::max(d.b.last_occupied[v], s.b.last_occupied[v]);
+          if (fs & KHR_VOX_SEM_VALID) {
+            if (fd & KHR_VOX_SEM_VALID) {
+              float best = 0.f;
+              uint32_t arg = 0;
+              for (int k = 0; k < K; ++k) {
+                const float l = d.lik[k * n + v] + s.lik[k * n + v];
+                d.lik[k * n + v] = l;
+                if (k == 0 || l > best) best = l, arg = static_cast<uint32_t>(k);
+              }
+              d.b.semantic_label[v] = arg;
+            } else {
+              for (int k = 0; k < K; ++k) d.lik[k * n + v] = s.lik[k * n + v];
+              d.b.semantic_label[v] = s.b.semantic_label[v];
+            }
+          }
+          d.b.flags[v] = static_cast<uint8_t>(((fd | fs) & (KHR_VOX_ACTIVE | KHR_VOX_SEM_VALID)) | (fd & fs & (KHR_VOX_EVER_FREE | KHR_VOX_TO_REMOVE)));
+        }
+      }
+      active = active || (d.b.flags[v] & KHR_VOX_ACTIVE);
+    }
+    d.b.block_flags |= KHR_BLK_UPDATED | KHR_BLK_MESH_UPDATED | KHR_BLK_TRACKING_UPDATED | (active ? KHR_BLK_HAS_ACTIVE_DATA : 0);
+  }
+  return st;
+}
+
+// aw_demo --merge <config.yaml> <width> <height> <frames>: the first half of the synthetic stream through one ActiveWindow, the
+// second half through another; the second map is then merged into the first on the device (VolumetricMap::merge, ALIGNED, zero
+// offset) and, from copies taken before, on one host thread by the same definition.  One JSON line: whether the two results are
+// equal layer for layer, the statistics, the wall-clock time of the device merge and of the host alternative (the download of both
+// maps and the merge; the upload of the result, which khr_checkpoint_load would only take into an empty map, is not in it).
+static int mergeDemo(int argc, char** argv) {
+  if (argc < 6) {
+    std::fprintf(stderr, "usage: aw_demo --merge <config.yaml> <width> <height> <frames>\n");
+    return 2;
+  }
+  std::ifstream in(argv[2]);
+  std::stringstream ss;
+  ss << in.rdbuf();
+  const int W = std::atoi(argv[3]), H = std::atoi(argv[4]), N = std::atoi(argv[5]);
+  ActiveWindow::Config cfg = ActiveWindow::Config::fromYamlString(ss.str());
+  cfg.max_frame_pixels = static_cast<uint32_t>(W) * H;
+  auto q1 = std::make_shared<ActiveWindow::OutputQueue>(), q2 = std::make_shared<ActiveWindow::OutputQueue>();
+  ActiveWindow aw1(cfg, q1), aw2(cfg, q2);
+  void* scene = synth_create(1234, 12, 1);
+  const size_t np = static_cast<size_t>(W) * H;
+  std::vector<float> depth(np);
+  std::vector<uint8_t> rgb(np * 3);
+  std::vector<int32_t> label(np);
+  for (int i = 0; i < N; ++i) {
+    hydra::InputPacket pkt;
+    pkt.timestamp_ns = static_cast<uint64_t>(std::llround((1.0 + 0.1 * i) * 1e9));
+    circlePose(0.1 * i, pkt.world_T_body);
+    pkt.sensor = {W, H, W / 2.f, W / 2.f, W / 2.f, H / 2.f, 0.1f, 5.f};
+    synth_render(scene, W, H, pkt.sensor.fx, pkt.sensor.fy, pkt.sensor.cx, pkt.sensor.cy, pkt.world_T_body, 0.1 * i, 5.f, 0.f,
+                 1234u + 7919u * i, depth.data(), rgb.data(), label.data(), 0);
+    pkt.depth = depth.data();
+    pkt.color = rgb.data();
+    pkt.labels = label.data();
+    const bool first = i < N / 2;
+    (first ? aw1 : aw2).step(pkt);
+    hydra::ActiveWindowOutput::Ptr popped;
+    while ((first ? q1 : q2)->pop(&popped)) {}
+  }
+  synth_destroy(scene);
+  VolumetricMap dst(aw1.getMap().config, aw1.getMap().ctx());
+  const VolumetricMap& src = aw2.getMap();
+  khr_config kc{};
+  if (khr_get_config(dst.ctx(), &kc) != KHR_OK) throw std::runtime_error(khr_last_error());
+  const int K = kc.with_semantics ? kc.num_labels : 0;
+  const size_t n = static_cast<size_t>(kc.voxels_per_side) * kc.voxels_per_side * kc.voxels_per_side;
+  using clk = std::chrono::steady_clock;
+  auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+  // the host alternative first: it needs the maps as they are before the merge
+  khr_sync(dst.ctx());
+  khr_sync(src.ctx());
+  const auto t0 = clk::now();
+  MergeBlocks hd = downloadMap(dst, K);
+  const MergeBlocks hs = downloadMap(src, K);
+  const size_t n_dst_before = hd.size();
+  const khr_merge_stats host_st = hostMerge(&hd, hs, n, K, kc.mesh_min_weight, kc.max_weight);
+  const auto t1 = clk::now();
+  const khr_merge_stats st = dst.merge(src, VolumetricMap::MergeRequest{});
+  khr_sync(dst.ctx());
+  const auto t2 = clk::now();
+  const MergeBlocks got = downloadMap(dst, K);
+  aw1.finishMapping();
+  aw2.finishMapping();
+  std::string diff;
+  if (std::memcmp(&st, &host_st, sizeof(st)) != 0) diff = "statistics";
+  else if (got.size() != hd.size()) diff = "block count";
+  MergeBlocks::const_iterator a = got.begin(), b = hd.begin();
+  for (; diff.empty() && a != got.end(); ++a, ++b) {
+    const char* layer = nullptr;
+    if (a->first != b->first) layer = "block index";
+    else if (!sameBits(a->second.b.distance, b->second.b.distance)) layer = "distance";
+    else if (!sameBits(a->second.b.weight, b->second.b.weight)) layer = "weight";
+    else if (a->second.b.color != b->second.b.color) layer = "color";
+    else if (a->second.b.last_observed != b->second.b.last_observed) layer = "last_observed";
+    else if (a->second.b.last_occupied != b->second.b.last_occupied) layer = "last_occupied";
+    else if (a->second.b.flags != b->second.b.flags) layer = "flags";
+    else if (a->second.b.semantic_label != b->second.b.semantic_label) layer = "sem_label";
+    else if (!sameBits(a->second.lik, b->second.lik)) layer = "likelihoods";
+    else if (a->second.b.block_flags != b->second.b.block_flags) layer = "block_flags";
+    if (layer) diff = std::string(layer) + " of block (" + std::to_string(a->first[0]) + ", " + std::to_string(a->first[1]) + ", " + std::to_string(a->first[2]) + ")";
+  }
+  std::printf("{\"what\": \"two half streams, the second map merged into the first: VolumetricMap::merge (device) vs block copies merged on one host "
+              "thread, %dx%d, voxel %.4g m\", \"frames\": %d, \"n_dst_blocks\": %zu, \"n_src_blocks\": %llu, \"n_candidate_blocks\": %llu, "
+              "\"n_touched_blocks\": %llu, \"n_new_blocks\": %llu, \"n_added_voxels\": %llu, \"n_merged_voxels\": %llu, \"equal\": %s, "
+              "\"first_mismatch\": \"%s\", \"device_merge_ms\": %.4f, \"host_merge_ms\": %.4f}\n",
+              W, H, static_cast<double>(kc.voxel_size), N, n_dst_before, static_cast<unsigned long long>(st.n_src_blocks),
+              static_cast<unsigned long long>(st.n_candidate_blocks), static_cast<unsigned long long>(st.n_touched_blocks),
+              static_cast<unsigned long long>(st.n_new_blocks), static_cast<unsigned long long>(st.n_added_voxels),
+              static_cast<unsigned long long>(st.n_merged_voxels), diff.empty() ? "true" : "false", diff.c_str(), ms(t1, t2), ms(t0, t1));
+  return diff.empty() ? 0 : 3;
+}
+
 int main(int argc, char** argv) {
   std::signal(SIGSEGV, onSegv);
   std::signal(SIGABRT, onSegv);
+  if (argc >= 2 && std::string(argv[1]) == "--merge") {
+    try {
+      return mergeDemo(argc, argv);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "aw_demo: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc >= 2 && std::string(argv[1]) == "--weld") {
     try {
       return weldDemo(argc, argv);

@@ -531,6 +531,25 @@ class VolumetricMap {
   // frontend's voxel-grid mesh compression (khr_weld_mesh, ASSUMPTIONS.md A.16).  Welded on the device; the indexed mesh alone
   // crosses to the host.  Throws std::runtime_error with khr_last_error's text.  (Defined below, behind IndexedMesh.)
   IndexedMesh weldedMesh(float resolution) const;
+  // Another map fused into this one on the device (voxblox's mergeLayerAintoLayerB role; khr_merge_map, ASSUMPTIONS.md A.17):
+  // voxel to voxel under an integer voxel offset, or resampled under a rigid dst_T_src.  `other` is only read.  Returns the
+  // statistics; throws std::runtime_error with khr_last_error's text, the map then is as it was.
+  struct MergeRequest {
+    bool resample = false;
+    int32_t voxel_offset[3] = {0, 0, 0};
+    double dst_T_src[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    float min_weight = 0.f;  // 0 = this map's mesh_min_weight
+  };
+  khr_merge_stats merge(const VolumetricMap& other, const MergeRequest& request) {
+    khr_merge_request rq{};
+    rq.mode = request.resample ? KHR_MERGE_RESAMPLE : KHR_MERGE_ALIGNED;
+    for (int i = 0; i < 3; ++i) rq.voxel_offset[i] = request.voxel_offset[i];
+    for (int i = 0; i < 16; ++i) rq.dst_T_src[i] = request.dst_T_src[i];
+    rq.min_weight = request.min_weight;
+    khr_merge_stats st{};
+    if (khr_merge_map(ctx_, other.ctx_, &rq, &st) != KHR_OK) throw std::runtime_error(std::string("khr_merge_map: ") + khr_last_error());
+    return st;
+  }
 
  private:
   static khr_align_request alignRequest(const double* prior, const AlignOptions& opt) {
