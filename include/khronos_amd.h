@@ -883,6 +883,59 @@ typedef struct khr_merge_stats {
 } khr_merge_stats;
 int khr_merge_map(khr_ctx* dst, khr_ctx* src, const khr_merge_request* request, khr_merge_stats* stats);
 
+/* ---- the live map compared with another map (ASSUMPTIONS.md A.18) -----------------------------------------------------
+ * khr_diff_map lists the voxels that appeared or vanished in the map of `ctx` ("now") against the map of `ref` ("then"): a side
+ * context that holds yesterday's checkpoint, the same stretch under a corrected pose, another robot's window.  Neither map is
+ * written.  `then` is sampled at the voxels of `now` exactly as khr_merge_map samples a source at the voxels of its destination
+ * (mode, voxel_offset and ctx_T_ref as there; min_weight 0 = ctx's mesh_min_weight, and the same threshold decides "observed" in
+ * `now`).  The blocks that take part are the candidate blocks of A.17 that are live in `now` (the present blocks).  A voxel of a
+ * present block that is observed in `now` and has a valid sample is compared: it APPEARED (kind 1) iff d_then >= free_distance
+ * and d_now <= occupied_distance, it DISAPPEARED (kind 2) iff d_then <= occupied_distance and d_now >= free_distance; the gap
+ * between the two thresholds keeps TSDF noise from counting as change.  The call takes the thresholds as given (the Python and
+ * C++ bindings default to occupied_distance = 0, free_distance = voxel_size).
+ *
+ * The result: the changed blocks in the (x, y, z) order of khr_block_indices, and per block its changed voxels in ascending
+ * linear index x + vps (y + vps z).  Per voxel: its global voxel index in ctx's frame, kind, d_now, d_then, the label of the
+ * occupied side (now's for kind 1, then's for kind 2; 0 without semantics), and last_observed of either side (0 without
+ * tracking).  Per block: its index, n_appeared, n_disappeared and `first`, the index of its first entry in the voxel list.
+ *
+ * khr_diff_map works in stream order on ctx's stream, ordered behind everything queued on ref's stream by an event, and ref's
+ * later work behind the diff's kernels by another, so ref may be used or destroyed as soon as the call returns.  There is one
+ * host wait, for the counts that fill `stats` (may be NULL) and size the result.  The result lives in buffers ctx owns: it stays
+ * valid across later frames until the next khr_diff_map, khr_reset_map, khr_checkpoint_load or khr_destroy; a failed diff
+ * discards an earlier result.  Both maps, the frame ring, the mesh layer, the detectors' state and the cumulative khr_stats
+ * counters are not touched.  KHR_EINVAL: as khr_merge_map for the pair and the request (NULL arguments or ref == ctx, different
+ * devices, a differing configuration field named in the text, an unknown mode, a negative or non-finite min_weight, |offset| >=
+ * 2^30, a pose that is non-finite, not rigid or a reflection); a threshold that is not finite, or occupied_distance >=
+ * free_distance.  KHR_ESTATE: world_size > 1 on either side.  There is no key-range error: a candidate outside the key range
+ * cannot be live in ctx.  An empty ref, or a diff without changes, is KHR_OK with empty lists.
+ *
+ * khr_diff_map_into copies the result of the last successful diff (KHR_ESTATE without one); any pointer may be NULL; it may be
+ * called several times.  on_device == 0: host arrays, filled when the call returns.  on_device != 0: device arrays, copied
+ * device-to-device in stream order, nothing is awaited.  voxels 3 int32 per changed voxel, the other voxel arrays one element per
+ * changed voxel (n_appeared + n_disappeared of them); blocks 3 int32 per changed block, the other block arrays one word per
+ * changed block (n_changed_blocks). */
+#define KHR_DIFF_APPEARED 1
+#define KHR_DIFF_DISAPPEARED 2
+typedef struct khr_diff_request {
+  int32_t mode;            /* KHR_MERGE_ALIGNED / KHR_MERGE_RESAMPLE */
+  int32_t voxel_offset[3]; /* ALIGNED: global voxel g of ctx is compared with global voxel g - voxel_offset of ref */
+  double ctx_T_ref[16];    /* RESAMPLE: row-major 4x4, rigid */
+  float min_weight;        /* observed iff weight >= this, on either side; 0 = ctx's mesh_min_weight */
+  float occupied_distance; /* occ(d) iff d <= occupied_distance */
+  float free_distance;     /* free(d) iff d >= free_distance; occupied_distance < free_distance */
+} khr_diff_request;
+typedef struct khr_diff_stats {
+  uint64_t n_ref_blocks, n_candidate_blocks; /* as khr_merge_stats' n_src_blocks and n_candidate_blocks */
+  uint64_t n_present_blocks;                 /* candidates that are live in ctx */
+  uint64_t n_compared_voxels, n_appeared, n_disappeared, n_only_now, n_only_then; /* over the present blocks */
+  uint64_t n_changed_blocks;                 /* present blocks with a kind-1 or kind-2 voxel */
+} khr_diff_stats;
+int khr_diff_map(khr_ctx* ctx, khr_ctx* ref, const khr_diff_request* request, khr_diff_stats* stats);
+int khr_diff_map_into(khr_ctx* ctx, int on_device, int32_t* voxels, uint8_t* kind, float* d_now, float* d_then, uint32_t* label,
+                      uint64_t* stamp_now, uint64_t* stamp_then, int32_t* blocks, uint32_t* block_appeared,
+                      uint32_t* block_disappeared, uint32_t* block_first);
+
 /* ---- tick path: the camera frames of ONE tick batched (sharded multi-camera runs) ------------------------------------
  * In a hash-range sharded run every rank sees every camera frame, so the per-camera work of a
  * rank is what does not shrink with the rank count.  These two calls are khr_upload_frame / khr_integrate for n_frames

@@ -73,6 +73,19 @@ class KhrMergeStats(C.Structure):
                                           "n_merged_voxels")]
 
 
+KHR_DIFF_APPEARED, KHR_DIFF_DISAPPEARED = 1, 2
+
+
+class KhrDiffRequest(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("voxel_offset", C.c_int32 * 3), ("ctx_T_ref", C.c_double * 16), ("min_weight", C.c_float),
+                ("occupied_distance", C.c_float), ("free_distance", C.c_float)]
+
+
+class KhrDiffStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_ref_blocks", "n_candidate_blocks", "n_present_blocks", "n_compared_voxels", "n_appeared",
+                                          "n_disappeared", "n_only_now", "n_only_then", "n_changed_blocks")]
+
+
 class KhrDfRequest(C.Structure):
     _fields_ = [("origin", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("ratio", C.c_int32), ("min_weight", C.c_float),
                 ("max_distance", C.c_float), ("surface_distance", C.c_float), ("unknown_is_obstacle", C.c_int32),
@@ -172,7 +185,7 @@ EXPORTS = [
     "khr_align_linearize", "khr_align_frame", "khr_distance_field",
     "khr_checkpoint_size", "khr_checkpoint_save", "khr_checkpoint_load", "khr_checkpoint_inspect",
     "khr_debug_live_resources", "khr_configure_object_voxel_sets",
-    "khr_weld_mesh", "khr_weld_mesh_into", "khr_merge_map",
+    "khr_weld_mesh", "khr_weld_mesh_into", "khr_merge_map", "khr_diff_map", "khr_diff_map_into",
 ]
 
 _lib = None
@@ -302,6 +315,8 @@ def load_library():
     lib.khr_weld_mesh.argtypes = [vp, C.c_float, C.POINTER(KhrWeldStats)]
     lib.khr_weld_mesh_into.argtypes = [vp, i32] + [vp] * 7
     lib.khr_merge_map.argtypes = [vp, vp, C.POINTER(KhrMergeRequest), C.POINTER(KhrMergeStats)]
+    lib.khr_diff_map.argtypes = [vp, vp, C.POINTER(KhrDiffRequest), C.POINTER(KhrDiffStats)]
+    lib.khr_diff_map_into.argtypes = [vp, i32] + [vp] * 11
     lib.khr_debug_read.argtypes = [vp, vp, i64]
     lib.khr_debug_live_resources.argtypes = [C.POINTER(i64)]
     lib.khr_tick_ingest.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
@@ -1288,6 +1303,57 @@ class FusionContext:
         rc, st = self.merge_map_rc(src, rq)
         self._chk(rc)
         return st
+
+    DIFF_FIELDS = (("voxels", np.int32, (3,), "v"), ("kind", np.uint8, (), "v"), ("d_now", np.float32, (), "v"), ("d_then", np.float32, (), "v"),
+                   ("label", np.uint32, (), "v"), ("stamp_now", np.uint64, (), "v"), ("stamp_then", np.uint64, (), "v"),
+                   ("blocks", np.int32, (3,), "b"), ("block_appeared", np.uint32, (), "b"), ("block_disappeared", np.uint32, (), "b"),
+                   ("block_first", np.uint32, (), "b"))
+
+    def diff_request(self, mode=KHR_MERGE_ALIGNED, voxel_offset=(0, 0, 0), pose=None, min_weight=0.0, occupied_distance=None, free_distance=None):
+        """khr_diff_request: mode / voxel_offset / pose (= ctx_T_ref) / min_weight as in merge_request; occupied_distance defaults to
+        0 and free_distance to this context's voxel_size"""
+        rq = KhrDiffRequest()
+        rq.mode = int(mode)
+        rq.voxel_offset[:] = [int(v) for v in voxel_offset]
+        rq.ctx_T_ref[:] = np.asarray(np.eye(4) if pose is None else pose, np.float64).reshape(16).tolist()
+        rq.min_weight = float(min_weight)
+        rq.occupied_distance = 0.0 if occupied_distance is None else float(occupied_distance)
+        rq.free_distance = float(self.cfg.voxel_size) if free_distance is None else float(free_distance)
+        return rq
+
+    def diff_map_rc(self, ref, request):
+        """khr_diff_map without raising: (return code, statistics dict)"""
+        st = KhrDiffStats()
+        rc = self.lib.khr_diff_map(self.h, ref.h if ref is not None else None, C.byref(request) if request is not None else None, C.byref(st))
+        return rc, {k: int(getattr(st, k)) for k, _ in KhrDiffStats._fields_}
+
+    def diff_map_into(self, out, on_device=False):
+        """khr_diff_map_into: the result of the last diff into caller buffers (`out`: DIFF_FIELDS name -> contiguous array, or an
+        integer device pointer with on_device; absent / None = not copied).  Returns the return code without raising."""
+        ptrs = []
+        for name, _, _, _ in self.DIFF_FIELDS:
+            a = out.get(name)
+            ptrs.append(None if a is None else (C.c_void_p(int(a)) if on_device else _ptr(a)))
+        return self.lib.khr_diff_map_into(self.h, int(on_device), *ptrs)
+
+    def diff_map(self, ref, mode=KHR_MERGE_ALIGNED, voxel_offset=(0, 0, 0), pose=None, min_weight=0.0, occupied_distance=None, free_distance=None,
+                 request=None):
+        """The voxels that appeared or vanished in this context's map against the map of the context `ref`, found on the device
+        (khr_diff_map, ASSUMPTIONS.md A.18); neither map is written.  `ref` is sampled as merge_map samples its source (mode,
+        voxel_offset, pose = ctx_T_ref, min_weight).  A compared voxel appeared iff d_then >= free_distance and d_now <=
+        occupied_distance, and disappeared iff d_then <= occupied_distance and d_now >= free_distance; the defaults are
+        occupied_distance = 0 and free_distance = voxel_size.  Returns a dict: the statistics under "stats", per changed voxel
+        voxels (n, 3) int32, kind uint8 (1 appeared, 2 disappeared), d_now / d_then float32, label uint32, stamp_now / stamp_then
+        uint64, per changed block blocks (m, 3) int32, block_appeared / block_disappeared / block_first uint32 -- blocks in (x, y, z)
+        order, the voxels of a block in ascending linear index."""
+        rq = request if request is not None else self.diff_request(mode, voxel_offset, pose, min_weight, occupied_distance, free_distance)
+        rc, stats = self.diff_map_rc(ref, rq)
+        self._chk(rc)
+        n = {"v": stats["n_appeared"] + stats["n_disappeared"], "b": stats["n_changed_blocks"]}
+        out = {k: np.zeros((n[w],) + sh, dt) for k, dt, sh, w in self.DIFF_FIELDS}
+        self._chk(self.diff_map_into(out))
+        out["stats"] = stats
+        return out
 
     def fetch_mesh_reuse(self, bufs):
         """fetch_mesh() into arrays the caller keeps (a consumer that takes one mesh per output must not pay page faults on 20 MB of

@@ -42,6 +42,7 @@
 #include "khr_kernels_checkpoint.h"
 #include "khr_kernels_weld.h"
 #include "khr_kernels_merge.h"
+#include "khr_kernels_diff.h"
 
 using namespace khr;
 
@@ -433,6 +434,11 @@ struct khr_ctx {
   DevBuf<uint32_t> d_merge_ctr;
   PinnedBuf<uint32_t> h_merge;
   Event ev_merge;
+  // map diffs (khr_diff_map, this context as `now`; the candidates and counters use the merge scratch above): the sorted changed
+  // list with its scan, the sort's and the scan's temporary storage and the result, each grown to the largest diff so far
+  DevBuf<uint8_t> d_diff_work, d_diff_cub, d_diff_out;
+  khr_diff_stats diff_stats{};
+  bool diff_valid = false;  // a diff succeeded and nothing has discarded its result
   // timing
   uint32_t timing = 0;  // bit i = timer i enabled
   std::vector<TimingRec> pending;
@@ -844,6 +850,7 @@ int khr_reset_map(khr_ctx* c, float voxel_size, float truncation_distance) {
   c->mesh_total = 0;
   c->mesh_stale = false;
   c->weld_valid = false;
+  c->diff_valid = false;
   c->host_index_valid = false, ++c->map_gen;
   c->explicit_blocks = 0;
   c->last_removed = 0;
@@ -5259,6 +5266,7 @@ int khr_checkpoint_load(khr_ctx* c, const void* buffer, uint64_t n_bytes, int64_
   if (!c || !buffer) return fail(KHR_EINVAL, "null argument");
   if (n_kept) *n_kept = 0;
   c->weld_valid = false;  // (khr_weld_mesh: the welded mesh belongs to the map before the load)
+  c->diff_valid = false;  // (khr_diff_map: so does the diff)
   khr_checkpoint_header h;
   int rc = khr_checkpoint_inspect(buffer, n_bytes, &h);
   if (rc) return rc;
@@ -6076,16 +6084,18 @@ int khr_weld_mesh_into(khr_ctx* c, int on_device, float* points, uint8_t* colors
 }
 
 // ---- another map fused into the live map (khr_merge_map; ASSUMPTIONS.md A.17, device side: khr_kernels_merge.h) ----------------
-int khr_merge_map(khr_ctx* c, khr_ctx* src, const khr_merge_request* rq, khr_merge_stats* stats) {
-  if (stats) *stats = khr_merge_stats{};
-  if (!c || !src || !rq) return fail(KHR_EINVAL, "khr_merge_map: null argument");
-  if (src == c) return fail(KHR_EINVAL, "khr_merge_map: src and dst are the same context");
-  if (c->device != src->device) return fail(KHR_EINVAL, "khr_merge_map: the contexts live on different devices (%d and %d)", src->device, c->device);
+// What khr_merge_map and khr_diff_map ask of their pair of contexts and of the sampling part of their request (`call` names the
+// caller in the texts); fills X's mode, min_weight, offset or transforms, row stride and stamps.
+static int mergeCheckPair(const char* call, khr_ctx* c, khr_ctx* src, const void* rq, int mode, const int32_t* voxel_offset, const double* T,
+                          float min_weight, MergeArgs* Xo) {
+  if (!c || !src || !rq) return fail(KHR_EINVAL, "%s: null argument", call);
+  if (src == c) return fail(KHR_EINVAL, "%s: src and dst are the same context", call);
+  if (c->device != src->device) return fail(KHR_EINVAL, "%s: the contexts live on different devices (%d and %d)", call, src->device, c->device);
   {
     const khr_checkpoint_header hs = ckptHeaderFor(src->cfg, 0), hd = ckptHeaderFor(c->cfg, 0);
 #define KHR_MERGE_FIELD(name, fmt, cast)                                                                                          \
   if (hs.name != hd.name)                                                                                                         \
-    return fail(KHR_EINVAL, "khr_merge_map: " #name " is " fmt " in the source and " fmt " in the destination", static_cast<cast>(hs.name), \
+    return fail(KHR_EINVAL, "%s: " #name " is " fmt " in the source and " fmt " in the destination", call, static_cast<cast>(hs.name), \
                 static_cast<cast>(hd.name));
     KHR_MERGE_FIELD(voxel_size, "%.9g", double)
     KHR_MERGE_FIELD(voxels_per_side, "%d", int)
@@ -6096,28 +6106,28 @@ int khr_merge_map(khr_ctx* c, khr_ctx* src, const khr_merge_request* rq, khr_mer
     KHR_MERGE_FIELD(semantic_mode, "%d", int)
 #undef KHR_MERGE_FIELD
   }
-  if (rq->mode != KHR_MERGE_ALIGNED && rq->mode != KHR_MERGE_RESAMPLE) return fail(KHR_EINVAL, "khr_merge_map: unknown mode %d", rq->mode);
-  if (!std::isfinite(rq->min_weight) || rq->min_weight < 0.f) return fail(KHR_EINVAL, "khr_merge_map: min_weight must be finite and >= 0");
+  if (mode != KHR_MERGE_ALIGNED && mode != KHR_MERGE_RESAMPLE) return fail(KHR_EINVAL, "%s: unknown mode %d", call, mode);
+  if (!std::isfinite(min_weight) || min_weight < 0.f) return fail(KHR_EINVAL, "%s: min_weight must be finite and >= 0", call);
   if (c->cfg.world_size > 1 || src->cfg.world_size > 1)
-    return fail(KHR_ESTATE, "khr_merge_map needs whole maps: world_size is %d in the source and %d in the destination", src->cfg.world_size,
+    return fail(KHR_ESTATE, "%s needs whole maps: world_size is %d in the source and %d in the destination", call, src->cfg.world_size,
                 c->cfg.world_size);
-  MergeArgs X{};
-  X.mode = rq->mode;
-  X.min_weight = rq->min_weight > 0.f ? rq->min_weight : c->p.mesh_min_weight;
+  MergeArgs& X = *Xo;
+  X = MergeArgs{};
+  X.mode = mode;
+  X.min_weight = min_weight > 0.f ? min_weight : c->p.mesh_min_weight;
   X.ks_src = src->p.KS;
   X.src_stamp = src->last_track_stamp;
   X.dst_stamp = c->last_track_stamp;
-  if (rq->mode == KHR_MERGE_ALIGNED) {
+  if (mode == KHR_MERGE_ALIGNED) {
     for (int a = 0; a < 3; ++a) {
-      const int64_t o = rq->voxel_offset[a];
-      if (o <= -(1ll << 30) || o >= (1ll << 30)) return fail(KHR_EINVAL, "khr_merge_map: voxel_offset[%d] = %lld, |offset| must be below 2^30", a, static_cast<long long>(o));
-      X.off[a] = rq->voxel_offset[a];
+      const int64_t o = voxel_offset[a];
+      if (o <= -(1ll << 30) || o >= (1ll << 30)) return fail(KHR_EINVAL, "%s: voxel_offset[%d] = %lld, |offset| must be below 2^30", call, a, static_cast<long long>(o));
+      X.off[a] = voxel_offset[a];
     }
   } else {
-    const double* T = rq->dst_T_src;
     for (int i = 0; i < 16; ++i)
-      if (!std::isfinite(T[i])) return fail(KHR_EINVAL, "khr_merge_map: dst_T_src is not finite");
-    if (T[12] != 0.0 || T[13] != 0.0 || T[14] != 0.0 || T[15] != 1.0) return fail(KHR_EINVAL, "khr_merge_map: the last row of dst_T_src is not 0 0 0 1");
+      if (!std::isfinite(T[i])) return fail(KHR_EINVAL, "%s: dst_T_src is not finite", call);
+    if (T[12] != 0.0 || T[13] != 0.0 || T[14] != 0.0 || T[15] != 1.0) return fail(KHR_EINVAL, "%s: the last row of dst_T_src is not 0 0 0 1", call);
     double worst = 0.0;
     for (int i = 0; i < 3; ++i)
       for (int j = 0; j < 3; ++j) {
@@ -6125,9 +6135,9 @@ int khr_merge_map(khr_ctx* c, khr_ctx* src, const khr_merge_request* rq, khr_mer
         for (int k = 0; k < 3; ++k) s += T[4 * k + i] * T[4 * k + j];
         worst = std::max(worst, std::fabs(s - (i == j ? 1.0 : 0.0)));
       }
-    if (worst > 1e-5) return fail(KHR_EINVAL, "khr_merge_map: dst_T_src is not rigid: max |R^T R - I| = %.3g", worst);
+    if (worst > 1e-5) return fail(KHR_EINVAL, "%s: dst_T_src is not rigid: max |R^T R - I| = %.3g", call, worst);
     const double det = T[0] * (T[5] * T[10] - T[6] * T[9]) - T[1] * (T[4] * T[10] - T[6] * T[8]) + T[2] * (T[4] * T[9] - T[5] * T[8]);
-    if (det < 0.0) return fail(KHR_EINVAL, "khr_merge_map: dst_T_src is a reflection (det R = %.3g)", det);
+    if (det < 0.0) return fail(KHR_EINVAL, "%s: dst_T_src is a reflection (det R = %.3g)", call, det);
     for (int a = 0; a < 3; ++a) {  // src_T_dst = [R^T | -R^T t] in double, cast once
       double t = 0.0;
       for (int k = 0; k < 3; ++k) {
@@ -6139,25 +6149,35 @@ int khr_merge_map(khr_ctx* c, khr_ctx* src, const khr_merge_request* rq, khr_mer
       X.F[4 * a + 3] = static_cast<float>(T[4 * a + 3]);
     }
   }
-  HIP_TRY(hipSetDevice(c->device));
-  // scratch, sized by what the source's pool can reach (its block count is not known without a wait)
-  const size_t reach = rq->mode == KHR_MERGE_ALIGNED ? kMergeReachAligned : kMergeReachResample;
+  return KHR_OK;
+}
+
+constexpr size_t kMergeCounterWords = 32;  // the counter block of a merge (12 words) or a diff (kDiffCounterWords)
+static_assert(kDiffCounterWords <= static_cast<int>(kMergeCounterWords), "the counters of a diff fit the block");
+
+// The scratch of a merge or a diff in context c (calls on one context are serialised: they share it), sized by what the pool of
+// `src` can reach (its block count is not known without a wait) with `words` 32-bit words per candidate behind the list; queues
+// the clears of the counters and the candidate set on c's stream, behind everything queued on src's stream.
+static int mergeBeginScratch(const char* call, khr_ctx* c, khr_ctx* src, int mode, size_t words, MergeScratch* So) {
+  const size_t reach = mode == KHR_MERGE_ALIGNED ? kMergeReachAligned : kMergeReachResample;
   const size_t cap = reach * static_cast<size_t>(src->m.capacity);
-  if (cap > (1ull << 30)) return fail(KHR_ENOMEM, "khr_merge_map: %zu candidate blocks, at most 2^30", cap);
+  if (cap > (1ull << 30)) return fail(KHR_ENOMEM, "%s: %zu candidate blocks, at most 2^30", call, cap);
   size_t set_n = 64;
   while (set_n < 2 * cap) set_n <<= 1;
-  if (set_n > c->d_merge_set.count() || cap > c->d_merge_cand.count() || !c->d_merge_ctr || !c->h_merge) {
+  if (set_n > c->d_merge_set.count() || cap > c->d_merge_cand.count() || words * cap > c->d_merge_words.count() ||
+      kMergeCounterWords > c->d_merge_ctr.count() || !c->h_merge) {
     HIP_TRY(hipStreamSynchronize(c->stream));  // (whatever still uses the old blocks)
     int rc = KHR_OK;
     KHR_CHAIN(c->d_merge_set.reserve(set_n));
     KHR_CHAIN(c->d_merge_cand.reserve(cap));
-    KHR_CHAIN(c->d_merge_words.reserve(3 * cap));
-    KHR_CHAIN(c->d_merge_ctr.reserve(16));
-    KHR_CHAIN(c->h_merge.reserve(16));
-    if (rc) return fail(KHR_ENOMEM, "khr_merge_map: scratch for %zu candidate blocks", cap);
+    KHR_CHAIN(c->d_merge_words.reserve(words * cap));
+    KHR_CHAIN(c->d_merge_ctr.reserve(kMergeCounterWords));
+    KHR_CHAIN(c->h_merge.reserve(kMergeCounterWords));
+    if (rc) return fail(KHR_ENOMEM, "%s: scratch for %zu candidate blocks", call, cap);
   }
   KHR_TRY(c->ev_merge.ensure());
-  MergeScratch S{};
+  MergeScratch& S = *So;
+  S = MergeScratch{};
   S.set_keys = c->d_merge_set;
   S.set_mask = static_cast<uint32_t>(set_n - 1);
   S.cand = c->d_merge_cand;
@@ -6172,8 +6192,20 @@ int khr_merge_map(khr_ctx* c, khr_ctx* src, const khr_merge_request* rq, khr_mer
     HIP_TRY(hipEventRecord(c->ev_merge, src->stream));
     HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_merge, 0));
   }
-  HIP_TRY(hipMemsetAsync(S.ctr, 0, 16 * sizeof(uint32_t), c->stream));
+  HIP_TRY(hipMemsetAsync(S.ctr, 0, kMergeCounterWords * sizeof(uint32_t), c->stream));
   HIP_TRY(hipMemsetAsync(S.set_keys, 0xff, set_n * sizeof(uint64_t), c->stream));
+  return KHR_OK;
+}
+
+int khr_merge_map(khr_ctx* c, khr_ctx* src, const khr_merge_request* rq, khr_merge_stats* stats) {
+  if (stats) *stats = khr_merge_stats{};
+  MergeArgs X{};
+  KHR_TRY(mergeCheckPair("khr_merge_map", c, src, rq, rq ? rq->mode : 0, rq ? rq->voxel_offset : nullptr, rq ? rq->dst_T_src : nullptr,
+                         rq ? rq->min_weight : 0.f, &X));
+  HIP_TRY(hipSetDevice(c->device));
+  MergeScratch S{};
+  KHR_TRY(mergeBeginScratch("khr_merge_map", c, src, rq->mode, 3, &S));
+  const size_t cap = S.cap;
   int rc = dispatchVps(c, [&](auto vps) {
     constexpr int V = decltype(vps)::value;
     hipLaunchKernelGGL((k_merge_candidates<V>), dim3(std::max(1, std::min(gridFor(src->m.capacity), 1024))), dim3(256), 0, c->stream, src->m, c->p, X, S);
@@ -6235,6 +6267,142 @@ int khr_merge_map(khr_ctx* c, khr_ctx* src, const khr_merge_request* rq, khr_mer
     if (c->explicit_blocks > 0) c->explicit_blocks += n_new;
   }
   if (stats) *stats = st;
+  return KHR_OK;
+}
+
+// ---- the live map compared with another map (khr_diff_map; ASSUMPTIONS.md A.18, device side: khr_kernels_diff.h) ----------------
+int khr_diff_map(khr_ctx* c, khr_ctx* ref, const khr_diff_request* rq, khr_diff_stats* stats) {
+  if (stats) *stats = khr_diff_stats{};
+  if (c) {  // (a failed diff discards the earlier result)
+    c->diff_valid = false;
+    c->diff_stats = khr_diff_stats{};
+  }
+  MergeArgs X{};
+  KHR_TRY(mergeCheckPair("khr_diff_map", c, ref, rq, rq ? rq->mode : 0, rq ? rq->voxel_offset : nullptr, rq ? rq->ctx_T_ref : nullptr,
+                         rq ? rq->min_weight : 0.f, &X));
+  if (!std::isfinite(rq->occupied_distance) || !std::isfinite(rq->free_distance))
+    return fail(KHR_EINVAL, "khr_diff_map: occupied_distance and free_distance must be finite");
+  if (!(rq->occupied_distance < rq->free_distance))
+    return fail(KHR_EINVAL, "khr_diff_map: occupied_distance (%.9g) must be below free_distance (%.9g)", static_cast<double>(rq->occupied_distance),
+                static_cast<double>(rq->free_distance));
+  const DiffArgs D{rq->occupied_distance, rq->free_distance};
+  HIP_TRY(hipSetDevice(c->device));
+  // per candidate: its slot in `now`, its two counts; the changed list: a candidate and a 64-bit key
+  MergeScratch S{};
+  KHR_TRY(mergeBeginScratch("khr_diff_map", c, ref, rq->mode, kDiffWordsPerCandidate, &S));
+  const size_t cap = S.cap;
+  DiffWork W{};
+  W.words = c->d_merge_words;
+  W.cap = S.cap;
+  hipStream_t st = c->stream;
+  int rc = dispatchVps(c, [&](auto vps) {
+    constexpr int V = decltype(vps)::value;
+    hipLaunchKernelGGL((k_merge_candidates<V>), dim3(std::max(1, std::min(gridFor(ref->m.capacity), 1024))), dim3(256), 0, st, ref->m, c->p, X, S);
+    HIP_TRY(hipGetLastError());
+    const dim3 grid(static_cast<uint32_t>(std::min<size_t>(cap, 8192)));
+    if (X.mode == kMergeAligned) hipLaunchKernelGGL((k_diff_count<V, kMergeAligned>), grid, dim3(256), 0, st, c->m, ref->m, c->p, X, D, S, W);
+    else hipLaunchKernelGGL((k_diff_count<V, kMergeResample>), grid, dim3(256), 0, st, c->m, ref->m, c->p, X, D, S, W);
+    HIP_TRY(hipGetLastError());
+    return KHR_OK;
+  });
+  if (rc) return rc;
+  // the one host wait: the counts
+  uint32_t* const h = c->h_merge;
+  HIP_TRY(hipMemcpyAsync(h, S.ctr, kDiffCounterWords * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (h[MC_ERR] & kMergeErrOverflow) return fail(KHR_EDEVICE, "khr_diff_map: the candidate list overflowed (%u entries, room for %u)", h[MC_LIST], S.cap);
+  uint64_t v64[DV_COUNT];
+  std::memcpy(v64, h + DC_COUNT, sizeof(v64));
+  khr_diff_stats s{};
+  s.n_ref_blocks = h[MC_SRC];
+  s.n_candidate_blocks = h[MC_CAND];
+  s.n_present_blocks = h[DC_PRESENT];
+  s.n_compared_voxels = v64[DV_COMPARED];
+  s.n_appeared = v64[DV_APPEARED];
+  s.n_disappeared = v64[DV_DISAPPEARED];
+  s.n_only_now = v64[DV_ONLY_NOW];
+  s.n_only_then = v64[DV_ONLY_THEN];
+  s.n_changed_blocks = h[DC_CHANGED];
+  const uint64_t n64 = s.n_appeared + s.n_disappeared;
+  if (n64 > (1ull << 30)) return fail(KHR_ENOMEM, "khr_diff_map: %llu changed voxels, at most 2^30", static_cast<unsigned long long>(n64));
+  if (h[DC_CHANGED] > S.cap || (h[DC_CHANGED] == 0) != (n64 == 0))
+    return fail(KHR_EDEVICE, "khr_diff_map: inconsistent counts (%u changed blocks, %llu changed voxels)", h[DC_CHANGED], static_cast<unsigned long long>(n64));
+  const uint32_t m = h[DC_CHANGED], n = static_cast<uint32_t>(n64);
+  if (m > 0) {
+    // the work area and the result; nothing is queued on the stream here (the wait above), so a growth frees nothing in use
+    auto al = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
+    size_t o = 0;
+    auto carve = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
+    const size_t w_key = carve(8ull * m), w_cand = carve(4ull * m), w_cnt = carve(4ull * (m + 1ull)), w_first = carve(4ull * (m + 1ull));
+    const size_t work_bytes = o, out_bytes = diffLayout(n, m).bytes;
+    size_t sort_bytes = 0, scan_bytes = 0;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, static_cast<const uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr),
+                                               static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), static_cast<int>(m), 0, 63, st));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, static_cast<uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), static_cast<int>(m + 1u), st));
+    const size_t cub_bytes = std::max<size_t>(std::max(sort_bytes, scan_bytes), 256);
+    if (c->d_diff_work.reserve(work_bytes) || c->d_diff_out.reserve(out_bytes) || c->d_diff_cub.reserve(cub_bytes))
+      return fail(KHR_ENOMEM, "khr_diff_map: buffers for %u changed voxels in %u blocks (%zu bytes)", n, m, work_bytes + out_bytes + cub_bytes);
+    uint8_t* const wb = c->d_diff_work;
+    W.sorted_key = reinterpret_cast<uint64_t*>(wb + w_key), W.sorted_cand = reinterpret_cast<uint32_t*>(wb + w_cand);
+    W.blk_count = reinterpret_cast<uint32_t*>(wb + w_cnt), W.blk_first = reinterpret_cast<uint32_t*>(wb + w_first);
+    W.n_blocks = m, W.n_voxels = n;
+    uint8_t* const out = c->d_diff_out;
+    // (x, y, z) order: the keys are unique, the result does not depend on the order the workgroups arrived in
+    size_t tb = c->d_diff_cub.count();
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(c->d_diff_cub.get(), tb, static_cast<const uint64_t*>(diffChangedKey(W)), W.sorted_key,
+                                               static_cast<const uint32_t*>(diffChangedCand(W)), W.sorted_cand, static_cast<int>(m), 0, 63, st));
+    hipLaunchKernelGGL(k_diff_block_counts, dim3(gridFor(static_cast<size_t>(m) + 1)), dim3(256), 0, st, W);
+    HIP_TRY(hipGetLastError());
+    tb = c->d_diff_cub.count();
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_diff_cub.get(), tb, W.blk_count, W.blk_first, static_cast<int>(m + 1u), st));
+    rc = dispatchVps(c, [&](auto vps) {
+      constexpr int V = decltype(vps)::value;
+      if (X.mode == kMergeAligned) hipLaunchKernelGGL((k_diff_emit<V, kMergeAligned>), dim3(m), dim3(256), 0, st, c->m, ref->m, c->p, X, D, static_cast<const int4*>(S.cand), W, out);
+      else hipLaunchKernelGGL((k_diff_emit<V, kMergeResample>), dim3(m), dim3(256), 0, st, c->m, ref->m, c->p, X, D, static_cast<const int4*>(S.cand), W, out);
+      HIP_TRY(hipGetLastError());
+      return KHR_OK;
+    });
+    if (rc) return rc;
+    // ... and ref's later work (a frame, a reset, its destruction) behind the kernel that still reads it
+    if (st != ref->stream) {
+      HIP_TRY(hipEventRecord(c->ev_merge, st));
+      HIP_TRY(hipStreamWaitEvent(ref->stream, c->ev_merge, 0));
+    }
+  }
+  c->diff_stats = s;
+  c->diff_valid = true;
+  if (stats) *stats = s;
+  return KHR_OK;
+}
+
+int khr_diff_map_into(khr_ctx* c, int on_device, int32_t* voxels, uint8_t* kind, float* d_now, float* d_then, uint32_t* label, uint64_t* stamp_now,
+                      uint64_t* stamp_then, int32_t* blocks, uint32_t* block_appeared, uint32_t* block_disappeared, uint32_t* block_first) {
+  if (!c) return fail(KHR_EINVAL, "null ctx");
+  if (!c->diff_valid) return fail(KHR_ESTATE, "no successful khr_diff_map before khr_diff_map_into");
+  const khr_diff_stats& s = c->diff_stats;
+  if (s.n_changed_blocks == 0) return KHR_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const hipMemcpyKind dir = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const size_t n = s.n_appeared + s.n_disappeared, m = s.n_changed_blocks;
+  const DiffLayout L = diffLayout(n, m);
+  const uint8_t* const ob = c->d_diff_out;
+  hipError_t e = hipSuccess;
+  auto field = [&](void* dst, const void* src, size_t bytes) {
+    if (e == hipSuccess && dst && bytes) e = hipMemcpyAsync(dst, src, bytes, dir, c->stream);
+  };
+  field(voxels, ob + L.voxels, 12 * n);
+  field(kind, ob + L.kind, n);
+  field(d_now, ob + L.d_now, 4 * n);
+  field(d_then, ob + L.d_then, 4 * n);
+  field(label, ob + L.label, 4 * n);
+  field(stamp_now, ob + L.stamp_now, 8 * n);
+  field(stamp_then, ob + L.stamp_then, 8 * n);
+  field(blocks, ob + L.blocks, 12 * m);
+  field(block_appeared, ob + L.block_appeared, 4 * m);
+  field(block_disappeared, ob + L.block_disappeared, 4 * m);
+  field(block_first, ob + L.block_first, 4 * m);
+  if (e != hipSuccess) return fail(KHR_EDEVICE, "khr_diff_map_into: copy failed: %s", hipGetErrorString(e));
+  if (!on_device) HIP_TRY(hipStreamSynchronize(c->stream));
   return KHR_OK;
 }
 

@@ -2,7 +2,7 @@
 // thread drives the reference (spinOnce per InputPacket, finishMapping at shutdown), and prints a JSON
 // summary that tests/test_gpu_host.py compares with the step-wise C-ABI path and the oracle.
 // usage: aw_demo <config.yaml> <width> <height> <frames> [object_label]
-//        aw_demo --slices | --render | --query | --distance | --align | --weld | --merge | --checkpoint | --bench | --rayver ... (below)
+//        aw_demo --slices | --render | --query | --distance | --align | --weld | --merge | --diff | --checkpoint | --bench | --rayver ... (below)
 //   object_label >= 0: the stand-in detector / tracker below; otherwise the plugins named in the config
 #include <execinfo.h>
 #include <csignal>
@@ -1421,9 +1421,181 @@ static int mergeDemo(int argc, char** argv) {
   return diff.empty() ? 0 : 3;
 }
 
+// ---- aw_demo --diff -----------------------------------------------------------------------------------------------------------
+using DiffBlocks = std::map<hydra::BlockIndex, hydra::BlockCopy>;
+
+static DiffBlocks downloadBlocks(const VolumetricMap& map) {
+  DiffBlocks out;
+  for (const auto& idx : map.allocatedBlockIndices()) out[idx] = map.cloneBlock(idx);
+  return out;
+}
+
+// ASSUMPTIONS.md A.18, ALIGNED with zero offset, one thread: `now` against `then` from block copies.  The candidates are the blocks
+// of `then`; the map's order is the (x, y, z) order of the result.
+static hydra::MapDiff hostDiff(const DiffBlocks& now, const DiffBlocks& then, int vps, float min_weight, float occupied, float free_d, bool sem,
+                               bool trk) {
+  hydra::MapDiff d;
+  d.stats.n_ref_blocks = d.stats.n_candidate_blocks = then.size();
+  const size_t n = static_cast<size_t>(vps) * vps * vps;
+  for (const auto& kv : now) {
+    const auto it = then.find(kv.first);
+    if (it == then.end()) continue;
+    ++d.stats.n_present_blocks;
+    const hydra::BlockCopy& a = kv.second;
+    const hydra::BlockCopy& b = it->second;
+    uint32_t n_app = 0, n_dis = 0;
+    const uint32_t first = static_cast<uint32_t>(d.kind.size());
+    for (size_t v = 0; v < n; ++v) {
+      const bool N = a.weight[v] >= min_weight, T = b.weight[v] >= min_weight;
+      if (N && !T) ++d.stats.n_only_now;
+      if (!N && T) ++d.stats.n_only_then;
+      if (!(N && T)) continue;
+      ++d.stats.n_compared_voxels;
+      const float dn = a.distance[v], dt = b.distance[v];
+      const bool app = dt >= free_d && dn <= occupied, dis = dt <= occupied && dn >= free_d;
+      if (!app && !dis) continue;
+      app ? ++n_app : ++n_dis;
+      d.voxels.push_back(kv.first[0] * vps + static_cast<int32_t>(v % vps));
+      d.voxels.push_back(kv.first[1] * vps + static_cast<int32_t>((v / vps) % vps));
+      d.voxels.push_back(kv.first[2] * vps + static_cast<int32_t>(v / (static_cast<size_t>(vps) * vps)));
+      d.kind.push_back(app ? hydra::MapDiff::kAppeared : hydra::MapDiff::kDisappeared);
+      d.d_now.push_back(dn);
+      d.d_then.push_back(dt);
+      d.label.push_back(sem ? (app ? a.semantic_label[v] : b.semantic_label[v]) : 0u);
+      d.stamp_now.push_back(trk ? a.last_observed[v] : 0ull);
+      d.stamp_then.push_back(trk ? b.last_observed[v] : 0ull);
+    }
+    d.stats.n_appeared += n_app;
+    d.stats.n_disappeared += n_dis;
+    if (n_app + n_dis == 0) continue;
+    ++d.stats.n_changed_blocks;
+    for (int k = 0; k < 3; ++k) d.blocks.push_back(kv.first[k]);
+    d.block_appeared.push_back(n_app);
+    d.block_disappeared.push_back(n_dis);
+    d.block_first.push_back(first);
+  }
+  return d;
+}
+
+// aw_demo --diff <config.yaml> <width> <height> <frames>: the synthetic stream through one ActiveWindow; halfway the live map is
+// checkpointed into a side context; at the end the live map is compared with the side context on the device
+// (VolumetricMap::diff, ALIGNED, zero offset, the default thresholds) and, from block copies of both maps, on one host thread by the
+// same definition.  One JSON line: whether the two results are equal list for list, the statistics, and wall-clock times: the
+// device diff through the completion of its last kernel (the first call, which creates the scratch, and a repeat), the diff with
+// the copy of its lists to the host, and the host alternative (the download of both maps and the comparison).
+static int diffDemo(int argc, char** argv) {
+  if (argc < 6) {
+    std::fprintf(stderr, "usage: aw_demo --diff <config.yaml> <width> <height> <frames>\n");
+    return 2;
+  }
+  std::ifstream in(argv[2]);
+  std::stringstream ss;
+  ss << in.rdbuf();
+  const int W = std::atoi(argv[3]), H = std::atoi(argv[4]), N = std::atoi(argv[5]);
+  ActiveWindow::Config cfg = ActiveWindow::Config::fromYamlString(ss.str());
+  cfg.max_frame_pixels = static_cast<uint32_t>(W) * H;
+  auto out_queue = std::make_shared<ActiveWindow::OutputQueue>();
+  ActiveWindow aw(cfg, out_queue);
+  void* scene = synth_create(1234, 12, 1);
+  const size_t np = static_cast<size_t>(W) * H;
+  std::vector<float> depth(np);
+  std::vector<uint8_t> rgb(np * 3);
+  std::vector<int32_t> label(np);
+  khr_ctx* side = nullptr;
+  for (int i = 0; i < N; ++i) {
+    hydra::InputPacket pkt;
+    pkt.timestamp_ns = static_cast<uint64_t>(std::llround((1.0 + 0.1 * i) * 1e9));
+    circlePose(0.1 * i, pkt.world_T_body);
+    pkt.sensor = {W, H, W / 2.f, W / 2.f, W / 2.f, H / 2.f, 0.1f, 5.f};
+    synth_render(scene, W, H, pkt.sensor.fx, pkt.sensor.fy, pkt.sensor.cx, pkt.sensor.cy, pkt.world_T_body, 0.1 * i, 5.f, 0.f,
+                 1234u + 7919u * i, depth.data(), rgb.data(), label.data(), 0);
+    pkt.depth = depth.data();
+    pkt.color = rgb.data();
+    pkt.labels = label.data();
+    aw.step(pkt);
+    hydra::ActiveWindowOutput::Ptr popped;
+    while (out_queue->pop(&popped)) {}
+    if (i + 1 == N / 2) {  // the checkpoint, through memory
+      khr_ctx* live = aw.getMap().ctx();
+      khr_config kc{};
+      uint64_t bytes = 0, written = 0;
+      int64_t blocks = 0, kept = 0;
+      if (khr_get_config(live, &kc) != KHR_OK || khr_checkpoint_size(live, &bytes, &blocks) != KHR_OK) throw std::runtime_error(khr_last_error());
+      std::vector<uint8_t> buf(bytes);
+      if (khr_checkpoint_save(live, buf.data(), bytes, &written) != KHR_OK) throw std::runtime_error(std::string("khr_checkpoint_save: ") + khr_last_error());
+      if (khr_create(&kc, &side) != KHR_OK) throw std::runtime_error(std::string("khr_create: ") + khr_last_error());
+      if (khr_checkpoint_load(side, buf.data(), written, &kept) != KHR_OK || kept != blocks)
+        throw std::runtime_error(std::string("khr_checkpoint_load: ") + khr_last_error());
+    }
+  }
+  synth_destroy(scene);
+  if (!side) throw std::runtime_error("aw_demo --diff needs at least two frames");
+  const VolumetricMap& now = aw.getMap();
+  const VolumetricMap then(now.config, side);
+  khr_config kc{};
+  if (khr_get_config(now.ctx(), &kc) != KHR_OK) throw std::runtime_error(khr_last_error());
+  using clk = std::chrono::steady_clock;
+  auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+  khr_sync(now.ctx());
+  khr_sync(side);
+  const auto t0 = clk::now();
+  const DiffBlocks hn = downloadBlocks(now), ht = downloadBlocks(then);
+  const hydra::MapDiff host = hostDiff(hn, ht, kc.voxels_per_side, kc.mesh_min_weight, 0.f, kc.voxel_size, kc.with_semantics != 0, kc.with_tracking != 0);
+  const auto t1 = clk::now();
+  khr_diff_request rq{};
+  rq.mode = KHR_MERGE_ALIGNED;
+  rq.ctx_T_ref[0] = rq.ctx_T_ref[5] = rq.ctx_T_ref[10] = rq.ctx_T_ref[15] = 1.0;
+  rq.occupied_distance = 0.f;
+  rq.free_distance = kc.voxel_size;
+  double call_ms[2];
+  for (int r = 0; r < 2; ++r) {
+    const auto a = clk::now();
+    if (khr_diff_map(now.ctx(), side, &rq, nullptr) != KHR_OK) throw std::runtime_error(std::string("khr_diff_map: ") + khr_last_error());
+    khr_sync(now.ctx());
+    call_ms[r] = ms(a, clk::now());
+  }
+  const auto t2 = clk::now();
+  const hydra::MapDiff dev = now.diff(then, VolumetricMap::DiffRequest{});
+  const auto t3 = clk::now();
+  aw.finishMapping();
+  khr_destroy(side);
+  const char* diff = nullptr;
+  if (std::memcmp(&dev.stats, &host.stats, sizeof(dev.stats)) != 0) diff = "statistics";
+  else if (dev.voxels != host.voxels) diff = "voxels";
+  else if (dev.kind != host.kind) diff = "kind";
+  else if (!sameBits(dev.d_now, host.d_now)) diff = "d_now";
+  else if (!sameBits(dev.d_then, host.d_then)) diff = "d_then";
+  else if (dev.label != host.label) diff = "label";
+  else if (dev.stamp_now != host.stamp_now) diff = "stamp_now";
+  else if (dev.stamp_then != host.stamp_then) diff = "stamp_then";
+  else if (dev.blocks != host.blocks) diff = "blocks";
+  else if (dev.block_appeared != host.block_appeared) diff = "block_appeared";
+  else if (dev.block_disappeared != host.block_disappeared) diff = "block_disappeared";
+  else if (dev.block_first != host.block_first) diff = "block_first";
+  const khr_diff_stats& st = dev.stats;
+  auto u = [](uint64_t v) { return static_cast<unsigned long long>(v); };
+  std::printf("{\"what\": \"one stream, the live map against its own checkpoint of frame %d: VolumetricMap::diff (device) vs block copies compared on "
+              "one host thread, %dx%d, voxel %.4g m\", \"frames\": %d, \"n_now_blocks\": %zu, \"n_ref_blocks\": %llu, \"n_candidate_blocks\": %llu, "
+              "\"n_present_blocks\": %llu, \"n_compared_voxels\": %llu, \"n_appeared\": %llu, \"n_disappeared\": %llu, \"n_only_now\": %llu, "
+              "\"n_only_then\": %llu, \"n_changed_blocks\": %llu, \"equal\": %s, \"first_mismatch\": \"%s\", \"device_diff_first_ms\": %.4f, "
+              "\"device_diff_ms\": %.4f, \"diff_with_lists_ms\": %.4f, \"host_diff_ms\": %.4f}\n",
+              N / 2, W, H, static_cast<double>(kc.voxel_size), N, hn.size(), u(st.n_ref_blocks), u(st.n_candidate_blocks), u(st.n_present_blocks),
+              u(st.n_compared_voxels), u(st.n_appeared), u(st.n_disappeared), u(st.n_only_now), u(st.n_only_then), u(st.n_changed_blocks),
+              diff ? "false" : "true", diff ? diff : "", call_ms[0], call_ms[1], ms(t2, t3), ms(t0, t1));
+  return diff ? 3 : 0;
+}
+
 int main(int argc, char** argv) {
   std::signal(SIGSEGV, onSegv);
   std::signal(SIGABRT, onSegv);
+  if (argc >= 2 && std::string(argv[1]) == "--diff") {
+    try {
+      return diffDemo(argc, argv);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "aw_demo: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc >= 2 && std::string(argv[1]) == "--merge") {
     try {
       return mergeDemo(argc, argv);

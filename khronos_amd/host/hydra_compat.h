@@ -366,6 +366,24 @@ struct DistanceField {
   }
 };
 
+// What changed between the live map and another map (VolumetricMap::diff; khr_diff_map, ASSUMPTIONS.md A.18): the changed blocks
+// in (x, y, z) order, the changed voxels of a block in ascending linear index.  Per voxel: x, y, z of its global voxel index in
+// this map's frame, kind, the two distances, the label of the occupied side and last_observed of either side; per block: its
+// index, its two counts and the index of its first entry in the voxel arrays.
+struct MapDiff {
+  enum Kind : uint8_t { kAppeared = KHR_DIFF_APPEARED, kDisappeared = KHR_DIFF_DISAPPEARED };
+  khr_diff_stats stats{};
+  std::vector<int32_t> voxels;  // 3 per changed voxel
+  std::vector<uint8_t> kind;
+  std::vector<float> d_now, d_then;
+  std::vector<uint32_t> label;
+  std::vector<uint64_t> stamp_now, stamp_then;
+  std::vector<int32_t> blocks;  // 3 per changed block
+  std::vector<uint32_t> block_appeared, block_disappeared, block_first;
+  size_t numVoxels() const { return kind.size(); }
+  size_t numBlocks() const { return block_first.size(); }
+};
+
 struct IndexedMesh;  // (below, behind Mesh)
 
 // hydra::VolumetricMap role: here a handle on the HBM-resident map of a fusion context.
@@ -549,6 +567,35 @@ class VolumetricMap {
     khr_merge_stats st{};
     if (khr_merge_map(ctx_, other.ctx_, &rq, &st) != KHR_OK) throw std::runtime_error(std::string("khr_merge_map: ") + khr_last_error());
     return st;
+  }
+  // This map ("now") compared with another ("then") on the device (khr_diff_map, ASSUMPTIONS.md A.18): the voxels that appeared
+  // or vanished, `then` sampled as merge() samples its source.  Neither map is written.  free_distance < 0 = this map's
+  // voxel_size; occupied_distance defaults to 0.  Throws std::runtime_error with khr_last_error's text.
+  struct DiffRequest {
+    bool resample = false;
+    int32_t voxel_offset[3] = {0, 0, 0};
+    double ctx_T_ref[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    float min_weight = 0.f;  // 0 = this map's mesh_min_weight
+    float occupied_distance = 0.f;
+    float free_distance = -1.f;
+  };
+  MapDiff diff(const VolumetricMap& then, const DiffRequest& request) const {
+    khr_diff_request rq{};
+    rq.mode = request.resample ? KHR_MERGE_RESAMPLE : KHR_MERGE_ALIGNED;
+    for (int i = 0; i < 3; ++i) rq.voxel_offset[i] = request.voxel_offset[i];
+    for (int i = 0; i < 16; ++i) rq.ctx_T_ref[i] = request.ctx_T_ref[i];
+    rq.min_weight = request.min_weight;
+    rq.occupied_distance = request.occupied_distance;
+    rq.free_distance = request.free_distance < 0.f ? config.voxel_size : request.free_distance;
+    MapDiff d;
+    if (khr_diff_map(ctx_, then.ctx_, &rq, &d.stats) != KHR_OK) throw std::runtime_error(std::string("khr_diff_map: ") + khr_last_error());
+    const size_t n = static_cast<size_t>(d.stats.n_appeared + d.stats.n_disappeared), m = static_cast<size_t>(d.stats.n_changed_blocks);
+    d.voxels.resize(3 * n); d.kind.resize(n); d.d_now.resize(n); d.d_then.resize(n); d.label.resize(n); d.stamp_now.resize(n);
+    d.stamp_then.resize(n); d.blocks.resize(3 * m); d.block_appeared.resize(m); d.block_disappeared.resize(m); d.block_first.resize(m);
+    if (khr_diff_map_into(ctx_, 0, d.voxels.data(), d.kind.data(), d.d_now.data(), d.d_then.data(), d.label.data(), d.stamp_now.data(),
+                          d.stamp_then.data(), d.blocks.data(), d.block_appeared.data(), d.block_disappeared.data(), d.block_first.data()) != KHR_OK)
+      throw std::runtime_error(std::string("khr_diff_map_into: ") + khr_last_error());
+    return d;
   }
 
  private:
