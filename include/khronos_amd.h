@@ -936,6 +936,60 @@ int khr_diff_map_into(khr_ctx* ctx, int on_device, int32_t* voxels, uint8_t* kin
                       uint64_t* stamp_now, uint64_t* stamp_then, int32_t* blocks, uint32_t* block_appeared,
                       uint32_t* block_disappeared, uint32_t* block_first);
 
+/* ---- connected components of the live map's occupied voxels (ASSUMPTIONS.md A.19) ---------------------------------------
+ * khr_segment_map answers which connected pieces of matter the map of `ctx` holds: static object candidates out of the fused
+ * geometry and labels, "these N things appeared" out of a diff, floating specks to drop.  The map is only read.  A voxel is a
+ * MEMBER iff its block is allocated, weight >= min_weight (0 = ctx's mesh_min_weight), distance <= surface_distance (the
+ * OBSTACLE class of khr_distance_field), (flags & flags_require) == flags_require, (flags & flags_exclude) == 0 (the KHR_VOX_*
+ * bits as khr_download_block hands them out) and, with n_labels > 0, its label (the sem_label of khr_download_block, 0 without
+ * semantics) equals one of labels[] as a 32-bit pattern.  Two members are ADJACENT iff their global voxel indices differ by an
+ * offset of the 6-, 18- or 26-neighbourhood (`connectivity`, as neighbor_connectivity) and, with by_label != 0, their labels are
+ * equal; block boundaries play no part, a neighbour in an absent block is simply no member.  Components are the classes of the
+ * transitive closure.
+ *
+ * Voxels are ordered by block in the (x, y, z) order of khr_block_indices, then by linear index x + vps (y + vps z).  A
+ * component's representative is its least voxel.  A component is kept iff min_voxels <= n <= max_voxels (min_voxels < 1 means 1,
+ * max_voxels <= 0 means unlimited); the kept components are numbered 1, 2, ... in ascending order of their representatives.  Per
+ * kept component: label (the representative's), n_voxels, bbox_min / bbox_max (global voxel indices, inclusive), sum (the int64
+ * sums of the members' global voxel indices, exact: the centroid is (sum / n + 0.5) * voxel_size), representative,
+ * last_observed_max (the latest last_observed of a member, 0 without tracking) and first, the offset of its run in the voxel
+ * list.  The voxel list (want_voxels != 0) holds the members of the kept components, grouped by component in ascending id and in
+ * ascending voxel order inside a component: the global voxel index and the component id.
+ *
+ * khr_segment_map works in stream order on ctx's stream with one host wait, for the counts that fill `stats` (may be NULL) and
+ * size the result.  The result lives in buffers ctx owns: it stays valid across later frames until the next khr_segment_map,
+ * khr_reset_map, khr_checkpoint_load or khr_destroy; a failed call discards an earlier result.  The map, the mesh layer, the
+ * frame ring, the detectors' state, the cumulative khr_stats counters and the results of khr_diff_map / khr_weld_mesh are not
+ * touched.  The scratch belongs to ctx and grows to the largest call: 12 bytes per voxel of the live blocks where the host
+ * knows their number without a wait (after khr_num_blocks / khr_block_indices / khr_download_block on the unchanged map), else
+ * of the pool's capacity.  KHR_EINVAL (nothing done): a NULL ctx or request, a connectivity other than 6 / 18 / 26, a negative
+ * or non-finite min_weight, a non-finite surface_distance, n_labels < 0 or > 64, n_labels > 0 with NULL labels, max_voxels > 0
+ * && max_voxels < max(min_voxels, 1).  KHR_ESTATE: world_size > 1 (a shard cannot see across faces it does not own).
+ * KHR_ENOMEM, with the needed bytes in khr_last_error: the scratch or the result cannot be allocated, or exceeds 2^31 - 2
+ * voxels to number / 2^30 listed voxels.  An empty map, or a map without members, is KHR_OK with zero counts.
+ *
+ * khr_segment_map_into copies the result of the last successful call (KHR_ESTATE without one); any pointer may be NULL; it may be
+ * called several times.  on_device == 0: host arrays, filled when the call returns.  on_device != 0: device arrays, copied
+ * device-to-device in stream order, nothing is awaited.  The comp_* arrays hold n_components entries (bbox_min, bbox_max, sum and
+ * representative three each), voxels 3 int32 and voxel_component one word per listed voxel (n_voxels of them); asking for
+ * either after a call with want_voxels == 0 is KHR_ESTATE. */
+typedef struct khr_segment_request {
+  float min_weight, surface_distance;
+  int32_t connectivity;            /* 6, 18, 26 */
+  int32_t by_label;
+  const int32_t* labels; int32_t n_labels;   /* host memory, at most 64; NULL / 0 = every label */
+  uint32_t flags_require, flags_exclude;
+  int64_t min_voxels, max_voxels;
+  int32_t want_voxels;
+} khr_segment_request;
+typedef struct khr_segment_stats {
+  uint64_t n_blocks, n_member_voxels, n_components_all, n_too_small, n_too_large, n_components, n_voxels;
+} khr_segment_stats;   /* n_components_all = n_too_small + n_too_large + n_components; n_voxels = members of kept components */
+int khr_segment_map(khr_ctx* ctx, const khr_segment_request* request, khr_segment_stats* stats);
+int khr_segment_map_into(khr_ctx* ctx, int on_device, int32_t* comp_label, uint64_t* comp_n_voxels, int32_t* comp_bbox_min,
+                         int32_t* comp_bbox_max, int64_t* comp_sum, int32_t* comp_representative, uint64_t* comp_last_observed,
+                         uint64_t* comp_first, int32_t* voxels, uint32_t* voxel_component);
+
 /* ---- tick path: the camera frames of ONE tick batched (sharded multi-camera runs) ------------------------------------
  * In a hash-range sharded run every rank sees every camera frame, so the per-camera work of a
  * rank is what does not shrink with the rank count.  These two calls are khr_upload_frame / khr_integrate for n_frames

@@ -86,6 +86,17 @@ class KhrDiffStats(C.Structure):
                                           "n_disappeared", "n_only_now", "n_only_then", "n_changed_blocks")]
 
 
+class KhrSegmentRequest(C.Structure):
+    _fields_ = [("min_weight", C.c_float), ("surface_distance", C.c_float), ("connectivity", C.c_int32), ("by_label", C.c_int32),
+                ("labels", C.POINTER(C.c_int32)), ("n_labels", C.c_int32), ("flags_require", C.c_uint32), ("flags_exclude", C.c_uint32),
+                ("min_voxels", C.c_int64), ("max_voxels", C.c_int64), ("want_voxels", C.c_int32)]
+
+
+class KhrSegmentStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_blocks", "n_member_voxels", "n_components_all", "n_too_small", "n_too_large", "n_components",
+                                          "n_voxels")]
+
+
 class KhrDfRequest(C.Structure):
     _fields_ = [("origin", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("ratio", C.c_int32), ("min_weight", C.c_float),
                 ("max_distance", C.c_float), ("surface_distance", C.c_float), ("unknown_is_obstacle", C.c_int32),
@@ -186,6 +197,7 @@ EXPORTS = [
     "khr_checkpoint_size", "khr_checkpoint_save", "khr_checkpoint_load", "khr_checkpoint_inspect",
     "khr_debug_live_resources", "khr_configure_object_voxel_sets",
     "khr_weld_mesh", "khr_weld_mesh_into", "khr_merge_map", "khr_diff_map", "khr_diff_map_into",
+    "khr_segment_map", "khr_segment_map_into",
 ]
 
 _lib = None
@@ -317,6 +329,8 @@ def load_library():
     lib.khr_merge_map.argtypes = [vp, vp, C.POINTER(KhrMergeRequest), C.POINTER(KhrMergeStats)]
     lib.khr_diff_map.argtypes = [vp, vp, C.POINTER(KhrDiffRequest), C.POINTER(KhrDiffStats)]
     lib.khr_diff_map_into.argtypes = [vp, i32] + [vp] * 11
+    lib.khr_segment_map.argtypes = [vp, C.POINTER(KhrSegmentRequest), C.POINTER(KhrSegmentStats)]
+    lib.khr_segment_map_into.argtypes = [vp, i32] + [vp] * 10
     lib.khr_debug_read.argtypes = [vp, vp, i64]
     lib.khr_debug_live_resources.argtypes = [C.POINTER(i64)]
     lib.khr_tick_ingest.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
@@ -1352,6 +1366,58 @@ class FusionContext:
         n = {"v": stats["n_appeared"] + stats["n_disappeared"], "b": stats["n_changed_blocks"]}
         out = {k: np.zeros((n[w],) + sh, dt) for k, dt, sh, w in self.DIFF_FIELDS}
         self._chk(self.diff_map_into(out))
+        out["stats"] = stats
+        return out
+
+    SEGMENT_FIELDS = (("label", np.int32, (), "c"), ("n_voxels", np.uint64, (), "c"), ("bbox_min", np.int32, (3,), "c"), ("bbox_max", np.int32, (3,), "c"),
+                      ("sum", np.int64, (3,), "c"), ("representative", np.int32, (3,), "c"), ("last_observed_max", np.uint64, (), "c"),
+                      ("first", np.uint64, (), "c"), ("voxels", np.int32, (3,), "v"), ("voxel_component", np.uint32, (), "v"))
+
+    def segment_request(self, min_weight=0.0, surface_distance=0.0, connectivity=26, by_label=None, labels=None, flags_require=0, flags_exclude=0,
+                        min_voxels=1, max_voxels=0, want_voxels=True):
+        """khr_segment_request: min_weight 0 = this context's mesh_min_weight; by_label defaults to True when the context has
+        semantics; labels None / empty = every label; max_voxels <= 0 = unlimited.  The request keeps its label array alive."""
+        rq = KhrSegmentRequest()
+        rq.min_weight, rq.surface_distance = float(min_weight), float(surface_distance)
+        rq.connectivity = int(connectivity)
+        rq.by_label = int(bool(self.cfg.with_semantics) if by_label is None else bool(by_label))
+        lab = [] if labels is None else [int(v) for v in labels]
+        rq._labels = (C.c_int32 * max(1, len(lab)))(*lab)
+        rq.labels = C.cast(rq._labels, C.POINTER(C.c_int32)) if lab else None
+        rq.n_labels = len(lab)
+        rq.flags_require, rq.flags_exclude = int(flags_require), int(flags_exclude)
+        rq.min_voxels, rq.max_voxels = int(min_voxels), int(max_voxels)
+        rq.want_voxels = int(bool(want_voxels))
+        return rq
+
+    def segment_map_rc(self, request):
+        """khr_segment_map without raising: (return code, statistics dict)"""
+        st = KhrSegmentStats()
+        rc = self.lib.khr_segment_map(self.h, C.byref(request) if request is not None else None, C.byref(st))
+        return rc, {k: int(getattr(st, k)) for k, _ in KhrSegmentStats._fields_}
+
+    def segment_map_into(self, out, on_device=False):
+        """khr_segment_map_into: the result of the last segmentation into caller buffers (`out`: SEGMENT_FIELDS name -> contiguous
+        array, or an integer device pointer with on_device; absent / None = not copied).  Returns the return code without raising."""
+        ptrs = []
+        for name, _, _, _ in self.SEGMENT_FIELDS:
+            a = out.get(name)
+            ptrs.append(None if a is None else (C.c_void_p(int(a)) if on_device else _ptr(a)))
+        return self.lib.khr_segment_map_into(self.h, int(on_device), *ptrs)
+
+    def segment_map(self, request=None, **kw):
+        """The connected components of this context's occupied voxels, found on the device (khr_segment_map, ASSUMPTIONS.md A.19);
+        the map is not written.  Keywords as segment_request.  Returns a dict: the statistics under "stats", per kept component
+        label int32, n_voxels uint64, bbox_min / bbox_max (m, 3) int32 (global voxel indices, inclusive), sum (m, 3) int64,
+        representative (m, 3) int32, last_observed_max uint64, first uint64 and centroid (m, 3) float64 in metres; with
+        want_voxels also voxels (n, 3) int32 and voxel_component uint32 (ids from 1), grouped by component in ascending id."""
+        rq = request if request is not None else self.segment_request(**kw)
+        rc, stats = self.segment_map_rc(rq)
+        self._chk(rc)
+        n = {"c": stats["n_components"], "v": stats["n_voxels"]}
+        out = {k: np.zeros((n[w],) + sh, dt) for k, dt, sh, w in self.SEGMENT_FIELDS if w == "c" or rq.want_voxels}
+        self._chk(self.segment_map_into(out))
+        out["centroid"] = (out["sum"].astype(np.float64) / np.maximum(out["n_voxels"], 1).astype(np.float64)[:, None] + 0.5) * float(self.cfg.voxel_size)
         out["stats"] = stats
         return out
 

@@ -43,6 +43,7 @@
 #include "khr_kernels_weld.h"
 #include "khr_kernels_merge.h"
 #include "khr_kernels_diff.h"
+#include "khr_kernels_segment.h"
 
 using namespace khr;
 
@@ -439,6 +440,13 @@ struct khr_ctx {
   DevBuf<uint8_t> d_diff_work, d_diff_cub, d_diff_out;
   khr_diff_stats diff_stats{};
   bool diff_valid = false;  // a diff succeeded and nothing has discarded its result
+  // map segmentation (khr_segment_map; the sorted block list is d_slice_keys above): the scratch (tables, parents, counts, numbers,
+  // counters), hipcub's temporary storage, the sort keys of the voxel list (twice) and the result, each grown to the largest call
+  DevBuf<uint8_t> d_seg_work, d_seg_cub, d_seg_sort, d_seg_out;
+  PinnedBuf<unsigned long long> h_seg;
+  khr_segment_stats seg_stats{};
+  bool seg_valid = false;   // a segmentation succeeded and nothing has discarded its result
+  bool seg_listed = false;  // ... and it holds the voxel list
   // timing
   uint32_t timing = 0;  // bit i = timer i enabled
   std::vector<TimingRec> pending;
@@ -851,6 +859,7 @@ int khr_reset_map(khr_ctx* c, float voxel_size, float truncation_distance) {
   c->mesh_stale = false;
   c->weld_valid = false;
   c->diff_valid = false;
+  c->seg_valid = false;
   c->host_index_valid = false, ++c->map_gen;
   c->explicit_blocks = 0;
   c->last_removed = 0;
@@ -5267,6 +5276,7 @@ int khr_checkpoint_load(khr_ctx* c, const void* buffer, uint64_t n_bytes, int64_
   if (n_kept) *n_kept = 0;
   c->weld_valid = false;  // (khr_weld_mesh: the welded mesh belongs to the map before the load)
   c->diff_valid = false;  // (khr_diff_map: so does the diff)
+  c->seg_valid = false;   // (khr_segment_map: and the segmentation)
   khr_checkpoint_header h;
   int rc = khr_checkpoint_inspect(buffer, n_bytes, &h);
   if (rc) return rc;
@@ -6402,6 +6412,197 @@ int khr_diff_map_into(khr_ctx* c, int on_device, int32_t* voxels, uint8_t* kind,
   field(block_disappeared, ob + L.block_disappeared, 4 * m);
   field(block_first, ob + L.block_first, 4 * m);
   if (e != hipSuccess) return fail(KHR_EDEVICE, "khr_diff_map_into: copy failed: %s", hipGetErrorString(e));
+  if (!on_device) HIP_TRY(hipStreamSynchronize(c->stream));
+  return KHR_OK;
+}
+
+// ---- connected components of the live map's occupied voxels (khr_segment_map; ASSUMPTIONS.md A.19, device side:
+// khr_kernels_segment.h) ----------------------------------------------------------------------------------------------------------
+int khr_segment_map(khr_ctx* c, const khr_segment_request* rq, khr_segment_stats* stats) {
+  if (stats) *stats = khr_segment_stats{};
+  if (c) {  // (a failed call discards the earlier result)
+    c->seg_valid = false;
+    c->seg_stats = khr_segment_stats{};
+  }
+  if (!c || !rq) return fail(KHR_EINVAL, "khr_segment_map: null argument");
+  if (rq->connectivity != 6 && rq->connectivity != 18 && rq->connectivity != 26)
+    return fail(KHR_EINVAL, "khr_segment_map: connectivity is %d, must be 6, 18 or 26", rq->connectivity);
+  if (!std::isfinite(rq->min_weight) || rq->min_weight < 0.f) return fail(KHR_EINVAL, "khr_segment_map: min_weight must be finite and >= 0");
+  if (!std::isfinite(rq->surface_distance)) return fail(KHR_EINVAL, "khr_segment_map: surface_distance is not finite");
+  if (rq->n_labels < 0 || rq->n_labels > 64) return fail(KHR_EINVAL, "khr_segment_map: n_labels is %d, must be 0 .. 64", rq->n_labels);
+  if (rq->n_labels > 0 && !rq->labels) return fail(KHR_EINVAL, "khr_segment_map: n_labels is %d and labels is null", rq->n_labels);
+  const int64_t min_voxels = std::max<int64_t>(rq->min_voxels, 1);
+  if (rq->max_voxels > 0 && rq->max_voxels < min_voxels)
+    return fail(KHR_EINVAL, "khr_segment_map: max_voxels (%lld) is below min_voxels (%lld)", static_cast<long long>(rq->max_voxels),
+                static_cast<long long>(min_voxels));
+  if (c->cfg.world_size > 1)
+    return fail(KHR_ESTATE, "khr_segment_map needs the whole map: world_size is %d (a shard cannot see across faces it does not own)", c->cfg.world_size);
+  SegMember M{};
+  M.min_weight = rq->min_weight > 0.f ? rq->min_weight : c->p.mesh_min_weight;
+  M.surface_distance = rq->surface_distance;
+  M.flags_require = rq->flags_require, M.flags_exclude = rq->flags_exclude;
+  M.n_labels = rq->n_labels;
+  for (int i = 0; i < rq->n_labels; ++i) M.labels[i] = static_cast<uint32_t>(rq->labels[i]);
+  SegRule R{};
+  R.n_dirs = rq->connectivity == 6 ? 3 : (rq->connectivity == 18 ? 9 : 13);
+  R.by_label = rq->by_label != 0;
+  R.min_voxels = static_cast<unsigned long long>(min_voxels);
+  R.max_voxels = rq->max_voxels > 0 ? static_cast<unsigned long long>(rq->max_voxels) : ~0ull;
+  HIP_TRY(hipSetDevice(c->device));
+  KHR_TRY(ensureSortKeys(c));
+  hipStream_t st = c->stream;
+  // The scratch holds `bound` blocks: the live blocks where the host index is current (their number is then known without a
+  // wait), else the pool's capacity.  Node ids are 32 bits.
+  const size_t nv = static_cast<size_t>(c->p.nvox), cap = c->m.capacity;
+  const size_t bound = std::max<size_t>(1, c->host_index_valid ? std::min(cap, c->host_index.size()) : cap);
+  const size_t nodes = bound * nv;
+  auto al = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
+  size_t o = 0;
+  auto carve = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
+  const size_t w_ctr = carve(8 * SC_COUNT), w_ros = carve(4 * cap), w_sor = carve(4 * bound), w_par = carve(4 * nodes), w_cnt = carve(4 * nodes),
+               w_num = carve(4 * (nodes + 1));
+  const size_t work_bytes = o;
+  if (nodes + 1 > static_cast<size_t>(INT32_MAX))  // (the scan counts in int; node ids then fit 32 bits with room for kSegNone)
+    return fail(KHR_ENOMEM, "khr_segment_map: %zu blocks of %zu voxels to number, at most 2^31 - 2 voxels (%zu bytes of scratch)", bound, nv, work_bytes);
+  size_t cub_bytes = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, static_cast<uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), static_cast<int>(nodes + 1), st));
+  cub_bytes = std::max<size_t>(cub_bytes, 256);
+  if (work_bytes > c->d_seg_work.count() || cub_bytes > c->d_seg_cub.count() || !c->h_seg) {
+    HIP_TRY(hipStreamSynchronize(st));  // (whatever still uses the old blocks)
+    if (c->d_seg_work.reserve(work_bytes) || c->d_seg_cub.reserve(cub_bytes) || c->h_seg.reserve(SC_COUNT + 1))
+      return fail(KHR_ENOMEM, "khr_segment_map: scratch for %zu blocks (%zu bytes)", bound, work_bytes + cub_bytes);
+  }
+  uint8_t* const wb = c->d_seg_work;
+  unsigned long long* const ctr = reinterpret_cast<unsigned long long*>(wb + w_ctr);
+  uint32_t* const parent = reinterpret_cast<uint32_t*>(wb + w_par);
+  uint32_t* const cnt = reinterpret_cast<uint32_t*>(wb + w_cnt);
+  uint32_t* const number = reinterpret_cast<uint32_t*>(wb + w_num);
+  SegBlocks B{};
+  B.keys = c->d_slice_keys, B.count = c->d_slice_count, B.bound = static_cast<uint32_t>(bound);
+  B.rank_of_slot = reinterpret_cast<uint32_t*>(wb + w_ros), B.slot_of_rank = reinterpret_cast<uint32_t*>(wb + w_sor);
+  // the live blocks in sorted (x, y, z) order, as the checkpoint stream orders them
+  HIP_TRY(hipMemsetAsync(c->d_slice_count, 0, sizeof(uint32_t), st));
+  HIP_TRY(hipMemsetAsync(ctr, 0, 8 * SC_COUNT, st));
+  hipLaunchKernelGGL(k_ckpt_select, dim3(std::min(gridFor(cap), 1024)), dim3(256), 0, st, c->m, c->d_slice_count, c->d_slice_keys);
+  HIP_TRY(hipGetLastError());
+  KHR_TRY(sortKeys(c));
+  const dim3 block_grid(static_cast<uint32_t>(std::min<size_t>(bound, 8192))), node_grid(static_cast<uint32_t>(std::min<size_t>(gridFor(nodes + 1), 8192)));
+  int rc = dispatchVps(c, [&](auto vps) {
+    constexpr int V = decltype(vps)::value;
+    hipLaunchKernelGGL((k_seg_local<V>), block_grid, dim3(256), 0, st, c->m, c->p, M, R, B, parent, cnt, ctr);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL((k_seg_seams<V>), block_grid, dim3(256), 0, st, c->m, c->p, R, B, parent);
+    HIP_TRY(hipGetLastError());
+    return KHR_OK;
+  });
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_seg_count, node_grid, dim3(256), 0, st, B, static_cast<uint32_t>(nv), parent, cnt);
+  hipLaunchKernelGGL(k_seg_flag, node_grid, dim3(256), 0, st, B, static_cast<uint32_t>(nv), R, static_cast<const uint32_t*>(parent),
+                     static_cast<const uint32_t*>(cnt), number, ctr);
+  HIP_TRY(hipGetLastError());
+  size_t tb = c->d_seg_cub.count();
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_seg_cub.get(), tb, number, number, static_cast<int>(nodes + 1), st));
+  // the one host wait: the counts
+  unsigned long long* const h = c->h_seg;
+  HIP_TRY(hipMemcpyAsync(h, ctr, 8 * SC_COUNT, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h + SC_COUNT, c->d_slice_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  uint32_t n_blocks = 0;
+  std::memcpy(&n_blocks, h + SC_COUNT, sizeof(n_blocks));
+  if ((h[SC_ERR] & kSegErrBound) || n_blocks > bound)
+    return fail(KHR_EDEVICE, "khr_segment_map: %u live blocks, the scratch was sized for %zu", n_blocks, bound);
+  khr_segment_stats s{};
+  s.n_blocks = n_blocks;
+  s.n_member_voxels = h[SC_MEMBERS];
+  s.n_components_all = h[SC_ALL], s.n_too_small = h[SC_SMALL], s.n_too_large = h[SC_LARGE], s.n_components = h[SC_KEPT];
+  s.n_voxels = h[SC_VOXELS];
+  if (s.n_components_all != s.n_too_small + s.n_too_large + s.n_components || s.n_voxels > s.n_member_voxels || s.n_components > s.n_voxels)
+    return fail(KHR_EDEVICE, "khr_segment_map: inconsistent counts (%llu components, %llu kept, %llu voxels)",
+                static_cast<unsigned long long>(s.n_components_all), static_cast<unsigned long long>(s.n_components), static_cast<unsigned long long>(s.n_voxels));
+  const bool list = rq->want_voxels != 0;
+  if (s.n_components > 0) {
+    const uint32_t m = static_cast<uint32_t>(s.n_components);  // (below 2^32: a component has a node id of its own)
+    const uint64_t n = list ? s.n_voxels : 0;
+    if (n > (1ull << 30)) return fail(KHR_ENOMEM, "khr_segment_map: a voxel list of %llu entries, at most 2^30 (%llu bytes)", static_cast<unsigned long long>(n),
+                                       static_cast<unsigned long long>(48 * n));
+    // the result and the sort's work area; nothing is queued on the stream here (the wait above), so a growth frees nothing in use
+    const size_t out_bytes = segLayout(m, n).bytes, sort_bytes = 2 * al(8 * n);
+    size_t scan64_bytes = 0, radix_bytes = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan64_bytes, static_cast<uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr), static_cast<int>(m), st));
+    if (n) HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, radix_bytes, static_cast<const uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr), static_cast<int>(n), 0, 64, st));
+    const size_t cub2_bytes = std::max(std::max(scan64_bytes, radix_bytes), cub_bytes);
+    if (c->d_seg_out.reserve(out_bytes) || c->d_seg_sort.reserve(sort_bytes) || c->d_seg_cub.reserve(cub2_bytes))
+      return fail(KHR_ENOMEM, "khr_segment_map: buffers for %u components and %llu listed voxels (%zu bytes)", m, static_cast<unsigned long long>(n),
+                  out_bytes + sort_bytes + cub2_bytes);
+    uint8_t* const out = c->d_seg_out;
+    const SegLayout L = segLayout(m, n);
+    uint64_t* const keys_in = n ? reinterpret_cast<uint64_t*>(c->d_seg_sort.get()) : nullptr;
+    uint64_t* const keys_out = n ? reinterpret_cast<uint64_t*>(c->d_seg_sort.get() + al(8 * n)) : nullptr;
+    const dim3 live_grid(static_cast<uint32_t>(std::min<size_t>(std::max<size_t>(1, gridFor(static_cast<size_t>(n_blocks) * nv)), 8192)));
+    rc = dispatchVps(c, [&](auto vps) {
+      constexpr int V = decltype(vps)::value;
+      hipLaunchKernelGGL((k_seg_heads<V>), live_grid, dim3(256), 0, st, c->m, c->p, R, B, static_cast<const uint32_t*>(parent), static_cast<const uint32_t*>(cnt),
+                         static_cast<const uint32_t*>(number), m, n, out);
+      HIP_TRY(hipGetLastError());
+      if (n) hipLaunchKernelGGL((k_seg_reduce<V, true>), live_grid, dim3(256), 0, st, c->m, c->p, R, B, static_cast<const uint32_t*>(parent),
+                                static_cast<const uint32_t*>(cnt), static_cast<const uint32_t*>(number), m, n, out, keys_in, ctr);
+      else hipLaunchKernelGGL((k_seg_reduce<V, false>), live_grid, dim3(256), 0, st, c->m, c->p, R, B, static_cast<const uint32_t*>(parent),
+                              static_cast<const uint32_t*>(cnt), static_cast<const uint32_t*>(number), m, n, out, keys_in, ctr);
+      HIP_TRY(hipGetLastError());
+      return KHR_OK;
+    });
+    if (rc) return rc;
+    tb = c->d_seg_cub.count();
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_seg_cub.get(), tb, reinterpret_cast<uint64_t*>(out + L.n_voxels), reinterpret_cast<uint64_t*>(out + L.first),
+                                             static_cast<int>(m), st));
+    if (n) {
+      tb = c->d_seg_cub.count();
+      HIP_TRY(hipcub::DeviceRadixSort::SortKeys(c->d_seg_cub.get(), tb, static_cast<const uint64_t*>(keys_in), keys_out, static_cast<int>(n), 0, 64, st));
+      rc = dispatchVps(c, [&](auto vps) {
+        hipLaunchKernelGGL((k_seg_emit<decltype(vps)::value>), dim3(static_cast<uint32_t>(std::min<size_t>(gridFor(n), 8192))), dim3(256), 0, st,
+                           static_cast<const uint64_t*>(c->d_slice_keys), static_cast<const uint64_t*>(keys_out), m, n, n_blocks, out);
+        HIP_TRY(hipGetLastError());
+        return KHR_OK;
+      });
+      if (rc) return rc;
+    }
+  }
+  c->seg_stats = s;
+  c->seg_valid = true;
+  c->seg_listed = list;
+  if (stats) *stats = s;
+  return KHR_OK;
+}
+
+int khr_segment_map_into(khr_ctx* c, int on_device, int32_t* comp_label, uint64_t* comp_n_voxels, int32_t* comp_bbox_min, int32_t* comp_bbox_max,
+                         int64_t* comp_sum, int32_t* comp_representative, uint64_t* comp_last_observed, uint64_t* comp_first, int32_t* voxels,
+                         uint32_t* voxel_component) {
+  if (!c) return fail(KHR_EINVAL, "null ctx");
+  if (!c->seg_valid) return fail(KHR_ESTATE, "no successful khr_segment_map before khr_segment_map_into");
+  if ((voxels || voxel_component) && !c->seg_listed)
+    return fail(KHR_ESTATE, "khr_segment_map_into: the last khr_segment_map ran with want_voxels = 0 and holds no voxel list");
+  const khr_segment_stats& s = c->seg_stats;
+  if (s.n_components == 0) return KHR_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const hipMemcpyKind dir = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const size_t m = s.n_components, n = c->seg_listed ? s.n_voxels : 0;
+  const SegLayout L = segLayout(m, n);
+  const uint8_t* const ob = c->d_seg_out;
+  hipError_t e = hipSuccess;
+  auto field = [&](void* dst, const void* src, size_t bytes) {
+    if (e == hipSuccess && dst && bytes) e = hipMemcpyAsync(dst, src, bytes, dir, c->stream);
+  };
+  field(comp_label, ob + L.label, 4 * m);
+  field(comp_n_voxels, ob + L.n_voxels, 8 * m);
+  field(comp_bbox_min, ob + L.bbox_min, 12 * m);
+  field(comp_bbox_max, ob + L.bbox_max, 12 * m);
+  field(comp_sum, ob + L.sum, 24 * m);
+  field(comp_representative, ob + L.representative, 12 * m);
+  field(comp_last_observed, ob + L.last_observed, 8 * m);
+  field(comp_first, ob + L.first, 8 * m);
+  field(voxels, ob + L.voxels, 12 * n);
+  field(voxel_component, ob + L.voxel_component, 4 * n);
+  if (e != hipSuccess) return fail(KHR_EDEVICE, "khr_segment_map_into: copy failed: %s", hipGetErrorString(e));
   if (!on_device) HIP_TRY(hipStreamSynchronize(c->stream));
   return KHR_OK;
 }

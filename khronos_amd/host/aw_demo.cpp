@@ -2,7 +2,7 @@
 // thread drives the reference (spinOnce per InputPacket, finishMapping at shutdown), and prints a JSON
 // summary that tests/test_gpu_host.py compares with the step-wise C-ABI path and the oracle.
 // usage: aw_demo <config.yaml> <width> <height> <frames> [object_label]
-//        aw_demo --slices | --render | --query | --distance | --align | --weld | --merge | --diff | --checkpoint | --bench | --rayver ... (below)
+//        aw_demo --slices | --render | --query | --distance | --align | --weld | --merge | --diff | --segment | --checkpoint | --bench | --rayver ... (below)
 //   object_label >= 0: the stand-in detector / tracker below; otherwise the plugins named in the config
 #include <execinfo.h>
 #include <csignal>
@@ -1585,9 +1585,207 @@ static int diffDemo(int argc, char** argv) {
   return diff ? 3 : 0;
 }
 
+// ---- aw_demo --segment --------------------------------------------------------------------------------------------------------
+// ASSUMPTIONS.md A.19 on one thread from block copies: the members into a hash of their global voxel indices, in voxel order; a
+// breadth-first flood fill from every member not yet reached; the components in the order their least voxels come up.
+static hydra::MapSegments hostSegment(const DiffBlocks& blocks, int vps, float min_weight, float surface_distance, int connectivity, bool by_label,
+                                      bool sem, bool trk, bool want_voxels) {
+  struct Member {
+    int32_t g[3];
+    uint32_t label;
+    uint64_t stamp;
+  };
+  std::vector<Member> mem;
+  struct VoxelHash {
+    size_t operator()(const std::array<int32_t, 3>& k) const {
+      uint64_t h = static_cast<uint32_t>(k[0]) * 0x9e3779b97f4a7c15ull;
+      h = (h ^ (h >> 29)) + static_cast<uint32_t>(k[1]) * 0xbf58476d1ce4e5b9ull;
+      h = (h ^ (h >> 31)) + static_cast<uint32_t>(k[2]) * 0x94d049bb133111ebull;
+      return static_cast<size_t>(h ^ (h >> 32));
+    }
+  };
+  std::unordered_map<std::array<int32_t, 3>, uint32_t, VoxelHash> at;
+  auto key = [](int32_t x, int32_t y, int32_t z) { return std::array<int32_t, 3>{x, y, z}; };
+  const size_t nv = static_cast<size_t>(vps) * vps * vps;
+  for (const auto& kv : blocks) {  // (std::map: the (x, y, z) order)
+    const hydra::BlockCopy& b = kv.second;
+    for (size_t v = 0; v < nv; ++v) {
+      if (!(b.weight[v] >= min_weight && b.distance[v] <= surface_distance)) continue;
+      Member m;
+      m.g[0] = kv.first[0] * vps + static_cast<int32_t>(v % vps);
+      m.g[1] = kv.first[1] * vps + static_cast<int32_t>((v / vps) % vps);
+      m.g[2] = kv.first[2] * vps + static_cast<int32_t>(v / (static_cast<size_t>(vps) * vps));
+      m.label = sem ? b.semantic_label[v] : 0u;
+      m.stamp = trk ? b.last_observed[v] : 0ull;
+      at[key(m.g[0], m.g[1], m.g[2])] = static_cast<uint32_t>(mem.size());
+      mem.push_back(m);
+    }
+  }
+  std::vector<std::array<int, 3>> steps;
+  for (int dz = -1; dz <= 1; ++dz)
+    for (int dy = -1; dy <= 1; ++dy)
+      for (int dx = -1; dx <= 1; ++dx) {
+        const int n = std::abs(dx) + std::abs(dy) + std::abs(dz);
+        if (n >= 1 && n <= (connectivity == 6 ? 1 : (connectivity == 18 ? 2 : 3))) steps.push_back({dx, dy, dz});
+      }
+  hydra::MapSegments s;
+  s.stats.n_blocks = blocks.size();
+  s.stats.n_member_voxels = mem.size();
+  std::vector<uint8_t> seen(mem.size(), 0);
+  std::vector<uint32_t> comp;
+  for (uint32_t start = 0; start < mem.size(); ++start) {
+    if (seen[start]) continue;
+    seen[start] = 1;
+    comp.assign(1, start);
+    for (size_t q = 0; q < comp.size(); ++q) {  // (the component's list is the queue)
+      const Member m = mem[comp[q]];
+      for (const auto& d : steps) {
+        const auto it = at.find(key(m.g[0] + d[0], m.g[1] + d[1], m.g[2] + d[2]));
+        if (it == at.end() || seen[it->second] || (by_label && mem[it->second].label != m.label)) continue;
+        seen[it->second] = 1;
+        comp.push_back(it->second);
+      }
+    }
+    std::sort(comp.begin(), comp.end());
+    ++s.stats.n_components_all, ++s.stats.n_components;  // (min_voxels = 1, no upper limit: every component is kept)
+    const uint32_t id = static_cast<uint32_t>(s.stats.n_components);
+    int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
+    int64_t sum[3] = {0, 0, 0};
+    uint64_t last = 0;
+    for (uint32_t i : comp) {
+      for (int a = 0; a < 3; ++a) {
+        lo[a] = std::min(lo[a], mem[i].g[a]), hi[a] = std::max(hi[a], mem[i].g[a]), sum[a] += mem[i].g[a];
+        if (want_voxels) s.voxels.push_back(mem[i].g[a]);
+      }
+      last = std::max(last, mem[i].stamp);
+      if (want_voxels) s.voxel_component.push_back(id);
+    }
+    s.label.push_back(static_cast<int32_t>(mem[start].label));
+    s.n_voxels.push_back(comp.size());
+    for (int a = 0; a < 3; ++a) {
+      s.bbox_min.push_back(lo[a]), s.bbox_max.push_back(hi[a]), s.sum.push_back(sum[a]), s.representative.push_back(mem[start].g[a]);
+    }
+    s.last_observed_max.push_back(last);
+    s.first.push_back(s.stats.n_voxels);
+    s.stats.n_voxels += comp.size();
+  }
+  return s;
+}
+
+// aw_demo --segment <config.yaml> <width> <height> <frames> [connectivity]: the synthetic stream through one ActiveWindow; then the
+// live map is segmented on the device (VolumetricMap::segment: the defaults, every component kept, with the voxel list) and, from
+// block copies, on one host thread by a breadth-first flood fill.  One JSON line: whether the two results are equal array for
+// array, the statistics, and wall-clock times: the device call through the completion of its last kernel (the first call, which
+// creates the scratch, a repeat, and a repeat once the host knows the live block count and the scratch is sized by it), the call
+// with the copy of its arrays to the host, and the host alternative (the download of the map and the flood fill).
+static int segmentDemo(int argc, char** argv) {
+  if (argc < 6) {
+    std::fprintf(stderr, "usage: aw_demo --segment <config.yaml> <width> <height> <frames> [connectivity]\n");
+    return 2;
+  }
+  std::ifstream in(argv[2]);
+  std::stringstream ss;
+  ss << in.rdbuf();
+  const int W = std::atoi(argv[3]), H = std::atoi(argv[4]), N = std::atoi(argv[5]), connectivity = argc > 6 ? std::atoi(argv[6]) : 26;
+  ActiveWindow::Config cfg = ActiveWindow::Config::fromYamlString(ss.str());
+  cfg.max_frame_pixels = static_cast<uint32_t>(W) * H;
+  auto out_queue = std::make_shared<ActiveWindow::OutputQueue>();
+  ActiveWindow aw(cfg, out_queue);
+  void* scene = synth_create(1234, 12, 1);
+  const size_t np = static_cast<size_t>(W) * H;
+  std::vector<float> depth(np);
+  std::vector<uint8_t> rgb(np * 3);
+  std::vector<int32_t> label(np);
+  for (int i = 0; i < N; ++i) {
+    hydra::InputPacket pkt;
+    pkt.timestamp_ns = static_cast<uint64_t>(std::llround((1.0 + 0.1 * i) * 1e9));
+    circlePose(0.1 * i, pkt.world_T_body);
+    pkt.sensor = {W, H, W / 2.f, W / 2.f, W / 2.f, H / 2.f, 0.1f, 5.f};
+    synth_render(scene, W, H, pkt.sensor.fx, pkt.sensor.fy, pkt.sensor.cx, pkt.sensor.cy, pkt.world_T_body, 0.1 * i, 5.f, 0.f,
+                 1234u + 7919u * i, depth.data(), rgb.data(), label.data(), 0);
+    pkt.depth = depth.data();
+    pkt.color = rgb.data();
+    pkt.labels = label.data();
+    aw.step(pkt);
+    hydra::ActiveWindowOutput::Ptr popped;
+    while (out_queue->pop(&popped)) {}
+  }
+  synth_destroy(scene);
+  const VolumetricMap& map = aw.getMap();
+  khr_config kc{};
+  if (khr_get_config(map.ctx(), &kc) != KHR_OK) throw std::runtime_error(khr_last_error());
+  using clk = std::chrono::steady_clock;
+  auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+  khr_sync(map.ctx());
+  khr_segment_request rq{};
+  rq.connectivity = connectivity;
+  rq.by_label = kc.with_semantics != 0;
+  rq.min_voxels = 1;
+  rq.want_voxels = 1;
+  double call_ms[2];
+  for (int r = 0; r < 2; ++r) {  // (right after a frame the host knows no block count: the scratch is sized by the pool)
+    const auto a = clk::now();
+    if (khr_segment_map(map.ctx(), &rq, nullptr) != KHR_OK) throw std::runtime_error(std::string("khr_segment_map: ") + khr_last_error());
+    khr_sync(map.ctx());
+    call_ms[r] = ms(a, clk::now());
+  }
+  const auto t0 = clk::now();
+  const DiffBlocks blocks = downloadBlocks(map);
+  const auto t1 = clk::now();
+  const hydra::MapSegments host = hostSegment(blocks, kc.voxels_per_side, kc.mesh_min_weight, 0.f, connectivity, rq.by_label != 0, kc.with_semantics != 0,
+                                              kc.with_tracking != 0, true);
+  const auto t2 = clk::now();
+  double live_ms = 0.0;
+  {  // (the download has brought the host index up to date: the scratch is sized by the live blocks now)
+    const auto a = clk::now();
+    if (khr_segment_map(map.ctx(), &rq, nullptr) != KHR_OK) throw std::runtime_error(std::string("khr_segment_map: ") + khr_last_error());
+    khr_sync(map.ctx());
+    live_ms = ms(a, clk::now());
+  }
+  const auto t2b = clk::now();
+  VolumetricMap::SegmentRequest srq;
+  srq.connectivity = connectivity;
+  const hydra::MapSegments dev = map.segment(srq);
+  const auto t3 = clk::now();
+  aw.finishMapping();
+  const char* diff = nullptr;
+  if (std::memcmp(&dev.stats, &host.stats, sizeof(dev.stats)) != 0) diff = "statistics";
+  else if (dev.label != host.label) diff = "label";
+  else if (dev.n_voxels != host.n_voxels) diff = "n_voxels";
+  else if (dev.bbox_min != host.bbox_min) diff = "bbox_min";
+  else if (dev.bbox_max != host.bbox_max) diff = "bbox_max";
+  else if (dev.sum != host.sum) diff = "sum";
+  else if (dev.representative != host.representative) diff = "representative";
+  else if (dev.last_observed_max != host.last_observed_max) diff = "last_observed_max";
+  else if (dev.first != host.first) diff = "first";
+  else if (dev.voxels != host.voxels) diff = "voxels";
+  else if (dev.voxel_component != host.voxel_component) diff = "voxel_component";
+  const khr_segment_stats& st = dev.stats;
+  uint64_t largest = 0;
+  for (uint64_t n : dev.n_voxels) largest = std::max(largest, n);
+  auto u = [](uint64_t v) { return static_cast<unsigned long long>(v); };
+  std::printf("{\"what\": \"one stream, then the connected components of the live map: VolumetricMap::segment (device) vs a breadth-first flood fill "
+              "over block copies on one host thread, %dx%d, voxel %.4g m, connectivity %d, by_label %d\", \"frames\": %d, \"n_blocks\": %llu, "
+              "\"n_member_voxels\": %llu, \"n_components\": %llu, \"n_voxels\": %llu, \"largest_component\": %llu, \"equal\": %s, "
+              "\"first_mismatch\": \"%s\", \"device_segment_first_ms\": %.4f, \"device_segment_ms\": %.4f, \"device_segment_live_sized_ms\": %.4f, "
+              "\"segment_with_arrays_ms\": %.4f, "
+              "\"host_download_ms\": %.4f, \"host_flood_fill_ms\": %.4f}\n",
+              W, H, static_cast<double>(kc.voxel_size), connectivity, rq.by_label, N, u(st.n_blocks), u(st.n_member_voxels), u(st.n_components),
+              u(st.n_voxels), u(largest), diff ? "false" : "true", diff ? diff : "", call_ms[0], call_ms[1], live_ms, ms(t2b, t3), ms(t0, t1), ms(t1, t2));
+  return diff ? 3 : 0;
+}
+
 int main(int argc, char** argv) {
   std::signal(SIGSEGV, onSegv);
   std::signal(SIGABRT, onSegv);
+  if (argc >= 2 && std::string(argv[1]) == "--segment") {
+    try {
+      return segmentDemo(argc, argv);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "aw_demo: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc >= 2 && std::string(argv[1]) == "--diff") {
     try {
       return diffDemo(argc, argv);

@@ -384,6 +384,29 @@ struct MapDiff {
   size_t numBlocks() const { return block_first.size(); }
 };
 
+// The connected pieces of matter in the live map (VolumetricMap::segment; khr_segment_map, ASSUMPTIONS.md A.19): the kept
+// components in ascending order of their representatives (ids 1, 2, ...: component i has id i + 1) and, where asked for, the
+// voxel list grouped by component in ascending id, ascending voxel order inside a component.  Indices are global voxel indices.
+struct MapSegments {
+  khr_segment_stats stats{};
+  std::vector<int32_t> label;
+  std::vector<uint64_t> n_voxels;
+  std::vector<int32_t> bbox_min, bbox_max;  // 3 per component, inclusive
+  std::vector<int64_t> sum;                 // 3 per component
+  std::vector<int32_t> representative;      // 3 per component
+  std::vector<uint64_t> last_observed_max, first;
+  std::vector<int32_t> voxels;  // 3 per listed voxel (empty without the list)
+  std::vector<uint32_t> voxel_component;
+  size_t numComponents() const { return label.size(); }
+  size_t numVoxels() const { return voxel_component.size(); }
+  // centre of mass of component i in metres, in double from the exact sums
+  std::array<double, 3> centroid(size_t i, double voxel_size) const {
+    const double n = static_cast<double>(n_voxels[i]);
+    return {(static_cast<double>(sum[3 * i]) / n + 0.5) * voxel_size, (static_cast<double>(sum[3 * i + 1]) / n + 0.5) * voxel_size,
+            (static_cast<double>(sum[3 * i + 2]) / n + 0.5) * voxel_size};
+  }
+};
+
 struct IndexedMesh;  // (below, behind Mesh)
 
 // hydra::VolumetricMap role: here a handle on the HBM-resident map of a fusion context.
@@ -596,6 +619,42 @@ class VolumetricMap {
                           d.stamp_then.data(), d.blocks.data(), d.block_appeared.data(), d.block_disappeared.data(), d.block_first.data()) != KHR_OK)
       throw std::runtime_error(std::string("khr_diff_map_into: ") + khr_last_error());
     return d;
+  }
+  // The connected components of this map's occupied voxels on the device (khr_segment_map, ASSUMPTIONS.md A.19).  The map is not
+  // written.  by_label < 0 = by label where the map has semantics.  Throws std::runtime_error with khr_last_error's text.
+  struct SegmentRequest {
+    float min_weight = 0.f;  // 0 = this map's mesh_min_weight
+    float surface_distance = 0.f;
+    int connectivity = 26;
+    int by_label = -1;
+    std::vector<int32_t> labels;  // at most 64; empty = every label
+    uint32_t flags_require = 0, flags_exclude = 0;
+    int64_t min_voxels = 1, max_voxels = 0;  // max_voxels <= 0 = unlimited
+    bool want_voxels = true;
+  };
+  MapSegments segment(const SegmentRequest& request) const {
+    khr_segment_request rq{};
+    rq.min_weight = request.min_weight;
+    rq.surface_distance = request.surface_distance;
+    rq.connectivity = request.connectivity;
+    khr_config kc{};
+    if (request.by_label < 0 && khr_get_config(ctx_, &kc) != KHR_OK) throw std::runtime_error(std::string("khr_get_config: ") + khr_last_error());
+    rq.by_label = request.by_label < 0 ? (kc.with_semantics != 0) : request.by_label;
+    rq.labels = request.labels.empty() ? nullptr : request.labels.data();
+    rq.n_labels = static_cast<int32_t>(request.labels.size());
+    rq.flags_require = request.flags_require, rq.flags_exclude = request.flags_exclude;
+    rq.min_voxels = request.min_voxels, rq.max_voxels = request.max_voxels;
+    rq.want_voxels = request.want_voxels;
+    MapSegments s;
+    if (khr_segment_map(ctx_, &rq, &s.stats) != KHR_OK) throw std::runtime_error(std::string("khr_segment_map: ") + khr_last_error());
+    const size_t m = static_cast<size_t>(s.stats.n_components), n = request.want_voxels ? static_cast<size_t>(s.stats.n_voxels) : 0;
+    s.label.resize(m); s.n_voxels.resize(m); s.bbox_min.resize(3 * m); s.bbox_max.resize(3 * m); s.sum.resize(3 * m); s.representative.resize(3 * m);
+    s.last_observed_max.resize(m); s.first.resize(m); s.voxels.resize(3 * n); s.voxel_component.resize(n);
+    if (khr_segment_map_into(ctx_, 0, s.label.data(), s.n_voxels.data(), s.bbox_min.data(), s.bbox_max.data(), s.sum.data(), s.representative.data(),
+                             s.last_observed_max.data(), s.first.data(), request.want_voxels ? s.voxels.data() : nullptr,
+                             request.want_voxels ? s.voxel_component.data() : nullptr) != KHR_OK)
+      throw std::runtime_error(std::string("khr_segment_map_into: ") + khr_last_error());
+    return s;
   }
 
  private:
