@@ -442,6 +442,20 @@ int khr_clear_updated(khr_ctx* ctx);
 int khr_allocate_blocks(khr_ctx* ctx, const int32_t* indices, int64_t n);
 /* replaces: confidence pruning loop of MeshObjectExtractor (mesh_object_extractor.cpp:246-264) */
 int khr_object_prune(khr_ctx* ctx, float min_confidence, float min_observations, int64_t* n_pruned);
+/* The object extractor's call sequence in fewer device commands.  The step-wise calls above remain and mean the same.
+ * khr_begin_object_map = khr_reset_map(voxel_size, truncation_distance) followed by khr_allocate_blocks of every block index of
+ * the dense box lo[d] <= index[d] <= hi[d] (x outermost, z innermost): the box travels as arguments instead of an index list,
+ * and one launch behind the reset allocates and zero-initialises the blocks and prepares the next `allocate = 0` integration,
+ * which then starts with its update launches.  A box of more blocks than the context holds is allocated step-wise (and counted
+ * in pool_exhausted). */
+int khr_begin_object_map(khr_ctx* ctx, float voxel_size, float truncation_distance, const int32_t lo[3], const int32_t hi[3]);
+/* khr_integrate_shared_batch(ctx, src, src_slots, object_ids, n_frames, allocate = 0, use_mask) followed by
+ * khr_object_prune(ctx, min_confidence, min_observations, n_pruned): same map, same count, same errors.  Where the batch runs as
+ * the multi-frame update of a binary object map, the pruning rule is applied in the update's last launch, on the voxel state it
+ * is about to store; every other batch is integrated as before and pruned by the pruning kernel.  n_pruned may be NULL (the call
+ * then stays asynchronous). */
+int khr_integrate_prune_batch(khr_ctx* ctx, khr_ctx* src, const int* src_slots, const int* object_ids, int n_frames, int use_mask,
+                              float min_confidence, float min_observations, int64_t* n_pruned);
 
 /* One ActiveWindow::spinOnce worth of volumetric work in a single call (active_window.cpp:118-174):
  * upload + normalise the frame, [KHR_PF_MOTION] FreeSpaceMotionDetector + dynamic mask, frustum

@@ -179,7 +179,7 @@ EXPORTS = [
     "khr_create", "khr_destroy", "khr_last_error", "khr_host_trace", "khr_set_stream", "khr_sync", "khr_default_config",
     "khr_upload_frame", "khr_set_frame_image", "khr_download_frame", "khr_frame_copy_create", "khr_frame_copy_download", "khr_frame_copy_release", "khr_integrate", "khr_update_tracking",
     "khr_detect_motion", "khr_generate_mesh", "khr_reset_inactive", "khr_mark_all_inactive", "khr_clear_updated",
-    "khr_allocate_blocks", "khr_object_prune", "khr_get_stats", "khr_num_blocks", "khr_block_indices",
+    "khr_allocate_blocks", "khr_object_prune", "khr_begin_object_map", "khr_integrate_prune_batch", "khr_get_stats", "khr_num_blocks", "khr_block_indices",
     "khr_download_block", "khr_mesh_num_vertices", "khr_download_mesh", "khr_fetch_mesh", "khr_fetch_mesh_into", "khr_timing_enable", "khr_timing_reset",
     "khr_timing_get", "khr_debug_read", "khr_tick_ingest", "khr_tick_integrate", "khr_tick_live_bound", "khr_tick_seed_counts", "khr_converted_bytes", "khr_export_converted",
     "khr_converted_views", "khr_tick_adopt", "khr_copy_frame_image", "khr_rv_detect_changes", "khr_last_removed", "khr_process_frame", "khr_ingest_ahead", "khr_ingest_ahead_host", "khr_ingest_cancel", "khr_integrate_shared", "khr_integrate_shared_batch", "khr_pixel_iou", "khr_forward_instances", "khr_update_tracking_phase",
@@ -278,6 +278,8 @@ def load_library():
     lib.khr_clear_updated.argtypes = [vp]
     lib.khr_allocate_blocks.argtypes = [vp, vp, i64]
     lib.khr_object_prune.argtypes = [vp, C.c_float, C.c_float, C.POINTER(i64)]
+    lib.khr_begin_object_map.argtypes = [vp, C.c_float, C.c_float, vp, vp]
+    lib.khr_integrate_prune_batch.argtypes = [vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, C.POINTER(i64)]
     lib.khr_get_stats.argtypes = [vp, C.POINTER(KhrStats)]
     lib.khr_num_blocks.argtypes = [vp]
     lib.khr_num_blocks.restype = i64
@@ -785,6 +787,22 @@ class FusionContext:
     def allocate_blocks(self, indices):
         idx = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1, 3)
         self._chk(self.lib.khr_allocate_blocks(self.h, _ptr(idx), idx.shape[0]))
+
+    def begin_object_map(self, voxel_size, truncation_distance, lo, hi):
+        """khr_begin_object_map: reset_map + allocate_blocks of the dense block box lo <= index <= hi, in two launches."""
+        lo3 = np.ascontiguousarray(lo, dtype=np.int32).reshape(3)
+        hi3 = np.ascontiguousarray(hi, dtype=np.int32).reshape(3)
+        self._chk(self.lib.khr_begin_object_map(self.h, float(voxel_size), float(truncation_distance), _ptr(lo3), _ptr(hi3)))
+        self.cfg.voxel_size, self.cfg.truncation_distance = float(voxel_size), float(truncation_distance)
+
+    def integrate_prune_batch(self, src, slots, object_ids, min_confidence, min_observations, use_mask=False):
+        """khr_integrate_prune_batch: integrate_shared_batch(allocate_blocks=False) + object_prune; returns the pruned count."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        ids = None if object_ids is None else np.ascontiguousarray(object_ids, dtype=np.int32)
+        n = C.c_int64(0)
+        self._chk(self.lib.khr_integrate_prune_batch(self.h, src.h, _ptr(sl), None if ids is None else _ptr(ids), len(sl),
+                                                     int(use_mask), min_confidence, min_observations, C.byref(n)))
+        return n.value
 
     def object_prune(self, min_confidence, min_observations):
         n = C.c_int64(0)

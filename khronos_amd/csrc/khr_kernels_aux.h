@@ -1606,9 +1606,11 @@ __global__ __launch_bounds__(256) void k_mesh_halo_adopt(const uint64_t* __restr
 // (re)generate (generateMesh(map, only_mesh_updated, ...)), their `regen` marks, and the carried-over vertex counts
 // of the blocks that keep their mesh (regenerated blocks get their count from the counting pass)
 __global__ __launch_bounds__(256) void k_mesh_prepare(DevMap m, uint32_t require_flags, uint32_t* __restrict__ work,
-                                                     uint32_t* __restrict__ n_work, uint8_t* __restrict__ regen,
-                                                     uint32_t* __restrict__ new_count, uint32_t* __restrict__ old_offset) {
+                                                     uint32_t* __restrict__ n_work, uint32_t* __restrict__ n_work_next,
+                                                     uint8_t* __restrict__ regen, uint32_t* __restrict__ new_count,
+                                                     uint32_t* __restrict__ old_offset) {
   const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s == 0u) *n_work_next = 0u;  // (the next pass counts into the other word: zero by then, no memset)
   // every meshing starts without the overflow mark of an earlier one (the emit pass of THIS call sets it again, in stream order,
   // if this call's mesh does not fit either): one overflow must not fail every later mesh of the context
   if (s == 0u) m.counters[C_MESH_OVERFLOW] = 0u;

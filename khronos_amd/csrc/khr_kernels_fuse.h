@@ -991,8 +991,20 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse2(FuseArgs a, FuseList l
 // no map memory at all.  The values and decisions are the functions of khr_fuse_math.h that k_fuse2 and fuseBandRecord call;
 // what is written out here is the binary layer's two-entry likelihood row (fuseBandRecord's row loop for K = 2, sem_mode 1).
 // ====================================================================================================================
+// FusePrune (an argument of its own: FuseArgs is k_fuse's argument block too): with `on`, the launch is the batch's last and applies
+// the extractor's confidence pruning (k_object_prune's rule, khr_kernels_aux.h) to the registers it is about to store -- distance,
+// flag byte and both likelihoods of every voxel are there.  The rule also covers voxels no frame ever touched (distance 0, no
+// semantic entry: pruned and counted), so the launch walks the items of `tail` behind the update list: the live items that
+// k_multi_order left out.  n_pruned has been zeroed; one atomic per workgroup.
+struct FusePrune {
+  int on;
+  float min_conf, min_obs;
+  const uint4* tail;
+  const uint32_t* n_tail;
+  unsigned long long* n_pruned;
+};
 template <bool EXACT, int WPW, int MINW>
-__global__ __launch_bounds__(64 * WPW, MINW) void k_fuse_obj(FuseArgs a, FuseList list) {
+__global__ __launch_bounds__(64 * WPW, MINW) void k_fuse_obj(FuseArgs a, FuseList list, FusePrune pr) {
   constexpr int VPS = 8, ZSPLIT = 4;
   constexpr int NV = VPS * VPS * VPS;
   constexpr int SL = VPS * VPS;
@@ -1002,23 +1014,32 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse_obj(FuseArgs a, FuseLis
   constexpr uint32_t S_LABEL = 0x100u, S_TSDF = 0x200u, S_COLOR = 0x400u, S_SEM = 0x800u, S_FLAG = 0x1000u;
   __shared__ uint32_t s_stat[WPW][2];
   __shared__ uint32_t s_q;
+  __shared__ uint32_t s_pruned[WPW];
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
   const int lane = static_cast<int>(threadIdx.x & 63);
   const float den = a.trunc - a.dropoff_eps;
   const float yden = rcpRefined(den);
-  const uint32_t nc0 = list.counts[0], nc1 = nc0 + list.counts[1], nc2 = nc1 + list.counts[2], n_items = nc2 + list.counts[3];
-  uint32_t n_upd = 0, n_band = 0;
+  const uint32_t nc0 = list.counts[0], nc1 = nc0 + list.counts[1], nc2 = nc1 + list.counts[2], n_listed = nc2 + list.counts[3];
+  const bool prune = pr.on != 0;
+  const uint32_t n_items = n_listed + (prune ? *pr.n_tail : 0u);
+  // descriptor of position i: the update list in deal order, then the untouched items of a pruning launch
+  auto descAt = [&](uint32_t i) -> uint4 {
+    if (i < n_listed) return descOf(list, nc0, nc1, nc2, i);
+    const u4v d = ((DescK)pr.tail)[i - n_listed];
+    return make_uint4(d.x, d.y, d.z, d.w);
+  };
+  uint32_t n_upd = 0, n_band = 0, n_pruned = 0;
   if (a.gate != nullptr && *a.gate != 0u) return;
   if (threadIdx.x == 0) s_q = 0u;
   __syncthreads();
   const uint32_t first = firstListPos();
   uint32_t item = pullListPos(&s_q, lane, first);
   uint4 desc = make_uint4(0u, 0u, 0u, 0u);
-  if (item < n_items) desc = descOf(list, nc0, nc1, nc2, item);
+  if (item < n_items) desc = descAt(item);
   while (item < n_items) {
     const uint32_t item_next = pullListPos(&s_q, lane, first);
     uint4 d_next = make_uint4(0u, 0u, 0u, 0u);
-    if (item_next < n_items) d_next = descOf(list, nc0, nc1, nc2, item_next);
+    if (item_next < n_items) d_next = descAt(item_next);
     const size_t slot = desc.x & 0xffffffu;
     const int sbi = static_cast<int>(desc.x >> 24);
     const int bx = static_cast<int>(desc.y), by = static_cast<int>(desc.z), bz = static_cast<int>(desc.w);
@@ -1171,7 +1192,28 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse_obj(FuseArgs a, FuseLis
         }
       }
     }  // frames
-    // ---- the item's voxel state back to the map, where a frame changed it ----
+    // ---- the batch's last launch: confidence pruning on the registers (k_object_prune's rule, value for value) ----
+    if (prune) {
+      bool rewrote = false;
+#pragma unroll
+      for (int k = 0; k < ZR; ++k) {
+        if (dreg[k] > 0.f) continue;
+        float conf = 0.f;
+        if (sreg[k] & VOX_SEM_VALID) {
+          const float total = lreg[k].x + lreg[k].y;
+          conf = total < pr.min_obs ? -1.f : lreg[k].y / total;
+        }
+        if (conf < pr.min_conf) {
+          dreg[k] = a.trunc;
+          sreg[k] |= S_TSDF;
+          ++n_pruned;
+          rewrote = true;
+        }
+      }
+      // a rewritten distance voids the tracking pass's per-block shortcuts (as k_object_prune)
+      if (__builtin_amdgcn_ballot_w64(rewrote) != 0ull && lane == 0) atomicOr(&a.blk_flags[slot], BLK_TRACK_DIRTY);
+    }
+    // ---- the item's voxel state back to the map, where a frame (or the pruning) changed it ----
 #pragma unroll
     for (int k = 0; k < ZR; ++k) {
       const uint32_t lin = static_cast<uint32_t>(lane + (z0 + k) * SL);
@@ -1190,6 +1232,18 @@ __global__ __launch_bounds__(64 * WPW, MINW) void k_fuse_obj(FuseArgs a, FuseLis
     multiItemEpilogue(a, slot, sbi, lane, touched, wrote_neg, cnt);
     item = item_next;
     desc = d_next;
+  }
+  if (prune) {  // (wave-uniform: the barrier below is reached by every wave of the workgroup)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n_pruned += __shfl_down(n_pruned, o);
+    if (lane == 0) s_pruned[wave] = n_pruned;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t np = 0u;
+#pragma unroll
+      for (int w = 0; w < WPW; ++w) np += s_pruned[w];
+      if (np) atomicAdd(pr.n_pruned, static_cast<unsigned long long>(np));
+    }
   }
   statsEpilogue<WPW>(s_stat, wave, lane, n_upd, n_band, a.wg_stats);
 }
@@ -1284,30 +1338,38 @@ __global__ __launch_bounds__(256) void k_multi_cull(const uint32_t* __restrict__
 // allocating integration or of a loaded checkpoint count too): the grid strides over them, once in the extractor's call sequence.
 __global__ __launch_bounds__(1024) void k_multi_order(const uint32_t* __restrict__ blk_flags, const int4* __restrict__ blk_index, const uint32_t* __restrict__ n_slots_ptr,
                                                      const uint32_t* __restrict__ bits, int n_words, int n_frames, uint32_t wpb, uint32_t live_flag,
-                                                     FuseList out) {
-  __shared__ uint32_t s_cnt[4], s_off[4];
+                                                     FuseList out, uint4* __restrict__ tail = nullptr, uint32_t* __restrict__ n_tail = nullptr) {
+  // tail != nullptr: the live items NO frame can touch are listed too, in a list of their own (class 4 below) -- the batch's last
+  // launch prunes in its store epilogue and has to see every voxel of the map once (FusePrune)
+  __shared__ uint32_t s_cnt[5], s_off[5];
   const uint32_t n_items = *n_slots_ptr * wpb;  // (a slot has 24 bits in an item's descriptor: no overflow here or in the loop)
   // the loop bound is the same for every thread of a workgroup: the barriers inside are reached by all of them
   for (uint32_t it0 = blockIdx.x * blockDim.x; it0 < n_items; it0 += gridDim.x * blockDim.x) {
-    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0u;
+    if (threadIdx.x < 5) s_cnt[threadIdx.x] = 0u;
     __syncthreads();
     const uint32_t it = it0 + threadIdx.x;
     uint32_t n = 0u, cls = 0u, pos = 0u;
-    if (it < n_items && (blk_flags[it / wpb] & live_flag))
+    const bool live = it < n_items && (blk_flags[it / wpb] & live_flag);
+    if (live)
       for (int w = 0; w < n_words; ++w) n += static_cast<uint32_t>(__popc(bits[static_cast<size_t>(it) * n_words + w]));
+    const bool listed = n != 0u || (live && tail != nullptr);
     if (n) {
       const uint32_t q = 4u * n, f = static_cast<uint32_t>(n_frames);
       cls = q >= 3u * f ? 0u : (q >= 2u * f ? 1u : (q >= f ? 2u : 3u));
-      pos = atomicAdd(&s_cnt[cls], 1u);
+    } else {
+      cls = 4u;
     }
+    if (listed) pos = atomicAdd(&s_cnt[cls], 1u);
     __syncthreads();
     if (threadIdx.x < 4) s_off[threadIdx.x] = s_cnt[threadIdx.x] ? atomicAdd(&out.counts[threadIdx.x], s_cnt[threadIdx.x]) : 0u;
+    if (threadIdx.x == 4) s_off[4] = s_cnt[4] ? atomicAdd(n_tail, s_cnt[4]) : 0u;  // (s_cnt[4] != 0 only with a tail)
     __syncthreads();
-    if (n) {
+    if (listed) {
       const uint32_t slot = it / wpb;
       const int4 bi = blk_index[slot];
-      *fuseDescPtr(out, cls, s_off[cls] + pos) =
-          make_uint4(slot | ((it % wpb) << 24), static_cast<uint32_t>(bi.x), static_cast<uint32_t>(bi.y), static_cast<uint32_t>(bi.z));
+      const uint4 d = make_uint4(slot | ((it % wpb) << 24), static_cast<uint32_t>(bi.x), static_cast<uint32_t>(bi.y), static_cast<uint32_t>(bi.z));
+      if (n) *fuseDescPtr(out, cls, s_off[cls] + pos) = d;
+      else tail[s_off[4] + pos] = d;
     }
   }
 }

@@ -618,13 +618,10 @@ __global__ __launch_bounds__(256) void k_list_live(DevMap m, uint32_t* __restric
   }
 }
 
-// zero-initialise freshly allocated blocks.  One workgroup per block, 16-byte stores.
-__device__ inline void initBlocks(const DevMap& m, const DevParams& p, const uint32_t* __restrict__ new_list, uint32_t bid,
-                                  uint32_t nblk) {
-  const uint32_t n = m.counters[C_N_NEW];
+// zero-initialise a freshly allocated block (the whole workgroup), 16-byte stores
+__device__ inline void initBlock(const DevMap& m, const DevParams& p, size_t slot) {
   const int nv = p.nvox;
-  for (uint32_t b = bid; b < n; b += nblk) {
-    const size_t slot = new_list[b];
+  {
     const uint4 z = make_uint4(0, 0, 0, 0);
     uint4* d4 = reinterpret_cast<uint4*>(m.dist + slot * nv);
     uint4* w4 = reinterpret_cast<uint4*>(m.weight + slot * nv);
@@ -653,6 +650,55 @@ __device__ inline void initBlocks(const DevMap& m, const DevParams& p, const uin
       }
     }
   }
+}
+
+// zero-initialise freshly allocated blocks.  One workgroup per block.
+__device__ inline void initBlocks(const DevMap& m, const DevParams& p, const uint32_t* __restrict__ new_list, uint32_t bid,
+                                  uint32_t nblk) {
+  const uint32_t n = m.counters[C_N_NEW];
+  for (uint32_t b = bid; b < n; b += nblk) initBlock(m, p, new_list[b]);
+}
+
+// khr_begin_object_map: a dense box of blocks [lo, lo + dim) into a map that k_reset_map has just emptied, ready for an
+// `allocate = false` integration -- what k_alloc_list, k_init_blocks, k_begin_integrate and k_list_live leave behind, in one launch
+// (the object extractor's mini-map).  After the reset the free list is the identity and nothing is allocated, so block b of the
+// box (x outermost, z innermost: the order of the sorted index list) takes slot b and the counters are plain stores; one
+// workgroup per block, the hash insert is the only atomic.  `zero` lists further words this call sequence wants cleared
+// (counters the later launches accumulate into), so that no memset has to be queued for them.
+struct BoxSetupZero {
+  uint32_t* w;  // nullptr: none
+  uint32_t n;   // words to clear at w (at most 256)
+};
+__global__ __launch_bounds__(256) void k_setup_box(DevMap m, DevParams p, int3 lo, int3 dim, uint32_t n,
+                                                  uint32_t* __restrict__ work, FuseList out, uint32_t wpb, uint32_t* wg_stats,
+                                                  BoxSetupZero zero) {
+  const uint32_t b = blockIdx.x;
+  if (b >= n) return;
+  if (b == 0) {
+    beginIntegrate(m, p.nvox, wg_stats);  // (thread 0 zeroes the per-call counters, C_N_NEW among them: the stores below are its own, in order)
+    if (threadIdx.x == 0) {
+      m.counters[C_FREE_HEAD] = n;
+      m.counters[C_MAX_SLOT] = n;
+      m.counters[C_N_VISIBLE] = n;
+      out.counts[3] = n * wpb;
+    }
+    if (zero.w != nullptr && threadIdx.x < zero.n) zero.w[threadIdx.x] = 0u;
+  }
+  const int bx = lo.x + static_cast<int>(b / static_cast<uint32_t>(dim.y * dim.z));
+  const int by = lo.y + static_cast<int>((b / static_cast<uint32_t>(dim.z)) % static_cast<uint32_t>(dim.y));
+  const int bz = lo.z + static_cast<int>(b % static_cast<uint32_t>(dim.z));
+  if (threadIdx.x == 0) {
+    m.blk_index[b] = make_int4(bx, by, bz, 0);
+    m.blk_flags[b] = BLK_LIVE | BLK_TRACK_DIRTY | BLK_ANY_KEEP;
+    m.mesh_desc[b] = MeshDesc{0u, 0u};
+    htInsertUnique(m, packKey(bx, by, bz), b);
+    work[b] = b;
+  }
+  // the block's wave items as descriptors of the update kernel, all class 3 (k_list_live)
+  if (threadIdx.x < wpb)
+    *fuseDescPtr(out, 3u, b * wpb + threadIdx.x) =
+        make_uint4(b | (threadIdx.x << 24), static_cast<uint32_t>(bx), static_cast<uint32_t>(by), static_cast<uint32_t>(bz));
+  initBlock(m, p, b);
 }
 
 __global__ __launch_bounds__(256) void k_init_blocks(DevMap m, DevParams p, const uint32_t* __restrict__ new_list) {

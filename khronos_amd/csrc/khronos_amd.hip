@@ -221,7 +221,13 @@ struct khr_ctx {
   // unknown): the update kernel of an `allocate = false` integration (object mini-maps) sizes its persistent grid from it
   // instead of filling the chip with workgroups that find no item
   uint64_t explicit_blocks = 0;
-  DevBuf<uint4> d_multi_list;       // integrateUpdateMulti: the items by frame count (k_multi_order) + 4 counters behind them
+  // integrateUpdateMulti: the items by frame count (k_multi_order): two arrays of item_cap descriptors, one uint4 of class counters,
+  // one uint4 whose first word counts the untouched items, and those items' item_cap descriptors (the pruning launch's tail)
+  DevBuf<uint4> d_multi_list;
+  uint64_t box_gen = 0;             // map_gen as khr_begin_object_map left it: while equal,
+  bool box_listed = false;          // ... the next integration's per-call reset is done and the live blocks are listed (k_setup_box),
+  bool multi_counts_zeroed = false; // ... k_multi_order's counters are zero
+  bool pruned_zeroed = false;       // ... and so is S_PRUNED
   DevBuf<uint32_t> d_frame_bits;    // integrateUpdateMulti: k_multi_cull's (item, frame) bits
   PinnedBuf<FuseFrame> h_frames;    // integrateUpdateMulti: per-frame arguments, pinned staging + device array
   DevBuf<FuseFrame> d_frames;
@@ -375,6 +381,10 @@ struct khr_ctx {
   uint8_t* d_regen = nullptr;
   uint32_t* d_mesh_old_off = nullptr;  // k_mesh_prepare's snapshot of mesh_desc[].offset (read by the copy of the kept meshes)
   uint32_t* d_mesh_nwork = nullptr;
+  // generateMesh's work-list counter: words 0 and 4 of d_mesh_nwork alternate, each pass zeroes the other one (k_mesh_prepare), so no
+  // memset is queued; mesh_nwork_last is the word of the latest pass (refreshMeshTotals)
+  int mesh_nwork_par = 0, mesh_nwork_last = 0;
+  bool mesh_made = false;  // a mesh was generated since the map was last emptied (only then can blocks keep vertices of an earlier pass)
   uint64_t mesh_total = 0;
   bool mesh_stale = false;
   // host mirrors
@@ -844,7 +854,8 @@ int khr_depend_on(khr_ctx* c, khr_ctx* other) {
   return KHR_OK;
 }
 
-int khr_reset_map(khr_ctx* c, float voxel_size, float truncation_distance) {
+// the reset itself (khr_reset_map, khr_begin_object_map): the launch and the host-side state that goes with the map's contents
+static int resetMap(khr_ctx* c, float voxel_size, float truncation_distance) {
   if (!c) return fail(KHR_EINVAL, "null ctx");
   if (!(voxel_size > 0.f) || !(truncation_distance > 0.f)) return fail(KHR_EINVAL, "voxel_size / truncation_distance must be > 0");
   HIP_TRY(hipSetDevice(c->device));
@@ -857,11 +868,13 @@ int khr_reset_map(khr_ctx* c, float voxel_size, float truncation_distance) {
   c->mesh_cur = 0;
   c->mesh_total = 0;
   c->mesh_stale = false;
+  c->mesh_made = false;
   c->weld_valid = false;
   c->diff_valid = false;
   c->seg_valid = false;
   c->host_index_valid = false, ++c->map_gen;
   c->explicit_blocks = 0;
+  c->box_listed = false;
   c->last_removed = 0;
   c->removed_pending = false;
   c->last_track_stamp = 0;
@@ -877,6 +890,8 @@ int khr_reset_map(khr_ctx* c, float voxel_size, float truncation_distance) {
   for (size_t i = 0; i < c->slots.size(); ++i) c->slot_leases[i].store(0);
   return KHR_OK;
 }
+
+int khr_reset_map(khr_ctx* c, float voxel_size, float truncation_distance) { return resetMap(c, voxel_size, truncation_distance); }
 
 int khr_get_config(khr_ctx* c, khr_config* out) {
   if (!c || !out) return fail(KHR_EINVAL, "null argument");
@@ -1018,7 +1033,7 @@ int khr_create(const khr_config* cfg, khr_ctx** out) {
     const size_t bits_words = static_cast<size_t>(c->item_cap) * 4;  // four words per item = 128 buffered frames
     if (c->h_frames.alloc(kMaxMultiFrames) || c->d_frames.alloc(kMaxMultiFrames) || c->ev_frames.ensure() ||
         hipEventRecord(c->ev_frames, c->stream) != hipSuccess || c->d_frame_bits.alloc(bits_words) ||
-        c->d_multi_list.alloc(2 * static_cast<size_t>(c->item_cap) + 1))  // (+ 1 uint4 = the 4 counters)
+        c->d_multi_list.alloc(3 * static_cast<size_t>(c->item_cap) + 2))  // (two lists, 4 + 1 counters, the untouched items)
       rc = fail(KHR_ENOMEM, "buffers of the multi-frame update");
     // ... and the small page-locked block and events its first extraction would otherwise create on the worker's thread
     if (rc == KHR_OK && (c->h_totals.alloc(C_COUNT + 2) || c->ev_up.ensure() || hipEventRecord(c->ev_up, c->stream) != hipSuccess ||
@@ -1488,6 +1503,17 @@ int khr_download_frame_image(khr_ctx* c, int slot, int which, int32_t* image) {
 // block allocation + culling of one integrate call (independent of the dynamic mask)
 static int integrateAlloc(khr_ctx* c, FrameSlot& s, const DevFrame& f, int allocate_blocks) {
   DevMap& m = c->m;
+  // khr_begin_object_map has done the per-call reset AND listed the box's blocks (k_setup_box): nothing to launch
+  const bool listed = c->box_listed;
+  c->box_listed = false;
+  if (listed) {
+    if (!allocate_blocks && c->box_gen == c->map_gen) return KHR_OK;
+    // (the block set has changed since, or this integration builds its own lists: back to the state behind k_begin_integrate, whose
+    // statistics are in already)
+    HIP_TRY(hipMemsetAsync(&m.counters[C_N_VISIBLE], 0, 2 * sizeof(uint32_t), c->stream));  // C_N_VISIBLE, C_N_NEW
+    HIP_TRY(hipMemsetAsync(&m.counters[C_N_ITEMS0], 0, 4 * sizeof(uint32_t), c->stream));
+    c->begun = true;
+  }
   // reset per-call counters (already done by k_frame_ingest inside khr_process_frame)
   if (!c->begun) hipLaunchKernelGGL(k_begin_integrate, dim3(1), dim3(256), 0, c->stream, m, c->p.nvox, c->d_wg_stats);
   c->begun = false;
@@ -1593,16 +1619,30 @@ static void fillFuseMap(khr_ctx* c, FuseArgs* a) {
   a->blend_pre = c->cfg.color_blend_weight != 0;
 }
 
+// the pruning request of a batch goes with its last launch only
+static FusePrune lastChunk(const FusePrune& pr, bool last) { return last ? pr : FusePrune{}; }
+
 // The frames of a batch in one launch per kMultiChunk of them (k_fuse_obj for the extractor's binary object map, k_fuse2 otherwise):
 // every wave item is walked through the frames in order.  Only for `allocate = false` integrations of 8^3-voxel maps with the
 // default integrator switches (the object extractor's mini-map);
 // returns 1 when the batch was not taken (the caller then integrates frame by frame).
-static int integrateUpdateMulti(khr_ctx* c, khr_ctx* src, const int* src_slots, const int* object_ids, int n_frames, int use_mask) {
-  if (c->cfg.voxels_per_side != 8 || n_frames < 2 || n_frames > kMaxMultiFrames) return 1;
+// the extractor's confidence pruning behind a batch (khr_integrate_prune_batch); `fused` reports whether the update's last launch did it
+struct PruneRequest {
+  float min_confidence, min_observations;
+  bool fused;
+};
+
+// does integrateUpdateMulti take a batch of n_frames frames?
+static bool multiApplies(const khr_ctx* c, int n_frames) {
+  if (c->cfg.voxels_per_side != 8 || n_frames < 2 || n_frames > kMaxMultiFrames) return false;
+  return c->p.range_mode == 0 && c->p.interp == 2 && c->p.use_dropoff && !c->p.const_weight;  // (the default integrator switches)
+}
+
+static int integrateUpdateMulti(khr_ctx* c, khr_ctx* src, const int* src_slots, const int* object_ids, int n_frames, int use_mask,
+                                PruneRequest* prune = nullptr) {
+  if (!multiApplies(c, n_frames)) return 1;
   FuseArgs a{};
   fillFuseMap(c, &a);
-  const bool defcfg = a.range_mode == 0 && a.interp == 2 && a.use_dropoff && !a.const_weight;
-  if (!defcfg) return 1;
   // per-frame arguments: pinned staging -> device array (reused only after the previous batch's copy has been consumed)
   if (!c->h_frames) {
     if (c->h_frames.alloc(kMaxMultiFrames) || c->d_frames.alloc(kMaxMultiFrames)) return fail(KHR_ENOMEM, "frame argument staging");
@@ -1645,22 +1685,30 @@ static int integrateUpdateMulti(khr_ctx* c, khr_ctx* src, const int* src_slots, 
     a.frame_words = n_words;
   }
   FuseList list{c->d_work4, c->d_work4 + c->item_cap, c->item_cap, &c->m.counters[C_N_ITEMS0]};
+  // the extractor's configuration (binary object layer, no tracking stamps) has a kernel of its own that keeps the whole voxel
+  // state in registers across a launch's frames (k_fuse_obj); every other map keeps k_fuse2
+  const bool object_map = c->p.with_semantics && a.sem_mode == 1 && a.K == 2 && a.KS == 2 && !a.with_tracking;
+  // ... and that kernel prunes in the batch's last launch, given the list of the items no frame touches (k_multi_order)
+  const bool fuse_prune = prune != nullptr && object_map && a.frame_bits != nullptr;
   if (a.frame_bits != nullptr) {
     // ... and the items in the order of their frame counts, the untouched ones left out (k_multi_order): a list of its own
     if (!c->d_multi_list) {
       HIP_TRY(hipStreamSynchronize(c->stream));
-      if (c->d_multi_list.alloc(2 * static_cast<size_t>(c->item_cap) + 1)) return fail(KHR_ENOMEM, "item list of the multi-frame update");
+      if (c->d_multi_list.alloc(3 * static_cast<size_t>(c->item_cap) + 2)) return fail(KHR_ENOMEM, "item list of the multi-frame update");
     }
     uint32_t* const counts = reinterpret_cast<uint32_t*>(c->d_multi_list + 2 * static_cast<size_t>(c->item_cap));
-    HIP_TRY(hipMemsetAsync(counts, 0, 16, c->stream));
+    if (!(c->multi_counts_zeroed && c->box_gen == c->map_gen)) HIP_TRY(hipMemsetAsync(counts, 0, 32, c->stream));  // (class counters + the tail's)
+    c->multi_counts_zeroed = false;
     list = FuseList{c->d_multi_list, c->d_multi_list + c->item_cap, c->item_cap, counts};
     const uint64_t n_it = static_cast<uint64_t>(c->explicit_blocks > 0 ? std::min<uint64_t>(c->explicit_blocks, c->m.capacity) : c->m.capacity) * c->wpb;
     hipLaunchKernelGGL(k_multi_order, dim3(static_cast<unsigned>((n_it + 1023) / 1024)), dim3(1024), 0, c->stream, c->m.blk_flags, c->m.blk_index,
-                       &c->m.counters[C_MAX_SLOT], static_cast<const uint32_t*>(c->d_frame_bits.get()), a.frame_words, n_frames, c->wpb, BLK_LIVE, list);
+                       &c->m.counters[C_MAX_SLOT], static_cast<const uint32_t*>(c->d_frame_bits.get()), a.frame_words, n_frames, c->wpb, BLK_LIVE, list,
+                       fuse_prune ? c->d_multi_list + 2 * static_cast<size_t>(c->item_cap) + 2 : static_cast<uint4*>(nullptr),
+                       fuse_prune ? counts + 4 : static_cast<uint32_t*>(nullptr));
     HIP_TRY(hipGetLastError());
   }
   constexpr int WPW = 8;
-  auto go = [&](auto kern) {
+  auto go = [&](auto kern, auto... extra) {
     // one workgroup per WPW items is enough (c->explicit_blocks bounds the map), at most what is resident
     // (fuse2Grid: the occupancy query is a driver call of tens of microseconds, once per instantiation, not once per extracted object)
     int grid = fuse2Grid(c, reinterpret_cast<const void*>(kern), WPW);
@@ -1675,15 +1723,21 @@ static int integrateUpdateMulti(khr_ctx* c, khr_ctx* src, const int* src_slots, 
       a.frames = c->d_frames + k0;
       a.n_frames = std::min(kMultiChunk, n_frames - k0);
       a.frame_bit0 = k0;
-      KHR_LAUNCH_TIMED(0, kern, dim3(grid), dim3(64 * WPW), a, list);
+      KHR_LAUNCH_TIMED(0, kern, dim3(grid), dim3(64 * WPW), a, list, lastChunk(extra, k0 + kMultiChunk >= n_frames)...);
     }
   };
-  // the extractor's configuration (binary object layer, no tracking stamps) has a kernel of its own that keeps the whole voxel
-  // state in registers across a launch's frames (k_fuse_obj); every other map keeps k_fuse2
-  const bool object_map = c->p.with_semantics && a.sem_mode == 1 && a.K == 2 && a.KS == 2 && !a.with_tracking;
   if (object_map) {
-    if (exactArithmetic(c)) go(&k_fuse_obj<true, WPW, 4>);
-    else go(&k_fuse_obj<false, WPW, 4>);
+    FusePrune pr{};
+    if (fuse_prune) {
+      if (!(c->pruned_zeroed && c->box_gen == c->map_gen)) HIP_TRY(hipMemsetAsync(&c->m.stats[S_PRUNED], 0, sizeof(unsigned long long), c->stream));
+      c->pruned_zeroed = false;
+      const uint32_t* const counts = reinterpret_cast<const uint32_t*>(c->d_multi_list + 2 * static_cast<size_t>(c->item_cap));
+      pr = FusePrune{1, prune->min_confidence, prune->min_observations, c->d_multi_list + 2 * static_cast<size_t>(c->item_cap) + 2, counts + 4,
+                     &c->m.stats[S_PRUNED]};
+      prune->fused = true;
+    }
+    if (exactArithmetic(c)) go(&k_fuse_obj<true, WPW, 4>, pr);
+    else go(&k_fuse_obj<false, WPW, 4>, pr);
   } else {
     if (exactArithmetic(c)) go(&k_fuse2<8, 4, true, WPW, 4>);
     else go(&k_fuse2<8, 4, false, WPW, 4>);
@@ -1783,8 +1837,8 @@ int khr_integrate_shared(khr_ctx* c, khr_ctx* src, int src_slot, int allocate_bl
   return integrateUpdate(c, s, f, allocate_blocks, use_mask, object_id, false);
 }
 
-int khr_integrate_shared_batch(khr_ctx* c, khr_ctx* src, const int* src_slots, const int* object_ids, int n_frames,
-                               int allocate_blocks, int use_mask) {
+static int integrateSharedBatch(khr_ctx* c, khr_ctx* src, const int* src_slots, const int* object_ids, int n_frames, int allocate_blocks,
+                                int use_mask, PruneRequest* prune) {
   if (!c || !src || !src_slots || n_frames < 0) return fail(KHR_EINVAL, "bad argument");
   for (int i = 0; i < n_frames; ++i)
     if (!validSlot(src, src_slots[i])) return fail(KHR_EINVAL, "bad source slot");
@@ -1811,7 +1865,7 @@ int khr_integrate_shared_batch(khr_ctx* c, khr_ctx* src, const int* src_slots, c
     if (rc) return rc;
   }
   {
-    const int rc = integrateUpdateMulti(c, src, src_slots, object_ids, n_frames, use_mask);
+    const int rc = integrateUpdateMulti(c, src, src_slots, object_ids, n_frames, use_mask, prune);
     if (rc <= 0) return rc;  // done (or failed); 1 = not applicable: frame by frame below
   }
   for (int i = 0; i < n_frames; ++i) {
@@ -1822,6 +1876,31 @@ int khr_integrate_shared_batch(khr_ctx* c, khr_ctx* src, const int* src_slots, c
   }
   // (statistics: cum_integrate_calls counts this batch once; the voxel counts cover all its frames)
   return KHR_OK;
+}
+
+int khr_integrate_shared_batch(khr_ctx* c, khr_ctx* src, const int* src_slots, const int* object_ids, int n_frames,
+                               int allocate_blocks, int use_mask) {
+  return integrateSharedBatch(c, src, src_slots, object_ids, n_frames, allocate_blocks, use_mask, nullptr);
+}
+
+static int readPruned(khr_ctx* c, int64_t* n_pruned) {
+  unsigned long long np = 0;
+  HIP_TRY(hipMemcpyAsync(&np, &c->m.stats[S_PRUNED], sizeof(np), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  *n_pruned = static_cast<int64_t>(np);
+  return KHR_OK;
+}
+
+// khr_integrate_shared_batch(allocate = 0) followed by khr_object_prune, the pruning inside the update's last launch where the batch
+// runs on k_fuse_obj; every other batch is integrated as before and pruned by k_object_prune
+int khr_integrate_prune_batch(khr_ctx* c, khr_ctx* src, const int* src_slots, const int* object_ids, int n_frames, int use_mask,
+                              float min_confidence, float min_observations, int64_t* n_pruned) {
+  PruneRequest pr{min_confidence, min_observations, false};
+  const bool can_prune = c && c->cfg.with_semantics && c->p.K >= 2;  // (khr_object_prune refuses every other map, after the batch)
+  const int rc = integrateSharedBatch(c, src, src_slots, object_ids, n_frames, 0, use_mask, can_prune ? &pr : nullptr);
+  if (rc) return rc;
+  if (!pr.fused) return khr_object_prune(c, min_confidence, min_observations, n_pruned);
+  return n_pruned ? readPruned(c, n_pruned) : KHR_OK;
 }
 
 // smallest unsigned x with  double(x) / 1e9 >= T  (T = toSeconds(now) - window, reference arithmetic:
@@ -3376,9 +3455,11 @@ static int generateMesh(khr_ctx* c, hipStream_t st, int only_mesh_updated, int c
   DevMap& m = c->m;
   const size_t cap = m.capacity;
   ScopedTimer tm(c, 5, st);
-  HIP_TRY(hipMemsetAsync(c->d_mesh_nwork, 0, sizeof(uint32_t), st));
+  uint32_t* const n_work = c->d_mesh_nwork + (c->mesh_nwork_par ? 4 : 0);
+  c->mesh_nwork_last = c->mesh_nwork_par ? 4 : 0;
+  c->mesh_nwork_par ^= 1;
   hipLaunchKernelGGL(k_mesh_prepare, dim3(gridFor(cap + 1)), dim3(256), 0, st, m, only_mesh_updated ? BLK_MESH_UPDATED : 0u,
-                     c->d_work, c->d_mesh_nwork, c->d_regen, c->d_mesh_count, c->d_mesh_old_off);
+                     c->d_work, n_work, c->d_mesh_nwork + (c->mesh_nwork_par ? 4 : 0), c->d_regen, c->d_mesh_count, c->d_mesh_old_off);
   MeshBuffers src = c->mesh[c->mesh_cur], dst = c->mesh[c->mesh_cur ^ 1];
   RemoteMeshHalo rmh{};
   if (c->mh_n) {
@@ -3395,22 +3476,24 @@ static int generateMesh(khr_ctx* c, hipStream_t st, int only_mesh_updated, int c
   int rc = dispatchVps(c, [&](auto vps) {
     constexpr int V = decltype(vps)::value;
     KHR_LAUNCH_TIMED_ON(8, st, (k_marching_cubes<V, false>), dim3(kStreamGrid), dim3(256), m, c->p, c->d_work,
-                     c->d_mesh_nwork, c->d_mesh_count, c->d_mesh_offset, dst, clear_flag, maxv, rmh, 0xffffffffu,
+                     n_work, c->d_mesh_count, c->d_mesh_offset, dst, clear_flag, maxv, rmh, 0xffffffffu,
                      static_cast<const uint8_t*>(nullptr), MeshBuffers{}, static_cast<const uint32_t*>(nullptr));
     size_t tb = c->cub_temp_bytes;
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_cub_temp, tb, c->d_mesh_count, c->d_mesh_offset,
                                              static_cast<int>(cap + 1), st));
     // no host round trip: the capacity check happens on the device (C_MESH_OVERFLOW), totals are read lazily
     // emit pass + the copy of the kept blocks' vertices in ONE launch (the trailing kMoveWgs workgroups copy)
-    constexpr uint32_t kMoveWgs = 1024;
+    // (no copy workgroups for the first mesh of an emptied map: no block holds vertices yet)
+    const uint32_t kMoveWgs = c->mesh_made ? 1024u : 0u;
     KHR_LAUNCH_TIMED_ON(9, st, (k_marching_cubes<V, true>), dim3(kStreamGrid + kMoveWgs), dim3(256), m, c->p, c->d_work,
-                     c->d_mesh_nwork, c->d_mesh_count, c->d_mesh_offset, dst, clear_flag, maxv, rmh, static_cast<uint32_t>(kStreamGrid),
+                     n_work, c->d_mesh_count, c->d_mesh_offset, dst, clear_flag, maxv, rmh, static_cast<uint32_t>(kStreamGrid),
                      static_cast<const uint8_t*>(c->d_regen), src, static_cast<const uint32_t*>(c->d_mesh_old_off));
     return KHR_OK;
   });
   if (rc) return rc;
   c->mesh_cur ^= 1;
   c->mesh_stale = true;
+  c->mesh_made = true;
   HIP_TRY(hipGetLastError());
   return KHR_OK;
 }
@@ -4138,23 +4221,54 @@ int khr_allocate_blocks(khr_ctx* c, const int32_t* indices, int64_t n) {
   return KHR_OK;
 }
 
+int khr_begin_object_map(khr_ctx* c, float voxel_size, float truncation_distance, const int32_t lo[3], const int32_t hi[3]) {
+  if (!c || !lo || !hi) return fail(KHR_EINVAL, "null argument");
+  uint64_t n = 1;
+  for (int d = 0; d < 3; ++d) {
+    if (hi[d] < lo[d]) return fail(KHR_EINVAL, "empty block box");
+    const uint64_t side = static_cast<uint64_t>(static_cast<int64_t>(hi[d]) - lo[d] + 1);
+    if (side > 0xffffffffull / n) return fail(KHR_EINVAL, "block box too large");
+    n *= side;
+  }
+  int rc = resetMap(c, voxel_size, truncation_distance);
+  if (rc) return rc;
+  if (n > c->m.capacity) {  // more blocks than the pool has: the step-wise allocation hands out what there is and counts the rest
+    std::vector<int32_t> idx;
+    for (int x = lo[0]; x <= hi[0]; ++x)
+      for (int y = lo[1]; y <= hi[1]; ++y)
+        for (int z = lo[2]; z <= hi[2]; ++z) idx.insert(idx.end(), {x, y, z});
+    return khr_allocate_blocks(c, idx.data(), static_cast<int64_t>(n));
+  }
+  BoxSetupZero zero{};
+  if (c->d_multi_list) {  // the counters of k_multi_order (8^3 maps)
+    zero.w = reinterpret_cast<uint32_t*>(c->d_multi_list + 2 * static_cast<size_t>(c->item_cap));
+    zero.n = 8;
+  }
+  hipLaunchKernelGGL(k_setup_box, dim3(static_cast<unsigned>(n)), dim3(256), 0, c->stream, c->m, c->p, make_int3(lo[0], lo[1], lo[2]),
+                     make_int3(hi[0] - lo[0] + 1, hi[1] - lo[1] + 1, hi[2] - lo[2] + 1), static_cast<uint32_t>(n), c->d_work,
+                     FuseList{c->d_work4, c->d_work4 + c->item_cap, c->item_cap, &c->m.counters[C_N_ITEMS0]}, c->wpb, c->d_wg_stats, zero);
+  HIP_TRY(hipGetLastError());
+  c->explicit_blocks = n;
+  c->host_index_valid = false, ++c->map_gen;
+  c->box_gen = c->map_gen;
+  c->box_listed = true;  // (the per-call reset and the block list of the next integration are done)
+  c->multi_counts_zeroed = static_cast<bool>(c->d_multi_list);
+  c->pruned_zeroed = true;  // (k_reset_map)
+  return KHR_OK;
+}
+
 int khr_object_prune(khr_ctx* c, float min_confidence, float min_observations, int64_t* n_pruned) {
   if (!c) return fail(KHR_EINVAL, "null ctx");
   if (!c->cfg.with_semantics || c->p.K < 2) return fail(KHR_ESTATE, "object pruning needs a binary semantic layer");
-  HIP_TRY(hipMemsetAsync(&c->m.stats[S_PRUNED], 0, sizeof(unsigned long long), c->stream));
+  if (!(c->pruned_zeroed && c->box_gen == c->map_gen)) HIP_TRY(hipMemsetAsync(&c->m.stats[S_PRUNED], 0, sizeof(unsigned long long), c->stream));
+  c->pruned_zeroed = false;
   int rc = dispatchVps(c, [&](auto vps) {
     hipLaunchKernelGGL((k_object_prune<decltype(vps)::value>), dim3(kStreamGrid), dim3(256), 0, c->stream, c->m, c->p,
                        min_confidence, min_observations);
     return KHR_OK;
   });
   if (rc) return rc;
-  if (n_pruned) {  // (asynchronous without a count request)
-    unsigned long long np = 0;
-    HIP_TRY(hipMemcpyAsync(&np, &c->m.stats[S_PRUNED], sizeof(np), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    *n_pruned = static_cast<int64_t>(np);
-  }
-  return KHR_OK;
+  return n_pruned ? readPruned(c, n_pruned) : KHR_OK;  // (asynchronous without a count request)
 }
 
 static int refreshMeshTotals(khr_ctx* c);
@@ -5152,8 +5266,10 @@ int ckptClearMap(khr_ctx* c) {
   c->mesh_cur = 0;
   c->mesh_total = 0;
   c->mesh_stale = false;
+  c->mesh_made = false;
   c->host_index_valid = false, ++c->map_gen;
   c->explicit_blocks = 0;
+  c->box_listed = false;
   c->last_removed = 0;
   c->removed_pending = false;
   c->last_track_stamp = 0;
@@ -5384,7 +5500,7 @@ static int refreshMeshTotals(khr_ctx* c) {
   if (!c->h_totals && c->h_totals.alloc(C_COUNT + 2)) return fail(KHR_ENOMEM, "pinned block for the mesh totals");
   uint32_t* hs = c->h_totals;
   HIP_TRY(hipMemcpyAsync(hs, c->d_mesh_offset + c->m.capacity, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(hs + 1, c->d_mesh_nwork, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(hs + 1, c->d_mesh_nwork + c->mesh_nwork_last, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(hs + 2, c->m.counters, sizeof(uint32_t) * C_COUNT, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   const uint32_t total = hs[0], nwork = hs[1];

@@ -138,7 +138,7 @@ MeshObjectExtractor::MeshObjectExtractor(const Config& cfg, const khr_config& aw
     throw std::invalid_argument("negative displacement / resolution");
   // The private object map is created HERE, once (hipMalloc / hipFree synchronise the whole device: creating it at the
   // first extraction stalled the active window for ~6 ms in the middle of the stream); extractions re-scale and empty it
-  // (khr_reset_map).  It only grows when an object needs more blocks than it holds.
+  // (khr_begin_object_map).  It only grows when an object needs more blocks than it holds.
   if (aw_device_config.max_frame_pixels > 0) {
     khr_config oc = objectMapConfig(0.05f);
     // large enough for almost every object at the default resolution (2 % of the largest extent: 50 voxels = 7 blocks per box
@@ -279,15 +279,9 @@ std::shared_ptr<KhronosObjectAttributes> MeshObjectExtractor::extractStaticObjec
   khr_config oc = objectMapConfig(ovs);
   int32_t mn[3], mx[3];
   objectBlockRange(extent, oc.voxel_size * 8.f, mn, mx);
-  std::vector<int32_t> idx;
-  for (int x = mn[0]; x <= mx[0]; ++x)
-    for (int y = mn[1]; y <= mx[1]; ++y)
-      for (int z = mn[2]; z <= mx[2]; ++z) {
-        idx.push_back(x);
-        idx.push_back(y);
-        idx.push_back(z);
-      }
-  const size_t n_blocks = idx.size() / 3;
+  size_t n_blocks = 1;  // (the dense box [mn, mx] of blocks, mesh_object_extractor.cpp:218-228)
+  for (int d = 0; d < 3; ++d) n_blocks *= static_cast<size_t>(std::max(0, mx[d] - mn[d] + 1));
+  if (n_blocks == 0) return nullptr;
   if (n_blocks > config.max_object_blocks) return nullptr;
   khr_host_trace("x_begin");
   if (!object_ctx_ || n_blocks + 1 > object_ctx_blocks_) {
@@ -297,19 +291,19 @@ std::shared_ptr<KhronosObjectAttributes> MeshObjectExtractor::extractStaticObjec
     oc.max_mesh_vertices = std::max<uint64_t>(1u << 16, static_cast<uint64_t>(oc.max_blocks) * 512ull * 15ull / 4);
     chk(khr_create(&oc, &object_ctx_), "khr_create(object map)");
     object_ctx_blocks_ = oc.max_blocks;
-  } else {
-    chk(khr_reset_map(object_ctx_, oc.voxel_size, oc.truncation_distance), "khr_reset_map(object map)");
   }
   khr_ctx* octx = object_ctx_;
   khr_host_trace("x_ctx_ready");
-  // the buffered frames were written on the active window's stream: one device-side dependency instead of a host wait per
-  // re-integrated frame (the extraction may run on a worker thread while the window keeps queueing frames)
-  chk(khr_depend_on(octx, frames.front().first->input.ctx), "khr_depend_on");
-  khr_host_trace("x_depends");
   std::shared_ptr<KhronosObjectAttributes> object;
   try {
-    chk(khr_allocate_blocks(octx, idx.data(), static_cast<int64_t>(n_blocks)), "khr_allocate_blocks");  // :218-228
+    // empty map at the object's voxel size with the box allocated (:218-228): the reset and one launch
+    chk(khr_begin_object_map(octx, oc.voxel_size, oc.truncation_distance, mn, mx), "khr_begin_object_map");
     khr_host_trace("x_allocated");
+    // the buffered frames were written on the active window's stream: one device-side dependency instead of a host wait per
+    // re-integrated frame (the extraction may run on a worker thread while the window keeps queueing frames).  Declared behind
+    // the reset, which ends an earlier declaration; the map's set-up does not read the frames and runs ahead of the wait
+    chk(khr_depend_on(octx, frames.front().first->input.ctx), "khr_depend_on");
+    khr_host_trace("x_depends");
     // projective re-integration of every buffered frame with the binary object label (:239-243): one call, the block
     // list and the per-call bookkeeping are set up once for all frames
     {
@@ -318,15 +312,18 @@ std::shared_ptr<KhronosObjectAttributes> MeshObjectExtractor::extractStaticObjec
         slots.push_back(fr.first->input.slot);
         ids.push_back(fr.second);
       }
-      chk(khr_integrate_shared_batch(octx, frames.front().first->input.ctx, slots.data(), ids.data(), static_cast<int>(slots.size()),
-                                     /*allocate=*/0, /*use_mask=*/0),
-          "khr_integrate_shared_batch");
+      // ... and low-confidence voxels erased (:246-264) in the update's last launch (no count requested: the call stays asynchronous)
+      if (!config.visualize_classification)
+        chk(khr_integrate_prune_batch(octx, frames.front().first->input.ctx, slots.data(), ids.data(), static_cast<int>(slots.size()),
+                                      /*use_mask=*/0, config.min_object_reconstruction_confidence,
+                                      config.min_object_reconstruction_observations, nullptr),
+            "khr_integrate_prune_batch");
+      else
+        chk(khr_integrate_shared_batch(octx, frames.front().first->input.ctx, slots.data(), ids.data(), static_cast<int>(slots.size()),
+                                       /*allocate=*/0, /*use_mask=*/0),
+            "khr_integrate_shared_batch");
     }
     khr_host_trace("x_integrated");
-    // erase low-confidence voxels (:246-264)
-    if (!config.visualize_classification)  // (no count requested: the call stays asynchronous)
-      chk(khr_object_prune(octx, config.min_object_reconstruction_confidence, config.min_object_reconstruction_observations, nullptr),
-          "khr_object_prune");
     chk(khr_generate_mesh(octx, 1, 0), "khr_generate_mesh");  // :267
     khr_host_trace("x_mesh_queued");
     object = std::make_shared<KhronosObjectAttributes>();
