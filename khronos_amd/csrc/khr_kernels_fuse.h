@@ -303,6 +303,11 @@ constexpr int kRowPasses = 8;  // part-B passes whose row vectors are in flight 
 __host__ __device__ inline bool fuseBandRowsOk(int KS, int sem_mode, int do_sem, int has_color) {
   return do_sem && has_color && sem_mode != 1 && (KS & 31) == 0 && KS <= 256;
 }
+// ... and so do padded rows of 96, 160, 192 or 224 floats, by the host's choice of band_mode (fillFuseMap): the KS / 4 lanes of a
+// record have to divide the wave -- a pass otherwise also holds a part of the next record, whose row it writes before the next
+// round of passes loads it, so that the increments are added twice -- and have to lie inside one 16-lane DPP row or cover whole
+// rows for the arg-max.  (On the host: the kernels' band dispatch stays as it is, k_fuse is sensitive to every value alive there.)
+inline bool fuseBandRowLanesOk(int KS) { return KS >= 32 && KS <= 256 && (KS & (KS - 1)) == 0; }
 // lane i <- lane i + OFF of the same 16-lane row (DPP row_shl; out-of-row sources read 0 and are never used)
 template <int OFF>
 __device__ __forceinline__ uint32_t rowDown(uint32_t v) {
@@ -319,7 +324,7 @@ __device__ __forceinline__ void fuseBandRows(FuseArgsK ka, FuseFrameK kf, size_t
   const FuseFrame __attribute__((address_space(4)))& f = *kf;
   const int K = a.K;
   const uint32_t row_bytes = static_cast<uint32_t>(a.KS) * 4u;
-  const uint32_t lpr = static_cast<uint32_t>(a.KS) >> 2;  // lanes per record in part B (8, 16, 32 or 64)
+  const uint32_t lpr = static_cast<uint32_t>(a.KS) >> 2;  // lanes per record in part B (8, 16, 32 or 64: fuseBandRowLanesOk)
   const uint32_t rpp = 64u / lpr;                          // records per part-B pass
   const uint32_t rl0 = static_cast<uint32_t>(lane) / lpr, j = static_cast<uint32_t>(lane) - rl0 * lpr;
   const uint32_t j16 = j * 16u;

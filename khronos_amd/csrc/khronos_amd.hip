@@ -1615,6 +1615,7 @@ static void fillFuseMap(khr_ctx* c, FuseArgs* a) {
   // spilling vector registers inside the item loop (scratch traffic is vector memory: every wait became vmcnt(0), 72 -> 95 us;
   // tests/test_cpu_host.py::test_update_kernel_keeps_its_registers guards the build against that)
   a->band_mode = c->cfg.max_frame_pixels <= 640u * 480u ? 0 : 1;
+  if (!fuseBandRowLanesOk(c->p.KS)) a->band_mode = 0;  // (rows whose lanes do not divide a wave: khr_kernels_fuse.h)
   a->sink = c->d_fuse_sink;
   a->blend_pre = c->cfg.color_blend_weight != 0;
 }

@@ -148,8 +148,9 @@ def band_rows_ok(cfg, frame_has_label=True, frame_has_color=True):
 
 
 def band_mode(cfg):
-    """khronos_amd.hip: fillFuseMap -- rows (1) above 640 x 480 pixels of frame capacity, records (0) up to it"""
-    return 0 if cfg.max_frame_pixels <= 640 * 480 else 1
+    """khronos_amd.hip: fillFuseMap -- rows (1) above 640 x 480 pixels of frame capacity where the lanes of a row divide a wave
+    (fuseBandRowLanesOk), records (0) otherwise"""
+    return 0 if cfg.max_frame_pixels <= 640 * 480 or padded_row(cfg) not in (32, 64, 128, 256) else 1
 
 
 # ------------------------------------------------------------------------------------------------------------------------- cases
