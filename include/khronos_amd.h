@@ -1004,6 +1004,65 @@ int khr_segment_map_into(khr_ctx* ctx, int on_device, int32_t* comp_label, uint6
                          int32_t* comp_bbox_max, int64_t* comp_sum, int32_t* comp_representative, uint64_t* comp_last_observed,
                          uint64_t* comp_first, int32_t* voxels, uint32_t* voxel_component);
 
+/* ---- nearest obstacle cell and generalized Voronoi cells of a map box (ASSUMPTIONS.md A.20) ------------------------------
+ * khr_voronoi_field is the second half of the stage khr_distance_field stands for (freespace_places.gvd of the reference's
+ * mapper configuration): besides the distance it tells WHERE the nearest obstacle is, and which free cells lie between
+ * obstacles that are apart (the generalized Voronoi diagram the places graph is extracted from).  No reference counterpart in
+ * its tree.  Box, cells, ratio, the cell classes, the obstacle set O (unknown_is_obstacle) and R = floor(max_distance /
+ * cell_size) are khr_distance_field's; only the outer transform exists: distance, d2 and status are those of khr_distance_field
+ * with positive_only != 0, bit for bit, and ONLY THE CELLS OF THE BOX TAKE PART here too.
+ * site: a cell c outside O with d2(c) <= R^2 has a site, the cell of O in the box at that squared distance that is least in
+ * (z, y, x) order, given as its linear index x + nx * (y + ny * z) in the box; every other cell has site = -1.
+ * Two sites p, q are SEPARATED as seen from c: never if p == q; KHR_VOR_L1: |p - q|_1 >= parent_l1_separation; KHR_VOR_ANGLE:
+ * with a = p - c, b = q - c, (double)(a.b) <= (double)parent_cos_angle_separation * sqrt((double)(a.a) * (double)(b.b));
+ * KHR_VOR_L1_THEN_ANGLE: the L1 test, else the angle test.
+ * basis: a cell is eligible iff it has a site and its float distance >= min_distance.  Its basis B starts as its own site; the
+ * 26 neighbours are visited dz outer, dy middle, dx inner (each -1 .. 1); a neighbour inside the box with a site q (eligible or
+ * not) appends q iff |B| < KHR_VOR_MAX_BASIS and q is separated from every entry of B.  basis = |B| (1 .. 4), 0 for a cell that
+ * is not eligible; a Voronoi cell has basis >= 2.  At exact ties the diagram is two cells thick or shifted by the tie-break.
+ * The list holds the cells with basis >= min_basis (0 means 2) in ascending linear index: the global cell index (origin +
+ * local), the distance, the basis and the entries of B as global cell indices (unused entries zero).
+ *
+ * khr_voronoi_field works in stream order on ctx's stream with one host wait, for the counters that fill `stats` (may be NULL)
+ * and size the list.  The result lives in buffers ctx owns: it stays valid across later frames until the next khr_voronoi_field,
+ * khr_reset_map, khr_checkpoint_load or khr_destroy.  The map is only read; the frame ring, the mesh layer, the detectors, the
+ * cumulative khr_stats counters and the results of khr_diff_map / khr_segment_map / khr_weld_mesh are not touched (the seeds use
+ * khr_distance_field's work grid, which holds nothing between calls).
+ * KHR_EINVAL (nothing done, an earlier result stays): a NULL ctx or request, everything khr_distance_field rejects for the box,
+ * ratio, min_weight, surface_distance and max_distance, a negative or non-finite min_distance, an unknown mode,
+ * parent_l1_separation < 1 with a mode that uses it, parent_cos_angle_separation non-finite or outside [-1, 1] with a mode that
+ * uses it, a min_basis other than 0, 2, 3, 4.  KHR_ESTATE (likewise): world_size > 1.  Every other failure discards an earlier
+ * result; KHR_ENOMEM leaves the needed bytes in khr_last_error.  A box with an empty O is KHR_OK: no sites, an empty list.
+ *
+ * khr_voronoi_field_into copies the result of the last successful call (KHR_ESTATE without one); any pointer may be NULL; it may
+ * be called several times.  on_device == 0: host arrays, filled when the call returns (through page-locked staging created at the
+ * first such call).  on_device != 0: device arrays, copied device-to-device in stream order, nothing is awaited.  The dense
+ * arrays hold one entry per cell of the box in the order x + nx * (y + ny * z); cells 3 int32, cell_distance and cell_basis one
+ * entry and cell_sites 3 * KHR_VOR_MAX_BASIS int32 per listed cell (n_listed of them). */
+#define KHR_VOR_L1 0
+#define KHR_VOR_ANGLE 1
+#define KHR_VOR_L1_THEN_ANGLE 2
+#define KHR_VOR_MAX_BASIS 4
+typedef struct khr_voronoi_request {
+  int32_t origin[3], dims[3];   /* cells */
+  int32_t ratio;                /* 1, 2, 4 */
+  float min_weight, max_distance, surface_distance;
+  int32_t unknown_is_obstacle;  /* the five above as in khr_df_request */
+  float min_distance;           /* metres */
+  int32_t mode;                 /* KHR_VOR_* */
+  int32_t parent_l1_separation; /* cells */
+  float parent_cos_angle_separation;
+  int32_t min_basis;            /* 0 (= 2), 2, 3, 4 */
+} khr_voronoi_request;
+typedef struct khr_voronoi_stats {
+  uint64_t n_observed, n_obstacle, n_free, n_in_range; /* as khr_df_stats */
+  uint64_t n_eligible, n_basis2, n_basis3, n_basis4;   /* cells with basis exactly 2 / 3 / 4 */
+  uint64_t n_listed;
+} khr_voronoi_stats;
+int khr_voronoi_field(khr_ctx* ctx, const khr_voronoi_request* request, khr_voronoi_stats* stats);
+int khr_voronoi_field_into(khr_ctx* ctx, int on_device, float* distance, int32_t* d2, uint8_t* status, int32_t* site, uint8_t* basis,
+                           int32_t* cells, float* cell_distance, uint8_t* cell_basis, int32_t* cell_sites);
+
 /* ---- tick path: the camera frames of ONE tick batched (sharded multi-camera runs) ------------------------------------
  * In a hash-range sharded run every rank sees every camera frame, so the per-camera work of a
  * rank is what does not shrink with the rank count.  These two calls are khr_upload_frame / khr_integrate for n_frames

@@ -111,6 +111,21 @@ KHR_DF_OBSERVED, KHR_DF_OBSTACLE, KHR_DF_IN_RANGE = 1, 2, 4
 KHR_DF_MAX_DIM, KHR_DF_FAR = 512, 1 << 30
 
 
+class KhrVoronoiRequest(C.Structure):
+    _fields_ = [("origin", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("ratio", C.c_int32), ("min_weight", C.c_float),
+                ("max_distance", C.c_float), ("surface_distance", C.c_float), ("unknown_is_obstacle", C.c_int32),
+                ("min_distance", C.c_float), ("mode", C.c_int32), ("parent_l1_separation", C.c_int32),
+                ("parent_cos_angle_separation", C.c_float), ("min_basis", C.c_int32)]
+
+
+class KhrVoronoiStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_observed", "n_obstacle", "n_free", "n_in_range", "n_eligible", "n_basis2", "n_basis3",
+                                          "n_basis4", "n_listed")]
+
+
+KHR_VOR_L1, KHR_VOR_ANGLE, KHR_VOR_L1_THEN_ANGLE, KHR_VOR_MAX_BASIS = 0, 1, 2, 4
+
+
 class KhrAlignRequest(C.Structure):
     _fields_ = [("n", C.c_int64), ("points", C.c_void_p), ("depth", C.c_void_p), ("sensor", KhrSensor), ("stride", C.c_int32),
                 ("weights", C.c_void_p), ("world_T_source", C.c_double * 16), ("min_weight", C.c_float), ("gate", C.c_float),
@@ -197,7 +212,7 @@ EXPORTS = [
     "khr_checkpoint_size", "khr_checkpoint_save", "khr_checkpoint_load", "khr_checkpoint_inspect",
     "khr_debug_live_resources", "khr_configure_object_voxel_sets",
     "khr_weld_mesh", "khr_weld_mesh_into", "khr_merge_map", "khr_diff_map", "khr_diff_map_into",
-    "khr_segment_map", "khr_segment_map_into",
+    "khr_segment_map", "khr_segment_map_into", "khr_voronoi_field", "khr_voronoi_field_into",
 ]
 
 _lib = None
@@ -333,6 +348,8 @@ def load_library():
     lib.khr_diff_map_into.argtypes = [vp, i32] + [vp] * 11
     lib.khr_segment_map.argtypes = [vp, C.POINTER(KhrSegmentRequest), C.POINTER(KhrSegmentStats)]
     lib.khr_segment_map_into.argtypes = [vp, i32] + [vp] * 10
+    lib.khr_voronoi_field.argtypes = [vp, C.POINTER(KhrVoronoiRequest), C.POINTER(KhrVoronoiStats)]
+    lib.khr_voronoi_field_into.argtypes = [vp, i32] + [vp] * 9
     lib.khr_debug_read.argtypes = [vp, vp, i64]
     lib.khr_debug_live_resources.argtypes = [C.POINTER(i64)]
     lib.khr_tick_ingest.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
@@ -1436,6 +1453,57 @@ class FusionContext:
         out = {k: np.zeros((n[w],) + sh, dt) for k, dt, sh, w in self.SEGMENT_FIELDS if w == "c" or rq.want_voxels}
         self._chk(self.segment_map_into(out))
         out["centroid"] = (out["sum"].astype(np.float64) / np.maximum(out["n_voxels"], 1).astype(np.float64)[:, None] + 0.5) * float(self.cfg.voxel_size)
+        out["stats"] = stats
+        return out
+
+    # name, dtype, trailing shape, "d" = one entry per cell of the box / "l" = one per listed cell
+    VOR_FIELDS = (("distance", np.float32, (), "d"), ("d2", np.int32, (), "d"), ("status", np.uint8, (), "d"), ("site", np.int32, (), "d"),
+                  ("basis", np.uint8, (), "d"), ("cells", np.int32, (3,), "l"), ("cell_distance", np.float32, (), "l"),
+                  ("cell_basis", np.uint8, (), "l"), ("cell_sites", np.int32, (KHR_VOR_MAX_BASIS, 3), "l"))
+
+    @staticmethod
+    def voronoi_request(origin, dims, ratio=1, max_distance=1.0, min_weight=0.0, surface_distance=0.0, unknown_is_obstacle=False,
+                        min_distance=0.0, mode=KHR_VOR_L1_THEN_ANGLE, parent_l1_separation=20, parent_cos_angle_separation=0.2, min_basis=2):
+        """a khr_voronoi_request: `origin` (first cell) and `dims` (cells per axis) as x, y, z"""
+        rq = KhrVoronoiRequest()
+        for a in range(3):
+            rq.origin[a], rq.dims[a] = int(origin[a]), int(dims[a])
+        rq.ratio = int(ratio)
+        rq.min_weight, rq.max_distance, rq.surface_distance = float(min_weight), float(max_distance), float(surface_distance)
+        rq.unknown_is_obstacle = int(bool(unknown_is_obstacle))
+        rq.min_distance, rq.mode, rq.parent_l1_separation = float(min_distance), int(mode), int(parent_l1_separation)
+        rq.parent_cos_angle_separation, rq.min_basis = float(parent_cos_angle_separation), int(min_basis)
+        return rq
+
+    def voronoi_field_rc(self, request):
+        """khr_voronoi_field without raising: (return code, statistics dict)"""
+        st = KhrVoronoiStats()
+        rc = self.lib.khr_voronoi_field(self.h, C.byref(request) if request is not None else None, C.byref(st))
+        return rc, {k: int(getattr(st, k)) for k, _ in KhrVoronoiStats._fields_}
+
+    def voronoi_field_into(self, out, on_device=False):
+        """khr_voronoi_field_into: the result of the last Voronoi field into caller buffers (`out`: VOR_FIELDS name -> contiguous
+        array, or an integer device pointer with on_device; absent / None = not copied).  Returns the return code without raising."""
+        ptrs = []
+        for name, _, _, _ in self.VOR_FIELDS:
+            a = out.get(name)
+            ptrs.append(None if a is None else (C.c_void_p(int(a)) if on_device else _ptr(a)))
+        return self.lib.khr_voronoi_field_into(self.h, int(on_device), *ptrs)
+
+    def voronoi_field(self, origin, dims, ratio=1, max_distance=1.0, request=None, **kw):
+        """The nearest obstacle cell and the generalized Voronoi cells of a box of the live map (khr_voronoi_field, ASSUMPTIONS.md
+        A.20); the map is not written.  Keywords as voronoi_request.  Returns a dict: distance float32, d2 int32, status uint8 (those
+        of distance_field(positive_only=True)), site int32 (the linear index x + nx * (y + ny * z) of the nearest obstacle cell, -1
+        without one) and basis uint8, shaped (nz, ny, nx); the list of the cells with basis >= min_basis in ascending linear index:
+        cells (m, 3) int32 global cell indices, cell_distance float32, cell_basis uint8, cell_sites (m, 4, 3) int32 (unused entries
+        zero); cell_size; and stats."""
+        rq = request if request is not None else self.voronoi_request(origin, dims, ratio, max_distance, **kw)
+        rc, stats = self.voronoi_field_rc(rq)
+        self._chk(rc)
+        shape = {"d": (int(rq.dims[2]), int(rq.dims[1]), int(rq.dims[0])), "l": (stats["n_listed"],)}
+        out = {k: np.zeros(shape[w] + sh, dt) for k, dt, sh, w in self.VOR_FIELDS}
+        self._chk(self.voronoi_field_into(out))
+        out["cell_size"] = float(np.float32(self.cfg.voxel_size) * np.float32(int(rq.ratio)))
         out["stats"] = stats
         return out
 

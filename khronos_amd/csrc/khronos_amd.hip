@@ -44,6 +44,7 @@
 #include "khr_kernels_merge.h"
 #include "khr_kernels_diff.h"
 #include "khr_kernels_segment.h"
+#include "khr_kernels_voronoi.h"
 
 using namespace khr;
 
@@ -457,6 +458,17 @@ struct khr_ctx {
   khr_segment_stats seg_stats{};
   bool seg_valid = false;   // a segmentation succeeded and nothing has discarded its result
   bool seg_listed = false;  // ... and it holds the voxel list
+  // Voronoi fields (khr_voronoi_field; the seeds use d_df_outer above): the key grid, the dense outputs with the per-workgroup
+  // list counts behind them, the scan's temporary storage, the list, the counters with their page-locked mirror, and the
+  // page-locked staging of khr_voronoi_field_into's host form; each grown to the largest call
+  DevBuf<uint64_t> d_vor_keys;
+  DevBuf<uint8_t> d_vor_dense, d_vor_cub, d_vor_list;
+  DevBuf<unsigned long long> d_vor_ctr;
+  PinnedBuf<unsigned long long> h_vor;
+  PinnedBuf<uint8_t> h_vor_stage;
+  khr_voronoi_stats vor_stats{};
+  size_t vor_cells = 0;     // cells of the box the result describes
+  bool vor_valid = false;   // a Voronoi field succeeded and nothing has discarded its result
   // timing
   uint32_t timing = 0;  // bit i = timer i enabled
   std::vector<TimingRec> pending;
@@ -872,6 +884,7 @@ static int resetMap(khr_ctx* c, float voxel_size, float truncation_distance) {
   c->weld_valid = false;
   c->diff_valid = false;
   c->seg_valid = false;
+  c->vor_valid = false;
   c->host_index_valid = false, ++c->map_gen;
   c->explicit_blocks = 0;
   c->box_listed = false;
@@ -4755,29 +4768,64 @@ int khr_query_points(khr_ctx* c, int64_t n, const float* points, float min_weigh
 
 // ---- the exact Euclidean distance field of a box of the live map (khr_distance_field; ASSUMPTIONS.md A.15, device side:
 // khr_kernels_distance.h) -----------------------------------------------------------------------------------------------------
-int khr_distance_field(khr_ctx* c, const khr_df_request* rq, int on_device, float* distance, int32_t* d2, uint8_t* status, khr_df_stats* stats) {
-  if (!c || !rq) return fail(KHR_EINVAL, "null argument");
-  const int ratio = rq->ratio, vps = c->cfg.voxels_per_side;
+namespace {
+
+// what khr_distance_field and khr_voronoi_field share: the checks of A.15's box and cell classes (KHR_EINVAL; `cells` and the
+// range R in cells on success), and the launch of k_df_gather over the blocks the box overlaps (g.box is filled here)
+int dfCheckBox(khr_ctx* c, const int32_t origin[3], const int32_t dims[3], int ratio, float min_weight, float max_distance, float surface_distance,
+               size_t* n_cells, int* range) {
+  const int vps = c->cfg.voxels_per_side;
   if (ratio != 1 && ratio != 2 && ratio != 4) return fail(KHR_EINVAL, "ratio %d: 1, 2 or 4", ratio);
   if (vps % ratio != 0) return fail(KHR_EINVAL, "ratio %d does not divide voxels_per_side %d", ratio, vps);
   uint64_t cells = 1;
   for (int a = 0; a < 3; ++a) {
-    if (rq->dims[a] < 1 || rq->dims[a] > KHR_DF_MAX_DIM) return fail(KHR_EINVAL, "dims[%d] = %d: 1 .. %d", a, rq->dims[a], KHR_DF_MAX_DIM);
-    cells *= static_cast<uint64_t>(rq->dims[a]);
-    const int64_t lo = static_cast<int64_t>(rq->origin[a]) * ratio, hi = (static_cast<int64_t>(rq->origin[a]) + rq->dims[a]) * ratio - 1;
+    if (dims[a] < 1 || dims[a] > KHR_DF_MAX_DIM) return fail(KHR_EINVAL, "dims[%d] = %d: 1 .. %d", a, dims[a], KHR_DF_MAX_DIM);
+    cells *= static_cast<uint64_t>(dims[a]);
+    const int64_t lo = static_cast<int64_t>(origin[a]) * ratio, hi = (static_cast<int64_t>(origin[a]) + dims[a]) * ratio - 1;
     if (lo <= -(int64_t(1) << 30) || hi >= (int64_t(1) << 30)) return fail(KHR_EINVAL, "the box leaves the voxel index range on axis %d", a);
   }
   if (cells > (uint64_t(1) << 24)) return fail(KHR_EINVAL, "%llu cells: at most 2^24", static_cast<unsigned long long>(cells));
-  if (!std::isfinite(rq->surface_distance)) return fail(KHR_EINVAL, "surface_distance is not finite");
-  if (!(rq->min_weight >= 0.f) || !std::isfinite(rq->min_weight)) return fail(KHR_EINVAL, "bad min_weight %g", static_cast<double>(rq->min_weight));
-  if (!(rq->max_distance > 0.f) || !std::isfinite(rq->max_distance)) return fail(KHR_EINVAL, "bad max_distance %g", static_cast<double>(rq->max_distance));
+  if (!std::isfinite(surface_distance)) return fail(KHR_EINVAL, "surface_distance is not finite");
+  if (!(min_weight >= 0.f) || !std::isfinite(min_weight)) return fail(KHR_EINVAL, "bad min_weight %g", static_cast<double>(min_weight));
+  if (!(max_distance > 0.f) || !std::isfinite(max_distance)) return fail(KHR_EINVAL, "bad max_distance %g", static_cast<double>(max_distance));
+  const float reach = max_distance / (c->p.vs * static_cast<float>(ratio));
+  if (!(reach < 32768.f)) return fail(KHR_EINVAL, "max_distance %g m is %g cells: fewer than 32768", static_cast<double>(max_distance), static_cast<double>(reach));
+  *n_cells = static_cast<size_t>(cells);
+  *range = static_cast<int>(std::floor(reach));
+  return KHR_OK;
+}
+
+int dfLaunchGather(khr_ctx* c, const int32_t origin[3], const int32_t dims[3], int ratio, DfGather& g) {
+  auto floorDiv = [](int64_t a, int64_t b) { return static_cast<int>(a >= 0 ? a / b : -((-a + b - 1) / b)); };
+  const int nx = dims[0], ny = dims[1], nz = dims[2];
+  g.box.ox = origin[0], g.box.oy = origin[1], g.box.oz = origin[2];
+  g.box.nx = nx, g.box.ny = ny, g.box.nz = nz;
+  const int cps = c->cfg.voxels_per_side / ratio;  // cells per block side
+  g.box.bx0 = floorDiv(origin[0], cps), g.box.by0 = floorDiv(origin[1], cps), g.box.bz0 = floorDiv(origin[2], cps);
+  const dim3 blocks(static_cast<unsigned>(floorDiv(static_cast<int64_t>(origin[0]) + nx - 1, cps) - g.box.bx0 + 1),
+                    static_cast<unsigned>(floorDiv(static_cast<int64_t>(origin[1]) + ny - 1, cps) - g.box.by0 + 1),
+                    static_cast<unsigned>(floorDiv(static_cast<int64_t>(origin[2]) + nz - 1, cps) - g.box.bz0 + 1));
+  return dispatchVps(c, [&](auto vps_c) {
+    constexpr int VPS = decltype(vps_c)::value;
+    if (ratio == 1) hipLaunchKernelGGL((k_df_gather<VPS, 1>), blocks, dim3(256), 0, c->stream, c->m, g);
+    else if (ratio == 2) hipLaunchKernelGGL((k_df_gather<VPS, 2>), blocks, dim3(256), 0, c->stream, c->m, g);
+    else hipLaunchKernelGGL((k_df_gather<VPS, 4>), blocks, dim3(256), 0, c->stream, c->m, g);
+    HIP_TRY(hipGetLastError());
+    return KHR_OK;
+  });
+}
+
+}  // namespace
+
+int khr_distance_field(khr_ctx* c, const khr_df_request* rq, int on_device, float* distance, int32_t* d2, uint8_t* status, khr_df_stats* stats) {
+  if (!c || !rq) return fail(KHR_EINVAL, "null argument");
+  const int ratio = rq->ratio;
+  size_t n = 0;
+  int R = 0;
+  KHR_TRY(dfCheckBox(c, rq->origin, rq->dims, ratio, rq->min_weight, rq->max_distance, rq->surface_distance, &n, &R));
   const float cell_size = c->p.vs * static_cast<float>(ratio);
-  const float reach = rq->max_distance / cell_size;
-  if (!(reach < 32768.f)) return fail(KHR_EINVAL, "max_distance %g m is %g cells: fewer than 32768", static_cast<double>(rq->max_distance), static_cast<double>(reach));
   if (c->cfg.world_size > 1) return fail(KHR_ESTATE, "khr_distance_field needs the whole map: world_size is %d", c->cfg.world_size);
   HIP_TRY(hipSetDevice(c->device));
-  const int R = static_cast<int>(std::floor(reach));
-  const size_t n = static_cast<size_t>(cells);
   const bool with_inner = rq->positive_only == 0;
   // the work grids grow on demand; what may still read the old ones is waited for first
   if (c->d_df_outer.count() < n || (with_inner && c->d_df_inner.count() < n)) {
@@ -4803,15 +4851,7 @@ int khr_distance_field(khr_ctx* c, const khr_df_request* rq, int on_device, floa
     HIP_TRY(hipMemsetAsync(c->d_df_stats, 0, sizeof(unsigned long long) * DFS_COUNT, c->stream));
   }
   const int nx = rq->dims[0], ny = rq->dims[1], nz = rq->dims[2];
-  auto floorDiv = [](int64_t a, int64_t b) { return static_cast<int>(a >= 0 ? a / b : -((-a + b - 1) / b)); };
   DfGather g{};
-  g.box.ox = rq->origin[0], g.box.oy = rq->origin[1], g.box.oz = rq->origin[2];
-  g.box.nx = nx, g.box.ny = ny, g.box.nz = nz;
-  const int cps = vps / ratio;  // cells per block side
-  g.box.bx0 = floorDiv(rq->origin[0], cps), g.box.by0 = floorDiv(rq->origin[1], cps), g.box.bz0 = floorDiv(rq->origin[2], cps);
-  const dim3 blocks(static_cast<unsigned>(floorDiv(static_cast<int64_t>(rq->origin[0]) + nx - 1, cps) - g.box.bx0 + 1),
-                    static_cast<unsigned>(floorDiv(static_cast<int64_t>(rq->origin[1]) + ny - 1, cps) - g.box.by0 + 1),
-                    static_cast<unsigned>(floorDiv(static_cast<int64_t>(rq->origin[2]) + nz - 1, cps) - g.box.bz0 + 1));
   g.min_weight = rq->min_weight == 0.f ? c->cfg.mesh_min_weight : rq->min_weight;
   g.surface_distance = rq->surface_distance;
   g.unknown_is_obstacle = rq->unknown_is_obstacle;
@@ -4819,15 +4859,7 @@ int khr_distance_field(khr_ctx* c, const khr_df_request* rq, int on_device, floa
   g.inner = with_inner ? c->d_df_inner.get() : nullptr;
   g.status = static_cast<uint8_t*>(dev[2]);
   g.stats = stats ? c->d_df_stats.get() : nullptr;
-  int rc = dispatchVps(c, [&](auto vps_c) {
-    constexpr int VPS = decltype(vps_c)::value;
-    if (ratio == 1) hipLaunchKernelGGL((k_df_gather<VPS, 1>), blocks, dim3(256), 0, c->stream, c->m, g);
-    else if (ratio == 2) hipLaunchKernelGGL((k_df_gather<VPS, 2>), blocks, dim3(256), 0, c->stream, c->m, g);
-    else hipLaunchKernelGGL((k_df_gather<VPS, 4>), blocks, dim3(256), 0, c->stream, c->m, g);
-    HIP_TRY(hipGetLastError());
-    return KHR_OK;
-  });
-  if (rc) return rc;
+  KHR_TRY(dfLaunchGather(c, rq->origin, rq->dims, ratio, g));
   // three in-place passes per grid; a pass along an axis of one cell (or with R = 0) changes nothing and is left out
   for (int32_t* grid : {g.outer, g.inner}) {
     if (!grid || R < 1) continue;
@@ -4871,6 +4903,180 @@ int khr_distance_field(khr_ctx* c, const khr_df_request* rq, int on_device, floa
     stats->n_free = h_stats[DFS_OBSERVED] - h_stats[DFS_OBSTACLE];
     stats->n_in_range = h_stats[DFS_IN_RANGE];
   }
+  return KHR_OK;
+}
+
+// ---- nearest obstacle cell and generalized Voronoi cells of a box of the live map (khr_voronoi_field; ASSUMPTIONS.md A.20,
+// device side: khr_kernels_voronoi.h) ------------------------------------------------------------------------------------------
+namespace {
+
+inline size_t vorAlign(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
+
+// the dense outputs of n cells one after the other, then the per-workgroup list counts (one word more than workgroups)
+struct VorDense {
+  size_t distance, d2, site, status, basis, wg_count, bytes;
+};
+VorDense vorDense(size_t n) {
+  VorDense L{};
+  size_t o = 0;
+  auto carve = [&](size_t bytes) { const size_t at = o; o += vorAlign(bytes); return at; };
+  L.distance = carve(4 * n), L.d2 = carve(4 * n), L.site = carve(4 * n), L.status = carve(n), L.basis = carve(n);
+  L.wg_count = carve(4 * (static_cast<size_t>(gridFor(n)) + 1));
+  L.bytes = o;
+  return L;
+}
+// the list of m cells
+struct VorList {
+  size_t cells, distance, basis, sites, bytes;
+};
+VorList vorList(size_t m) {
+  VorList L{};
+  size_t o = 0;
+  auto carve = [&](size_t bytes) { const size_t at = o; o += vorAlign(bytes); return at; };
+  L.cells = carve(12 * m), L.distance = carve(4 * m), L.basis = carve(m), L.sites = carve(12 * KHR_VOR_MAX_BASIS * m);
+  L.bytes = std::max<size_t>(o, 256);  // (never empty: the owner exists from the first call on)
+  return L;
+}
+
+}  // namespace
+
+int khr_voronoi_field(khr_ctx* c, const khr_voronoi_request* rq, khr_voronoi_stats* stats) {
+  if (stats) *stats = khr_voronoi_stats{};
+  if (!c || !rq) return fail(KHR_EINVAL, "khr_voronoi_field: null argument");
+  // KHR_EINVAL / KHR_ESTATE: nothing is done, an earlier result stays
+  const int ratio = rq->ratio;
+  size_t n = 0;
+  int R = 0;
+  KHR_TRY(dfCheckBox(c, rq->origin, rq->dims, ratio, rq->min_weight, rq->max_distance, rq->surface_distance, &n, &R));
+  if (!(rq->min_distance >= 0.f) || !std::isfinite(rq->min_distance)) return fail(KHR_EINVAL, "khr_voronoi_field: bad min_distance %g", static_cast<double>(rq->min_distance));
+  if (rq->mode != KHR_VOR_L1 && rq->mode != KHR_VOR_ANGLE && rq->mode != KHR_VOR_L1_THEN_ANGLE)
+    return fail(KHR_EINVAL, "khr_voronoi_field: mode %d: KHR_VOR_L1, KHR_VOR_ANGLE or KHR_VOR_L1_THEN_ANGLE", rq->mode);
+  if (rq->mode != KHR_VOR_ANGLE && rq->parent_l1_separation < 1)
+    return fail(KHR_EINVAL, "khr_voronoi_field: parent_l1_separation is %d, must be >= 1", rq->parent_l1_separation);
+  if (rq->mode != KHR_VOR_L1 && !(rq->parent_cos_angle_separation >= -1.f && rq->parent_cos_angle_separation <= 1.f))
+    return fail(KHR_EINVAL, "khr_voronoi_field: parent_cos_angle_separation is %g, must lie in [-1, 1]", static_cast<double>(rq->parent_cos_angle_separation));
+  if (rq->min_basis != 0 && (rq->min_basis < 2 || rq->min_basis > KHR_VOR_MAX_BASIS))
+    return fail(KHR_EINVAL, "khr_voronoi_field: min_basis is %d: 0, 2, 3 or 4", rq->min_basis);
+  if (c->cfg.world_size > 1) return fail(KHR_ESTATE, "khr_voronoi_field needs the whole map: world_size is %d", c->cfg.world_size);
+  // from here on a failure discards the earlier result
+  c->vor_valid = false;
+  c->vor_stats = khr_voronoi_stats{};
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const int nx = rq->dims[0], ny = rq->dims[1], nz = rq->dims[2];
+  const uint32_t n_wg = static_cast<uint32_t>(gridFor(n));
+  const VorDense D = vorDense(n);
+  size_t cub_bytes = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, static_cast<uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), static_cast<int>(n_wg + 1), st));
+  cub_bytes = std::max<size_t>(cub_bytes, 256);
+  if (c->d_df_outer.count() < n || c->d_vor_keys.count() < n || c->d_vor_dense.count() < D.bytes || c->d_vor_cub.count() < cub_bytes || !c->d_vor_ctr || !c->h_vor) {
+    HIP_TRY(hipStreamSynchronize(st));  // (whatever still reads the old blocks)
+    if (c->d_df_outer.reserve(n) || c->d_vor_keys.reserve(n) || c->d_vor_dense.reserve(D.bytes) || c->d_vor_cub.reserve(cub_bytes) ||
+        c->d_vor_ctr.reserve(VS_COUNT) || c->h_vor.reserve(VS_COUNT))
+      return fail(KHR_ENOMEM, "khr_voronoi_field: work grids and outputs of %zu cells (%zu bytes)", n, 12 * n + D.bytes + cub_bytes);
+  }
+  uint8_t* const db = c->d_vor_dense;
+  HIP_TRY(hipMemsetAsync(c->d_vor_ctr, 0, sizeof(unsigned long long) * VS_COUNT, st));
+  DfGather g{};
+  g.min_weight = rq->min_weight == 0.f ? c->cfg.mesh_min_weight : rq->min_weight;
+  g.surface_distance = rq->surface_distance;
+  g.unknown_is_obstacle = rq->unknown_is_obstacle;
+  g.outer = c->d_df_outer;
+  g.inner = nullptr;
+  g.status = db + D.status;
+  g.stats = c->d_vor_ctr;
+  KHR_TRY(dfLaunchGather(c, rq->origin, rq->dims, ratio, g));
+  // the x pass turns the seeds into keys and always runs; a y / z pass along one cell (or with R = 0) changes nothing
+  uint64_t* const keys = c->d_vor_keys;
+  {
+    const int per_wg = std::max(1, kVorTileCells / nx);
+    const long long lines = static_cast<long long>(ny) * nz;
+    hipLaunchKernelGGL((k_vor_pass<0>), dim3(static_cast<unsigned>((lines + per_wg - 1) / per_wg)), dim3(256), 0, st, static_cast<const int32_t*>(g.outer), keys, nx, ny, nz, R, per_wg);
+  }
+  if (ny > 1 && R >= 1) {
+    const int per_wg = std::max(1, kVorTileCells / (ny * kDfStrip));
+    hipLaunchKernelGGL((k_vor_pass<1>), dim3((nx + kDfStrip - 1) / kDfStrip, (nz + per_wg - 1) / per_wg), dim3(256), 0, st, static_cast<const int32_t*>(nullptr), keys, nx, ny, nz, R, per_wg);
+  }
+  if (nz > 1 && R >= 1) {
+    const int per_wg = std::max(1, kVorTileCells / (nz * kDfStrip));
+    hipLaunchKernelGGL((k_vor_pass<2>), dim3((nx + kDfStrip - 1) / kDfStrip, (ny + per_wg - 1) / per_wg), dim3(256), 0, st, static_cast<const int32_t*>(nullptr), keys, nx, ny, nz, R, per_wg);
+  }
+  HIP_TRY(hipGetLastError());
+  VorField f{};
+  f.ox = rq->origin[0], f.oy = rq->origin[1], f.oz = rq->origin[2];
+  f.nx = nx, f.ny = ny, f.nz = nz;
+  f.keys = keys;
+  f.rule.r2 = R * R;
+  f.rule.cell_size = c->p.vs * static_cast<float>(ratio), f.rule.max_distance = rq->max_distance, f.rule.min_distance = rq->min_distance;
+  f.rule.mode = rq->mode, f.rule.l1_sep = rq->parent_l1_separation, f.rule.cos_sep = rq->parent_cos_angle_separation;
+  f.rule.min_basis = rq->min_basis == 0 ? 2 : rq->min_basis;
+  f.distance = reinterpret_cast<float*>(db + D.distance), f.d2 = reinterpret_cast<int32_t*>(db + D.d2), f.status = db + D.status;
+  f.site = reinterpret_cast<int32_t*>(db + D.site), f.basis = db + D.basis;
+  f.wg_count = reinterpret_cast<uint32_t*>(db + D.wg_count);
+  f.stats = c->d_vor_ctr;
+  HIP_TRY(hipMemsetAsync(f.wg_count + n_wg, 0, sizeof(uint32_t), st));
+  hipLaunchKernelGGL(k_vor_classify, dim3(n_wg), dim3(256), 0, st, f);
+  HIP_TRY(hipGetLastError());
+  size_t tb = c->d_vor_cub.count();
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_vor_cub.get(), tb, f.wg_count, f.wg_count, static_cast<int>(n_wg + 1), st));
+  // the one host wait: the counters
+  unsigned long long* const h = c->h_vor;
+  HIP_TRY(hipMemcpyAsync(h, c->d_vor_ctr, sizeof(unsigned long long) * VS_COUNT, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  khr_voronoi_stats s{};
+  s.n_observed = h[DFS_OBSERVED], s.n_obstacle = h[DFS_OBSTACLE], s.n_free = h[DFS_OBSERVED] - h[DFS_OBSTACLE], s.n_in_range = h[DFS_IN_RANGE];
+  s.n_eligible = h[VS_ELIGIBLE], s.n_basis2 = h[VS_BASIS2], s.n_basis3 = h[VS_BASIS3], s.n_basis4 = h[VS_BASIS4], s.n_listed = h[VS_LISTED];
+  if (s.n_listed > n || s.n_basis2 + s.n_basis3 + s.n_basis4 > s.n_eligible || s.n_eligible > s.n_in_range)
+    return fail(KHR_EDEVICE, "khr_voronoi_field: inconsistent counts (%llu listed of %zu cells)", static_cast<unsigned long long>(s.n_listed), n);
+  // the list; nothing is queued on the stream here (the wait above), so a growth frees nothing in use
+  const VorList L = vorList(static_cast<size_t>(s.n_listed));
+  if (c->d_vor_list.reserve(L.bytes)) return fail(KHR_ENOMEM, "khr_voronoi_field: a list of %llu cells (%zu bytes)", static_cast<unsigned long long>(s.n_listed), L.bytes);
+  if (s.n_listed > 0) {
+    uint8_t* const lb = c->d_vor_list;
+    f.n_listed = static_cast<uint32_t>(s.n_listed);
+    f.cells = reinterpret_cast<int32_t*>(lb + L.cells), f.cell_distance = reinterpret_cast<float*>(lb + L.distance), f.cell_basis = lb + L.basis;
+    f.cell_sites = reinterpret_cast<int32_t*>(lb + L.sites);
+    hipLaunchKernelGGL(k_vor_emit, dim3(n_wg), dim3(256), 0, st, f);
+    HIP_TRY(hipGetLastError());
+  }
+  c->vor_stats = s;
+  c->vor_cells = n;
+  c->vor_valid = true;
+  if (stats) *stats = s;
+  return KHR_OK;
+}
+
+int khr_voronoi_field_into(khr_ctx* c, int on_device, float* distance, int32_t* d2, uint8_t* status, int32_t* site, uint8_t* basis, int32_t* cells,
+                           float* cell_distance, uint8_t* cell_basis, int32_t* cell_sites) {
+  if (!c) return fail(KHR_EINVAL, "null ctx");
+  if (!c->vor_valid) return fail(KHR_ESTATE, "no successful khr_voronoi_field before khr_voronoi_field_into");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = c->vor_cells, m = static_cast<size_t>(c->vor_stats.n_listed);
+  const VorDense D = vorDense(n);
+  const VorList L = vorList(m);
+  const uint8_t* const db = c->d_vor_dense;
+  const uint8_t* const lb = c->d_vor_list;
+  void* const dst[9] = {distance, d2, status, site, basis, cells, cell_distance, cell_basis, cell_sites};
+  const void* const src[9] = {db + D.distance, db + D.d2, db + D.status, db + D.site, db + D.basis, lb + L.cells, lb + L.distance, lb + L.basis, lb + L.sites};
+  const size_t bytes[9] = {4 * n, 4 * n, n, 4 * n, n, 12 * m, 4 * m, m, 12 * KHR_VOR_MAX_BASIS * m};
+  if (on_device) {
+    for (int k = 0; k < 9; ++k)
+      if (dst[k] && bytes[k]) HIP_TRY(hipMemcpyAsync(dst[k], src[k], bytes[k], hipMemcpyDeviceToDevice, c->stream));
+    return KHR_OK;
+  }
+  // the host form: through the page-locked staging, one wait
+  size_t off[9], stage_bytes = 0;
+  for (int k = 0; k < 9; ++k) {
+    off[k] = stage_bytes;
+    if (dst[k]) stage_bytes += vorAlign(bytes[k]);
+  }
+  if (stage_bytes == 0) return KHR_OK;
+  if (c->h_vor_stage.reserve(stage_bytes)) return fail(KHR_ENOMEM, "khr_voronoi_field_into: %zu bytes of page-locked staging", stage_bytes);
+  for (int k = 0; k < 9; ++k)
+    if (dst[k] && bytes[k]) HIP_TRY(hipMemcpyAsync(c->h_vor_stage + off[k], src[k], bytes[k], hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int k = 0; k < 9; ++k)
+    if (dst[k] && bytes[k]) std::memcpy(dst[k], c->h_vor_stage + off[k], bytes[k]);
   return KHR_OK;
 }
 
@@ -5394,6 +5600,7 @@ int khr_checkpoint_load(khr_ctx* c, const void* buffer, uint64_t n_bytes, int64_
   c->weld_valid = false;  // (khr_weld_mesh: the welded mesh belongs to the map before the load)
   c->diff_valid = false;  // (khr_diff_map: so does the diff)
   c->seg_valid = false;   // (khr_segment_map: and the segmentation)
+  c->vor_valid = false;   // (khr_voronoi_field: and the Voronoi field)
   khr_checkpoint_header h;
   int rc = khr_checkpoint_inspect(buffer, n_bytes, &h);
   if (rc) return rc;

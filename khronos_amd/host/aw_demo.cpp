@@ -2,7 +2,7 @@
 // thread drives the reference (spinOnce per InputPacket, finishMapping at shutdown), and prints a JSON
 // summary that tests/test_gpu_host.py compares with the step-wise C-ABI path and the oracle.
 // usage: aw_demo <config.yaml> <width> <height> <frames> [object_label]
-//        aw_demo --slices | --render | --query | --distance | --align | --weld | --merge | --diff | --segment | --checkpoint | --bench | --rayver ... (below)
+//        aw_demo --slices | --render | --query | --distance | --voronoi | --align | --weld | --merge | --diff | --segment | --checkpoint | --bench | --rayver ... (below)
 //   object_label >= 0: the stand-in detector / tracker below; otherwise the plugins named in the config
 #include <execinfo.h>
 #include <csignal>
@@ -802,6 +802,165 @@ static int distanceDemo(int argc, char** argv) {
               frames, agree, first_mismatch.c_str(), timed, cells, static_cast<unsigned long long>(last_stats.n_observed),
               static_cast<unsigned long long>(last_stats.n_obstacle), static_cast<unsigned long long>(last_stats.n_free),
               static_cast<unsigned long long>(last_stats.n_in_range), ms_dev / d, ms_copy / d);
+  return agree == frames && frames == N ? 0 : 3;
+}
+
+// ASSUMPTIONS.md A.20 checked on the host from the arrays VolumetricMap::voronoiField returned, and from nothing else: every site is
+// a cell of the obstacle set (by status and unknown_is_obstacle) at the squared distance d2 says; the basis rule applied to the
+// site array gives the basis array; the list is the ascending run of the cells with basis >= min_basis.  Returns what differs first,
+// or nullptr.
+static const char* voronoiCheck(const hydra::VoronoiField& f, const hydra::VoronoiRequest& rq) {
+  const int nx = f.dims[0], ny = f.dims[1], nz = f.dims[2];
+  const size_t n = static_cast<size_t>(nx) * ny * nz;
+  if (f.distance.size() != n || f.d2.size() != n || f.status.size() != n || f.site.size() != n || f.basis.size() != n) return "array sizes";
+  auto separated = [&](const std::array<int32_t, 3>& c, const std::array<int32_t, 3>& p, const std::array<int32_t, 3>& q) {
+    if (p == q) return false;
+    const int l1 = std::abs(p[0] - q[0]) + std::abs(p[1] - q[1]) + std::abs(p[2] - q[2]);
+    if (rq.mode != KHR_VOR_ANGLE && l1 >= rq.parent_l1_separation) return true;
+    if (rq.mode == KHR_VOR_L1) return false;
+    int64_t dot = 0, aa = 0, bb = 0;
+    for (int k = 0; k < 3; ++k) {
+      const int64_t a = p[k] - c[k], b = q[k] - c[k];
+      dot += a * b, aa += a * a, bb += b * b;
+    }
+    return static_cast<double>(dot) <= static_cast<double>(rq.parent_cos_angle_separation) * std::sqrt(static_cast<double>(aa) * static_cast<double>(bb));
+  };
+  const int min_basis = rq.min_basis == 0 ? 2 : rq.min_basis;
+  size_t listed = 0;
+  uint64_t n_eligible = 0, n_basis[KHR_VOR_MAX_BASIS + 1] = {0, 0, 0, 0, 0};
+  for (int z = 0; z < nz; ++z)
+    for (int y = 0; y < ny; ++y)
+      for (int x = 0; x < nx; ++x) {
+        const size_t i = f.index(x, y, z);
+        const int32_t s = f.site[i];
+        const bool in_set = (f.status[i] & KHR_DF_OBSTACLE) != 0 || (rq.unknown_is_obstacle && !(f.status[i] & KHR_DF_OBSERVED));
+        if ((s >= 0) != (!in_set && (f.status[i] & KHR_DF_IN_RANGE) != 0)) return "which cells have a site";
+        int nb = 0;
+        std::array<int32_t, 3> B[KHR_VOR_MAX_BASIS] = {};
+        if (s >= 0) {
+          if (static_cast<size_t>(s) >= n) return "a site outside the box";
+          const uint8_t st = f.status[s];
+          if (!((st & KHR_DF_OBSTACLE) != 0 || (rq.unknown_is_obstacle && !(st & KHR_DF_OBSERVED)))) return "a site outside the obstacle set";
+          const std::array<int32_t, 3> p = f.cellAt(s);
+          const int64_t dx = x - p[0], dy = y - p[1], dz = z - p[2];
+          if (dx * dx + dy * dy + dz * dz != f.d2[i]) return "the distance to the site";
+          if (f.distance[i] >= rq.min_distance) {
+            ++n_eligible;
+            B[nb++] = p;
+            for (int oz = -1; oz <= 1; ++oz)
+              for (int oy = -1; oy <= 1; ++oy)
+                for (int ox = -1; ox <= 1; ++ox) {
+                  const int X = x + ox, Y = y + oy, Z = z + oz;
+                  if ((ox == 0 && oy == 0 && oz == 0) || X < 0 || X >= nx || Y < 0 || Y >= ny || Z < 0 || Z >= nz || nb == KHR_VOR_MAX_BASIS) continue;
+                  const int32_t t = f.site[f.index(X, Y, Z)];
+                  if (t < 0) continue;
+                  const std::array<int32_t, 3> q = f.cellAt(t);
+                  bool apart = true;
+                  for (int j = 0; j < nb && apart; ++j) apart = separated({x, y, z}, B[j], q);
+                  if (apart) B[nb++] = q;
+                }
+          }
+        }
+        if (nb != f.basis[i]) return "basis";
+        ++n_basis[nb];
+        if (nb < min_basis) continue;
+        if (listed >= f.numListed() || f.cells.size() != 3 * f.numListed() || f.cell_sites.size() != 3 * KHR_VOR_MAX_BASIS * f.numListed() ||
+            f.cell_distance.size() != f.numListed())
+          return "the length of the list";
+        if (f.cells[3 * listed] != f.origin[0] + x || f.cells[3 * listed + 1] != f.origin[1] + y || f.cells[3 * listed + 2] != f.origin[2] + z) return "the listed cells";
+        if (f.cell_basis[listed] != nb || std::memcmp(&f.cell_distance[listed], &f.distance[i], sizeof(float)) != 0) return "the listed basis or distance";
+        for (int j = 0; j < KHR_VOR_MAX_BASIS; ++j)
+          for (int k = 0; k < 3; ++k)
+            if (f.cell_sites[(listed * KHR_VOR_MAX_BASIS + j) * 3 + k] != (j < nb ? f.origin[k] + B[j][k] : 0)) return "the listed sites";
+        ++listed;
+      }
+  if (listed != f.numListed() || listed != f.stats.n_listed) return "the length of the list";
+  if (n_eligible != f.stats.n_eligible || n_basis[2] != f.stats.n_basis2 || n_basis[3] != f.stats.n_basis3 || n_basis[4] != f.stats.n_basis4) return "stats";
+  return nullptr;
+}
+
+// aw_demo --voronoi <config.yaml> <width> <height> <frames>: a Khronos sink asks, per output, for the Voronoi field of a box around
+// the sensor -- hydra::DistanceFieldConfig and hydra::VoronoiConfig from the file's freespace_places -- through
+// VolumetricMap::voronoiField (khr_voronoi_field) and checks the returned arrays against A.20 on the host.  One JSON line.
+static int voronoiDemo(int argc, char** argv) {
+  if (argc < 6) {
+    std::fprintf(stderr, "usage: aw_demo --voronoi <config.yaml> <width> <height> <frames>\n");
+    return 2;
+  }
+  std::ifstream in(argv[2]);
+  std::stringstream ss;
+  ss << in.rdbuf();
+  const int W = std::atoi(argv[3]), H = std::atoi(argv[4]), N = std::atoi(argv[5]);
+  constexpr int kWarm = 3;  // frames before the average (the buffers grow on the first call)
+  ActiveWindow::Config cfg = ActiveWindow::Config::fromYamlString(ss.str());
+  cfg.max_frame_pixels = static_cast<uint32_t>(W) * H;
+  const khronos_amd::YamlNode root = khronos_amd::parseYaml(ss.str());
+  const hydra::DistanceFieldConfig dfc = hydra::DistanceFieldConfig::fromYaml(root);
+  const hydra::VoronoiConfig vc = hydra::VoronoiConfig::fromYaml(root);
+  auto out_queue = std::make_shared<ActiveWindow::OutputQueue>();
+  ActiveWindow aw(cfg, out_queue);
+  int frames = 0, agree = 0, timed = 0;
+  double ms_dev = 0;
+  size_t cells = 0;
+  khr_voronoi_stats last_stats{};
+  std::string first_mismatch;
+  using clk = std::chrono::steady_clock;
+  aw.addKhronosSink([&](const FrameData& data, const VolumetricMap& map, const Tracks&) {
+    hydra::VoronoiRequest rq(dfc, vc);
+    const float cell = map.config.voxel_size * static_cast<float>(rq.ratio);
+    // the sensor's cell in the middle of a box that reaches the range plus a margin on x and y, half of that on z
+    const int half = std::min(KHR_DF_MAX_DIM / 2, static_cast<int>(std::floor(rq.max_distance / cell)) + 12);
+    const int hd[3] = {half, half, std::max(1, half / 2)};
+    for (int a = 0; a < 3; ++a) {
+      rq.origin[a] = static_cast<int32_t>(std::floor(data.input.world_T_sensor[4 * a + 3] / static_cast<double>(cell))) - hd[a];
+      rq.dims[a] = 2 * hd[a];
+    }
+    khr_sync(map.ctx());
+    const auto t0 = clk::now();
+    const hydra::VoronoiField f = map.voronoiField(rq);
+    const auto t1 = clk::now();
+    const char* diff = voronoiCheck(f, rq);
+    if (!diff) ++agree;
+    else if (first_mismatch.empty()) first_mismatch = "frame " + std::to_string(frames) + ": " + diff + " differs";
+    last_stats = f.stats;
+    cells = f.size();
+    if (frames >= kWarm) {
+      ms_dev += std::chrono::duration<double, std::milli>(t1 - t0).count();
+      ++timed;
+    }
+    ++frames;
+  });
+  void* scene = synth_create(1234, 12, 1);
+  const size_t n = static_cast<size_t>(W) * H;
+  std::vector<float> depth(n);
+  std::vector<uint8_t> rgb(n * 3);
+  std::vector<int32_t> label(n);
+  for (int i = 0; i < N; ++i) {
+    hydra::InputPacket pkt;
+    pkt.timestamp_ns = static_cast<uint64_t>(std::llround((1.0 + 0.1 * i) * 1e9));
+    circlePose(0.1 * i, pkt.world_T_body);
+    pkt.sensor = {W, H, W / 2.f, W / 2.f, W / 2.f, H / 2.f, 0.1f, 5.f};
+    synth_render(scene, W, H, pkt.sensor.fx, pkt.sensor.fy, pkt.sensor.cx, pkt.sensor.cy, pkt.world_T_body, 0.1 * i, 5.f, 0.f,
+                 1234u + 7919u * i, depth.data(), rgb.data(), label.data(), 0);
+    pkt.depth = depth.data();
+    pkt.color = rgb.data();
+    pkt.labels = label.data();
+    aw.step(pkt);
+    hydra::ActiveWindowOutput::Ptr popped;
+    while (out_queue->pop(&popped)) {}
+  }
+  aw.finishMapping();
+  synth_destroy(scene);
+  const double d = timed ? static_cast<double>(timed) : 1.0;
+  auto u = [](uint64_t v) { return static_cast<unsigned long long>(v); };
+  std::printf("{\"what\": \"the Voronoi field of a box around the sensor (VolumetricMap::voronoiField, checked on the host from its own arrays), %dx%d, "
+              "voxel %.4g m, ratio %d, max_distance %.4g m, mode %d, min_basis %d\", \"frames\": %d, \"agree_frames\": %d, \"first_mismatch\": \"%s\", "
+              "\"timed_frames\": %d, \"cells\": %zu, \"n_listed\": %llu, \"last_stats\": {\"n_observed\": %llu, \"n_obstacle\": %llu, \"n_free\": %llu, "
+              "\"n_in_range\": %llu, \"n_eligible\": %llu, \"n_basis2\": %llu, \"n_basis3\": %llu, \"n_basis4\": %llu, \"n_listed\": %llu}, \"device_ms\": %.4f}\n",
+              W, H, static_cast<double>(cfg.volumetric_map.voxel_size), dfc.ratio, static_cast<double>(dfc.max_distance_m), vc.mode, vc.min_basis, frames, agree,
+              first_mismatch.c_str(), timed, cells, u(last_stats.n_listed), u(last_stats.n_observed), u(last_stats.n_obstacle), u(last_stats.n_free),
+              u(last_stats.n_in_range), u(last_stats.n_eligible), u(last_stats.n_basis2), u(last_stats.n_basis3), u(last_stats.n_basis4), u(last_stats.n_listed),
+              ms_dev / d);
   return agree == frames && frames == N ? 0 : 3;
 }
 
@@ -1837,6 +1996,14 @@ int main(int argc, char** argv) {
   if (argc >= 2 && std::string(argv[1]) == "--distance") {
     try {
       return distanceDemo(argc, argv);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "aw_demo: %s\n", e.what());
+      return 1;
+    }
+  }
+  if (argc >= 2 && std::string(argv[1]) == "--voronoi") {
+    try {
+      return voronoiDemo(argc, argv);
     } catch (const std::exception& e) {
       std::fprintf(stderr, "aw_demo: %s\n", e.what());
       return 1;

@@ -231,6 +231,51 @@ int main(int argc, char** argv) {
                 static_cast<double>(c.min_weight), c.positive_distance_only ? 1 : 0, c.ratio);
     return 0;
   }
+  if (argc > 1 && std::strcmp(argv[1], "--voronoi-config") == 0) {
+    // hydra::VoronoiConfig on the values the reference's jackal mapper file sets under frontend.freespace_places.gvd
+    // (tests/test_cpu_voronoi_replica.py); then every mode string, and the clamp of min_basis at both ends
+    const std::string text =
+        "frontend:\n"
+        "  freespace_places:\n"
+        "    type: gvd\n"
+        "    gvd:\n"
+        "      max_distance_m: 4.5\n"
+        "      min_distance_m: 0.1\n"
+        "      min_weight: 1.0e-6\n"
+        "      positive_distance_only: true\n"
+        "      min_basis_for_extraction: 1\n"
+        "      voronoi_config:\n"
+        "        mode: L1_THEN_ANGLE\n"
+        "        min_distance_m: 0.30\n"
+        "        parent_l1_separation: 20\n"
+        "        parent_cos_angle_separation: 0.2\n"
+        "    tsdf_interpolator:\n"
+        "      type: downsample\n"
+        "      ratio: 2\n";
+    const khronos_amd::YamlNode root = khronos_amd::parseYaml(text);
+    const hydra::VoronoiConfig c = hydra::VoronoiConfig::fromYaml(root);
+    const hydra::VoronoiRequest rq(hydra::DistanceFieldConfig::fromYaml(root), c);
+    if (rq.ratio != 2 || rq.max_distance != 4.5f || rq.min_distance != c.min_distance_m || rq.mode != c.mode || rq.min_basis != c.min_basis ||
+        rq.parent_l1_separation != c.parent_l1_separation || rq.parent_cos_angle_separation != c.parent_cos_angle_separation) {
+      std::fprintf(stderr, "VoronoiRequest does not carry its two configurations\n");
+      return 1;
+    }
+    bool threw = false;
+    try {
+      hydra::VoronoiConfig::modeFromString("L2");
+    } catch (const std::exception&) {
+      threw = true;
+    }
+    if (!threw) {
+      std::fprintf(stderr, "an unknown mode string was accepted\n");
+      return 1;
+    }
+    std::printf("mode=%d min_distance_m=%.9g parent_l1_separation=%d parent_cos_angle_separation=%.9g min_basis_for_extraction=%d min_basis=%d modes=%d,%d,%d clamped=%d,%d\n",
+                c.mode, static_cast<double>(c.min_distance_m), c.parent_l1_separation, static_cast<double>(c.parent_cos_angle_separation), c.min_basis_for_extraction,
+                c.min_basis, hydra::VoronoiConfig::modeFromString("L1"), hydra::VoronoiConfig::modeFromString("ANGLE"),
+                hydra::VoronoiConfig::modeFromString("L1_THEN_ANGLE"), hydra::VoronoiConfig::minBasisFor(-3), hydra::VoronoiConfig::minBasisFor(9));
+    return 0;
+  }
   // ---- YAML ----
   if (argc > 1) {
     std::ifstream in(argv[1]);

@@ -366,6 +366,85 @@ struct DistanceField {
   }
 };
 
+// The Voronoi parameters of the same stage (freespace_places.gvd.voronoi_config and gvd.min_basis_for_extraction of the mapper
+// files): when two neighbouring cells' nearest obstacles count as apart, and how many such obstacles a cell needs to be extracted.
+// min_basis is min_basis_for_extraction + 1 (the cell's own obstacle counts here), clamped to 2 .. KHR_VOR_MAX_BASIS.  fromYaml
+// takes what DistanceFieldConfig::fromYaml takes; an unknown mode string throws.
+struct VoronoiConfig {
+  int mode = KHR_VOR_L1_THEN_ANGLE;
+  float min_distance_m = 0.f;
+  int parent_l1_separation = 20;
+  float parent_cos_angle_separation = 0.2f;
+  int min_basis_for_extraction = 1;
+  int min_basis = 2;
+  static int modeFromString(const std::string& name) {
+    if (name == "L1") return KHR_VOR_L1;
+    if (name == "ANGLE") return KHR_VOR_ANGLE;
+    if (name == "L1_THEN_ANGLE") return KHR_VOR_L1_THEN_ANGLE;
+    throw std::runtime_error("voronoi_config: unknown mode '" + name + "' (L1, ANGLE, L1_THEN_ANGLE)");
+  }
+  static int minBasisFor(int min_basis_for_extraction) { return std::min<int>(KHR_VOR_MAX_BASIS, std::max(2, min_basis_for_extraction + 1)); }
+  static VoronoiConfig fromYaml(const khronos_amd::YamlNode& root) {
+    VoronoiConfig c;
+    const khronos_amd::YamlNode* fp = root.find("freespace_places");
+    if (!fp)
+      if (const khronos_amd::YamlNode* fe = root.find("frontend")) fp = fe->find("freespace_places");
+    const khronos_amd::YamlNode* gvd = fp ? fp->find("gvd") : nullptr;
+    if (!gvd) return c;
+    if (gvd->has("min_basis_for_extraction")) gvd->read("min_basis_for_extraction", c.min_basis_for_extraction);
+    c.min_basis = minBasisFor(c.min_basis_for_extraction);
+    if (const khronos_amd::YamlNode* vc = gvd->find("voronoi_config")) {
+      if (const khronos_amd::YamlNode* m = vc->find("mode")) c.mode = modeFromString(khronos_amd::detail::unquote(khronos_amd::detail::trim(m->scalar)));
+      if (vc->has("min_distance_m")) vc->read("min_distance_m", c.min_distance_m);
+      if (vc->has("parent_l1_separation")) vc->read("parent_l1_separation", c.parent_l1_separation);
+      if (vc->has("parent_cos_angle_separation")) vc->read("parent_cos_angle_separation", c.parent_cos_angle_separation);
+    }
+    return c;
+  }
+};
+
+// What to compute (VolumetricMap::voronoiField): DistanceFieldRequest's box and cell classes (positive_only plays no part: only
+// the outer transform exists) plus the Voronoi parameters.
+struct VoronoiRequest {
+  std::array<int32_t, 3> origin{0, 0, 0}, dims{1, 1, 1};
+  int ratio = 1;
+  float min_weight = 0.f;        // 0 = the mesh's minimum weight
+  float max_distance = 1.f;      // metres
+  float surface_distance = 0.f;
+  bool unknown_is_obstacle = false;
+  float min_distance = 0.f;      // metres: nearer cells are no Voronoi cells
+  int mode = KHR_VOR_L1_THEN_ANGLE;
+  int parent_l1_separation = 20;
+  float parent_cos_angle_separation = 0.2f;
+  int min_basis = 2;
+  VoronoiRequest() = default;
+  VoronoiRequest(const DistanceFieldConfig& d, const VoronoiConfig& v)
+      : ratio(d.ratio), min_weight(d.min_weight), max_distance(d.max_distance_m), min_distance(v.min_distance_m), mode(v.mode),
+        parent_l1_separation(v.parent_l1_separation), parent_cos_angle_separation(v.parent_cos_angle_separation), min_basis(v.min_basis) {}
+};
+
+// Nearest obstacle cell and generalized Voronoi cells of a box of the live map (khr_voronoi_field; ASSUMPTIONS.md A.20).  The dense
+// arrays hold one entry per cell in the order x + nx * (y + ny * z); the list holds the cells with basis >= min_basis in that order.
+struct VoronoiField {
+  std::array<int32_t, 3> origin{0, 0, 0}, dims{0, 0, 0};
+  float cell_size = 0.f;
+  std::vector<float> distance;  // metres; max_distance out of range, 0 in the obstacle set
+  std::vector<int32_t> d2;      // squared cell units; KHR_DF_FAR out of range
+  std::vector<uint8_t> status;  // DistanceField::Status bits
+  std::vector<int32_t> site;    // linear index in the box of the nearest obstacle cell; -1 without one
+  std::vector<uint8_t> basis;   // 0 = not eligible, else 1 .. KHR_VOR_MAX_BASIS; a Voronoi cell has >= 2
+  std::vector<int32_t> cells;          // 3 per listed cell: its global cell index
+  std::vector<float> cell_distance;
+  std::vector<uint8_t> cell_basis;
+  std::vector<int32_t> cell_sites;     // 3 * KHR_VOR_MAX_BASIS per listed cell: global cell indices, unused entries zero
+  khr_voronoi_stats stats{};
+  size_t size() const { return status.size(); }
+  size_t numListed() const { return cell_basis.size(); }
+  size_t index(int x, int y, int z) const { return static_cast<size_t>(x) + static_cast<size_t>(dims[0]) * (static_cast<size_t>(y) + static_cast<size_t>(dims[1]) * static_cast<size_t>(z)); }
+  // the box-local cell of a linear index (a site)
+  std::array<int32_t, 3> cellAt(int32_t linear) const { return {linear % dims[0], (linear / dims[0]) % dims[1], linear / (dims[0] * dims[1])}; }
+};
+
 // What changed between the live map and another map (VolumetricMap::diff; khr_diff_map, ASSUMPTIONS.md A.18): the changed blocks
 // in (x, y, z) order, the changed voxels of a block in ascending linear index.  Per voxel: x, y, z of its global voxel index in
 // this map's frame, kind, the two distances, the label of the occupied side and last_observed of either side; per block: its
@@ -558,6 +637,29 @@ class VolumetricMap {
     f.distance.resize(n); f.d2.resize(n); f.status.resize(n);
     if (khr_distance_field(ctx_, &rq, 0, f.distance.data(), f.d2.data(), f.status.data(), &f.stats) != KHR_OK)
       throw std::runtime_error(std::string("khr_distance_field: ") + khr_last_error());
+    return f;
+  }
+  // Where the nearest obstacle of every cell of a box is, and which cells lie between obstacles that are apart (khr_voronoi_field):
+  // the generalized Voronoi diagram the places graph is extracted from.  Computed on the device; one host wait for the counters, then
+  // the arrays are copied.  Throws on a bad request.
+  VoronoiField voronoiField(const VoronoiRequest& request) const {
+    khr_voronoi_request rq{};
+    for (int a = 0; a < 3; ++a) rq.origin[a] = request.origin[a], rq.dims[a] = request.dims[a];
+    rq.ratio = request.ratio;
+    rq.min_weight = request.min_weight, rq.max_distance = request.max_distance, rq.surface_distance = request.surface_distance;
+    rq.unknown_is_obstacle = request.unknown_is_obstacle ? 1 : 0;
+    rq.min_distance = request.min_distance, rq.mode = request.mode, rq.parent_l1_separation = request.parent_l1_separation;
+    rq.parent_cos_angle_separation = request.parent_cos_angle_separation, rq.min_basis = request.min_basis;
+    VoronoiField f;
+    f.origin = request.origin, f.dims = request.dims;
+    f.cell_size = config.voxel_size * static_cast<float>(request.ratio);
+    if (khr_voronoi_field(ctx_, &rq, &f.stats) != KHR_OK) throw std::runtime_error(std::string("khr_voronoi_field: ") + khr_last_error());
+    const size_t n = static_cast<size_t>(request.dims[0]) * request.dims[1] * request.dims[2], m = static_cast<size_t>(f.stats.n_listed);
+    f.distance.resize(n); f.d2.resize(n); f.status.resize(n); f.site.resize(n); f.basis.resize(n);
+    f.cells.resize(3 * m); f.cell_distance.resize(m); f.cell_basis.resize(m); f.cell_sites.resize(3 * KHR_VOR_MAX_BASIS * m);
+    if (khr_voronoi_field_into(ctx_, 0, f.distance.data(), f.d2.data(), f.status.data(), f.site.data(), f.basis.data(), f.cells.data(), f.cell_distance.data(),
+                               f.cell_basis.data(), f.cell_sites.data()) != KHR_OK)
+      throw std::runtime_error(std::string("khr_voronoi_field_into: ") + khr_last_error());
     return f;
   }
   // The map save / load role of hydra::VolumetricMap (un-vendored upstream; the reference's own tree has no counterpart): the live
