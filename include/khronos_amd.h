@@ -1063,6 +1063,63 @@ int khr_voronoi_field(khr_ctx* ctx, const khr_voronoi_request* request, khr_voro
 int khr_voronoi_field_into(khr_ctx* ctx, int on_device, float* distance, int32_t* d2, uint8_t* status, int32_t* site, uint8_t* basis,
                            int32_t* cells, float* cell_distance, uint8_t* cell_basis, int32_t* cell_sites);
 
+/* ---- places and their links from the Voronoi cells of a box (ASSUMPTIONS.md A.21) ------------------------------------------
+ * The last step of the stage khr_distance_field and khr_voronoi_field stand for (freespace_places of the reference's mapper
+ * configuration: graph.compression_distance_m, graph.min_node_distance_m, filter_places, min_places_component_size): a sparse
+ * graph of free-space places with a clearance each, linked where they touch, small islands filtered out.  No reference counterpart
+ * in its tree; the definition is this library's, all integers and bit copies.
+ * khr_places_graph reads distance, d2, basis and site of the last successful khr_voronoi_field of ctx (KHR_ESTATE without one; the
+ * Voronoi result is only read and stays valid).  khr_places_graph_from takes the box (origin, dims: 3 int32 each, cells) and the
+ * four arrays of dims[0] * dims[1] * dims[2] entries in the order lin = x + nx * (y + ny * z) from the caller -- host arrays
+ * (on_device == 0, copied through page-locked staging) or device arrays read in stream order -- and is the same code from there.
+ * MEMBERS: basis >= min_basis (0 means 2), distance >= min_node_distance (float32), 0 <= d2 < 2^30.
+ * BUCKETS: floor((origin + cell) / compression) per axis, towards minus infinity: anchored in the world, not in the box.
+ * PLACES: the classes of members joined when 26-adjacent and in the same bucket; the representative is the member of least lin.
+ * Centre: the member of greatest d2, the least lin among equals.  EDGES: distinct places with a 26-adjacent pair of members,
+ * whatever their buckets; clearance_d2 = the maximum over those pairs of min(d2, d2), n_contacts = their number.  COMPONENTS: the
+ * classes of the places under the edges; kept iff they hold at least min_component_size (< 1 means 1) places.  Kept places are
+ * numbered in ascending lin of their representatives, kept components in ascending order of their least place, kept edges (a < b)
+ * in ascending (a, b).
+ * Result: place, int32 per cell of the box: the kept place of a member, -1 otherwise.  Per kept place: centre (3 int32, global
+ * cell), centre_d2, radius (the centre's distance, bit for bit), basis (the centre's), site (the centre's site as a global cell;
+ * zeros for a site that is -1 or outside the box), n_cells, sum (3 int64: the members' global cells summed, exact), degree (kept
+ * edges at the place), component.  Per kept edge: edge_a < edge_b, edge_clearance_d2, edge_n_contacts.
+ *
+ * Both calls work in stream order on ctx's stream with TWO host waits, whatever the map: for the counts of members, places and
+ * adjacent pairs that size the work lists, and for the kept counts that size the result and fill `stats` (may be NULL).  The
+ * result lives in buffers ctx owns: it stays valid across later frames until the next places call, the next khr_voronoi_field
+ * (for khr_places_graph's results), khr_reset_map, khr_checkpoint_load or khr_destroy.  The map, the frame ring, the mesh layer,
+ * khr_stats and the results of the other readers are not touched.
+ * KHR_EINVAL (nothing done, an earlier result stays): a NULL ctx, request or, for _from, origin, dims or input array; a min_basis
+ * other than 0, 2, 3, 4; compression outside 1 .. KHR_PL_MAX_COMPRESSION; a negative or non-finite min_node_distance; for _from
+ * dims outside 1 .. KHR_DF_MAX_DIM, more than 2^24 cells or a box that leaves the cell index range.  KHR_ESTATE (likewise):
+ * world_size > 1, no Voronoi result.  Every other failure discards an earlier result; KHR_ENOMEM leaves the needed bytes in
+ * khr_last_error.  No members is KHR_OK: empty lists, place all -1.
+ *
+ * khr_places_graph_into copies the result of the last successful call (KHR_ESTATE without one); any pointer may be NULL; it may
+ * be called several times.  on_device == 0: host arrays, filled when the call returns (through page-locked staging);
+ * on_device != 0: device arrays, copied device-to-device in stream order, nothing is awaited.  khr_places_graph_box tells the box
+ * that result describes (origin, dims: 3 int32 each, either may be NULL), i.e. the size of `place`; KHR_ESTATE without a result. */
+#define KHR_PL_MAX_COMPRESSION 16
+typedef struct khr_places_request {
+  int32_t min_basis;          /* 0 (= 2), 2, 3, 4 */
+  float min_node_distance;    /* metres */
+  int32_t compression;        /* cells, 1 .. KHR_PL_MAX_COMPRESSION */
+  int32_t min_component_size; /* places; < 1 means 1 */
+} khr_places_request;
+typedef struct khr_places_stats {
+  uint64_t n_members;
+  uint64_t n_places_all, n_edges_all, n_components_all; /* before the component filter */
+  uint64_t n_places, n_edges, n_components;             /* kept */
+} khr_places_stats;
+int khr_places_graph(khr_ctx* ctx, const khr_places_request* request, khr_places_stats* stats);
+int khr_places_graph_from(khr_ctx* ctx, const khr_places_request* request, const int32_t* origin, const int32_t* dims, int on_device,
+                          const float* distance, const int32_t* d2, const uint8_t* basis, const int32_t* site, khr_places_stats* stats);
+int khr_places_graph_box(khr_ctx* ctx, int32_t* origin, int32_t* dims);
+int khr_places_graph_into(khr_ctx* ctx, int on_device, int32_t* place, int32_t* centre, int32_t* centre_d2, float* radius, uint8_t* basis,
+                          int32_t* site, uint32_t* n_cells, int64_t* sum, uint32_t* degree, uint32_t* component, uint32_t* edge_a,
+                          uint32_t* edge_b, int32_t* edge_clearance_d2, uint32_t* edge_n_contacts);
+
 /* ---- tick path: the camera frames of ONE tick batched (sharded multi-camera runs) ------------------------------------
  * In a hash-range sharded run every rank sees every camera frame, so the per-camera work of a
  * rank is what does not shrink with the rank count.  These two calls are khr_upload_frame / khr_integrate for n_frames

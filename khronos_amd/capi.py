@@ -126,6 +126,17 @@ class KhrVoronoiStats(C.Structure):
 KHR_VOR_L1, KHR_VOR_ANGLE, KHR_VOR_L1_THEN_ANGLE, KHR_VOR_MAX_BASIS = 0, 1, 2, 4
 
 
+class KhrPlacesRequest(C.Structure):
+    _fields_ = [("min_basis", C.c_int32), ("min_node_distance", C.c_float), ("compression", C.c_int32), ("min_component_size", C.c_int32)]
+
+
+class KhrPlacesStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_members", "n_places_all", "n_edges_all", "n_components_all", "n_places", "n_edges", "n_components")]
+
+
+KHR_PL_MAX_COMPRESSION = 16
+
+
 class KhrAlignRequest(C.Structure):
     _fields_ = [("n", C.c_int64), ("points", C.c_void_p), ("depth", C.c_void_p), ("sensor", KhrSensor), ("stride", C.c_int32),
                 ("weights", C.c_void_p), ("world_T_source", C.c_double * 16), ("min_weight", C.c_float), ("gate", C.c_float),
@@ -213,6 +224,7 @@ EXPORTS = [
     "khr_debug_live_resources", "khr_configure_object_voxel_sets",
     "khr_weld_mesh", "khr_weld_mesh_into", "khr_merge_map", "khr_diff_map", "khr_diff_map_into",
     "khr_segment_map", "khr_segment_map_into", "khr_voronoi_field", "khr_voronoi_field_into",
+    "khr_places_graph", "khr_places_graph_from", "khr_places_graph_into", "khr_places_graph_box",
 ]
 
 _lib = None
@@ -350,6 +362,10 @@ def load_library():
     lib.khr_segment_map_into.argtypes = [vp, i32] + [vp] * 10
     lib.khr_voronoi_field.argtypes = [vp, C.POINTER(KhrVoronoiRequest), C.POINTER(KhrVoronoiStats)]
     lib.khr_voronoi_field_into.argtypes = [vp, i32] + [vp] * 9
+    lib.khr_places_graph.argtypes = [vp, C.POINTER(KhrPlacesRequest), C.POINTER(KhrPlacesStats)]
+    lib.khr_places_graph_from.argtypes = [vp, C.POINTER(KhrPlacesRequest), vp, vp, i32, vp, vp, vp, vp, C.POINTER(KhrPlacesStats)]
+    lib.khr_places_graph_into.argtypes = [vp, i32] + [vp] * 14
+    lib.khr_places_graph_box.argtypes = [vp, vp, vp]
     lib.khr_debug_read.argtypes = [vp, vp, i64]
     lib.khr_debug_live_resources.argtypes = [C.POINTER(i64)]
     lib.khr_tick_ingest.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
@@ -1506,6 +1522,88 @@ class FusionContext:
         out["cell_size"] = float(np.float32(self.cfg.voxel_size) * np.float32(int(rq.ratio)))
         out["stats"] = stats
         return out
+
+    # name, dtype, trailing shape, "d" = one entry per cell of the box / "p" = one per kept place / "e" = one per kept edge
+    PL_FIELDS = (("place", np.int32, (), "d"), ("centre", np.int32, (3,), "p"), ("centre_d2", np.int32, (), "p"), ("radius", np.float32, (), "p"),
+                 ("basis", np.uint8, (), "p"), ("site", np.int32, (3,), "p"), ("n_cells", np.uint32, (), "p"), ("sum", np.int64, (3,), "p"),
+                 ("degree", np.uint32, (), "p"), ("component", np.uint32, (), "p"), ("edge_a", np.uint32, (), "e"), ("edge_b", np.uint32, (), "e"),
+                 ("edge_clearance_d2", np.int32, (), "e"), ("edge_n_contacts", np.uint32, (), "e"))
+    PL_INPUTS = (("distance", np.float32), ("d2", np.int32), ("basis", np.uint8), ("site", np.int32))
+
+    @staticmethod
+    def places_request(min_basis=0, min_node_distance=0.0, compression=4, min_component_size=1):
+        """a khr_places_request"""
+        rq = KhrPlacesRequest()
+        rq.min_basis, rq.min_node_distance, rq.compression, rq.min_component_size = int(min_basis), float(min_node_distance), int(compression), int(min_component_size)
+        return rq
+
+    def places_graph_rc(self, request):
+        """khr_places_graph without raising: (return code, statistics dict)"""
+        st = KhrPlacesStats()
+        rc = self.lib.khr_places_graph(self.h, C.byref(request) if request is not None else None, C.byref(st))
+        return rc, {k: int(getattr(st, k)) for k, _ in KhrPlacesStats._fields_}
+
+    def places_graph_from_rc(self, request, origin, dims, field, on_device=False):
+        """khr_places_graph_from without raising: (return code, statistics dict).  `field`: PL_INPUTS name -> contiguous array of
+        the box's cells, or an integer device pointer with on_device; origin / dims / an input may be None (an argument error)"""
+        st = KhrPlacesStats()
+        o = None if origin is None else (C.c_int32 * 3)(*[int(v) for v in origin])
+        d = None if dims is None else (C.c_int32 * 3)(*[int(v) for v in dims])
+        ptrs, keep = [], []
+        for name, dt in self.PL_INPUTS:
+            a = field.get(name)
+            if a is None:
+                ptrs.append(None)
+            elif on_device:
+                ptrs.append(C.c_void_p(int(a)))
+            else:
+                a = np.ascontiguousarray(a, dt)
+                keep.append(a)
+                ptrs.append(_ptr(a))
+        rc = self.lib.khr_places_graph_from(self.h, C.byref(request) if request is not None else None, o, d, int(on_device), *ptrs, C.byref(st))
+        return rc, {k: int(getattr(st, k)) for k, _ in KhrPlacesStats._fields_}
+
+    def places_graph_into(self, out, on_device=False):
+        """khr_places_graph_into: the result of the last places graph into caller buffers (`out`: PL_FIELDS name -> contiguous array,
+        or an integer device pointer with on_device; absent / None = not copied).  Returns the return code without raising."""
+        ptrs = []
+        for name, _, _, _ in self.PL_FIELDS:
+            a = out.get(name)
+            ptrs.append(None if a is None else (C.c_void_p(int(a)) if on_device else _ptr(a)))
+        return self.lib.khr_places_graph_into(self.h, int(on_device), *ptrs)
+
+    def places_graph_box(self):
+        """khr_places_graph_box: (origin, dims) of the box the last places graph describes, as x, y, z"""
+        o, d = (C.c_int32 * 3)(), (C.c_int32 * 3)()
+        self._chk(self.lib.khr_places_graph_box(self.h, o, d))
+        return tuple(int(v) for v in o), tuple(int(v) for v in d)
+
+    def _places_result(self, stats):
+        dims = self.places_graph_box()[1]
+        shape = {"d": (int(dims[2]), int(dims[1]), int(dims[0])), "p": (stats["n_places"],), "e": (stats["n_edges"],)}
+        out = {k: np.zeros(shape[w] + sh, dt) for k, dt, sh, w in self.PL_FIELDS}
+        self._chk(self.places_graph_into(out))
+        out["centroid"] = out["sum"].astype(np.float64) / np.maximum(out["n_cells"], 1).astype(np.float64)[:, None]
+        out["stats"] = stats
+        return out
+
+    def places_graph(self, min_basis=0, min_node_distance=0.0, compression=4, min_component_size=1):
+        """The places and their links from the last voronoi_field of this context (khr_places_graph, ASSUMPTIONS.md A.21).  Returns a
+        dict: place int32 (nz, ny, nx) over that field's box, the kept place of a member cell or -1; per kept place centre (p, 3)
+        int32 global cell, centre_d2, radius float32, basis, site (p, 3), n_cells, sum (p, 3) int64, centroid (p, 3) float64 =
+        sum / n_cells, degree, component; per kept edge edge_a < edge_b, edge_clearance_d2, edge_n_contacts; and stats."""
+        rc, stats = self.places_graph_rc(self.places_request(min_basis, min_node_distance, compression, min_component_size))
+        self._chk(rc)
+        return self._places_result(stats)
+
+    def places_graph_from(self, origin, dims, distance, d2, basis, site, min_basis=0, min_node_distance=0.0, compression=4, min_component_size=1,
+                          on_device=False):
+        """places_graph on a field the caller brings (khr_places_graph_from): the box and four arrays of its cells in the order
+        x + nx * (y + ny * z) -- numpy arrays, or integer device pointers with on_device"""
+        rq = self.places_request(min_basis, min_node_distance, compression, min_component_size)
+        rc, stats = self.places_graph_from_rc(rq, origin, dims, dict(distance=distance, d2=d2, basis=basis, site=site), on_device)
+        self._chk(rc)
+        return self._places_result(stats)
 
     def fetch_mesh_reuse(self, bufs):
         """fetch_mesh() into arrays the caller keeps (a consumer that takes one mesh per output must not pay page faults on 20 MB of

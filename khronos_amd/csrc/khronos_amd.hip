@@ -45,6 +45,7 @@
 #include "khr_kernels_diff.h"
 #include "khr_kernels_segment.h"
 #include "khr_kernels_voronoi.h"
+#include "khr_kernels_places.h"
 
 using namespace khr;
 
@@ -469,6 +470,20 @@ struct khr_ctx {
   khr_voronoi_stats vor_stats{};
   size_t vor_cells = 0;     // cells of the box the result describes
   bool vor_valid = false;   // a Voronoi field succeeded and nothing has discarded its result
+  int32_t vor_origin[3] = {0, 0, 0}, vor_dims[3] = {0, 0, 0};  // ... its box and cell size (khr_places_graph reads the field)
+  float vor_cell_size = 0.f;
+  // places graphs (khr_places_graph / khr_places_graph_from): the device copy of a host caller's field, the per-cell work arrays
+  // with the dense place ids, the pair / edge / component work lists, the scan's and the sort's temporary storage, the result
+  // lists, the counters with their page-locked mirror, and the page-locked staging of the host forms; each grown to the largest call
+  DevBuf<uint8_t> d_pl_in, d_pl_dense, d_pl_work, d_pl_cub, d_pl_out;
+  DevBuf<unsigned long long> d_pl_ctr;
+  PinnedBuf<unsigned long long> h_pl;
+  PinnedBuf<uint8_t> h_pl_stage;
+  khr_places_stats pl_stats{};
+  size_t pl_cells = 0;         // cells of the box the result describes
+  int32_t pl_origin[3] = {0, 0, 0}, pl_dims[3] = {0, 0, 0};  // ... and the box (khr_places_graph_box)
+  bool pl_valid = false;       // a places graph succeeded and nothing has discarded its result
+  bool pl_from_voronoi = false;  // ... and it was read from the Voronoi result
   // timing
   uint32_t timing = 0;  // bit i = timer i enabled
   std::vector<TimingRec> pending;
@@ -885,6 +900,7 @@ static int resetMap(khr_ctx* c, float voxel_size, float truncation_distance) {
   c->diff_valid = false;
   c->seg_valid = false;
   c->vor_valid = false;
+  c->pl_valid = false;
   c->host_index_valid = false, ++c->map_gen;
   c->explicit_blocks = 0;
   c->box_listed = false;
@@ -4961,6 +4977,7 @@ int khr_voronoi_field(khr_ctx* c, const khr_voronoi_request* rq, khr_voronoi_sta
   // from here on a failure discards the earlier result
   c->vor_valid = false;
   c->vor_stats = khr_voronoi_stats{};
+  if (c->pl_from_voronoi) c->pl_valid = false;  // (khr_places_graph: its graph belongs to the field this call replaces)
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = c->stream;
   const int nx = rq->dims[0], ny = rq->dims[1], nz = rq->dims[2];
@@ -5041,6 +5058,8 @@ int khr_voronoi_field(khr_ctx* c, const khr_voronoi_request* rq, khr_voronoi_sta
   }
   c->vor_stats = s;
   c->vor_cells = n;
+  for (int a = 0; a < 3; ++a) c->vor_origin[a] = rq->origin[a], c->vor_dims[a] = rq->dims[a];
+  c->vor_cell_size = f.rule.cell_size;
   c->vor_valid = true;
   if (stats) *stats = s;
   return KHR_OK;
@@ -5077,6 +5096,329 @@ int khr_voronoi_field_into(khr_ctx* c, int on_device, float* distance, int32_t* 
   HIP_TRY(hipStreamSynchronize(c->stream));
   for (int k = 0; k < 9; ++k)
     if (dst[k] && bytes[k]) std::memcpy(dst[k], c->h_vor_stage + off[k], bytes[k]);
+  return KHR_OK;
+}
+
+// ---- places and their links from the Voronoi cells of a box (khr_places_graph / khr_places_graph_from; ASSUMPTIONS.md A.21,
+// device side: khr_kernels_places.h) -------------------------------------------------------------------------------------------
+namespace {
+
+// per-cell work arrays of n cells, the dense place ids last
+struct PlDense {
+  size_t label, number, pair_count, rec_key, rec_acc, place, bytes;
+};
+PlDense plDense(size_t n) {
+  PlDense L{};
+  size_t o = 0;
+  auto carve = [&](size_t bytes) { const size_t at = o; o += vorAlign(bytes); return at; };
+  L.rec_key = carve(8 * n), L.rec_acc = carve(8 * n), L.label = carve(4 * n), L.number = carve(4 * (n + 1)), L.pair_count = carve(4 * (n + 1)), L.place = carve(4 * n);
+  L.bytes = o;
+  return L;
+}
+// work lists of m adjacent pairs and p places (before the filter)
+struct PlWork {
+  size_t keys, keys_sorted, vals, vals_sorted, head, n_unique, edge_a, edge_b, edge_clear, edge_contacts, edge_new, parent, root, size, place_new, comp_new, bytes;
+};
+PlWork plWork(size_t m, size_t p) {
+  PlWork L{};
+  size_t o = 0;
+  auto carve = [&](size_t bytes) { const size_t at = o; o += vorAlign(bytes); return at; };
+  L.keys = carve(8 * m), L.keys_sorted = carve(8 * m), L.vals = carve(4 * m), L.vals_sorted = carve(4 * m), L.head = carve(4 * (m + 1)), L.n_unique = carve(4);
+  L.edge_a = carve(4 * m), L.edge_b = carve(4 * m), L.edge_clear = carve(4 * m), L.edge_contacts = carve(4 * m), L.edge_new = carve(4 * (m + 1));
+  L.parent = carve(4 * p), L.root = carve(4 * p), L.size = carve(4 * p), L.place_new = carve(4 * (p + 1)), L.comp_new = carve(4 * (p + 1));
+  L.bytes = o;
+  return L;
+}
+// the result lists of p kept places and e kept edges
+struct PlOut {
+  size_t centre, centre_d2, radius, basis, site, n_cells, sum, degree, component, edge_a, edge_b, edge_clear, edge_contacts, bytes;
+};
+PlOut plOut(size_t p, size_t e) {
+  PlOut L{};
+  size_t o = 0;
+  auto carve = [&](size_t bytes) { const size_t at = o; o += vorAlign(bytes); return at; };
+  L.sum = carve(24 * p), L.centre = carve(12 * p), L.centre_d2 = carve(4 * p), L.radius = carve(4 * p), L.basis = carve(p), L.site = carve(12 * p);
+  L.n_cells = carve(4 * p), L.degree = carve(4 * p), L.component = carve(4 * p);
+  L.edge_a = carve(4 * e), L.edge_b = carve(4 * e), L.edge_clear = carve(4 * e), L.edge_contacts = carve(4 * e);
+  L.bytes = std::max<size_t>(o, 256);  // (never empty: the owner exists from the first call on)
+  return L;
+}
+
+// the request checks both calls share (KHR_EINVAL / KHR_ESTATE: nothing is done)
+int plCheckRequest(khr_ctx* c, const khr_places_request* rq, const char* who) {
+  if (rq->min_basis != 0 && (rq->min_basis < 2 || rq->min_basis > KHR_VOR_MAX_BASIS)) return fail(KHR_EINVAL, "%s: min_basis is %d: 0, 2, 3 or 4", who, rq->min_basis);
+  if (rq->compression < 1 || rq->compression > KHR_PL_MAX_COMPRESSION)
+    return fail(KHR_EINVAL, "%s: compression is %d cells: 1 .. %d", who, rq->compression, KHR_PL_MAX_COMPRESSION);
+  if (!(rq->min_node_distance >= 0.f) || !std::isfinite(rq->min_node_distance))
+    return fail(KHR_EINVAL, "%s: bad min_node_distance %g", who, static_cast<double>(rq->min_node_distance));
+  if (c->cfg.world_size > 1) return fail(KHR_ESTATE, "%s needs the whole map: world_size is %d", who, c->cfg.world_size);
+  return KHR_OK;
+}
+
+// the stage itself, on device arrays of the box's cells; two host waits
+int plRun(khr_ctx* c, const khr_places_request* rq, const int32_t origin[3], const int32_t dims[3], const float* distance, const int32_t* d2,
+          const uint8_t* basis, const int32_t* site, const PlDense& D, khr_places_stats* stats) {
+  hipStream_t st = c->stream;
+  const int nx = dims[0], ny = dims[1], nz = dims[2];
+  const size_t n = static_cast<size_t>(nx) * ny * nz;
+  uint8_t* const db = c->d_pl_dense;
+  PlField f{};
+  f.ox = origin[0], f.oy = origin[1], f.oz = origin[2];
+  f.nx = nx, f.ny = ny, f.nz = nz;
+  f.distance = distance, f.d2 = d2, f.basis = basis, f.site = site;
+  f.min_basis = rq->min_basis == 0 ? 2 : rq->min_basis;
+  f.min_node_distance = rq->min_node_distance;
+  f.compression = rq->compression, f.edge = plTileBuckets(rq->compression) * rq->compression;
+  f.tx0 = plFloorDiv(origin[0], f.edge), f.ty0 = plFloorDiv(origin[1], f.edge), f.tz0 = plFloorDiv(origin[2], f.edge);
+  f.ntx = plFloorDiv(origin[0] + nx - 1, f.edge) - f.tx0 + 1, f.nty = plFloorDiv(origin[1] + ny - 1, f.edge) - f.ty0 + 1;
+  f.ntz = plFloorDiv(origin[2] + nz - 1, f.edge) - f.tz0 + 1;
+  f.label = reinterpret_cast<uint32_t*>(db + D.label), f.number = reinterpret_cast<uint32_t*>(db + D.number);
+  f.pair_count = reinterpret_cast<uint32_t*>(db + D.pair_count);
+  f.rec_key = reinterpret_cast<uint64_t*>(db + D.rec_key), f.rec_acc = reinterpret_cast<uint64_t*>(db + D.rec_acc);
+  f.ctr = c->d_pl_ctr;
+  const uint32_t n_wg = static_cast<uint32_t>(gridFor(n));
+  HIP_TRY(hipMemsetAsync(c->d_pl_ctr, 0, sizeof(unsigned long long) * PLC_COUNT, st));
+  HIP_TRY(hipMemsetAsync(f.label, 0xff, 4 * n, st));
+  HIP_TRY(hipMemsetAsync(f.number, 0, 4 * (n + 1), st));
+  HIP_TRY(hipMemsetAsync(f.pair_count + n, 0, 4, st));
+  hipLaunchKernelGGL(k_pl_label, dim3(static_cast<unsigned>(f.ntx) * f.nty * f.ntz), dim3(256), 0, st, f);
+  HIP_TRY(hipGetLastError());
+  size_t tb = c->d_pl_cub.count();
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_pl_cub.get(), tb, f.number, f.number, static_cast<int>(n + 1), st));
+  hipLaunchKernelGGL((k_pl_pairs<0>), dim3(n_wg), dim3(256), 0, st, f, static_cast<uint64_t*>(nullptr), static_cast<int32_t*>(nullptr), 0u);
+  HIP_TRY(hipGetLastError());
+  tb = c->d_pl_cub.count();
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_pl_cub.get(), tb, f.pair_count, f.pair_count, static_cast<int>(n + 1), st));
+  // host wait 1: members, places, adjacent pairs
+  unsigned long long* const h = c->h_pl;
+  HIP_TRY(hipMemcpyAsync(h, c->d_pl_ctr, sizeof(unsigned long long) * PLC_COUNT, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  khr_places_stats s{};
+  s.n_members = h[PLC_MEMBERS], s.n_places_all = h[PLC_PLACES_ALL];
+  const size_t m = static_cast<size_t>(h[PLC_PAIRS]), P = static_cast<size_t>(s.n_places_all);
+  if (h[PLC_ERR] != 0)
+    return fail(KHR_EDEVICE, "khr_places_graph: %llu tiles hold more than %d places", static_cast<unsigned long long>(h[PLC_ERR]), kPlSlots);
+  if (s.n_members > n || P > s.n_members || m > 13 * n)
+    return fail(KHR_EDEVICE, "khr_places_graph: inconsistent counts (%llu places of %llu members of %zu cells)", static_cast<unsigned long long>(P),
+                static_cast<unsigned long long>(s.n_members), n);
+  // the work lists and the sort's storage; nothing is queued on the stream here, so a growth frees nothing in use
+  const PlWork W = plWork(m, P);
+  size_t sort_bytes = 0, scan_bytes = 0;
+  int end_bit = 33;
+  while (end_bit < 64 && (P >> (end_bit - 32)) != 0) ++end_bit;
+  if (m > 0)
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, static_cast<const uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr), static_cast<const int32_t*>(nullptr),
+                                               static_cast<int32_t*>(nullptr), static_cast<int>(m), 0, end_bit, st));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, static_cast<uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), static_cast<int>(std::max(m, P) + 1), st));
+  const size_t cub_bytes = std::max(sort_bytes, scan_bytes);
+  if (c->d_pl_work.reserve(std::max<size_t>(W.bytes, 256)) || c->d_pl_cub.reserve(cub_bytes))
+    return fail(KHR_ENOMEM, "khr_places_graph: work lists of %zu adjacent pairs and %zu places (%zu bytes)", m, P, W.bytes + cub_bytes);
+  uint8_t* const wb = c->d_pl_work;
+  PlGraph g{};
+  g.n_pairs = static_cast<uint32_t>(m), g.n_places = static_cast<uint32_t>(P);
+  g.keys = reinterpret_cast<const uint64_t*>(wb + W.keys_sorted), g.vals = reinterpret_cast<const int32_t*>(wb + W.vals_sorted);
+  g.head = reinterpret_cast<uint32_t*>(wb + W.head), g.n_unique = reinterpret_cast<uint32_t*>(wb + W.n_unique);
+  g.edge_a = reinterpret_cast<uint32_t*>(wb + W.edge_a), g.edge_b = reinterpret_cast<uint32_t*>(wb + W.edge_b);
+  g.edge_clear = reinterpret_cast<int32_t*>(wb + W.edge_clear), g.edge_contacts = reinterpret_cast<uint32_t*>(wb + W.edge_contacts);
+  g.edge_new = reinterpret_cast<uint32_t*>(wb + W.edge_new);
+  g.parent = reinterpret_cast<uint32_t*>(wb + W.parent), g.root = reinterpret_cast<uint32_t*>(wb + W.root), g.size = reinterpret_cast<uint32_t*>(wb + W.size);
+  g.place_new = reinterpret_cast<uint32_t*>(wb + W.place_new), g.comp_new = reinterpret_cast<uint32_t*>(wb + W.comp_new);
+  g.min_size = static_cast<uint32_t>(std::max<int32_t>(rq->min_component_size, 1));
+  g.ctr = c->d_pl_ctr;
+  if (P > 0) {
+    const unsigned wide = static_cast<unsigned>(gridFor(std::max(m, P)));
+    HIP_TRY(hipMemsetAsync(g.n_unique, 0, 4, st));
+    HIP_TRY(hipMemsetAsync(g.head + m, 0, 4, st));
+    HIP_TRY(hipMemsetAsync(g.edge_new + m, 0, 4, st));
+    HIP_TRY(hipMemsetAsync(g.size, 0, 4 * P, st));
+    HIP_TRY(hipMemsetAsync(g.place_new + P, 0, 4, st));
+    HIP_TRY(hipMemsetAsync(g.comp_new + P, 0, 4, st));
+    if (m > 0) {
+      HIP_TRY(hipMemsetAsync(g.edge_clear, 0, 4 * m, st));
+      HIP_TRY(hipMemsetAsync(g.edge_contacts, 0, 4 * m, st));
+      uint64_t* const keys = reinterpret_cast<uint64_t*>(wb + W.keys);
+      int32_t* const vals = reinterpret_cast<int32_t*>(wb + W.vals);
+      hipLaunchKernelGGL((k_pl_pairs<1>), dim3(n_wg), dim3(256), 0, st, f, keys, vals, g.n_pairs);
+      HIP_TRY(hipGetLastError());
+      tb = c->d_pl_cub.count();
+      HIP_TRY(hipcub::DeviceRadixSort::SortPairs(c->d_pl_cub.get(), tb, static_cast<const uint64_t*>(keys), reinterpret_cast<uint64_t*>(wb + W.keys_sorted),
+                                                 static_cast<const int32_t*>(vals), reinterpret_cast<int32_t*>(wb + W.vals_sorted), static_cast<int>(m), 0, end_bit, st));
+    }
+    hipLaunchKernelGGL(k_pl_edge_heads, dim3(wide), dim3(256), 0, st, g);
+    HIP_TRY(hipGetLastError());
+    if (m > 0) {
+      tb = c->d_pl_cub.count();
+      HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_pl_cub.get(), tb, g.head, g.head, static_cast<int>(m + 1), st));
+      hipLaunchKernelGGL(k_pl_edge_reduce, dim3(gridFor(m)), dim3(256), 0, st, g);
+      hipLaunchKernelGGL(k_pl_comp_union, dim3(gridFor(m)), dim3(256), 0, st, g);
+    }
+    hipLaunchKernelGGL(k_pl_comp_flatten, dim3(gridFor(P)), dim3(256), 0, st, g);
+    hipLaunchKernelGGL(k_pl_comp_keep, dim3(wide), dim3(256), 0, st, g);
+    HIP_TRY(hipGetLastError());
+    tb = c->d_pl_cub.count();
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_pl_cub.get(), tb, g.place_new, g.place_new, static_cast<int>(P + 1), st));
+    tb = c->d_pl_cub.count();
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_pl_cub.get(), tb, g.comp_new, g.comp_new, static_cast<int>(P + 1), st));
+    tb = c->d_pl_cub.count();
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_pl_cub.get(), tb, g.edge_new, g.edge_new, static_cast<int>(m + 1), st));
+    // host wait 2: the kept counts
+    HIP_TRY(hipMemcpyAsync(h, c->d_pl_ctr, sizeof(unsigned long long) * PLC_COUNT, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    s.n_edges_all = h[PLC_EDGES_ALL], s.n_components_all = h[PLC_COMPS_ALL], s.n_places = h[PLC_PLACES], s.n_edges = h[PLC_EDGES], s.n_components = h[PLC_COMPS];
+    if (s.n_places > P || s.n_edges > s.n_edges_all || s.n_edges_all > m || s.n_components > s.n_components_all || s.n_components_all > P)
+      return fail(KHR_EDEVICE, "khr_places_graph: inconsistent counts (%llu of %zu places, %llu of %llu edges)", static_cast<unsigned long long>(s.n_places), P,
+                  static_cast<unsigned long long>(s.n_edges), static_cast<unsigned long long>(s.n_edges_all));
+  }
+  const PlOut L = plOut(static_cast<size_t>(s.n_places), static_cast<size_t>(s.n_edges));
+  if (c->d_pl_out.reserve(L.bytes)) return fail(KHR_ENOMEM, "khr_places_graph: %llu places and %llu edges (%zu bytes)", static_cast<unsigned long long>(s.n_places),
+                                                static_cast<unsigned long long>(s.n_edges), L.bytes);
+  uint8_t* const ob = c->d_pl_out;
+  PlResult r{};
+  r.n_places = static_cast<uint32_t>(s.n_places), r.n_edges = static_cast<uint32_t>(s.n_edges);
+  r.place = reinterpret_cast<int32_t*>(db + D.place);
+  r.centre = reinterpret_cast<int32_t*>(ob + L.centre), r.centre_d2 = reinterpret_cast<int32_t*>(ob + L.centre_d2), r.radius = reinterpret_cast<float*>(ob + L.radius);
+  r.basis = ob + L.basis, r.site = reinterpret_cast<int32_t*>(ob + L.site), r.n_cells = reinterpret_cast<uint32_t*>(ob + L.n_cells);
+  r.sum = reinterpret_cast<long long*>(ob + L.sum), r.degree = reinterpret_cast<uint32_t*>(ob + L.degree), r.component = reinterpret_cast<uint32_t*>(ob + L.component);
+  r.edge_a = reinterpret_cast<uint32_t*>(ob + L.edge_a), r.edge_b = reinterpret_cast<uint32_t*>(ob + L.edge_b);
+  r.edge_clear = reinterpret_cast<int32_t*>(ob + L.edge_clear), r.edge_contacts = reinterpret_cast<uint32_t*>(ob + L.edge_contacts);
+  if (s.n_places > 0) {
+    HIP_TRY(hipMemsetAsync(r.degree, 0, 4 * static_cast<size_t>(s.n_places), st));
+    hipLaunchKernelGGL(k_pl_finish_cells, dim3(n_wg), dim3(256), 0, st, f, g, r);
+    if (s.n_edges > 0) hipLaunchKernelGGL(k_pl_finish_edges, dim3(gridFor(m)), dim3(256), 0, st, g, r);
+    HIP_TRY(hipGetLastError());
+  } else {
+    HIP_TRY(hipMemsetAsync(r.place, 0xff, 4 * n, st));  // (no place is kept: -1 everywhere)
+  }
+  c->pl_stats = s;
+  c->pl_cells = n;
+  for (int a = 0; a < 3; ++a) c->pl_origin[a] = origin[a], c->pl_dims[a] = dims[a];
+  c->pl_valid = true;
+  if (stats) *stats = s;
+  return KHR_OK;
+}
+
+// the buffers every call needs before its first launch, for a box of n cells (`in_bytes` of a host caller's field)
+int plReserve(khr_ctx* c, size_t n, size_t in_bytes, const PlDense& D) {
+  size_t cub_bytes = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, static_cast<uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), static_cast<int>(n + 1), c->stream));
+  cub_bytes = std::max<size_t>(cub_bytes, 256);
+  if (c->d_pl_in.count() < in_bytes || c->d_pl_dense.count() < D.bytes || c->d_pl_cub.count() < cub_bytes || !c->d_pl_ctr || !c->h_pl) {
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (whatever still reads the old blocks)
+    if (c->d_pl_in.reserve(in_bytes) || c->d_pl_dense.reserve(D.bytes) || c->d_pl_cub.reserve(cub_bytes) || c->d_pl_ctr.reserve(PLC_COUNT) || c->h_pl.reserve(PLC_COUNT))
+      return fail(KHR_ENOMEM, "khr_places_graph: work arrays of %zu cells (%zu bytes)", n, in_bytes + D.bytes + cub_bytes);
+  }
+  return KHR_OK;
+}
+
+}  // namespace
+
+int khr_places_graph(khr_ctx* c, const khr_places_request* rq, khr_places_stats* stats) {
+  if (stats) *stats = khr_places_stats{};
+  if (!c || !rq) return fail(KHR_EINVAL, "khr_places_graph: null argument");
+  KHR_TRY(plCheckRequest(c, rq, "khr_places_graph"));
+  if (!c->vor_valid) return fail(KHR_ESTATE, "no successful khr_voronoi_field before khr_places_graph");
+  // from here on a failure discards the earlier result
+  c->pl_valid = false;
+  c->pl_stats = khr_places_stats{};
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = c->vor_cells;
+  const PlDense D = plDense(n);
+  KHR_TRY(plReserve(c, n, 0, D));
+  const VorDense V = vorDense(n);
+  const uint8_t* const vb = c->d_vor_dense;
+  c->pl_from_voronoi = true;
+  return plRun(c, rq, c->vor_origin, c->vor_dims, reinterpret_cast<const float*>(vb + V.distance), reinterpret_cast<const int32_t*>(vb + V.d2), vb + V.basis,
+               reinterpret_cast<const int32_t*>(vb + V.site), D, stats);
+}
+
+int khr_places_graph_from(khr_ctx* c, const khr_places_request* rq, const int32_t* origin, const int32_t* dims, int on_device, const float* distance,
+                          const int32_t* d2, const uint8_t* basis, const int32_t* site, khr_places_stats* stats) {
+  if (stats) *stats = khr_places_stats{};
+  if (!c || !rq || !origin || !dims || !distance || !d2 || !basis || !site) return fail(KHR_EINVAL, "khr_places_graph_from: null argument");
+  KHR_TRY(plCheckRequest(c, rq, "khr_places_graph_from"));
+  uint64_t cells = 1;
+  for (int a = 0; a < 3; ++a) {
+    if (dims[a] < 1 || dims[a] > KHR_DF_MAX_DIM) return fail(KHR_EINVAL, "khr_places_graph_from: dims[%d] = %d: 1 .. %d", a, dims[a], KHR_DF_MAX_DIM);
+    cells *= static_cast<uint64_t>(dims[a]);
+    const int64_t lo = origin[a], hi = static_cast<int64_t>(origin[a]) + dims[a] - 1;
+    if (lo <= -(int64_t(1) << 30) || hi >= (int64_t(1) << 30)) return fail(KHR_EINVAL, "khr_places_graph_from: the box leaves the cell index range on axis %d", a);
+  }
+  if (cells > (uint64_t(1) << 24)) return fail(KHR_EINVAL, "khr_places_graph_from: %llu cells: at most 2^24", static_cast<unsigned long long>(cells));
+  // from here on a failure discards the earlier result
+  c->pl_valid = false;
+  c->pl_stats = khr_places_stats{};
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = static_cast<size_t>(cells);
+  const PlDense D = plDense(n);
+  c->pl_from_voronoi = false;
+  if (on_device) {
+    KHR_TRY(plReserve(c, n, 0, D));
+    return plRun(c, rq, origin, dims, distance, d2, basis, site, D, stats);
+  }
+  // a host field: through the page-locked staging into a device copy
+  const size_t off[4] = {0, vorAlign(4 * n), 2 * vorAlign(4 * n), 2 * vorAlign(4 * n) + vorAlign(n)};
+  const size_t in_bytes = off[3] + vorAlign(4 * n);
+  KHR_TRY(plReserve(c, n, in_bytes, D));
+  if (c->h_pl_stage.reserve(in_bytes)) return fail(KHR_ENOMEM, "khr_places_graph_from: %zu bytes of page-locked staging", in_bytes);
+  const void* const src[4] = {distance, d2, basis, site};
+  const size_t bytes[4] = {4 * n, 4 * n, n, 4 * n};
+  const size_t at[4] = {off[0], off[1], off[2], off[3]};
+  for (int k = 0; k < 4; ++k) {
+    std::memcpy(c->h_pl_stage + at[k], src[k], bytes[k]);
+    HIP_TRY(hipMemcpyAsync(c->d_pl_in + at[k], c->h_pl_stage + at[k], bytes[k], hipMemcpyHostToDevice, c->stream));
+  }
+  const uint8_t* const ib = c->d_pl_in;
+  return plRun(c, rq, origin, dims, reinterpret_cast<const float*>(ib + at[0]), reinterpret_cast<const int32_t*>(ib + at[1]), ib + at[2],
+               reinterpret_cast<const int32_t*>(ib + at[3]), D, stats);
+}
+
+int khr_places_graph_box(khr_ctx* c, int32_t* origin, int32_t* dims) {
+  if (!c) return fail(KHR_EINVAL, "null ctx");
+  if (!c->pl_valid) return fail(KHR_ESTATE, "no successful khr_places_graph before khr_places_graph_box");
+  for (int a = 0; a < 3; ++a) {
+    if (origin) origin[a] = c->pl_origin[a];
+    if (dims) dims[a] = c->pl_dims[a];
+  }
+  return KHR_OK;
+}
+
+int khr_places_graph_into(khr_ctx* c, int on_device, int32_t* place, int32_t* centre, int32_t* centre_d2, float* radius, uint8_t* basis, int32_t* site,
+                          uint32_t* n_cells, int64_t* sum, uint32_t* degree, uint32_t* component, uint32_t* edge_a, uint32_t* edge_b,
+                          int32_t* edge_clearance_d2, uint32_t* edge_n_contacts) {
+  if (!c) return fail(KHR_EINVAL, "null ctx");
+  if (!c->pl_valid) return fail(KHR_ESTATE, "no successful khr_places_graph before khr_places_graph_into");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = c->pl_cells, p = static_cast<size_t>(c->pl_stats.n_places), e = static_cast<size_t>(c->pl_stats.n_edges);
+  const PlDense D = plDense(n);
+  const PlOut L = plOut(p, e);
+  const uint8_t* const db = c->d_pl_dense;
+  const uint8_t* const ob = c->d_pl_out;
+  constexpr int K = 14;
+  void* const dst[K] = {place, centre, centre_d2, radius, basis, site, n_cells, sum, degree, component, edge_a, edge_b, edge_clearance_d2, edge_n_contacts};
+  const void* const src[K] = {db + D.place, ob + L.centre, ob + L.centre_d2, ob + L.radius, ob + L.basis, ob + L.site, ob + L.n_cells, ob + L.sum, ob + L.degree,
+                              ob + L.component, ob + L.edge_a, ob + L.edge_b, ob + L.edge_clear, ob + L.edge_contacts};
+  const size_t bytes[K] = {4 * n, 12 * p, 4 * p, 4 * p, p, 12 * p, 4 * p, 24 * p, 4 * p, 4 * p, 4 * e, 4 * e, 4 * e, 4 * e};
+  if (on_device) {
+    for (int k = 0; k < K; ++k)
+      if (dst[k] && bytes[k]) HIP_TRY(hipMemcpyAsync(dst[k], src[k], bytes[k], hipMemcpyDeviceToDevice, c->stream));
+    return KHR_OK;
+  }
+  // the host form: through the page-locked staging, one wait
+  size_t off[K], stage_bytes = 0;
+  for (int k = 0; k < K; ++k) {
+    off[k] = stage_bytes;
+    if (dst[k]) stage_bytes += vorAlign(bytes[k]);
+  }
+  if (stage_bytes == 0) return KHR_OK;
+  if (c->h_pl_stage.count() < stage_bytes) {
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (a copy of khr_places_graph_from may still read the old block)
+    if (c->h_pl_stage.reserve(stage_bytes)) return fail(KHR_ENOMEM, "khr_places_graph_into: %zu bytes of page-locked staging", stage_bytes);
+  }
+  for (int k = 0; k < K; ++k)
+    if (dst[k] && bytes[k]) HIP_TRY(hipMemcpyAsync(c->h_pl_stage + off[k], src[k], bytes[k], hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int k = 0; k < K; ++k)
+    if (dst[k] && bytes[k]) std::memcpy(dst[k], c->h_pl_stage + off[k], bytes[k]);
   return KHR_OK;
 }
 
@@ -5601,6 +5943,7 @@ int khr_checkpoint_load(khr_ctx* c, const void* buffer, uint64_t n_bytes, int64_
   c->diff_valid = false;  // (khr_diff_map: so does the diff)
   c->seg_valid = false;   // (khr_segment_map: and the segmentation)
   c->vor_valid = false;   // (khr_voronoi_field: and the Voronoi field)
+  c->pl_valid = false;    // (khr_places_graph: and the places graph)
   khr_checkpoint_header h;
   int rc = khr_checkpoint_inspect(buffer, n_bytes, &h);
   if (rc) return rc;

@@ -2,7 +2,7 @@
 // thread drives the reference (spinOnce per InputPacket, finishMapping at shutdown), and prints a JSON
 // summary that tests/test_gpu_host.py compares with the step-wise C-ABI path and the oracle.
 // usage: aw_demo <config.yaml> <width> <height> <frames> [object_label]
-//        aw_demo --slices | --render | --query | --distance | --voronoi | --align | --weld | --merge | --diff | --segment | --checkpoint | --bench | --rayver ... (below)
+//        aw_demo --slices | --render | --query | --distance | --voronoi | --places | --align | --weld | --merge | --diff | --segment | --checkpoint | --bench | --rayver ... (below)
 //   object_label >= 0: the stand-in detector / tracker below; otherwise the plugins named in the config
 #include <execinfo.h>
 #include <csignal>
@@ -961,6 +961,208 @@ static int voronoiDemo(int argc, char** argv) {
               first_mismatch.c_str(), timed, cells, u(last_stats.n_listed), u(last_stats.n_observed), u(last_stats.n_obstacle), u(last_stats.n_free),
               u(last_stats.n_in_range), u(last_stats.n_eligible), u(last_stats.n_basis2), u(last_stats.n_basis3), u(last_stats.n_basis4), u(last_stats.n_listed),
               ms_dev / d);
+  return agree == frames && frames == N ? 0 : 3;
+}
+
+// what VolumetricMap::placesGraph replaces: the host's flood fill over the downloaded Voronoi field and its pair search (A.21),
+// held against the returned graph; nullptr when they agree, else the name of the first output that differs
+static const char* placesCheck(const hydra::VoronoiField& f, const hydra::PlacesGraph& g, const khr_places_request& rq) {
+  const int nx = f.dims[0], ny = f.dims[1], nz = f.dims[2];
+  const size_t n = f.size();
+  const int mb = rq.min_basis == 0 ? 2 : rq.min_basis, C = rq.compression;
+  auto fdiv = [](int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
+  std::vector<int32_t> place(n, -1);
+  std::vector<uint8_t> member(n, 0);
+  for (size_t i = 0; i < n; ++i) member[i] = f.basis[i] >= mb && f.distance[i] >= rq.min_node_distance && f.d2[i] >= 0 && f.d2[i] < (1 << 30);
+  struct Place { int32_t centre, d2; uint32_t cells; int64_t sum[3]; };
+  std::vector<Place> places;
+  std::vector<int32_t> queue;
+  for (size_t s = 0; s < n; ++s) {
+    if (!member[s] || place[s] >= 0) continue;
+    const int32_t id = static_cast<int32_t>(places.size());
+    Place p{static_cast<int32_t>(s), f.d2[s], 0, {0, 0, 0}};
+    const auto c0 = f.cellAt(static_cast<int32_t>(s));
+    const int b0[3] = {fdiv(f.origin[0] + c0[0], C), fdiv(f.origin[1] + c0[1], C), fdiv(f.origin[2] + c0[2], C)};
+    queue.assign(1, static_cast<int32_t>(s));
+    place[s] = id;
+    for (size_t h = 0; h < queue.size(); ++h) {
+      const int32_t i = queue[h];
+      const auto c = f.cellAt(i);
+      ++p.cells;
+      for (int a = 0; a < 3; ++a) p.sum[a] += f.origin[a] + c[a];
+      if (f.d2[i] > p.d2 || (f.d2[i] == p.d2 && i < p.centre)) p.centre = i, p.d2 = f.d2[i];
+      for (int dz = -1; dz <= 1; ++dz)
+        for (int dy = -1; dy <= 1; ++dy)
+          for (int dx = -1; dx <= 1; ++dx) {
+            const int x = c[0] + dx, y = c[1] + dy, z = c[2] + dz;
+            if (x < 0 || x >= nx || y < 0 || y >= ny || z < 0 || z >= nz) continue;
+            if (fdiv(f.origin[0] + x, C) != b0[0] || fdiv(f.origin[1] + y, C) != b0[1] || fdiv(f.origin[2] + z, C) != b0[2]) continue;
+            const size_t j = f.index(x, y, z);
+            if (member[j] && place[j] < 0) place[j] = id, queue.push_back(static_cast<int32_t>(j));
+          }
+    }
+    places.push_back(p);
+  }
+  // the pair search: every unordered adjacent pair once, from its lower cell
+  std::map<std::pair<int32_t, int32_t>, std::pair<int32_t, uint32_t>> pairs;
+  for (size_t i = 0; i < n; ++i) {
+    if (place[i] < 0) continue;
+    const auto c = f.cellAt(static_cast<int32_t>(i));
+    for (int dz = 0; dz <= 1; ++dz)
+      for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+          if (dz == 0 && (dy < 0 || (dy == 0 && dx <= 0))) continue;
+          const int x = c[0] + dx, y = c[1] + dy, z = c[2] + dz;
+          if (x < 0 || x >= nx || y < 0 || y >= ny || z >= nz) continue;
+          const size_t j = f.index(x, y, z);
+          if (place[j] < 0 || place[j] == place[i]) continue;
+          auto& e = pairs[{std::min(place[i], place[j]), std::max(place[i], place[j])}];
+          e.first = std::max(e.first, std::min(f.d2[i], f.d2[j]));
+          ++e.second;
+        }
+  }
+  // components by relaxation over the edges (the least place of each), the filter, the renumbering
+  std::vector<int32_t> comp(places.size());
+  for (size_t p = 0; p < places.size(); ++p) comp[p] = static_cast<int32_t>(p);
+  for (bool changed = true; changed;) {
+    changed = false;
+    for (const auto& e : pairs) {
+      const int32_t m = std::min(comp[e.first.first], comp[e.first.second]);
+      if (comp[e.first.first] != m || comp[e.first.second] != m) comp[e.first.first] = comp[e.first.second] = m, changed = true;
+    }
+  }
+  std::vector<uint32_t> size(places.size(), 0);
+  for (size_t p = 0; p < places.size(); ++p) ++size[comp[p]];
+  const uint32_t need = static_cast<uint32_t>(std::max(rq.min_component_size, 1));
+  std::vector<int32_t> place_new(places.size(), -1), comp_new(places.size(), -1);
+  uint32_t kept = 0, kept_comps = 0, comps_all = 0;
+  for (size_t p = 0; p < places.size(); ++p) {
+    if (comp[p] == static_cast<int32_t>(p)) ++comps_all;
+    if (size[comp[p]] < need) continue;
+    if (comp[p] == static_cast<int32_t>(p)) comp_new[p] = static_cast<int32_t>(kept_comps++);
+    place_new[p] = static_cast<int32_t>(kept++);
+  }
+  if (g.stats.n_places_all != places.size() || g.stats.n_edges_all != pairs.size() || g.stats.n_components_all != comps_all || g.stats.n_places != kept ||
+      g.stats.n_components != kept_comps || g.numPlaces() != kept)
+    return "stats";
+  for (size_t i = 0; i < n; ++i)
+    if (g.place[i] != (place[i] < 0 ? -1 : place_new[place[i]])) return "place";
+  std::vector<uint32_t> degree(kept, 0);
+  size_t e_out = 0;
+  for (const auto& e : pairs) {
+    const int32_t a = place_new[e.first.first], b = place_new[e.first.second];
+    if (a < 0) continue;
+    if (e_out >= g.numEdges() || g.edge_a[e_out] != static_cast<uint32_t>(a) || g.edge_b[e_out] != static_cast<uint32_t>(b) ||
+        g.edge_clearance_d2[e_out] != e.second.first || g.edge_n_contacts[e_out] != e.second.second)
+      return "edges";
+    ++degree[a], ++degree[b], ++e_out;
+  }
+  if (e_out != g.numEdges() || g.stats.n_edges != e_out) return "edges";
+  for (size_t p = 0; p < places.size(); ++p) {
+    if (place_new[p] < 0) continue;
+    const size_t q = static_cast<size_t>(place_new[p]);
+    const Place& P = places[p];
+    const auto c = f.cellAt(P.centre);
+    for (int a = 0; a < 3; ++a)
+      if (g.centre[3 * q + a] != f.origin[a] + c[a] || g.sum[3 * q + a] != P.sum[a]) return "centre";
+    if (g.centre_d2[q] != P.d2 || std::memcmp(&g.radius[q], &f.distance[P.centre], 4) != 0 || g.basis[q] != f.basis[P.centre] || g.n_cells[q] != P.cells) return "centre";
+    const int32_t s = f.site[P.centre];
+    const auto sc = s >= 0 ? f.cellAt(s) : std::array<int32_t, 3>{0, 0, 0};
+    for (int a = 0; a < 3; ++a)
+      if (g.site[3 * q + a] != (s >= 0 ? f.origin[a] + sc[a] : 0)) return "site";
+    if (g.degree[q] != degree[q] || g.component[q] != static_cast<uint32_t>(comp_new[comp[p]])) return "component";
+  }
+  return nullptr;
+}
+
+// aw_demo --places <config.yaml> <width> <height> <frames>: a Khronos sink asks, per output, for the Voronoi field of a box around the
+// sensor and for the places graph of that field -- hydra::PlacesConfig from the file's freespace_places -- through
+// VolumetricMap::placesGraph (khr_places_graph), and sets it against the host's flood fill and pair search over the downloaded
+// field, which the call replaces.  One JSON line.
+static int placesDemo(int argc, char** argv) {
+  if (argc < 6) {
+    std::fprintf(stderr, "usage: aw_demo --places <config.yaml> <width> <height> <frames>\n");
+    return 2;
+  }
+  std::ifstream in(argv[2]);
+  std::stringstream ss;
+  ss << in.rdbuf();
+  const int W = std::atoi(argv[3]), H = std::atoi(argv[4]), N = std::atoi(argv[5]);
+  constexpr int kWarm = 3;  // frames before the average (the buffers grow on the first calls)
+  ActiveWindow::Config cfg = ActiveWindow::Config::fromYamlString(ss.str());
+  cfg.max_frame_pixels = static_cast<uint32_t>(W) * H;
+  const khronos_amd::YamlNode root = khronos_amd::parseYaml(ss.str());
+  const hydra::DistanceFieldConfig dfc = hydra::DistanceFieldConfig::fromYaml(root);
+  const hydra::VoronoiConfig vc = hydra::VoronoiConfig::fromYaml(root);
+  const hydra::PlacesConfig pc = hydra::PlacesConfig::fromYaml(root);
+  auto out_queue = std::make_shared<ActiveWindow::OutputQueue>();
+  ActiveWindow aw(cfg, out_queue);
+  int frames = 0, agree = 0, timed = 0, compression = 0;
+  double ms_dev = 0, ms_host = 0;
+  size_t cells = 0;
+  khr_places_stats last{};
+  std::string first_mismatch;
+  using clk = std::chrono::steady_clock;
+  aw.addKhronosSink([&](const FrameData& data, const VolumetricMap& map, const Tracks&) {
+    hydra::VoronoiRequest rq(dfc, vc);
+    const float cell = map.config.voxel_size * static_cast<float>(rq.ratio);
+    const int half = std::min(KHR_DF_MAX_DIM / 2, static_cast<int>(std::floor(rq.max_distance / cell)) + 12);
+    const int hd[3] = {half, half, std::max(1, half / 2)};
+    for (int a = 0; a < 3; ++a) {
+      rq.origin[a] = static_cast<int32_t>(std::floor(data.input.world_T_sensor[4 * a + 3] / static_cast<double>(cell))) - hd[a];
+      rq.dims[a] = 2 * hd[a];
+    }
+    const hydra::VoronoiField f = map.voronoiField(rq);
+    const khr_places_request prq = pc.request(f.cell_size, vc.min_basis);
+    compression = prq.compression;
+    khr_sync(map.ctx());
+    const auto t0 = clk::now();
+    const hydra::PlacesGraph g = map.placesGraph(f, prq);
+    const auto t1 = clk::now();
+    const char* diff = placesCheck(f, g, prq);
+    const auto t2 = clk::now();
+    if (!diff) ++agree;
+    else if (first_mismatch.empty()) first_mismatch = "frame " + std::to_string(frames) + ": " + diff + " differs";
+    last = g.stats;
+    cells = f.size();
+    if (frames >= kWarm) {
+      ms_dev += std::chrono::duration<double, std::milli>(t1 - t0).count();
+      ms_host += std::chrono::duration<double, std::milli>(t2 - t1).count();
+      ++timed;
+    }
+    ++frames;
+  });
+  void* scene = synth_create(1234, 12, 1);
+  const size_t n = static_cast<size_t>(W) * H;
+  std::vector<float> depth(n);
+  std::vector<uint8_t> rgb(n * 3);
+  std::vector<int32_t> label(n);
+  for (int i = 0; i < N; ++i) {
+    hydra::InputPacket pkt;
+    pkt.timestamp_ns = static_cast<uint64_t>(std::llround((1.0 + 0.1 * i) * 1e9));
+    circlePose(0.1 * i, pkt.world_T_body);
+    pkt.sensor = {W, H, W / 2.f, W / 2.f, W / 2.f, H / 2.f, 0.1f, 5.f};
+    synth_render(scene, W, H, pkt.sensor.fx, pkt.sensor.fy, pkt.sensor.cx, pkt.sensor.cy, pkt.world_T_body, 0.1 * i, 5.f, 0.f,
+                 1234u + 7919u * i, depth.data(), rgb.data(), label.data(), 0);
+    pkt.depth = depth.data();
+    pkt.color = rgb.data();
+    pkt.labels = label.data();
+    aw.step(pkt);
+    hydra::ActiveWindowOutput::Ptr popped;
+    while (out_queue->pop(&popped)) {}
+  }
+  aw.finishMapping();
+  synth_destroy(scene);
+  const double d = timed ? static_cast<double>(timed) : 1.0;
+  auto u = [](uint64_t v) { return static_cast<unsigned long long>(v); };
+  std::printf("{\"what\": \"the places graph of the Voronoi field of a box around the sensor (VolumetricMap::placesGraph, against the host's flood fill and "
+              "pair search over the downloaded field), %dx%d, voxel %.4g m, ratio %d, compression %d cells, min_node_distance %.4g m, min_component_size %d\", "
+              "\"frames\": %d, \"agree_frames\": %d, \"first_mismatch\": \"%s\", \"timed_frames\": %d, \"cells\": %zu, \"last_stats\": {\"n_members\": %llu, "
+              "\"n_places_all\": %llu, \"n_edges_all\": %llu, \"n_components_all\": %llu, \"n_places\": %llu, \"n_edges\": %llu, \"n_components\": %llu}, "
+              "\"device_ms\": %.4f, \"host_ms\": %.4f}\n",
+              W, H, static_cast<double>(cfg.volumetric_map.voxel_size), dfc.ratio, compression, static_cast<double>(pc.min_node_distance_m), pc.minComponentSize(),
+              frames, agree, first_mismatch.c_str(), timed, cells, u(last.n_members), u(last.n_places_all), u(last.n_edges_all), u(last.n_components_all),
+              u(last.n_places), u(last.n_edges), u(last.n_components), ms_dev / d, ms_host / d);
   return agree == frames && frames == N ? 0 : 3;
 }
 
@@ -2004,6 +2206,14 @@ int main(int argc, char** argv) {
   if (argc >= 2 && std::string(argv[1]) == "--voronoi") {
     try {
       return voronoiDemo(argc, argv);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "aw_demo: %s\n", e.what());
+      return 1;
+    }
+  }
+  if (argc >= 2 && std::string(argv[1]) == "--places") {
+    try {
+      return placesDemo(argc, argv);
     } catch (const std::exception& e) {
       std::fprintf(stderr, "aw_demo: %s\n", e.what());
       return 1;

@@ -231,6 +231,39 @@ int main(int argc, char** argv) {
                 static_cast<double>(c.min_weight), c.positive_distance_only ? 1 : 0, c.ratio);
     return 0;
   }
+  if (argc > 1 && std::strcmp(argv[1], "--places-config") == 0) {
+    // hydra::PlacesConfig on the values the reference's mapper files set under frontend.freespace_places
+    // (tests/test_cpu_places_replica.py); then the clamp of the compression at both ends and the filter switched off
+    const std::string text =
+        "frontend:\n"
+        "  freespace_places:\n"
+        "    type: gvd\n"
+        "    filter_places: true\n"
+        "    min_places_component_size: 3\n"
+        "    gvd:\n"
+        "      max_distance_m: 4.5\n"
+        "      extract_graph: true\n"
+        "    graph:\n"
+        "      type: CompressionGraphExtractor\n"
+        "      compression_distance_m: 1.5\n"
+        "      min_node_distance_m: 0.4\n"
+        "    tsdf_interpolator:\n"
+        "      type: downsample\n"
+        "      ratio: 2\n";
+    const khronos_amd::YamlNode root = khronos_amd::parseYaml(text);
+    const hydra::PlacesConfig c = hydra::PlacesConfig::fromYaml(root);
+    const khr_places_request rq = c.request(0.1f * 2.f, 3);
+    if (rq.min_basis != 3 || rq.compression != c.compressionFor(0.2f) || rq.min_node_distance != c.min_node_distance_m || rq.min_component_size != 3) {
+      std::fprintf(stderr, "PlacesConfig::request does not carry its configuration\n");
+      return 1;
+    }
+    hydra::PlacesConfig off = c;
+    off.filter_places = false;
+    std::printf("compression=%d min_node_distance=%.9g min_component_size=%d compression_small_cells=%d compression_large_cells=%d unfiltered_min_component_size=%d\n",
+                rq.compression, static_cast<double>(rq.min_node_distance), rq.min_component_size, c.compressionFor(0.01f), c.compressionFor(5.f),
+                off.minComponentSize());
+    return 0;
+  }
   if (argc > 1 && std::strcmp(argv[1], "--voronoi-config") == 0) {
     // hydra::VoronoiConfig on the values the reference's jackal mapper file sets under frontend.freespace_places.gvd
     // (tests/test_cpu_voronoi_replica.py); then every mode string, and the clamp of min_basis at both ends

@@ -445,6 +445,66 @@ struct VoronoiField {
   std::array<int32_t, 3> cellAt(int32_t linear) const { return {linear % dims[0], (linear / dims[0]) % dims[1], linear / (dims[0] * dims[1])}; }
 };
 
+// The graph parameters of the same stage (freespace_places.graph, filter_places and min_places_component_size of the mapper files):
+// how far a place reaches, how near an obstacle it may lie, and which islands of places are dropped.  compressionFor turns
+// compression_distance_m into cells of the field: floor(distance / cell size), clamped to 1 .. KHR_PL_MAX_COMPRESSION (the
+// reference's 1.5 m over cells of 0.2 m gives 7).  Without filter_places every component is kept.
+struct PlacesConfig {
+  float compression_distance_m = 1.0f;
+  float min_node_distance_m = 0.f;
+  bool filter_places = false;
+  int min_places_component_size = 1;
+  static PlacesConfig fromYaml(const khronos_amd::YamlNode& root) {
+    PlacesConfig c;
+    const khronos_amd::YamlNode* fp = root.find("freespace_places");
+    if (!fp)
+      if (const khronos_amd::YamlNode* fe = root.find("frontend")) fp = fe->find("freespace_places");
+    if (!fp) return c;
+    if (fp->has("filter_places")) fp->read("filter_places", c.filter_places);
+    if (fp->has("min_places_component_size")) fp->read("min_places_component_size", c.min_places_component_size);
+    if (const khronos_amd::YamlNode* g = fp->find("graph")) {
+      if (g->has("compression_distance_m")) g->read("compression_distance_m", c.compression_distance_m);
+      if (g->has("min_node_distance_m")) g->read("min_node_distance_m", c.min_node_distance_m);
+    }
+    return c;
+  }
+  int compressionFor(float cell_size) const {
+    return std::min<int>(KHR_PL_MAX_COMPRESSION, std::max(1, static_cast<int>(std::floor(compression_distance_m / cell_size))));
+  }
+  int minComponentSize() const { return filter_places ? std::max(1, min_places_component_size) : 1; }
+  // the request for a field of `cell_size` metres per cell; min_basis as VoronoiConfig gives it
+  khr_places_request request(float cell_size, int min_basis = 0) const {
+    khr_places_request rq{};
+    rq.min_basis = min_basis, rq.min_node_distance = min_node_distance_m, rq.compression = compressionFor(cell_size), rq.min_component_size = minComponentSize();
+    return rq;
+  }
+};
+
+// Places and their links from the Voronoi cells of the last voronoiField (khr_places_graph; ASSUMPTIONS.md A.21): one row per kept
+// place and per kept edge, and the kept place of every cell of that field's box (-1 for none).
+struct PlacesGraph {
+  std::vector<int32_t> place;       // per cell of the box, x + nx * (y + ny * z)
+  std::vector<int32_t> centre;      // 3 per place: global cell
+  std::vector<int32_t> centre_d2;
+  std::vector<float> radius;        // metres: the centre's distance
+  std::vector<uint8_t> basis;
+  std::vector<int32_t> site;        // 3 per place: the centre's nearest obstacle cell, global
+  std::vector<uint32_t> n_cells;
+  std::vector<int64_t> sum;         // 3 per place: the members' global cells summed
+  std::vector<uint32_t> degree, component;
+  std::vector<uint32_t> edge_a, edge_b;
+  std::vector<int32_t> edge_clearance_d2;
+  std::vector<uint32_t> edge_n_contacts;
+  khr_places_stats stats{};
+  size_t numPlaces() const { return n_cells.size(); }
+  size_t numEdges() const { return edge_a.size(); }
+  // the mean of a place's member cells, in cells
+  std::array<double, 3> centroid(size_t p) const {
+    const double n = static_cast<double>(n_cells[p]);
+    return {static_cast<double>(sum[3 * p]) / n, static_cast<double>(sum[3 * p + 1]) / n, static_cast<double>(sum[3 * p + 2]) / n};
+  }
+};
+
 // What changed between the live map and another map (VolumetricMap::diff; khr_diff_map, ASSUMPTIONS.md A.18): the changed blocks
 // in (x, y, z) order, the changed voxels of a block in ascending linear index.  Per voxel: x, y, z of its global voxel index in
 // this map's frame, kind, the two distances, the label of the occupied side and last_observed of either side; per block: its
@@ -661,6 +721,26 @@ class VolumetricMap {
                                f.cell_basis.data(), f.cell_sites.data()) != KHR_OK)
       throw std::runtime_error(std::string("khr_voronoi_field_into: ") + khr_last_error());
     return f;
+  }
+
+  // The places graph of the last voronoiField `field` of this map (khr_places_graph): computed on the device, two host waits for the
+  // counts, then the lists are copied.  Throws on a bad request or without a Voronoi field.
+  PlacesGraph placesGraph(const VoronoiField& field, const khr_places_request& request) const {
+    PlacesGraph g;
+    if (khr_places_graph(ctx_, &request, &g.stats) != KHR_OK) throw std::runtime_error(std::string("khr_places_graph: ") + khr_last_error());
+    const size_t p = static_cast<size_t>(g.stats.n_places), e = static_cast<size_t>(g.stats.n_edges);
+    g.place.resize(field.size());
+    g.centre.resize(3 * p); g.centre_d2.resize(p); g.radius.resize(p); g.basis.resize(p); g.site.resize(3 * p); g.n_cells.resize(p); g.sum.resize(3 * p);
+    g.degree.resize(p); g.component.resize(p);
+    g.edge_a.resize(e); g.edge_b.resize(e); g.edge_clearance_d2.resize(e); g.edge_n_contacts.resize(e);
+    if (khr_places_graph_into(ctx_, 0, g.place.data(), g.centre.data(), g.centre_d2.data(), g.radius.data(), g.basis.data(), g.site.data(), g.n_cells.data(),
+                              g.sum.data(), g.degree.data(), g.component.data(), g.edge_a.data(), g.edge_b.data(), g.edge_clearance_d2.data(),
+                              g.edge_n_contacts.data()) != KHR_OK)
+      throw std::runtime_error(std::string("khr_places_graph_into: ") + khr_last_error());
+    return g;
+  }
+  PlacesGraph placesGraph(const VoronoiField& field, const PlacesConfig& config, int min_basis = 0) const {
+    return placesGraph(field, config.request(field.cell_size, min_basis));
   }
   // The map save / load role of hydra::VolumetricMap (un-vendored upstream; the reference's own tree has no counterpart): the live
   // map as one checkpoint file (khr_checkpoint_save: the format is in include/khronos_amd.h) and back into an EMPTY map of the
