@@ -1120,6 +1120,74 @@ int khr_places_graph_into(khr_ctx* ctx, int on_device, int32_t* place, int32_t* 
                           int32_t* site, uint32_t* n_cells, int64_t* sum, uint32_t* degree, uint32_t* component, uint32_t* edge_a,
                           uint32_t* edge_b, int32_t* edge_clearance_d2, uint32_t* edge_n_contacts);
 
+/* ---- clearance-bounded travel cost and paths in a box of cells (ASSUMPTIONS.md A.22) -----------------------------------------
+ * What a caller of the free-space stage asks after the places: can a body of radius `clearance` get from here to there, how far
+ * is it going round the obstacles, and by which cells.  No reference counterpart in its tree; the definition is this library's,
+ * all integers apart from one float32 compare, so the result is the same bit for bit under any schedule.
+ * khr_travel_field reads distance and status of the last successful khr_voronoi_field of ctx (KHR_ESTATE without one; the Voronoi
+ * result is only read and stays valid).  khr_travel_field_from takes the box (origin, dims: 3 int32 each, cells) and the two
+ * arrays of dims[0] * dims[1] * dims[2] entries in the order lin = x + nx * (y + ny * z) from the caller, as khr_distance_field
+ * and khr_voronoi_field write them -- host arrays (on_device == 0, copied through page-locked staging) or device arrays read in
+ * stream order; `goals` lies where the field lies -- and is the same code from there.  Only the cells of the box take part.
+ * TRAVERSABLE: distance >= clearance (float32; a NaN is not) and KHR_DF_OBSERVED set with KHR_DF_OBSTACLE clear; with
+ * allow_unknown != 0 also every cell without KHR_DF_OBSERVED.  MOVES: to the 6, 18 or 26 neighbours, cost 10 along an axis, 14
+ * across a face diagonal, 17 across a space diagonal, allowed iff both end cells are traversable and inside the box; no further
+ * corner rule (the clearance carries that).  GOALS: n_goals global cells (3 int32 each); a goal outside the box or on a cell that
+ * is not traversable is ignored; of several goals on one cell the least index counts.
+ * Result per cell: (cost, goal) = the lexicographic minimum over the usable goals g of (the least move-cost sum from g to the cell,
+ * g): cost uint32, goal int32 = the least index among the goals at least cost; KHR_TF_UNREACHED and -1 for a cell no goal reaches.
+ * A non-zero max_cost reports every cell above it as unreached.  parent (uint8): 13 at a goal's own cell, 255 for an unreached
+ * cell, otherwise the code (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1) of the first allowed neighbour n = cell + (dx, dy, dz), visited
+ * dz outer, dy middle, dx inner, with cost(n) + weight == cost(cell) and goal(n) == goal(cell); following it leads to the goal.
+ * stats (may be NULL): n_traversable, n_goals_used (usable goals, those sharing a cell counted each), n_reached, max_cost (the
+ * greatest cost of a reached cell) describe the result; n_rounds (relaxation rounds in which a tile of KHR_TF_TILE_EDGE^3 cells
+ * ran) and n_waits (host waits for the rounds' "goes on" words, one per KHR_TF_ROUNDS_PER_WAIT rounds queued) describe the
+ * schedule and may differ between two runs.
+ *
+ * Both calls work in stream order on ctx's stream; they wait n_waits times for the rounds and once more for the counts.  The
+ * result lives in buffers ctx owns: it stays valid across later frames until the next travel call, the next khr_voronoi_field
+ * (for khr_travel_field's results), khr_reset_map, khr_checkpoint_load or khr_destroy.  The map, the frame ring, the mesh layer,
+ * khr_stats and the results of the other readers are not touched.
+ * KHR_EINVAL (nothing done, an earlier result stays): a NULL ctx, request, goals or, for _from, origin, dims or input array; a
+ * connectivity other than 6, 18, 26; a negative or non-finite clearance; n_goals outside 1 .. 2^20; for _from dims outside
+ * 1 .. KHR_DF_MAX_DIM, more than 2^24 cells or a box that leaves the cell index range.  KHR_ESTATE (likewise): world_size > 1, no
+ * Voronoi result.  Every other failure discards an earlier result; KHR_ENOMEM leaves the needed bytes in khr_last_error;
+ * KHR_EDEVICE when the rounds exceed their cap of (cells + KHR_TF_ROUNDS_PER_WAIT).  No usable goal is KHR_OK: all unreached.
+ *
+ * khr_travel_field_into copies the result of the last successful call (KHR_ESTATE without one); any pointer may be NULL; it may
+ * be called several times.  on_device == 0: host arrays, filled when the call returns (through page-locked staging);
+ * on_device != 0: device arrays, copied device-to-device in stream order, nothing is awaited.  khr_travel_field_box tells the box
+ * that result describes (origin, dims: 3 int32 each, either may be NULL); KHR_ESTATE without a result.
+ *
+ * khr_travel_paths follows `parent` from each of n_starts (1 .. 2^20) start cells (3 int32 each, global; host or device) of the
+ * last travel result to its goal, one lane per start, with one host wait for the total (*n_cells_total, may be NULL).  A path
+ * lists its cells, start and goal included; a start outside the box or unreached has length 0, path_cost KHR_TF_UNREACHED and
+ * path_goal -1.  KHR_ESTATE without a travel result; KHR_ENOMEM, the needed count in khr_last_error, when the paths hold more
+ * than 2^26 cells; neither touches the travel result.  khr_travel_paths_into copies the paths of the last successful
+ * khr_travel_paths on the travel result that is still valid (KHR_ESTATE otherwise): offsets (int64, n_starts + 1: path i is
+ * cells[3 * offsets[i] .. 3 * offsets[i + 1])), cells (3 int32 per path cell, global), path_cost, path_goal; any may be NULL. */
+#define KHR_TF_UNREACHED 0xFFFFFFFFu
+#define KHR_TF_TILE_EDGE 8
+#define KHR_TF_ROUNDS_PER_WAIT 8
+typedef struct khr_travel_request {
+  float clearance;        /* metres; >= 0 */
+  int32_t connectivity;   /* 6, 18, 26 */
+  int32_t allow_unknown;  /* != 0: cells without KHR_DF_OBSERVED are traversable too */
+  uint32_t max_cost;      /* 0: no limit */
+} khr_travel_request;
+typedef struct khr_travel_stats {
+  uint64_t n_traversable, n_goals_used, n_reached, max_cost;
+  uint64_t n_rounds, n_waits; /* the schedule, not the result */
+} khr_travel_stats;
+int khr_travel_field(khr_ctx* ctx, const khr_travel_request* request, const int32_t* goals, uint64_t n_goals, int goals_on_device,
+                     khr_travel_stats* stats);
+int khr_travel_field_from(khr_ctx* ctx, const khr_travel_request* request, const int32_t* origin, const int32_t* dims, int on_device,
+                          const float* distance, const uint8_t* status, const int32_t* goals, uint64_t n_goals, khr_travel_stats* stats);
+int khr_travel_field_box(khr_ctx* ctx, int32_t* origin, int32_t* dims);
+int khr_travel_field_into(khr_ctx* ctx, int on_device, uint32_t* cost, int32_t* goal, uint8_t* parent);
+int khr_travel_paths(khr_ctx* ctx, uint64_t n_starts, const int32_t* starts, int on_device, uint64_t* n_cells_total);
+int khr_travel_paths_into(khr_ctx* ctx, int on_device, int64_t* offsets, int32_t* cells, uint32_t* path_cost, int32_t* path_goal);
+
 /* ---- tick path: the camera frames of ONE tick batched (sharded multi-camera runs) ------------------------------------
  * In a hash-range sharded run every rank sees every camera frame, so the per-camera work of a
  * rank is what does not shrink with the rank count.  These two calls are khr_upload_frame / khr_integrate for n_frames

@@ -137,6 +137,17 @@ class KhrPlacesStats(C.Structure):
 KHR_PL_MAX_COMPRESSION = 16
 
 
+class KhrTravelRequest(C.Structure):
+    _fields_ = [("clearance", C.c_float), ("connectivity", C.c_int32), ("allow_unknown", C.c_int32), ("max_cost", C.c_uint32)]
+
+
+class KhrTravelStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_traversable", "n_goals_used", "n_reached", "max_cost", "n_rounds", "n_waits")]
+
+
+KHR_TF_UNREACHED, KHR_TF_TILE_EDGE, KHR_TF_ROUNDS_PER_WAIT = 0xFFFFFFFF, 8, 8
+
+
 class KhrAlignRequest(C.Structure):
     _fields_ = [("n", C.c_int64), ("points", C.c_void_p), ("depth", C.c_void_p), ("sensor", KhrSensor), ("stride", C.c_int32),
                 ("weights", C.c_void_p), ("world_T_source", C.c_double * 16), ("min_weight", C.c_float), ("gate", C.c_float),
@@ -225,6 +236,7 @@ EXPORTS = [
     "khr_weld_mesh", "khr_weld_mesh_into", "khr_merge_map", "khr_diff_map", "khr_diff_map_into",
     "khr_segment_map", "khr_segment_map_into", "khr_voronoi_field", "khr_voronoi_field_into",
     "khr_places_graph", "khr_places_graph_from", "khr_places_graph_into", "khr_places_graph_box",
+    "khr_travel_field", "khr_travel_field_from", "khr_travel_field_box", "khr_travel_field_into", "khr_travel_paths", "khr_travel_paths_into",
 ]
 
 _lib = None
@@ -366,6 +378,12 @@ def load_library():
     lib.khr_places_graph_from.argtypes = [vp, C.POINTER(KhrPlacesRequest), vp, vp, i32, vp, vp, vp, vp, C.POINTER(KhrPlacesStats)]
     lib.khr_places_graph_into.argtypes = [vp, i32] + [vp] * 14
     lib.khr_places_graph_box.argtypes = [vp, vp, vp]
+    lib.khr_travel_field.argtypes = [vp, C.POINTER(KhrTravelRequest), vp, C.c_uint64, i32, C.POINTER(KhrTravelStats)]
+    lib.khr_travel_field_from.argtypes = [vp, C.POINTER(KhrTravelRequest), vp, vp, i32, vp, vp, vp, C.c_uint64, C.POINTER(KhrTravelStats)]
+    lib.khr_travel_field_box.argtypes = [vp, vp, vp]
+    lib.khr_travel_field_into.argtypes = [vp, i32, vp, vp, vp]
+    lib.khr_travel_paths.argtypes = [vp, C.c_uint64, vp, i32, C.POINTER(C.c_uint64)]
+    lib.khr_travel_paths_into.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.khr_debug_read.argtypes = [vp, vp, i64]
     lib.khr_debug_live_resources.argtypes = [C.POINTER(i64)]
     lib.khr_tick_ingest.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
@@ -1541,6 +1559,8 @@ class FusionContext:
         """khr_places_graph without raising: (return code, statistics dict)"""
         st = KhrPlacesStats()
         rc = self.lib.khr_places_graph(self.h, C.byref(request) if request is not None else None, C.byref(st))
+        if rc == 0:
+            self._places_kept = int(st.n_places)  # (travel_field(goals="places") sizes its goals with it)
         return rc, {k: int(getattr(st, k)) for k, _ in KhrPlacesStats._fields_}
 
     def places_graph_from_rc(self, request, origin, dims, field, on_device=False):
@@ -1561,6 +1581,8 @@ class FusionContext:
                 keep.append(a)
                 ptrs.append(_ptr(a))
         rc = self.lib.khr_places_graph_from(self.h, C.byref(request) if request is not None else None, o, d, int(on_device), *ptrs, C.byref(st))
+        if rc == 0:
+            self._places_kept = int(st.n_places)
         return rc, {k: int(getattr(st, k)) for k, _ in KhrPlacesStats._fields_}
 
     def places_graph_into(self, out, on_device=False):
@@ -1604,6 +1626,136 @@ class FusionContext:
         rc, stats = self.places_graph_from_rc(rq, origin, dims, dict(distance=distance, d2=d2, basis=basis, site=site), on_device)
         self._chk(rc)
         return self._places_result(stats)
+
+    # name, dtype of the per-cell results of a travel field; of the per-start results of its paths
+    TF_FIELDS = (("cost", np.uint32), ("goal", np.int32), ("parent", np.uint8))
+    TF_INPUTS = (("distance", np.float32), ("status", np.uint8))
+
+    @staticmethod
+    def travel_request(clearance=0.0, connectivity=26, allow_unknown=False, max_cost=0):
+        """a khr_travel_request"""
+        rq = KhrTravelRequest()
+        rq.clearance, rq.connectivity, rq.allow_unknown, rq.max_cost = float(clearance), int(connectivity), int(bool(allow_unknown)), int(max_cost)
+        return rq
+
+    @staticmethod
+    def _travel_goals(goals, on_device, n_goals):
+        """(pointer, count, what to keep alive) of a goal list: an (n, 3) array, or an integer device pointer with n_goals"""
+        if goals is None:
+            return None, 0 if n_goals is None else int(n_goals), None
+        if on_device:
+            return C.c_void_p(int(goals)), int(n_goals), None
+        g = np.ascontiguousarray(goals, np.int32).reshape(-1, 3)
+        return _ptr(g), (len(g) if n_goals is None else int(n_goals)), g
+
+    def travel_field_rc(self, request, goals, goals_on_device=False, n_goals=None):
+        """khr_travel_field without raising: (return code, statistics dict)"""
+        st = KhrTravelStats()
+        gp, n, keep = self._travel_goals(goals, goals_on_device, n_goals)
+        rc = self.lib.khr_travel_field(self.h, C.byref(request) if request is not None else None, gp, n, int(goals_on_device), C.byref(st))
+        return rc, {k: int(getattr(st, k)) for k, _ in KhrTravelStats._fields_}
+
+    def travel_field_from_rc(self, request, origin, dims, field, goals, on_device=False, n_goals=None):
+        """khr_travel_field_from without raising: (return code, statistics dict).  `field`: TF_INPUTS name -> contiguous array of the
+        box's cells, or an integer device pointer with on_device (then `goals` is one too, with n_goals); origin / dims / an input /
+        goals may be None (an argument error)"""
+        st = KhrTravelStats()
+        o = None if origin is None else (C.c_int32 * 3)(*[int(v) for v in origin])
+        d = None if dims is None else (C.c_int32 * 3)(*[int(v) for v in dims])
+        ptrs, keep = [], []
+        for name, dt in self.TF_INPUTS:
+            a = field.get(name)
+            if a is None:
+                ptrs.append(None)
+            elif on_device:
+                ptrs.append(C.c_void_p(int(a)))
+            else:
+                a = np.ascontiguousarray(a, dt)
+                keep.append(a)
+                ptrs.append(_ptr(a))
+        gp, n, g = self._travel_goals(goals, on_device, n_goals)
+        rc = self.lib.khr_travel_field_from(self.h, C.byref(request) if request is not None else None, o, d, int(on_device), *ptrs, gp, n, C.byref(st))
+        return rc, {k: int(getattr(st, k)) for k, _ in KhrTravelStats._fields_}
+
+    def travel_field_into(self, out, on_device=False):
+        """khr_travel_field_into: the last travel field into caller buffers (`out`: TF_FIELDS name -> contiguous array, or an integer
+        device pointer with on_device; absent / None = not copied).  Returns the return code without raising."""
+        ptrs = []
+        for name, _ in self.TF_FIELDS:
+            a = out.get(name)
+            ptrs.append(None if a is None else (C.c_void_p(int(a)) if on_device else _ptr(a)))
+        return self.lib.khr_travel_field_into(self.h, int(on_device), *ptrs)
+
+    def travel_field_box(self):
+        """khr_travel_field_box: (origin, dims) of the box the last travel field describes, as x, y, z"""
+        o, d = (C.c_int32 * 3)(), (C.c_int32 * 3)()
+        self._chk(self.lib.khr_travel_field_box(self.h, o, d))
+        return tuple(int(v) for v in o), tuple(int(v) for v in d)
+
+    def _travel_result(self, stats):
+        origin, dims = self.travel_field_box()
+        shape = (int(dims[2]), int(dims[1]), int(dims[0]))
+        out = {k: np.zeros(shape, dt) for k, dt in self.TF_FIELDS}
+        self._chk(self.travel_field_into(out))
+        out["origin"], out["dims"], out["stats"] = origin, dims, stats
+        return out
+
+    def places_centres(self):
+        """the centres (p, 3) int32, global cells, of the kept places of the last places graph, in place order"""
+        p = getattr(self, "_places_kept", None)
+        centre = np.zeros((0 if p is None else p, 3), np.int32)
+        self._chk(self.places_graph_into({"centre": centre}))  # (KHR_ESTATE without a graph)
+        return centre
+
+    def travel_field(self, goals, clearance, connectivity=26, allow_unknown=False, max_cost=0, field=None):
+        """Travel cost to the nearest goal by travel, for a body of radius `clearance` metres (khr_travel_field, ASSUMPTIONS.md A.22),
+        over the box of the last voronoi_field of this context -- or over `field` = (origin, dims, distance, status), arrays of the
+        box's cells as distance_field / voronoi_field return them (khr_travel_field_from).  `goals`: (n, 3) global cells, or
+        "places": the centres of the kept places of the last places graph, in place order, so that `goal` says to which place a cell
+        belongs by travel.  Returns a dict: cost uint32 (nz, ny, nx), KHR_TF_UNREACHED where no goal reaches; goal int32, -1 there;
+        parent uint8, the code of the next cell towards the goal (13 at a goal, 255 unreached); origin, dims; stats."""
+        if isinstance(goals, str):
+            if goals != "places":
+                raise ValueError("goals: an (n, 3) array of cells or \"places\"")
+            goals = self.places_centres()
+        rq = self.travel_request(clearance, connectivity, allow_unknown, max_cost)
+        if field is None:
+            rc, stats = self.travel_field_rc(rq, goals)
+        else:
+            origin, dims, distance, status = field
+            rc, stats = self.travel_field_from_rc(rq, origin, dims, dict(distance=distance, status=status), goals)
+        self._chk(rc)
+        return self._travel_result(stats)
+
+    def travel_paths_rc(self, starts, on_device=False, n_starts=None):
+        """khr_travel_paths without raising: (return code, cells in all paths)"""
+        total = C.c_uint64(0)
+        sp, n, keep = self._travel_goals(starts, on_device, n_starts)
+        rc = self.lib.khr_travel_paths(self.h, n, sp, int(on_device), C.byref(total))
+        if rc == 0:
+            self._travel_paths_shape = (n, int(total.value))
+        return rc, int(total.value)
+
+    def travel_paths_into(self, out, on_device=False):
+        """khr_travel_paths_into: offsets / cells / path_cost / path_goal of the last travel_paths into caller buffers"""
+        ptrs = []
+        for name in ("offsets", "cells", "path_cost", "path_goal"):
+            a = out.get(name)
+            ptrs.append(None if a is None else (C.c_void_p(int(a)) if on_device else _ptr(a)))
+        return self.lib.khr_travel_paths_into(self.h, int(on_device), *ptrs)
+
+    def travel_paths(self, starts):
+        """The paths from `starts` ((n, 3) global cells) to their goals through the last travel field (khr_travel_paths).  Returns a
+        dict: offsets int64 (n + 1), cells (total, 3) int32 global cells -- path i is cells[offsets[i]:offsets[i + 1]], start and
+        goal included, empty for a start outside the box or unreached --, path_cost uint32, path_goal int32, and paths, the list of
+        the per-start slices of cells."""
+        rc, total = self.travel_paths_rc(starts)
+        self._chk(rc)
+        n = self._travel_paths_shape[0]
+        out = {"offsets": np.zeros(n + 1, np.int64), "cells": np.zeros((total, 3), np.int32), "path_cost": np.zeros(n, np.uint32), "path_goal": np.zeros(n, np.int32)}
+        self._chk(self.travel_paths_into(out))
+        out["paths"] = [out["cells"][out["offsets"][i]:out["offsets"][i + 1]] for i in range(n)]
+        return out
 
     def fetch_mesh_reuse(self, bufs):
         """fetch_mesh() into arrays the caller keeps (a consumer that takes one mesh per output must not pay page faults on 20 MB of

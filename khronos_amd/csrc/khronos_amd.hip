@@ -46,6 +46,7 @@
 #include "khr_kernels_segment.h"
 #include "khr_kernels_voronoi.h"
 #include "khr_kernels_places.h"
+#include "khr_kernels_travel.h"
 
 using namespace khr;
 
@@ -484,6 +485,20 @@ struct khr_ctx {
   int32_t pl_origin[3] = {0, 0, 0}, pl_dims[3] = {0, 0, 0};  // ... and the box (khr_places_graph_box)
   bool pl_valid = false;       // a places graph succeeded and nothing has discarded its result
   bool pl_from_voronoi = false;  // ... and it was read from the Voronoi result
+  // travel fields and paths (khr_travel_field / khr_travel_field_from / khr_travel_paths): the device copy of a host caller's field
+  // and goals, the per-cell keys, masks, tile flags and result arrays, the counters with their page-locked mirror, the page-locked
+  // staging of the host forms; the per-start arrays, the scan's temporary storage and the path cells; each grown to the largest call
+  DevBuf<uint8_t> d_tf_in, d_tf_dense, d_tf_path, d_tf_cub, d_tf_cells;
+  DevBuf<unsigned long long> d_tf_ctr;
+  PinnedBuf<unsigned long long> h_tf;
+  PinnedBuf<uint8_t> h_tf_stage;
+  khr_travel_stats tf_stats{};
+  size_t tf_cells = 0;         // cells of the box the result describes
+  int32_t tf_origin[3] = {0, 0, 0}, tf_dims[3] = {0, 0, 0};  // ... and the box (khr_travel_field_box)
+  bool tf_valid = false;       // a travel field succeeded and nothing has discarded its result
+  bool tf_from_voronoi = false;  // ... and it was read from the Voronoi result
+  size_t tfp_starts = 0, tfp_total = 0;  // starts and path cells of the last khr_travel_paths
+  bool tfp_valid = false;      // ... which succeeded, on the travel field that is still there
   // timing
   uint32_t timing = 0;  // bit i = timer i enabled
   std::vector<TimingRec> pending;
@@ -901,6 +916,7 @@ static int resetMap(khr_ctx* c, float voxel_size, float truncation_distance) {
   c->seg_valid = false;
   c->vor_valid = false;
   c->pl_valid = false;
+  c->tf_valid = c->tfp_valid = false;
   c->host_index_valid = false, ++c->map_gen;
   c->explicit_blocks = 0;
   c->box_listed = false;
@@ -4978,6 +4994,7 @@ int khr_voronoi_field(khr_ctx* c, const khr_voronoi_request* rq, khr_voronoi_sta
   c->vor_valid = false;
   c->vor_stats = khr_voronoi_stats{};
   if (c->pl_from_voronoi) c->pl_valid = false;  // (khr_places_graph: its graph belongs to the field this call replaces)
+  if (c->tf_from_voronoi) c->tf_valid = c->tfp_valid = false;  // (khr_travel_field: so does its travel field)
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = c->stream;
   const int nx = rq->dims[0], ny = rq->dims[1], nz = rq->dims[2];
@@ -5420,6 +5437,326 @@ int khr_places_graph_into(khr_ctx* c, int on_device, int32_t* place, int32_t* ce
   for (int k = 0; k < K; ++k)
     if (dst[k] && bytes[k]) std::memcpy(dst[k], c->h_pl_stage + off[k], bytes[k]);
   return KHR_OK;
+}
+
+// ---- clearance-bounded travel cost and paths in a box of cells (khr_travel_field / khr_travel_field_from / khr_travel_paths;
+// ASSUMPTIONS.md A.22, device side: khr_kernels_travel.h) ----------------------------------------------------------------------
+namespace {
+
+static_assert(kTfRoundsPerWait == KHR_TF_ROUNDS_PER_WAIT && kTfEdge == KHR_TF_TILE_EDGE && kTfUnreached == KHR_TF_UNREACHED, "khr_kernels_travel.h and khronos_amd.h");
+constexpr uint32_t kTfMaxGoals = 1u << 20, kTfMaxStarts = 1u << 20;
+constexpr uint64_t kTfMaxPathCells = uint64_t(1) << 26;
+
+inline size_t tfTiles(const int32_t dims[3]) {
+  size_t t = 1;
+  for (int a = 0; a < 3; ++a) t *= static_cast<size_t>((dims[a] + kTfEdge - 1) / kTfEdge);
+  return t;
+}
+// the per-cell arrays of n cells in `tiles` tiles: the result first, then the work arrays
+struct TfDense {
+  size_t keys, cost, goal, parent, mask, flags, go_on, bytes;
+};
+TfDense tfDense(size_t n, size_t tiles) {
+  TfDense L{};
+  size_t o = 0;
+  auto carve = [&](size_t bytes) { const size_t at = o; o += vorAlign(bytes); return at; };
+  L.keys = carve(8 * n), L.cost = carve(4 * n), L.goal = carve(4 * n), L.parent = carve(n), L.mask = carve(n), L.flags = carve(2 * tiles), L.go_on = carve(4 * kTfRoundsPerWait);
+  L.bytes = o;
+  return L;
+}
+// the per-start arrays of s starts
+struct TfStarts {
+  size_t offsets, starts, path_cost, path_goal, bytes;
+};
+TfStarts tfStarts(size_t s) {
+  TfStarts L{};
+  size_t o = 0;
+  auto carve = [&](size_t bytes) { const size_t at = o; o += vorAlign(bytes); return at; };
+  L.offsets = carve(8 * (s + 1)), L.starts = carve(12 * s), L.path_cost = carve(4 * s), L.path_goal = carve(4 * s);
+  L.bytes = o;
+  return L;
+}
+
+// the request checks both calls share (KHR_EINVAL / KHR_ESTATE: nothing is done)
+int tfCheckRequest(khr_ctx* c, const khr_travel_request* rq, uint64_t n_goals, const char* who) {
+  if (rq->connectivity != 6 && rq->connectivity != 18 && rq->connectivity != 26) return fail(KHR_EINVAL, "%s: connectivity is %d: 6, 18 or 26", who, rq->connectivity);
+  if (!(rq->clearance >= 0.f) || !std::isfinite(rq->clearance)) return fail(KHR_EINVAL, "%s: bad clearance %g", who, static_cast<double>(rq->clearance));
+  if (n_goals < 1 || n_goals > kTfMaxGoals) return fail(KHR_EINVAL, "%s: %llu goals: 1 .. %u", who, static_cast<unsigned long long>(n_goals), kTfMaxGoals);
+  if (c->cfg.world_size > 1) return fail(KHR_ESTATE, "%s needs the whole map: world_size is %d", who, c->cfg.world_size);
+  return KHR_OK;
+}
+
+// the buffers a call needs before its first launch: a box of n cells in `tiles` tiles, `in_bytes` of a host caller's field and goals
+int tfReserve(khr_ctx* c, size_t in_bytes, const TfDense& D) {
+  constexpr size_t kMirror = TFC_COUNT + kTfRoundsPerWait + 1;  // the counters, the rounds' words, the paths' total
+  if (c->d_tf_in.count() < in_bytes || c->d_tf_dense.count() < D.bytes || !c->d_tf_ctr || !c->h_tf || c->h_tf_stage.count() < in_bytes) {
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (whatever still reads the old blocks)
+    if (c->d_tf_in.reserve(in_bytes) || c->d_tf_dense.reserve(D.bytes) || c->d_tf_ctr.reserve(TFC_COUNT) || c->h_tf.reserve(kMirror) || c->h_tf_stage.reserve(in_bytes))
+      return fail(KHR_ENOMEM, "khr_travel_field: work arrays of %zu bytes", in_bytes + D.bytes);
+  }
+  return KHR_OK;
+}
+
+// the stage itself, on device arrays of the box's cells and of the goals
+int tfRun(khr_ctx* c, const khr_travel_request* rq, const int32_t origin[3], const int32_t dims[3], const float* distance, const uint8_t* status,
+          const int32_t* goals, uint64_t n_goals, const TfDense& D, khr_travel_stats* stats) {
+  hipStream_t st = c->stream;
+  const size_t n = static_cast<size_t>(dims[0]) * dims[1] * dims[2], tiles = tfTiles(dims);
+  uint8_t* const db = c->d_tf_dense;
+  TfField f{};
+  f.ox = origin[0], f.oy = origin[1], f.oz = origin[2];
+  f.nx = dims[0], f.ny = dims[1], f.nz = dims[2];
+  f.ntx = (dims[0] + kTfEdge - 1) / kTfEdge, f.nty = (dims[1] + kTfEdge - 1) / kTfEdge, f.ntz = (dims[2] + kTfEdge - 1) / kTfEdge;
+  f.distance = distance, f.status = status;
+  f.clearance = rq->clearance, f.allow_unknown = rq->allow_unknown, f.max_cost = rq->max_cost;
+  f.goals = goals, f.n_goals = static_cast<uint32_t>(n_goals);
+  f.mask = db + D.mask, f.keys = reinterpret_cast<unsigned long long*>(db + D.keys), f.flags = db + D.flags;
+  f.go_on = reinterpret_cast<uint32_t*>(db + D.go_on);
+  f.ctr = c->d_tf_ctr;
+  f.cost = reinterpret_cast<uint32_t*>(db + D.cost), f.goal = reinterpret_cast<int32_t*>(db + D.goal), f.parent = db + D.parent;
+  HIP_TRY(hipMemsetAsync(c->d_tf_ctr, 0, sizeof(unsigned long long) * TFC_COUNT, st));
+  HIP_TRY(hipMemsetAsync(f.keys, 0xff, 8 * n, st));
+  HIP_TRY(hipMemsetAsync(f.flags, 0, 2 * tiles, st));
+  hipLaunchKernelGGL(k_tf_seed, dim3(gridFor(std::max<size_t>(n, static_cast<size_t>(n_goals)))), dim3(256), 0, st, f);
+  HIP_TRY(hipGetLastError());
+  // the rounds: kTfRoundsPerWait launches, then one look at their words.  A shortest path crosses fewer than n tile faces and a
+  // round carries every key across one, so n rounds settle any box; more than that is an error, not a longer loop.
+  unsigned long long* const h = c->h_tf;
+  uint32_t* const h_go = reinterpret_cast<uint32_t*>(h + TFC_COUNT);
+  const uint64_t cap = static_cast<uint64_t>(n) + kTfRoundsPerWait;
+  khr_travel_stats s{};
+  uint64_t queued = 0;
+  bool carry = true;
+  while (carry) {
+    if (queued >= cap) return fail(KHR_EDEVICE, "khr_travel_field: not settled after %llu rounds over %zu cells", static_cast<unsigned long long>(queued), n);
+    HIP_TRY(hipMemsetAsync(f.go_on, 0, 4 * kTfRoundsPerWait, st));
+    for (uint32_t j = 0; j < kTfRoundsPerWait; ++j) {
+      const uint32_t round = static_cast<uint32_t>(queued) + j;
+      if (rq->connectivity == 6) tfLaunchRelax<6>(f, static_cast<unsigned>(tiles), round, j, st);
+      else if (rq->connectivity == 18) tfLaunchRelax<18>(f, static_cast<unsigned>(tiles), round, j, st);
+      else tfLaunchRelax<26>(f, static_cast<unsigned>(tiles), round, j, st);
+    }
+    HIP_TRY(hipGetLastError());
+    queued += kTfRoundsPerWait;
+    HIP_TRY(hipMemcpyAsync(h_go, f.go_on, 4 * kTfRoundsPerWait, hipMemcpyDeviceToHost, st));
+    if (queued == kTfRoundsPerWait) HIP_TRY(hipMemcpyAsync(h, c->d_tf_ctr, sizeof(unsigned long long) * TFC_COUNT, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    ++s.n_waits;
+    if (queued == kTfRoundsPerWait && h[TFC_GOALS_USED] == 0) carry = false;  // (no usable goal: no tile ran)
+    // rounds in which a tile ran: the batch's first if the batch before said so, round j + 1 if round j raised a flag
+    if (carry) ++s.n_rounds;
+    for (uint32_t j = 0; j + 1 < kTfRoundsPerWait; ++j) s.n_rounds += h_go[j] ? 1 : 0;
+    carry = h_go[kTfRoundsPerWait - 1] != 0;
+  }
+  if (rq->connectivity == 6) tfLaunchFinish<6>(f, n, st);
+  else if (rq->connectivity == 18) tfLaunchFinish<18>(f, n, st);
+  else tfLaunchFinish<26>(f, n, st);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h, c->d_tf_ctr, sizeof(unsigned long long) * TFC_COUNT, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  s.n_traversable = h[TFC_TRAVERSABLE], s.n_goals_used = h[TFC_GOALS_USED], s.n_reached = h[TFC_REACHED], s.max_cost = h[TFC_MAX_COST];
+  if (s.n_traversable > n || s.n_reached > s.n_traversable || s.n_goals_used > n_goals)
+    return fail(KHR_EDEVICE, "khr_travel_field: inconsistent counts (%llu reached of %llu traversable of %zu cells)", static_cast<unsigned long long>(s.n_reached),
+                static_cast<unsigned long long>(s.n_traversable), n);
+  c->tf_stats = s;
+  c->tf_cells = n;
+  for (int a = 0; a < 3; ++a) c->tf_origin[a] = origin[a], c->tf_dims[a] = dims[a];
+  c->tf_valid = true;
+  if (stats) *stats = s;
+  return KHR_OK;
+}
+
+// host goals through the page-locked staging into the device copy, at byte `at` of both
+int tfStageGoals(khr_ctx* c, const int32_t* goals, uint64_t n_goals, size_t at) {
+  std::memcpy(c->h_tf_stage + at, goals, 12 * static_cast<size_t>(n_goals));
+  HIP_TRY(hipMemcpyAsync(c->d_tf_in + at, c->h_tf_stage + at, 12 * static_cast<size_t>(n_goals), hipMemcpyHostToDevice, c->stream));
+  return KHR_OK;
+}
+
+}  // namespace
+
+int khr_travel_field(khr_ctx* c, const khr_travel_request* rq, const int32_t* goals, uint64_t n_goals, int goals_on_device, khr_travel_stats* stats) {
+  if (stats) *stats = khr_travel_stats{};
+  if (!c || !rq || !goals) return fail(KHR_EINVAL, "khr_travel_field: null argument");
+  KHR_TRY(tfCheckRequest(c, rq, n_goals, "khr_travel_field"));
+  if (!c->vor_valid) return fail(KHR_ESTATE, "no successful khr_voronoi_field before khr_travel_field");
+  // from here on a failure discards the earlier result
+  c->tf_valid = c->tfp_valid = false;
+  c->tf_stats = khr_travel_stats{};
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = c->vor_cells;
+  const TfDense D = tfDense(n, tfTiles(c->vor_dims));
+  KHR_TRY(tfReserve(c, goals_on_device ? 0 : vorAlign(12 * static_cast<size_t>(n_goals)), D));
+  if (!goals_on_device) KHR_TRY(tfStageGoals(c, goals, n_goals, 0));
+  const VorDense V = vorDense(n);
+  const uint8_t* const vb = c->d_vor_dense;
+  c->tf_from_voronoi = true;
+  return tfRun(c, rq, c->vor_origin, c->vor_dims, reinterpret_cast<const float*>(vb + V.distance), vb + V.status,
+               goals_on_device ? goals : reinterpret_cast<const int32_t*>(c->d_tf_in.get()), n_goals, D, stats);
+}
+
+int khr_travel_field_from(khr_ctx* c, const khr_travel_request* rq, const int32_t* origin, const int32_t* dims, int on_device, const float* distance,
+                          const uint8_t* status, const int32_t* goals, uint64_t n_goals, khr_travel_stats* stats) {
+  if (stats) *stats = khr_travel_stats{};
+  if (!c || !rq || !origin || !dims || !distance || !status || !goals) return fail(KHR_EINVAL, "khr_travel_field_from: null argument");
+  KHR_TRY(tfCheckRequest(c, rq, n_goals, "khr_travel_field_from"));
+  uint64_t cells = 1;
+  for (int a = 0; a < 3; ++a) {
+    if (dims[a] < 1 || dims[a] > KHR_DF_MAX_DIM) return fail(KHR_EINVAL, "khr_travel_field_from: dims[%d] = %d: 1 .. %d", a, dims[a], KHR_DF_MAX_DIM);
+    cells *= static_cast<uint64_t>(dims[a]);
+    const int64_t lo = origin[a], hi = static_cast<int64_t>(origin[a]) + dims[a] - 1;
+    if (lo <= -(int64_t(1) << 30) || hi >= (int64_t(1) << 30)) return fail(KHR_EINVAL, "khr_travel_field_from: the box leaves the cell index range on axis %d", a);
+  }
+  if (cells > (uint64_t(1) << 24)) return fail(KHR_EINVAL, "khr_travel_field_from: %llu cells: at most 2^24", static_cast<unsigned long long>(cells));
+  // from here on a failure discards the earlier result
+  c->tf_valid = c->tfp_valid = false;
+  c->tf_stats = khr_travel_stats{};
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = static_cast<size_t>(cells);
+  const TfDense D = tfDense(n, tfTiles(dims));
+  c->tf_from_voronoi = false;
+  if (on_device) {
+    KHR_TRY(tfReserve(c, 0, D));
+    return tfRun(c, rq, origin, dims, distance, status, goals, n_goals, D, stats);
+  }
+  // a host field and host goals: through the page-locked staging into a device copy
+  const size_t at[3] = {0, vorAlign(4 * n), vorAlign(4 * n) + vorAlign(n)};
+  const size_t in_bytes = at[2] + vorAlign(12 * static_cast<size_t>(n_goals));
+  KHR_TRY(tfReserve(c, in_bytes, D));
+  const void* const src[2] = {distance, status};
+  const size_t bytes[2] = {4 * n, n};
+  for (int k = 0; k < 2; ++k) {
+    std::memcpy(c->h_tf_stage + at[k], src[k], bytes[k]);
+    HIP_TRY(hipMemcpyAsync(c->d_tf_in + at[k], c->h_tf_stage + at[k], bytes[k], hipMemcpyHostToDevice, c->stream));
+  }
+  KHR_TRY(tfStageGoals(c, goals, n_goals, at[2]));
+  const uint8_t* const ib = c->d_tf_in;
+  return tfRun(c, rq, origin, dims, reinterpret_cast<const float*>(ib + at[0]), ib + at[1], reinterpret_cast<const int32_t*>(ib + at[2]), n_goals, D, stats);
+}
+
+int khr_travel_field_box(khr_ctx* c, int32_t* origin, int32_t* dims) {
+  if (!c) return fail(KHR_EINVAL, "null ctx");
+  if (!c->tf_valid) return fail(KHR_ESTATE, "no successful khr_travel_field before khr_travel_field_box");
+  for (int a = 0; a < 3; ++a) {
+    if (origin) origin[a] = c->tf_origin[a];
+    if (dims) dims[a] = c->tf_dims[a];
+  }
+  return KHR_OK;
+}
+
+namespace {
+
+// K result arrays out of ctx's buffers into the caller's: device-to-device in stream order, or through the page-locked staging with one wait
+int tfCopyOut(khr_ctx* c, int on_device, int K, void* const* dst, const void* const* src, const size_t* bytes, const char* who) {
+  if (on_device) {
+    for (int k = 0; k < K; ++k)
+      if (dst[k] && bytes[k]) HIP_TRY(hipMemcpyAsync(dst[k], src[k], bytes[k], hipMemcpyDeviceToDevice, c->stream));
+    return KHR_OK;
+  }
+  size_t off[4], stage_bytes = 0;
+  for (int k = 0; k < K; ++k) {
+    off[k] = stage_bytes;
+    if (dst[k]) stage_bytes += vorAlign(bytes[k]);
+  }
+  if (stage_bytes == 0) return KHR_OK;
+  if (c->h_tf_stage.count() < stage_bytes) {
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (a copy of khr_travel_field_from may still read the old block)
+    if (c->h_tf_stage.reserve(stage_bytes)) return fail(KHR_ENOMEM, "%s: %zu bytes of page-locked staging", who, stage_bytes);
+  }
+  for (int k = 0; k < K; ++k)
+    if (dst[k] && bytes[k]) HIP_TRY(hipMemcpyAsync(c->h_tf_stage + off[k], src[k], bytes[k], hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int k = 0; k < K; ++k)
+    if (dst[k] && bytes[k]) std::memcpy(dst[k], c->h_tf_stage + off[k], bytes[k]);
+  return KHR_OK;
+}
+
+}  // namespace
+
+int khr_travel_field_into(khr_ctx* c, int on_device, uint32_t* cost, int32_t* goal, uint8_t* parent) {
+  if (!c) return fail(KHR_EINVAL, "null ctx");
+  if (!c->tf_valid) return fail(KHR_ESTATE, "no successful khr_travel_field before khr_travel_field_into");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = c->tf_cells;
+  const TfDense D = tfDense(n, tfTiles(c->tf_dims));
+  const uint8_t* const db = c->d_tf_dense;
+  void* const dst[3] = {cost, goal, parent};
+  const void* const src[3] = {db + D.cost, db + D.goal, db + D.parent};
+  const size_t bytes[3] = {4 * n, 4 * n, n};
+  return tfCopyOut(c, on_device, 3, dst, src, bytes, "khr_travel_field_into");
+}
+
+int khr_travel_paths(khr_ctx* c, uint64_t n_starts, const int32_t* starts, int on_device, uint64_t* n_cells_total) {
+  if (n_cells_total) *n_cells_total = 0;
+  if (!c || !starts) return fail(KHR_EINVAL, "khr_travel_paths: null argument");
+  if (n_starts < 1 || n_starts > kTfMaxStarts) return fail(KHR_EINVAL, "khr_travel_paths: %llu starts: 1 .. %u", static_cast<unsigned long long>(n_starts), kTfMaxStarts);
+  if (!c->tf_valid) return fail(KHR_ESTATE, "no successful khr_travel_field before khr_travel_paths");
+  // from here on a failure discards the earlier paths (the travel field stays)
+  c->tfp_valid = false;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const size_t s = static_cast<size_t>(n_starts);
+  const TfStarts L = tfStarts(s);
+  size_t cub_bytes = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, static_cast<long long*>(nullptr), static_cast<long long*>(nullptr), static_cast<int>(s + 1), st));
+  cub_bytes = std::max<size_t>(cub_bytes, 256);
+  const size_t stage_bytes = on_device ? 0 : 12 * s;
+  if (c->d_tf_path.count() < L.bytes || c->d_tf_cub.count() < cub_bytes || c->h_tf_stage.count() < stage_bytes) {
+    HIP_TRY(hipStreamSynchronize(st));  // (whatever still reads the old blocks)
+    if (c->d_tf_path.reserve(L.bytes) || c->d_tf_cub.reserve(cub_bytes) || c->h_tf_stage.reserve(stage_bytes))
+      return fail(KHR_ENOMEM, "khr_travel_paths: work arrays of %zu starts (%zu bytes)", s, L.bytes + cub_bytes);
+  }
+  uint8_t* const pb = c->d_tf_path;
+  if (on_device) {
+    HIP_TRY(hipMemcpyAsync(pb + L.starts, starts, 12 * s, hipMemcpyDeviceToDevice, st));
+  } else {
+    std::memcpy(c->h_tf_stage.get(), starts, 12 * s);
+    HIP_TRY(hipMemcpyAsync(pb + L.starts, c->h_tf_stage.get(), 12 * s, hipMemcpyHostToDevice, st));
+  }
+  const TfDense D = tfDense(c->tf_cells, tfTiles(c->tf_dims));
+  const uint8_t* const db = c->d_tf_dense;
+  TfPaths p{};
+  p.ox = c->tf_origin[0], p.oy = c->tf_origin[1], p.oz = c->tf_origin[2];
+  p.nx = c->tf_dims[0], p.ny = c->tf_dims[1], p.nz = c->tf_dims[2];
+  p.cost = reinterpret_cast<const uint32_t*>(db + D.cost), p.goal = reinterpret_cast<const int32_t*>(db + D.goal), p.parent = db + D.parent;
+  p.starts = reinterpret_cast<const int32_t*>(pb + L.starts), p.n_starts = static_cast<uint32_t>(s);
+  p.offsets = reinterpret_cast<long long*>(pb + L.offsets);
+  p.path_cost = reinterpret_cast<uint32_t*>(pb + L.path_cost), p.path_goal = reinterpret_cast<int32_t*>(pb + L.path_goal);
+  hipLaunchKernelGGL(k_tf_path_count, dim3(gridFor(s + 1)), dim3(256), 0, st, p);
+  HIP_TRY(hipGetLastError());
+  size_t tb = c->d_tf_cub.count();
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_tf_cub.get(), tb, p.offsets, p.offsets, static_cast<int>(s + 1), st));
+  // the one host wait: the total sizes the list
+  unsigned long long* const h_total = c->h_tf + TFC_COUNT + kTfRoundsPerWait;
+  HIP_TRY(hipMemcpyAsync(h_total, p.offsets + s, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint64_t total = *h_total;
+  if (total > kTfMaxPathCells)
+    return fail(KHR_ENOMEM, "khr_travel_paths: the paths hold %llu cells: at most 2^26 in one call", static_cast<unsigned long long>(total));
+  if (c->d_tf_cells.reserve(std::max<size_t>(12 * static_cast<size_t>(total), 256)))
+    return fail(KHR_ENOMEM, "khr_travel_paths: a list of %llu cells (%zu bytes)", static_cast<unsigned long long>(total), 12 * static_cast<size_t>(total));
+  p.cells = reinterpret_cast<int32_t*>(c->d_tf_cells.get()), p.n_cells_total = static_cast<long long>(total);
+  if (total > 0) {
+    hipLaunchKernelGGL(k_tf_path_emit, dim3(gridFor(s)), dim3(256), 0, st, p);
+    HIP_TRY(hipGetLastError());
+  }
+  c->tfp_starts = s, c->tfp_total = static_cast<size_t>(total);
+  c->tfp_valid = true;
+  if (n_cells_total) *n_cells_total = total;
+  return KHR_OK;
+}
+
+int khr_travel_paths_into(khr_ctx* c, int on_device, int64_t* offsets, int32_t* cells, uint32_t* path_cost, int32_t* path_goal) {
+  if (!c) return fail(KHR_EINVAL, "null ctx");
+  if (!c->tf_valid || !c->tfp_valid) return fail(KHR_ESTATE, "no successful khr_travel_paths before khr_travel_paths_into");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t s = c->tfp_starts, total = c->tfp_total;
+  const TfStarts L = tfStarts(s);
+  const uint8_t* const pb = c->d_tf_path;
+  void* const dst[4] = {offsets, cells, path_cost, path_goal};
+  const void* const src[4] = {pb + L.offsets, c->d_tf_cells.get(), pb + L.path_cost, pb + L.path_goal};
+  const size_t bytes[4] = {8 * (s + 1), 12 * total, 4 * s, 4 * s};
+  return tfCopyOut(c, on_device, 4, dst, src, bytes, "khr_travel_paths_into");
 }
 
 // ---- the live map as a registration target (khr_align_linearize / khr_align_frame; ASSUMPTIONS.md A.14, device side:
@@ -5944,6 +6281,7 @@ int khr_checkpoint_load(khr_ctx* c, const void* buffer, uint64_t n_bytes, int64_
   c->seg_valid = false;   // (khr_segment_map: and the segmentation)
   c->vor_valid = false;   // (khr_voronoi_field: and the Voronoi field)
   c->pl_valid = false;    // (khr_places_graph: and the places graph)
+  c->tf_valid = c->tfp_valid = false;  // (khr_travel_field: and the travel field with its paths)
   khr_checkpoint_header h;
   int rc = khr_checkpoint_inspect(buffer, n_bytes, &h);
   if (rc) return rc;

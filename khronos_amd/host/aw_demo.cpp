@@ -2,7 +2,7 @@
 // thread drives the reference (spinOnce per InputPacket, finishMapping at shutdown), and prints a JSON
 // summary that tests/test_gpu_host.py compares with the step-wise C-ABI path and the oracle.
 // usage: aw_demo <config.yaml> <width> <height> <frames> [object_label]
-//        aw_demo --slices | --render | --query | --distance | --voronoi | --places | --align | --weld | --merge | --diff | --segment | --checkpoint | --bench | --rayver ... (below)
+//        aw_demo --slices | --render | --query | --distance | --voronoi | --places | --travel | --align | --weld | --merge | --diff | --segment | --checkpoint | --bench | --rayver ... (below)
 //   object_label >= 0: the stand-in detector / tracker below; otherwise the plugins named in the config
 #include <execinfo.h>
 #include <csignal>
@@ -10,6 +10,7 @@
 #include <cinttypes>
 #include <cmath>
 #include <cstdio>
+#include <queue>
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
@@ -1166,6 +1167,179 @@ static int placesDemo(int argc, char** argv) {
   return agree == frames && frames == N ? 0 : 3;
 }
 
+// what VolumetricMap::travelField replaces: Dijkstra on the host over the downloaded distance and status (A.22), pairs (cost, goal)
+// in a binary heap.  Returns what differs first, or nullptr.
+static const char* travelCheck(const hydra::VoronoiField& f, const hydra::TravelField& t, const std::vector<int32_t>& goals, const khr_travel_request& rq) {
+  const int nx = f.dims[0], ny = f.dims[1], nz = f.dims[2];
+  const size_t n = f.size();
+  std::vector<uint8_t> trav(n);
+  uint64_t n_trav = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const bool cls = (f.status[i] & KHR_DF_OBSERVED) ? !(f.status[i] & KHR_DF_OBSTACLE) : rq.allow_unknown != 0;
+    trav[i] = cls && f.distance[i] >= rq.clearance;
+    n_trav += trav[i];
+  }
+  const uint64_t far = ~0ull;
+  std::vector<uint64_t> key(n, far);
+  using Item = std::pair<uint64_t, uint32_t>;  // key, cell
+  std::priority_queue<Item, std::vector<Item>, std::greater<Item>> heap;
+  uint64_t used = 0;
+  for (size_t g = 0; g < goals.size() / 3; ++g) {
+    const std::array<int32_t, 3> cell{goals[3 * g], goals[3 * g + 1], goals[3 * g + 2]};
+    if (!t.contains(cell) || !trav[t.index(cell)]) continue;
+    ++used;
+    if (g < key[t.index(cell)]) key[t.index(cell)] = g, heap.push({g, static_cast<uint32_t>(t.index(cell))});
+  }
+  const int most = rq.connectivity == 6 ? 1 : rq.connectivity == 18 ? 2 : 3;
+  while (!heap.empty()) {
+    const Item it = heap.top();
+    heap.pop();
+    if (it.first != key[it.second]) continue;
+    const int x = static_cast<int>(it.second % nx), y = static_cast<int>((it.second / nx) % ny), z = static_cast<int>(it.second / (static_cast<uint32_t>(nx) * ny));
+    for (int c = 0; c < 27; ++c) {
+      const int dx = c % 3 - 1, dy = (c / 3) % 3 - 1, dz = c / 9 - 1, nzr = (dx != 0) + (dy != 0) + (dz != 0);
+      const int X = x + dx, Y = y + dy, Z = z + dz;
+      if (nzr == 0 || nzr > most || X < 0 || X >= nx || Y < 0 || Y >= ny || Z < 0 || Z >= nz) continue;
+      const size_t q = f.index(X, Y, Z);
+      const uint64_t cand = it.first + (static_cast<uint64_t>(nzr == 1 ? 10 : nzr == 2 ? 14 : 17) << 32);
+      if (!trav[q] || (rq.max_cost && (cand >> 32) > rq.max_cost) || cand >= key[q]) continue;
+      key[q] = cand;
+      heap.push({cand, static_cast<uint32_t>(q)});
+    }
+  }
+  uint64_t reached = 0, top = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const bool r = key[i] != far;
+    reached += r;
+    if (r) top = std::max<uint64_t>(top, key[i] >> 32);
+    if (t.cost[i] != (r ? static_cast<uint32_t>(key[i] >> 32) : KHR_TF_UNREACHED)) return "cost";
+    if (t.goal[i] != (r ? static_cast<int32_t>(static_cast<uint32_t>(key[i])) : -1)) return "goal";
+    if ((t.parent[i] == 255) != !r || (t.parent[i] == 13) != (r && (key[i] >> 32) == 0)) return "parent";
+  }
+  if (t.stats.n_traversable != n_trav || t.stats.n_goals_used != used || t.stats.n_reached != reached || t.stats.max_cost != top) return "stats";
+  return nullptr;
+}
+
+// aw_demo --travel <config.yaml> <width> <height> <frames>: a Khronos sink asks, per output, for the Voronoi field of a box around the
+// sensor and for the travel field from the camera's cell -- hydra::TravelConfig from the file's freespace_places.travel -- through
+// VolumetricMap::travelField (khr_travel_field), sets it against Dijkstra on the host over the downloaded field, which the call
+// replaces, and traces the path from the reached cell furthest away (VolumetricMap::travelPaths).  One JSON line: the reach from the
+// camera's cell and that path.
+static int travelDemo(int argc, char** argv) {
+  if (argc < 6) {
+    std::fprintf(stderr, "usage: aw_demo --travel <config.yaml> <width> <height> <frames>\n");
+    return 2;
+  }
+  std::ifstream in(argv[2]);
+  std::stringstream ss;
+  ss << in.rdbuf();
+  const int W = std::atoi(argv[3]), H = std::atoi(argv[4]), N = std::atoi(argv[5]);
+  constexpr int kWarm = 3;  // frames before the average (the buffers grow on the first calls)
+  ActiveWindow::Config cfg = ActiveWindow::Config::fromYamlString(ss.str());
+  cfg.max_frame_pixels = static_cast<uint32_t>(W) * H;
+  const khronos_amd::YamlNode root = khronos_amd::parseYaml(ss.str());
+  const hydra::DistanceFieldConfig dfc = hydra::DistanceFieldConfig::fromYaml(root);
+  const hydra::VoronoiConfig vc = hydra::VoronoiConfig::fromYaml(root);
+  const hydra::TravelConfig tc = hydra::TravelConfig::fromYaml(root);
+  auto out_queue = std::make_shared<ActiveWindow::OutputQueue>();
+  ActiveWindow aw(cfg, out_queue);
+  int frames = 0, agree = 0, timed = 0, paths_ok = 0;
+  double ms_dev = 0, ms_host = 0;
+  size_t cells = 0, path_cells = 0;
+  uint32_t path_cost = 0;
+  khr_travel_stats last{};
+  std::string first_mismatch, path_text;
+  using clk = std::chrono::steady_clock;
+  aw.addKhronosSink([&](const FrameData& data, const VolumetricMap& map, const Tracks&) {
+    hydra::VoronoiRequest rq(dfc, vc);
+    const float cell = map.config.voxel_size * static_cast<float>(rq.ratio);
+    const int half = std::min(KHR_DF_MAX_DIM / 2, static_cast<int>(std::floor(rq.max_distance / cell)) + 12);
+    const int hd[3] = {half, half, std::max(1, half / 2)};
+    std::vector<int32_t> camera(3);
+    for (int a = 0; a < 3; ++a) {
+      camera[a] = static_cast<int32_t>(std::floor(data.input.world_T_sensor[4 * a + 3] / static_cast<double>(cell)));
+      rq.origin[a] = camera[a] - hd[a];
+      rq.dims[a] = 2 * hd[a];
+    }
+    const hydra::VoronoiField f = map.voronoiField(rq);
+    const khr_travel_request trq = tc.request(f.cell_size);
+    khr_sync(map.ctx());
+    const auto t0 = clk::now();
+    const hydra::TravelField t = map.travelField(f, camera, trq);
+    const auto t1 = clk::now();
+    const char* diff = travelCheck(f, t, camera, trq);
+    const auto t2 = clk::now();
+    if (!diff) ++agree;
+    else if (first_mismatch.empty()) first_mismatch = "frame " + std::to_string(frames) + ": " + diff + " differs";
+    // the path from the reached cell furthest away (the first such cell), and from a cell outside the box
+    size_t far_cell = 0;
+    for (size_t i = 0; i < t.size(); ++i)
+      if (t.cost[i] != KHR_TF_UNREACHED && (t.cost[far_cell] == KHR_TF_UNREACHED || t.cost[i] > t.cost[far_cell])) far_cell = i;
+    const std::array<int32_t, 3> fc = f.cellAt(static_cast<int32_t>(far_cell));
+    const std::vector<int32_t> starts = {t.origin[0] + fc[0], t.origin[1] + fc[1], t.origin[2] + fc[2], t.origin[0] - 1, t.origin[1], t.origin[2]};
+    const hydra::TravelPaths p = map.travelPaths(starts);
+    bool ok = p.numPaths() == 2 && p.length(1) == 0 && p.path_cost[1] == KHR_TF_UNREACHED && p.path_goal[1] == -1;
+    if (ok && t.stats.n_reached > 0) {
+      const size_t len = p.length(0);
+      ok = len >= 1 && p.path_cost[0] == t.cost[far_cell] && p.path_goal[0] == 0 && p.cells[0] == starts[0] && p.cells[1] == starts[1] && p.cells[2] == starts[2];
+      for (int a = 0; a < 3 && ok; ++a) ok = p.cells[3 * (len - 1) + a] == camera[a];
+      // every step moves to a neighbour and loses the move's weight
+      for (size_t k = 0; k + 1 < len && ok; ++k) {
+        const std::array<int32_t, 3> a{p.cells[3 * k], p.cells[3 * k + 1], p.cells[3 * k + 2]}, b{p.cells[3 * k + 3], p.cells[3 * k + 4], p.cells[3 * k + 5]};
+        const int nzr = (a[0] != b[0]) + (a[1] != b[1]) + (a[2] != b[2]);
+        ok = std::abs(a[0] - b[0]) <= 1 && std::abs(a[1] - b[1]) <= 1 && std::abs(a[2] - b[2]) <= 1 && nzr >= 1 &&
+             t.cost[t.index(a)] - t.cost[t.index(b)] == (nzr == 1 ? 10u : nzr == 2 ? 14u : 17u);
+      }
+      path_cells = len, path_cost = p.path_cost[0];
+      path_text = "[" + std::to_string(starts[0]) + ", " + std::to_string(starts[1]) + ", " + std::to_string(starts[2]) + "]";
+    } else if (ok) {
+      ok = p.length(0) == 0;
+    }
+    if (ok) ++paths_ok;
+    else if (first_mismatch.empty()) first_mismatch = "frame " + std::to_string(frames) + ": the path differs";
+    last = t.stats;
+    cells = f.size();
+    if (frames >= kWarm) {
+      ms_dev += std::chrono::duration<double, std::milli>(t1 - t0).count();
+      ms_host += std::chrono::duration<double, std::milli>(t2 - t1).count();
+      ++timed;
+    }
+    ++frames;
+  });
+  void* scene = synth_create(1234, 12, 1);
+  const size_t n = static_cast<size_t>(W) * H;
+  std::vector<float> depth(n);
+  std::vector<uint8_t> rgb(n * 3);
+  std::vector<int32_t> label(n);
+  for (int i = 0; i < N; ++i) {
+    hydra::InputPacket pkt;
+    pkt.timestamp_ns = static_cast<uint64_t>(std::llround((1.0 + 0.1 * i) * 1e9));
+    circlePose(0.1 * i, pkt.world_T_body);
+    pkt.sensor = {W, H, W / 2.f, W / 2.f, W / 2.f, H / 2.f, 0.1f, 5.f};
+    synth_render(scene, W, H, pkt.sensor.fx, pkt.sensor.fy, pkt.sensor.cx, pkt.sensor.cy, pkt.world_T_body, 0.1 * i, 5.f, 0.f,
+                 1234u + 7919u * i, depth.data(), rgb.data(), label.data(), 0);
+    pkt.depth = depth.data();
+    pkt.color = rgb.data();
+    pkt.labels = label.data();
+    aw.step(pkt);
+    hydra::ActiveWindowOutput::Ptr popped;
+    while (out_queue->pop(&popped)) {}
+  }
+  aw.finishMapping();
+  synth_destroy(scene);
+  const double d = timed ? static_cast<double>(timed) : 1.0;
+  auto u = [](uint64_t v) { return static_cast<unsigned long long>(v); };
+  std::printf("{\"what\": \"the travel field from the camera's cell over the Voronoi field of a box around the sensor (VolumetricMap::travelField, against "
+              "Dijkstra on the host over the downloaded field) and the path from the furthest reached cell, %dx%d, voxel %.4g m, ratio %d, clearance %.4g m, "
+              "connectivity %d\", \"frames\": %d, \"agree_frames\": %d, \"path_frames\": %d, \"first_mismatch\": \"%s\", \"timed_frames\": %d, \"cells\": %zu, "
+              "\"last_stats\": {\"n_traversable\": %llu, \"n_goals_used\": %llu, \"n_reached\": %llu, \"max_cost\": %llu, \"n_rounds\": %llu, \"n_waits\": %llu}, "
+              "\"last_path\": {\"start\": %s, \"cells\": %zu, \"cost\": %u}, \"device_ms\": %.4f, \"host_ms\": %.4f}\n",
+              W, H, static_cast<double>(cfg.volumetric_map.voxel_size), dfc.ratio, static_cast<double>(tc.clearance_m), tc.connectivity, frames, agree, paths_ok,
+              first_mismatch.c_str(), timed, cells, u(last.n_traversable), u(last.n_goals_used), u(last.n_reached), u(last.max_cost), u(last.n_rounds), u(last.n_waits),
+              path_text.empty() ? "null" : path_text.c_str(), path_cells, path_cost, ms_dev / d, ms_host / d);
+  return agree == frames && paths_ok == frames && frames == N ? 0 : 3;
+}
+
 // 64-bit digest of an image's bytes: sum_i mix(i * L + byte_i) mod 2^64, mix = the splitmix64 step of khr_map_digest
 // (tests/test_gpu_render_view.py restates it in numpy)
 static uint64_t imageDigest(const void* data, size_t bytes) {
@@ -2214,6 +2388,14 @@ int main(int argc, char** argv) {
   if (argc >= 2 && std::string(argv[1]) == "--places") {
     try {
       return placesDemo(argc, argv);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "aw_demo: %s\n", e.what());
+      return 1;
+    }
+  }
+  if (argc >= 2 && std::string(argv[1]) == "--travel") {
+    try {
+      return travelDemo(argc, argv);
     } catch (const std::exception& e) {
       std::fprintf(stderr, "aw_demo: %s\n", e.what());
       return 1;

@@ -264,6 +264,32 @@ int main(int argc, char** argv) {
                 off.minComponentSize());
     return 0;
   }
+  if (argc > 1 && std::strcmp(argv[1], "--travel-config") == 0) {
+    // hydra::TravelConfig on its keys under frontend.freespace_places.travel (tests/test_cpu_travel_replica.py); then the defaults
+    // without the section, and a connectivity that is none
+    const std::string text =
+        "frontend:\n"
+        "  freespace_places:\n"
+        "    type: gvd\n"
+        "    travel:\n"
+        "      clearance_m: 0.35\n"
+        "      connectivity: 18\n"
+        "      allow_unknown: true\n"
+        "      max_distance_m: 50\n";
+    const hydra::TravelConfig c = hydra::TravelConfig::fromYaml(khronos_amd::parseYaml(text));
+    const khr_travel_request rq = c.request(0.2f);
+    const hydra::TravelConfig none = hydra::TravelConfig::fromYaml(khronos_amd::parseYaml("frontend:\n  freespace_places:\n    type: gvd\n"));
+    bool rejected = false;
+    try {
+      hydra::TravelConfig::fromYaml(khronos_amd::parseYaml("freespace_places:\n  travel:\n    connectivity: 8\n"));
+    } catch (const std::runtime_error&) {
+      rejected = true;
+    }
+    std::printf("clearance=%.9g connectivity=%d allow_unknown=%d max_cost=%u default_connectivity=%d default_max_cost=%u bad_connectivity=%s\n",
+                static_cast<double>(rq.clearance), rq.connectivity, rq.allow_unknown, rq.max_cost, none.connectivity, none.request(0.2f).max_cost,
+                rejected ? "rejected" : "accepted");
+    return 0;
+  }
   if (argc > 1 && std::strcmp(argv[1], "--voronoi-config") == 0) {
     // hydra::VoronoiConfig on the values the reference's jackal mapper file sets under frontend.freespace_places.gvd
     // (tests/test_cpu_voronoi_replica.py); then every mode string, and the clamp of min_basis at both ends

@@ -505,6 +505,72 @@ struct PlacesGraph {
   }
 };
 
+// What a body needs to move through the free space of the same stage (freespace_places.travel; this library's keys, the reference
+// has no counterpart): clearance_m, the body's radius; connectivity 6, 18 or 26 (anything else throws); allow_unknown, whether
+// unobserved cells may be crossed; max_distance_m, how far to look (0 = everywhere), which maxCostFor turns into move cost: 10 per
+// cell along an axis.
+struct TravelConfig {
+  float clearance_m = 0.f;
+  int connectivity = 26;
+  bool allow_unknown = false;
+  float max_distance_m = 0.f;
+  static TravelConfig fromYaml(const khronos_amd::YamlNode& root) {
+    TravelConfig c;
+    const khronos_amd::YamlNode* fp = root.find("freespace_places");
+    if (!fp)
+      if (const khronos_amd::YamlNode* fe = root.find("frontend")) fp = fe->find("freespace_places");
+    const khronos_amd::YamlNode* t = fp ? fp->find("travel") : nullptr;
+    if (!t) return c;
+    if (t->has("clearance_m")) t->read("clearance_m", c.clearance_m);
+    if (t->has("connectivity")) t->read("connectivity", c.connectivity);
+    if (t->has("allow_unknown")) t->read("allow_unknown", c.allow_unknown);
+    if (t->has("max_distance_m")) t->read("max_distance_m", c.max_distance_m);
+    if (c.connectivity != 6 && c.connectivity != 18 && c.connectivity != 26)
+      throw std::runtime_error("freespace_places.travel.connectivity is " + std::to_string(c.connectivity) + ": 6, 18 or 26");
+    return c;
+  }
+  uint32_t maxCostFor(float cell_size) const {
+    return max_distance_m > 0.f ? static_cast<uint32_t>(std::max(1.0, std::round(10.0 * static_cast<double>(max_distance_m) / static_cast<double>(cell_size)))) : 0u;
+  }
+  // the request for a field of `cell_size` metres per cell
+  khr_travel_request request(float cell_size) const {
+    khr_travel_request rq{};
+    rq.clearance = clearance_m, rq.connectivity = connectivity, rq.allow_unknown = allow_unknown ? 1 : 0, rq.max_cost = maxCostFor(cell_size);
+    return rq;
+  }
+};
+
+// Travel cost, nearest goal by travel and the step towards it for every cell of the last voronoiField's box (khr_travel_field;
+// ASSUMPTIONS.md A.22), in the order x + nx * (y + ny * z).
+struct TravelField {
+  std::array<int32_t, 3> origin{0, 0, 0}, dims{0, 0, 0};
+  std::vector<uint32_t> cost;   // KHR_TF_UNREACHED where no goal reaches
+  std::vector<int32_t> goal;    // index into the goals given; -1 unreached
+  std::vector<uint8_t> parent;  // (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1) of the next cell towards the goal; 13 at a goal, 255 unreached
+  khr_travel_stats stats{};
+  size_t size() const { return cost.size(); }
+  bool contains(const std::array<int32_t, 3>& cell) const {
+    for (int a = 0; a < 3; ++a)
+      if (cell[a] < origin[a] || cell[a] >= origin[a] + dims[a]) return false;
+    return true;
+  }
+  size_t index(const std::array<int32_t, 3>& cell) const {
+    return static_cast<size_t>(cell[0] - origin[0]) + static_cast<size_t>(dims[0]) * (static_cast<size_t>(cell[1] - origin[1]) + static_cast<size_t>(dims[1]) * static_cast<size_t>(cell[2] - origin[2]));
+  }
+  bool reached(const std::array<int32_t, 3>& cell) const { return contains(cell) && cost[index(cell)] != KHR_TF_UNREACHED; }
+};
+
+// The paths of VolumetricMap::travelPaths: path i is cells[3 * offsets[i] .. 3 * offsets[i + 1]), global cells from the start to its
+// goal, both included; empty, with cost KHR_TF_UNREACHED and goal -1, for a start outside the box or unreached.
+struct TravelPaths {
+  std::vector<int64_t> offsets;
+  std::vector<int32_t> cells;
+  std::vector<uint32_t> path_cost;
+  std::vector<int32_t> path_goal;
+  size_t numPaths() const { return path_cost.size(); }
+  size_t length(size_t i) const { return static_cast<size_t>(offsets[i + 1] - offsets[i]); }
+};
+
 // What changed between the live map and another map (VolumetricMap::diff; khr_diff_map, ASSUMPTIONS.md A.18): the changed blocks
 // in (x, y, z) order, the changed voxels of a block in ascending linear index.  Per voxel: x, y, z of its global voxel index in
 // this map's frame, kind, the two distances, the label of the occupied side and last_observed of either side; per block: its
@@ -741,6 +807,31 @@ class VolumetricMap {
   }
   PlacesGraph placesGraph(const VoronoiField& field, const PlacesConfig& config, int min_basis = 0) const {
     return placesGraph(field, config.request(field.cell_size, min_basis));
+  }
+  // Travel cost from `goals` (3 int32 each, global cells) over the box of the last voronoiField `field` of this map
+  // (khr_travel_field): relaxed on the device in rounds, then copied.  Throws on a bad request or without a Voronoi field.
+  TravelField travelField(const VoronoiField& field, const std::vector<int32_t>& goals, const khr_travel_request& request) const {
+    TravelField t;
+    if (khr_travel_field(ctx_, &request, goals.data(), goals.size() / 3, 0, &t.stats) != KHR_OK) throw std::runtime_error(std::string("khr_travel_field: ") + khr_last_error());
+    t.origin = field.origin, t.dims = field.dims;
+    t.cost.resize(field.size()); t.goal.resize(field.size()); t.parent.resize(field.size());
+    if (khr_travel_field_into(ctx_, 0, t.cost.data(), t.goal.data(), t.parent.data()) != KHR_OK)
+      throw std::runtime_error(std::string("khr_travel_field_into: ") + khr_last_error());
+    return t;
+  }
+  TravelField travelField(const VoronoiField& field, const std::vector<int32_t>& goals, const TravelConfig& config) const {
+    return travelField(field, goals, config.request(field.cell_size));
+  }
+  // The paths from `starts` (3 int32 each, global cells) to their goals through the last travelField (khr_travel_paths).
+  TravelPaths travelPaths(const std::vector<int32_t>& starts) const {
+    TravelPaths p;
+    uint64_t total = 0;
+    const size_t n = starts.size() / 3;
+    if (khr_travel_paths(ctx_, n, starts.data(), 0, &total) != KHR_OK) throw std::runtime_error(std::string("khr_travel_paths: ") + khr_last_error());
+    p.offsets.resize(n + 1); p.cells.resize(3 * static_cast<size_t>(total)); p.path_cost.resize(n); p.path_goal.resize(n);
+    if (khr_travel_paths_into(ctx_, 0, p.offsets.data(), p.cells.data(), p.path_cost.data(), p.path_goal.data()) != KHR_OK)
+      throw std::runtime_error(std::string("khr_travel_paths_into: ") + khr_last_error());
+    return p;
   }
   // The map save / load role of hydra::VolumetricMap (un-vendored upstream; the reference's own tree has no counterpart): the live
   // map as one checkpoint file (khr_checkpoint_save: the format is in include/khronos_amd.h) and back into an EMPTY map of the
