@@ -30,6 +30,7 @@
 #include "../../include/khronos_amd.h"
 #include "khr_device.h"
 #include "khr_owned.h"
+#include "khr_box_host.h"
 #include "khr_kernels_aux.h"
 #include "khr_kernels_fusion.h"
 #include "khr_kernels_fuse.h"
@@ -469,9 +470,7 @@ struct khr_ctx {
   PinnedBuf<unsigned long long> h_vor;
   PinnedBuf<uint8_t> h_vor_stage;
   khr_voronoi_stats vor_stats{};
-  size_t vor_cells = 0;     // cells of the box the result describes
-  bool vor_valid = false;   // a Voronoi field succeeded and nothing has discarded its result
-  int32_t vor_origin[3] = {0, 0, 0}, vor_dims[3] = {0, 0, 0};  // ... its box and cell size (khr_places_graph reads the field)
+  BoxResult vor;            // the box of the last Voronoi field and its cell size (khr_places_graph and khr_travel_field read the field)
   float vor_cell_size = 0.f;
   // places graphs (khr_places_graph / khr_places_graph_from): the device copy of a host caller's field, the per-cell work arrays
   // with the dense place ids, the pair / edge / component work lists, the scan's and the sort's temporary storage, the result
@@ -481,10 +480,8 @@ struct khr_ctx {
   PinnedBuf<unsigned long long> h_pl;
   PinnedBuf<uint8_t> h_pl_stage;
   khr_places_stats pl_stats{};
-  size_t pl_cells = 0;         // cells of the box the result describes
-  int32_t pl_origin[3] = {0, 0, 0}, pl_dims[3] = {0, 0, 0};  // ... and the box (khr_places_graph_box)
-  bool pl_valid = false;       // a places graph succeeded and nothing has discarded its result
-  bool pl_from_voronoi = false;  // ... and it was read from the Voronoi result
+  BoxResult pl;                  // the box of the last places graph (khr_places_graph_box)
+  bool pl_from_voronoi = false;  // ... which was read from the Voronoi result
   // travel fields and paths (khr_travel_field / khr_travel_field_from / khr_travel_paths): the device copy of a host caller's field
   // and goals, the per-cell keys, masks, tile flags and result arrays, the counters with their page-locked mirror, the page-locked
   // staging of the host forms; the per-start arrays, the scan's temporary storage and the path cells; each grown to the largest call
@@ -493,10 +490,8 @@ struct khr_ctx {
   PinnedBuf<unsigned long long> h_tf;
   PinnedBuf<uint8_t> h_tf_stage;
   khr_travel_stats tf_stats{};
-  size_t tf_cells = 0;         // cells of the box the result describes
-  int32_t tf_origin[3] = {0, 0, 0}, tf_dims[3] = {0, 0, 0};  // ... and the box (khr_travel_field_box)
-  bool tf_valid = false;       // a travel field succeeded and nothing has discarded its result
-  bool tf_from_voronoi = false;  // ... and it was read from the Voronoi result
+  BoxResult tf;                  // the box of the last travel field (khr_travel_field_box)
+  bool tf_from_voronoi = false;  // ... which was read from the Voronoi result
   size_t tfp_starts = 0, tfp_total = 0;  // starts and path cells of the last khr_travel_paths
   bool tfp_valid = false;      // ... which succeeded, on the travel field that is still there
   // timing
@@ -728,6 +723,66 @@ constexpr int kStreamGrid = 4096;
 // exact (bit-for-bit) arithmetic in the update kernels unless the configuration asks for the relaxed form
 inline bool exactArithmetic(const khr_ctx* c) { return c->cfg.relaxed_arithmetic == 0; }
 
+// ---- what the box-field calls share on the host (khr_distance_field, khr_voronoi_field, khr_places_graph, khr_travel_field;
+// khr_box_host.h holds the part without HIP) ---------------------------------------------------------------------------------
+
+// checkCellBox as the calls report it (KHR_EINVAL; `cells` on success)
+int checkBox(const char* who, const int32_t origin[3], const int32_t dims[3], int ratio, size_t* cells) {
+  int a = -1;
+  switch (checkCellBox(origin, dims, ratio, cells, &a)) {
+    case BOX_BAD_DIM: return fail(KHR_EINVAL, "%s: dims[%d] = %d: 1 .. %d", who, a, dims[a], KHR_DF_MAX_DIM);
+    case BOX_BAD_RANGE: return fail(KHR_EINVAL, "%s: the box leaves the index range on axis %d", who, a);
+    case BOX_BAD_CELLS: return fail(KHR_EINVAL, "%s: %zu cells: at most 2^24", who, *cells);
+    case BOX_OK: break;
+  }
+  return KHR_OK;
+}
+
+// K result arrays out of the context's buffers into the caller's: device-to-device in stream order, or through the feature's
+// page-locked staging with one wait.  A growth of the staging waits first for whatever may still read the old block.
+template <size_t K>
+int copyOut(khr_ctx* c, PinnedBuf<uint8_t>& stage, int on_device, void* const (&dst)[K], const void* const (&src)[K], const size_t (&bytes)[K], const char* who) {
+  if (on_device) {
+    for (size_t k = 0; k < K; ++k)
+      if (dst[k] && bytes[k]) HIP_TRY(hipMemcpyAsync(dst[k], src[k], bytes[k], hipMemcpyDeviceToDevice, c->stream));
+    return KHR_OK;
+  }
+  Arena a;
+  size_t off[K];
+  for (size_t k = 0; k < K; ++k) off[k] = dst[k] ? a.take(bytes[k]) : 0;
+  if (a.bytes() == 0) return KHR_OK;
+  if (stage.count() < a.bytes()) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (stage.reserve(a.bytes())) return fail(KHR_ENOMEM, "%s: %zu bytes of page-locked staging", who, a.bytes());
+  }
+  for (size_t k = 0; k < K; ++k)
+    if (dst[k] && bytes[k]) HIP_TRY(hipMemcpyAsync(stage + off[k], src[k], bytes[k], hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (size_t k = 0; k < K; ++k)
+    if (dst[k] && bytes[k]) std::memcpy(dst[k], stage + off[k], bytes[k]);
+  return KHR_OK;
+}
+
+// a host array into device memory through page-locked staging (the caller has reserved both) ...
+int copyIn(khr_ctx* c, uint8_t* d_in, uint8_t* stage, const void* src, size_t bytes) {
+  std::memcpy(stage, src, bytes);
+  HIP_TRY(hipMemcpyAsync(d_in, stage, bytes, hipMemcpyHostToDevice, c->stream));
+  return KHR_OK;
+}
+// ... and K of them, each at byte at[k] of a device block and of its page-locked mirror
+template <size_t K>
+int copyIn(khr_ctx* c, uint8_t* d_in, uint8_t* stage, const void* const (&src)[K], const size_t (&bytes)[K], const size_t (&at)[K]) {
+  for (size_t k = 0; k < K; ++k) KHR_TRY(copyIn(c, d_in + at[k], stage + at[k], src[k], bytes[k]));
+  return KHR_OK;
+}
+
+// device words into page-locked memory, and the wait for them
+int readWords(khr_ctx* c, const void* d_src, void* h_dst, size_t bytes) {
+  HIP_TRY(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return KHR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -914,9 +969,9 @@ static int resetMap(khr_ctx* c, float voxel_size, float truncation_distance) {
   c->weld_valid = false;
   c->diff_valid = false;
   c->seg_valid = false;
-  c->vor_valid = false;
-  c->pl_valid = false;
-  c->tf_valid = c->tfp_valid = false;
+  c->vor.valid = false;
+  c->pl.valid = false;
+  c->tf.valid = c->tfp_valid = false;
   c->host_index_valid = false, ++c->map_gen;
   c->explicit_blocks = 0;
   c->box_listed = false;
@@ -4804,25 +4859,17 @@ namespace {
 
 // what khr_distance_field and khr_voronoi_field share: the checks of A.15's box and cell classes (KHR_EINVAL; `cells` and the
 // range R in cells on success), and the launch of k_df_gather over the blocks the box overlaps (g.box is filled here)
-int dfCheckBox(khr_ctx* c, const int32_t origin[3], const int32_t dims[3], int ratio, float min_weight, float max_distance, float surface_distance,
-               size_t* n_cells, int* range) {
+int dfCheckBox(khr_ctx* c, const char* who, const int32_t origin[3], const int32_t dims[3], int ratio, float min_weight, float max_distance,
+               float surface_distance, size_t* n_cells, int* range) {
   const int vps = c->cfg.voxels_per_side;
   if (ratio != 1 && ratio != 2 && ratio != 4) return fail(KHR_EINVAL, "ratio %d: 1, 2 or 4", ratio);
   if (vps % ratio != 0) return fail(KHR_EINVAL, "ratio %d does not divide voxels_per_side %d", ratio, vps);
-  uint64_t cells = 1;
-  for (int a = 0; a < 3; ++a) {
-    if (dims[a] < 1 || dims[a] > KHR_DF_MAX_DIM) return fail(KHR_EINVAL, "dims[%d] = %d: 1 .. %d", a, dims[a], KHR_DF_MAX_DIM);
-    cells *= static_cast<uint64_t>(dims[a]);
-    const int64_t lo = static_cast<int64_t>(origin[a]) * ratio, hi = (static_cast<int64_t>(origin[a]) + dims[a]) * ratio - 1;
-    if (lo <= -(int64_t(1) << 30) || hi >= (int64_t(1) << 30)) return fail(KHR_EINVAL, "the box leaves the voxel index range on axis %d", a);
-  }
-  if (cells > (uint64_t(1) << 24)) return fail(KHR_EINVAL, "%llu cells: at most 2^24", static_cast<unsigned long long>(cells));
+  KHR_TRY(checkBox(who, origin, dims, ratio, n_cells));
   if (!std::isfinite(surface_distance)) return fail(KHR_EINVAL, "surface_distance is not finite");
   if (!(min_weight >= 0.f) || !std::isfinite(min_weight)) return fail(KHR_EINVAL, "bad min_weight %g", static_cast<double>(min_weight));
   if (!(max_distance > 0.f) || !std::isfinite(max_distance)) return fail(KHR_EINVAL, "bad max_distance %g", static_cast<double>(max_distance));
   const float reach = max_distance / (c->p.vs * static_cast<float>(ratio));
   if (!(reach < 32768.f)) return fail(KHR_EINVAL, "max_distance %g m is %g cells: fewer than 32768", static_cast<double>(max_distance), static_cast<double>(reach));
-  *n_cells = static_cast<size_t>(cells);
   *range = static_cast<int>(std::floor(reach));
   return KHR_OK;
 }
@@ -4854,7 +4901,7 @@ int khr_distance_field(khr_ctx* c, const khr_df_request* rq, int on_device, floa
   const int ratio = rq->ratio;
   size_t n = 0;
   int R = 0;
-  KHR_TRY(dfCheckBox(c, rq->origin, rq->dims, ratio, rq->min_weight, rq->max_distance, rq->surface_distance, &n, &R));
+  KHR_TRY(dfCheckBox(c, "khr_distance_field", rq->origin, rq->dims, ratio, rq->min_weight, rq->max_distance, rq->surface_distance, &n, &R));
   const float cell_size = c->p.vs * static_cast<float>(ratio);
   if (c->cfg.world_size > 1) return fail(KHR_ESTATE, "khr_distance_field needs the whole map: world_size is %d", c->cfg.world_size);
   HIP_TRY(hipSetDevice(c->device));
@@ -4867,11 +4914,10 @@ int khr_distance_field(khr_ctx* c, const khr_df_request* rq, int on_device, floa
   // the host form: the outputs one after the other in the device staging and its page-locked mirror
   void* const host[3] = {distance, d2, status};
   const size_t per_cell[3] = {4, 4, 1};
-  size_t off[3], stage_bytes = 0;
-  for (int f = 0; f < 3; ++f) {
-    off[f] = stage_bytes;
-    if (host[f]) stage_bytes += (n * per_cell[f] + 255) / 256 * 256;
-  }
+  Arena stage;
+  size_t off[3];
+  for (int f = 0; f < 3; ++f) off[f] = host[f] ? stage.take(n * per_cell[f]) : 0;
+  const size_t stage_bytes = stage.bytes();
   void* dev[3] = {distance, d2, status};
   if (!on_device && stage_bytes) {
     if (stage_bytes > c->d_df_stage.count() || stage_bytes > c->h_df_stage.count()) HIP_TRY(hipStreamSynchronize(c->stream));
@@ -4895,19 +4941,14 @@ int khr_distance_field(khr_ctx* c, const khr_df_request* rq, int on_device, floa
   // three in-place passes per grid; a pass along an axis of one cell (or with R = 0) changes nothing and is left out
   for (int32_t* grid : {g.outer, g.inner}) {
     if (!grid || R < 1) continue;
-    if (nx > 1) {
-      const int per_wg = std::max(1, kDfTileCells / nx);
-      const long long lines = static_cast<long long>(ny) * nz;
-      hipLaunchKernelGGL((k_df_pass<0>), dim3(static_cast<unsigned>((lines + per_wg - 1) / per_wg)), dim3(256), 0, c->stream, grid, nx, ny, nz, R, per_wg);
-    }
-    if (ny > 1) {
-      const int per_wg = std::max(1, kDfTileCells / (ny * kDfStrip));
-      hipLaunchKernelGGL((k_df_pass<1>), dim3((nx + kDfStrip - 1) / kDfStrip, (nz + per_wg - 1) / per_wg), dim3(256), 0, c->stream, grid, nx, ny, nz, R, per_wg);
-    }
-    if (nz > 1) {
-      const int per_wg = std::max(1, kDfTileCells / (nz * kDfStrip));
-      hipLaunchKernelGGL((k_df_pass<2>), dim3((nx + kDfStrip - 1) / kDfStrip, (ny + per_wg - 1) / per_wg), dim3(256), 0, c->stream, grid, nx, ny, nz, R, per_wg);
-    }
+    auto pass = [&](auto axis) {
+      constexpr int A = decltype(axis)::value;
+      const PassGrid p = axisPassGrid(A, nx, ny, nz, kDfTileCells, kDfStrip);
+      hipLaunchKernelGGL((k_df_pass<A>), dim3(p.gx, p.gy), dim3(256), 0, c->stream, grid, nx, ny, nz, R, p.per_wg);
+    };
+    if (nx > 1) pass(std::integral_constant<int, 0>());
+    if (ny > 1) pass(std::integral_constant<int, 1>());
+    if (nz > 1) pass(std::integral_constant<int, 2>());
     HIP_TRY(hipGetLastError());
   }
   DfFinish f{};
@@ -4939,38 +4980,7 @@ int khr_distance_field(khr_ctx* c, const khr_df_request* rq, int on_device, floa
 }
 
 // ---- nearest obstacle cell and generalized Voronoi cells of a box of the live map (khr_voronoi_field; ASSUMPTIONS.md A.20,
-// device side: khr_kernels_voronoi.h) ------------------------------------------------------------------------------------------
-namespace {
-
-inline size_t vorAlign(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
-
-// the dense outputs of n cells one after the other, then the per-workgroup list counts (one word more than workgroups)
-struct VorDense {
-  size_t distance, d2, site, status, basis, wg_count, bytes;
-};
-VorDense vorDense(size_t n) {
-  VorDense L{};
-  size_t o = 0;
-  auto carve = [&](size_t bytes) { const size_t at = o; o += vorAlign(bytes); return at; };
-  L.distance = carve(4 * n), L.d2 = carve(4 * n), L.site = carve(4 * n), L.status = carve(n), L.basis = carve(n);
-  L.wg_count = carve(4 * (static_cast<size_t>(gridFor(n)) + 1));
-  L.bytes = o;
-  return L;
-}
-// the list of m cells
-struct VorList {
-  size_t cells, distance, basis, sites, bytes;
-};
-VorList vorList(size_t m) {
-  VorList L{};
-  size_t o = 0;
-  auto carve = [&](size_t bytes) { const size_t at = o; o += vorAlign(bytes); return at; };
-  L.cells = carve(12 * m), L.distance = carve(4 * m), L.basis = carve(m), L.sites = carve(12 * KHR_VOR_MAX_BASIS * m);
-  L.bytes = std::max<size_t>(o, 256);  // (never empty: the owner exists from the first call on)
-  return L;
-}
-
-}  // namespace
+// device side: khr_kernels_voronoi.h; the layouts of its buffers: vorDense and vorList of khr_box_host.h) -----------------------
 
 int khr_voronoi_field(khr_ctx* c, const khr_voronoi_request* rq, khr_voronoi_stats* stats) {
   if (stats) *stats = khr_voronoi_stats{};
@@ -4979,7 +4989,7 @@ int khr_voronoi_field(khr_ctx* c, const khr_voronoi_request* rq, khr_voronoi_sta
   const int ratio = rq->ratio;
   size_t n = 0;
   int R = 0;
-  KHR_TRY(dfCheckBox(c, rq->origin, rq->dims, ratio, rq->min_weight, rq->max_distance, rq->surface_distance, &n, &R));
+  KHR_TRY(dfCheckBox(c, "khr_voronoi_field", rq->origin, rq->dims, ratio, rq->min_weight, rq->max_distance, rq->surface_distance, &n, &R));
   if (!(rq->min_distance >= 0.f) || !std::isfinite(rq->min_distance)) return fail(KHR_EINVAL, "khr_voronoi_field: bad min_distance %g", static_cast<double>(rq->min_distance));
   if (rq->mode != KHR_VOR_L1 && rq->mode != KHR_VOR_ANGLE && rq->mode != KHR_VOR_L1_THEN_ANGLE)
     return fail(KHR_EINVAL, "khr_voronoi_field: mode %d: KHR_VOR_L1, KHR_VOR_ANGLE or KHR_VOR_L1_THEN_ANGLE", rq->mode);
@@ -4991,10 +5001,10 @@ int khr_voronoi_field(khr_ctx* c, const khr_voronoi_request* rq, khr_voronoi_sta
     return fail(KHR_EINVAL, "khr_voronoi_field: min_basis is %d: 0, 2, 3 or 4", rq->min_basis);
   if (c->cfg.world_size > 1) return fail(KHR_ESTATE, "khr_voronoi_field needs the whole map: world_size is %d", c->cfg.world_size);
   // from here on a failure discards the earlier result
-  c->vor_valid = false;
+  c->vor.valid = false;
   c->vor_stats = khr_voronoi_stats{};
-  if (c->pl_from_voronoi) c->pl_valid = false;  // (khr_places_graph: its graph belongs to the field this call replaces)
-  if (c->tf_from_voronoi) c->tf_valid = c->tfp_valid = false;  // (khr_travel_field: so does its travel field)
+  if (c->pl_from_voronoi) c->pl.valid = false;  // (khr_places_graph: its graph belongs to the field this call replaces)
+  if (c->tf_from_voronoi) c->tf.valid = c->tfp_valid = false;  // (khr_travel_field: so does its travel field)
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = c->stream;
   const int nx = rq->dims[0], ny = rq->dims[1], nz = rq->dims[2];
@@ -5022,19 +5032,14 @@ int khr_voronoi_field(khr_ctx* c, const khr_voronoi_request* rq, khr_voronoi_sta
   KHR_TRY(dfLaunchGather(c, rq->origin, rq->dims, ratio, g));
   // the x pass turns the seeds into keys and always runs; a y / z pass along one cell (or with R = 0) changes nothing
   uint64_t* const keys = c->d_vor_keys;
-  {
-    const int per_wg = std::max(1, kVorTileCells / nx);
-    const long long lines = static_cast<long long>(ny) * nz;
-    hipLaunchKernelGGL((k_vor_pass<0>), dim3(static_cast<unsigned>((lines + per_wg - 1) / per_wg)), dim3(256), 0, st, static_cast<const int32_t*>(g.outer), keys, nx, ny, nz, R, per_wg);
-  }
-  if (ny > 1 && R >= 1) {
-    const int per_wg = std::max(1, kVorTileCells / (ny * kDfStrip));
-    hipLaunchKernelGGL((k_vor_pass<1>), dim3((nx + kDfStrip - 1) / kDfStrip, (nz + per_wg - 1) / per_wg), dim3(256), 0, st, static_cast<const int32_t*>(nullptr), keys, nx, ny, nz, R, per_wg);
-  }
-  if (nz > 1 && R >= 1) {
-    const int per_wg = std::max(1, kVorTileCells / (nz * kDfStrip));
-    hipLaunchKernelGGL((k_vor_pass<2>), dim3((nx + kDfStrip - 1) / kDfStrip, (ny + per_wg - 1) / per_wg), dim3(256), 0, st, static_cast<const int32_t*>(nullptr), keys, nx, ny, nz, R, per_wg);
-  }
+  auto pass = [&](auto axis, const int32_t* seeds) {
+    constexpr int A = decltype(axis)::value;
+    const PassGrid p = axisPassGrid(A, nx, ny, nz, kVorTileCells, kDfStrip);
+    hipLaunchKernelGGL((k_vor_pass<A>), dim3(p.gx, p.gy), dim3(256), 0, st, seeds, keys, nx, ny, nz, R, p.per_wg);
+  };
+  pass(std::integral_constant<int, 0>(), g.outer);
+  if (ny > 1 && R >= 1) pass(std::integral_constant<int, 1>(), nullptr);
+  if (nz > 1 && R >= 1) pass(std::integral_constant<int, 2>(), nullptr);
   HIP_TRY(hipGetLastError());
   VorField f{};
   f.ox = rq->origin[0], f.oy = rq->origin[1], f.oz = rq->origin[2];
@@ -5055,8 +5060,7 @@ int khr_voronoi_field(khr_ctx* c, const khr_voronoi_request* rq, khr_voronoi_sta
   HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_vor_cub.get(), tb, f.wg_count, f.wg_count, static_cast<int>(n_wg + 1), st));
   // the one host wait: the counters
   unsigned long long* const h = c->h_vor;
-  HIP_TRY(hipMemcpyAsync(h, c->d_vor_ctr, sizeof(unsigned long long) * VS_COUNT, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  KHR_TRY(readWords(c, c->d_vor_ctr, h, sizeof(unsigned long long) * VS_COUNT));
   khr_voronoi_stats s{};
   s.n_observed = h[DFS_OBSERVED], s.n_obstacle = h[DFS_OBSTACLE], s.n_free = h[DFS_OBSERVED] - h[DFS_OBSTACLE], s.n_in_range = h[DFS_IN_RANGE];
   s.n_eligible = h[VS_ELIGIBLE], s.n_basis2 = h[VS_BASIS2], s.n_basis3 = h[VS_BASIS3], s.n_basis4 = h[VS_BASIS4], s.n_listed = h[VS_LISTED];
@@ -5074,10 +5078,8 @@ int khr_voronoi_field(khr_ctx* c, const khr_voronoi_request* rq, khr_voronoi_sta
     HIP_TRY(hipGetLastError());
   }
   c->vor_stats = s;
-  c->vor_cells = n;
-  for (int a = 0; a < 3; ++a) c->vor_origin[a] = rq->origin[a], c->vor_dims[a] = rq->dims[a];
   c->vor_cell_size = f.rule.cell_size;
-  c->vor_valid = true;
+  c->vor.set(rq->origin, rq->dims, n);
   if (stats) *stats = s;
   return KHR_OK;
 }
@@ -5085,9 +5087,9 @@ int khr_voronoi_field(khr_ctx* c, const khr_voronoi_request* rq, khr_voronoi_sta
 int khr_voronoi_field_into(khr_ctx* c, int on_device, float* distance, int32_t* d2, uint8_t* status, int32_t* site, uint8_t* basis, int32_t* cells,
                            float* cell_distance, uint8_t* cell_basis, int32_t* cell_sites) {
   if (!c) return fail(KHR_EINVAL, "null ctx");
-  if (!c->vor_valid) return fail(KHR_ESTATE, "no successful khr_voronoi_field before khr_voronoi_field_into");
+  if (!c->vor.valid) return fail(KHR_ESTATE, "no successful khr_voronoi_field before khr_voronoi_field_into");
   HIP_TRY(hipSetDevice(c->device));
-  const size_t n = c->vor_cells, m = static_cast<size_t>(c->vor_stats.n_listed);
+  const size_t n = c->vor.cells, m = static_cast<size_t>(c->vor_stats.n_listed);
   const VorDense D = vorDense(n);
   const VorList L = vorList(m);
   const uint8_t* const db = c->d_vor_dense;
@@ -5095,71 +5097,12 @@ int khr_voronoi_field_into(khr_ctx* c, int on_device, float* distance, int32_t* 
   void* const dst[9] = {distance, d2, status, site, basis, cells, cell_distance, cell_basis, cell_sites};
   const void* const src[9] = {db + D.distance, db + D.d2, db + D.status, db + D.site, db + D.basis, lb + L.cells, lb + L.distance, lb + L.basis, lb + L.sites};
   const size_t bytes[9] = {4 * n, 4 * n, n, 4 * n, n, 12 * m, 4 * m, m, 12 * KHR_VOR_MAX_BASIS * m};
-  if (on_device) {
-    for (int k = 0; k < 9; ++k)
-      if (dst[k] && bytes[k]) HIP_TRY(hipMemcpyAsync(dst[k], src[k], bytes[k], hipMemcpyDeviceToDevice, c->stream));
-    return KHR_OK;
-  }
-  // the host form: through the page-locked staging, one wait
-  size_t off[9], stage_bytes = 0;
-  for (int k = 0; k < 9; ++k) {
-    off[k] = stage_bytes;
-    if (dst[k]) stage_bytes += vorAlign(bytes[k]);
-  }
-  if (stage_bytes == 0) return KHR_OK;
-  if (c->h_vor_stage.reserve(stage_bytes)) return fail(KHR_ENOMEM, "khr_voronoi_field_into: %zu bytes of page-locked staging", stage_bytes);
-  for (int k = 0; k < 9; ++k)
-    if (dst[k] && bytes[k]) HIP_TRY(hipMemcpyAsync(c->h_vor_stage + off[k], src[k], bytes[k], hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  for (int k = 0; k < 9; ++k)
-    if (dst[k] && bytes[k]) std::memcpy(dst[k], c->h_vor_stage + off[k], bytes[k]);
-  return KHR_OK;
+  return copyOut(c, c->h_vor_stage, on_device, dst, src, bytes, "khr_voronoi_field_into");
 }
 
 // ---- places and their links from the Voronoi cells of a box (khr_places_graph / khr_places_graph_from; ASSUMPTIONS.md A.21,
-// device side: khr_kernels_places.h) -------------------------------------------------------------------------------------------
+// device side: khr_kernels_places.h; the layouts of its buffers: plIn, plDense, plWork and plOut of khr_box_host.h) -------------
 namespace {
-
-// per-cell work arrays of n cells, the dense place ids last
-struct PlDense {
-  size_t label, number, pair_count, rec_key, rec_acc, place, bytes;
-};
-PlDense plDense(size_t n) {
-  PlDense L{};
-  size_t o = 0;
-  auto carve = [&](size_t bytes) { const size_t at = o; o += vorAlign(bytes); return at; };
-  L.rec_key = carve(8 * n), L.rec_acc = carve(8 * n), L.label = carve(4 * n), L.number = carve(4 * (n + 1)), L.pair_count = carve(4 * (n + 1)), L.place = carve(4 * n);
-  L.bytes = o;
-  return L;
-}
-// work lists of m adjacent pairs and p places (before the filter)
-struct PlWork {
-  size_t keys, keys_sorted, vals, vals_sorted, head, n_unique, edge_a, edge_b, edge_clear, edge_contacts, edge_new, parent, root, size, place_new, comp_new, bytes;
-};
-PlWork plWork(size_t m, size_t p) {
-  PlWork L{};
-  size_t o = 0;
-  auto carve = [&](size_t bytes) { const size_t at = o; o += vorAlign(bytes); return at; };
-  L.keys = carve(8 * m), L.keys_sorted = carve(8 * m), L.vals = carve(4 * m), L.vals_sorted = carve(4 * m), L.head = carve(4 * (m + 1)), L.n_unique = carve(4);
-  L.edge_a = carve(4 * m), L.edge_b = carve(4 * m), L.edge_clear = carve(4 * m), L.edge_contacts = carve(4 * m), L.edge_new = carve(4 * (m + 1));
-  L.parent = carve(4 * p), L.root = carve(4 * p), L.size = carve(4 * p), L.place_new = carve(4 * (p + 1)), L.comp_new = carve(4 * (p + 1));
-  L.bytes = o;
-  return L;
-}
-// the result lists of p kept places and e kept edges
-struct PlOut {
-  size_t centre, centre_d2, radius, basis, site, n_cells, sum, degree, component, edge_a, edge_b, edge_clear, edge_contacts, bytes;
-};
-PlOut plOut(size_t p, size_t e) {
-  PlOut L{};
-  size_t o = 0;
-  auto carve = [&](size_t bytes) { const size_t at = o; o += vorAlign(bytes); return at; };
-  L.sum = carve(24 * p), L.centre = carve(12 * p), L.centre_d2 = carve(4 * p), L.radius = carve(4 * p), L.basis = carve(p), L.site = carve(12 * p);
-  L.n_cells = carve(4 * p), L.degree = carve(4 * p), L.component = carve(4 * p);
-  L.edge_a = carve(4 * e), L.edge_b = carve(4 * e), L.edge_clear = carve(4 * e), L.edge_contacts = carve(4 * e);
-  L.bytes = std::max<size_t>(o, 256);  // (never empty: the owner exists from the first call on)
-  return L;
-}
 
 // the request checks both calls share (KHR_EINVAL / KHR_ESTATE: nothing is done)
 int plCheckRequest(khr_ctx* c, const khr_places_request* rq, const char* who) {
@@ -5208,8 +5151,7 @@ int plRun(khr_ctx* c, const khr_places_request* rq, const int32_t origin[3], con
   HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_pl_cub.get(), tb, f.pair_count, f.pair_count, static_cast<int>(n + 1), st));
   // host wait 1: members, places, adjacent pairs
   unsigned long long* const h = c->h_pl;
-  HIP_TRY(hipMemcpyAsync(h, c->d_pl_ctr, sizeof(unsigned long long) * PLC_COUNT, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  KHR_TRY(readWords(c, c->d_pl_ctr, h, sizeof(unsigned long long) * PLC_COUNT));
   khr_places_stats s{};
   s.n_members = h[PLC_MEMBERS], s.n_places_all = h[PLC_PLACES_ALL];
   const size_t m = static_cast<size_t>(h[PLC_PAIRS]), P = static_cast<size_t>(s.n_places_all);
@@ -5279,8 +5221,7 @@ int plRun(khr_ctx* c, const khr_places_request* rq, const int32_t origin[3], con
     tb = c->d_pl_cub.count();
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_pl_cub.get(), tb, g.edge_new, g.edge_new, static_cast<int>(m + 1), st));
     // host wait 2: the kept counts
-    HIP_TRY(hipMemcpyAsync(h, c->d_pl_ctr, sizeof(unsigned long long) * PLC_COUNT, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    KHR_TRY(readWords(c, c->d_pl_ctr, h, sizeof(unsigned long long) * PLC_COUNT));
     s.n_edges_all = h[PLC_EDGES_ALL], s.n_components_all = h[PLC_COMPS_ALL], s.n_places = h[PLC_PLACES], s.n_edges = h[PLC_EDGES], s.n_components = h[PLC_COMPS];
     if (s.n_places > P || s.n_edges > s.n_edges_all || s.n_edges_all > m || s.n_components > s.n_components_all || s.n_components_all > P)
       return fail(KHR_EDEVICE, "khr_places_graph: inconsistent counts (%llu of %zu places, %llu of %llu edges)", static_cast<unsigned long long>(s.n_places), P,
@@ -5307,9 +5248,7 @@ int plRun(khr_ctx* c, const khr_places_request* rq, const int32_t origin[3], con
     HIP_TRY(hipMemsetAsync(r.place, 0xff, 4 * n, st));  // (no place is kept: -1 everywhere)
   }
   c->pl_stats = s;
-  c->pl_cells = n;
-  for (int a = 0; a < 3; ++a) c->pl_origin[a] = origin[a], c->pl_dims[a] = dims[a];
-  c->pl_valid = true;
+  c->pl.set(origin, dims, n);
   if (stats) *stats = s;
   return KHR_OK;
 }
@@ -5333,18 +5272,18 @@ int khr_places_graph(khr_ctx* c, const khr_places_request* rq, khr_places_stats*
   if (stats) *stats = khr_places_stats{};
   if (!c || !rq) return fail(KHR_EINVAL, "khr_places_graph: null argument");
   KHR_TRY(plCheckRequest(c, rq, "khr_places_graph"));
-  if (!c->vor_valid) return fail(KHR_ESTATE, "no successful khr_voronoi_field before khr_places_graph");
+  if (!c->vor.valid) return fail(KHR_ESTATE, "no successful khr_voronoi_field before khr_places_graph");
   // from here on a failure discards the earlier result
-  c->pl_valid = false;
+  c->pl.valid = false;
   c->pl_stats = khr_places_stats{};
   HIP_TRY(hipSetDevice(c->device));
-  const size_t n = c->vor_cells;
+  const size_t n = c->vor.cells;
   const PlDense D = plDense(n);
   KHR_TRY(plReserve(c, n, 0, D));
   const VorDense V = vorDense(n);
   const uint8_t* const vb = c->d_vor_dense;
   c->pl_from_voronoi = true;
-  return plRun(c, rq, c->vor_origin, c->vor_dims, reinterpret_cast<const float*>(vb + V.distance), reinterpret_cast<const int32_t*>(vb + V.d2), vb + V.basis,
+  return plRun(c, rq, c->vor.origin, c->vor.dims, reinterpret_cast<const float*>(vb + V.distance), reinterpret_cast<const int32_t*>(vb + V.d2), vb + V.basis,
                reinterpret_cast<const int32_t*>(vb + V.site), D, stats);
 }
 
@@ -5353,19 +5292,12 @@ int khr_places_graph_from(khr_ctx* c, const khr_places_request* rq, const int32_
   if (stats) *stats = khr_places_stats{};
   if (!c || !rq || !origin || !dims || !distance || !d2 || !basis || !site) return fail(KHR_EINVAL, "khr_places_graph_from: null argument");
   KHR_TRY(plCheckRequest(c, rq, "khr_places_graph_from"));
-  uint64_t cells = 1;
-  for (int a = 0; a < 3; ++a) {
-    if (dims[a] < 1 || dims[a] > KHR_DF_MAX_DIM) return fail(KHR_EINVAL, "khr_places_graph_from: dims[%d] = %d: 1 .. %d", a, dims[a], KHR_DF_MAX_DIM);
-    cells *= static_cast<uint64_t>(dims[a]);
-    const int64_t lo = origin[a], hi = static_cast<int64_t>(origin[a]) + dims[a] - 1;
-    if (lo <= -(int64_t(1) << 30) || hi >= (int64_t(1) << 30)) return fail(KHR_EINVAL, "khr_places_graph_from: the box leaves the cell index range on axis %d", a);
-  }
-  if (cells > (uint64_t(1) << 24)) return fail(KHR_EINVAL, "khr_places_graph_from: %llu cells: at most 2^24", static_cast<unsigned long long>(cells));
+  size_t n = 0;
+  KHR_TRY(checkBox("khr_places_graph_from", origin, dims, 1, &n));
   // from here on a failure discards the earlier result
-  c->pl_valid = false;
+  c->pl.valid = false;
   c->pl_stats = khr_places_stats{};
   HIP_TRY(hipSetDevice(c->device));
-  const size_t n = static_cast<size_t>(cells);
   const PlDense D = plDense(n);
   c->pl_from_voronoi = false;
   if (on_device) {
@@ -5373,29 +5305,22 @@ int khr_places_graph_from(khr_ctx* c, const khr_places_request* rq, const int32_
     return plRun(c, rq, origin, dims, distance, d2, basis, site, D, stats);
   }
   // a host field: through the page-locked staging into a device copy
-  const size_t off[4] = {0, vorAlign(4 * n), 2 * vorAlign(4 * n), 2 * vorAlign(4 * n) + vorAlign(n)};
-  const size_t in_bytes = off[3] + vorAlign(4 * n);
-  KHR_TRY(plReserve(c, n, in_bytes, D));
-  if (c->h_pl_stage.reserve(in_bytes)) return fail(KHR_ENOMEM, "khr_places_graph_from: %zu bytes of page-locked staging", in_bytes);
+  const PlIn I = plIn(n);
+  KHR_TRY(plReserve(c, n, I.bytes, D));
+  if (c->h_pl_stage.reserve(I.bytes)) return fail(KHR_ENOMEM, "khr_places_graph_from: %zu bytes of page-locked staging", I.bytes);
   const void* const src[4] = {distance, d2, basis, site};
   const size_t bytes[4] = {4 * n, 4 * n, n, 4 * n};
-  const size_t at[4] = {off[0], off[1], off[2], off[3]};
-  for (int k = 0; k < 4; ++k) {
-    std::memcpy(c->h_pl_stage + at[k], src[k], bytes[k]);
-    HIP_TRY(hipMemcpyAsync(c->d_pl_in + at[k], c->h_pl_stage + at[k], bytes[k], hipMemcpyHostToDevice, c->stream));
-  }
+  const size_t at[4] = {I.distance, I.d2, I.basis, I.site};
+  KHR_TRY(copyIn(c, c->d_pl_in, c->h_pl_stage, src, bytes, at));
   const uint8_t* const ib = c->d_pl_in;
-  return plRun(c, rq, origin, dims, reinterpret_cast<const float*>(ib + at[0]), reinterpret_cast<const int32_t*>(ib + at[1]), ib + at[2],
-               reinterpret_cast<const int32_t*>(ib + at[3]), D, stats);
+  return plRun(c, rq, origin, dims, reinterpret_cast<const float*>(ib + I.distance), reinterpret_cast<const int32_t*>(ib + I.d2), ib + I.basis,
+               reinterpret_cast<const int32_t*>(ib + I.site), D, stats);
 }
 
 int khr_places_graph_box(khr_ctx* c, int32_t* origin, int32_t* dims) {
   if (!c) return fail(KHR_EINVAL, "null ctx");
-  if (!c->pl_valid) return fail(KHR_ESTATE, "no successful khr_places_graph before khr_places_graph_box");
-  for (int a = 0; a < 3; ++a) {
-    if (origin) origin[a] = c->pl_origin[a];
-    if (dims) dims[a] = c->pl_dims[a];
-  }
+  if (!c->pl.valid) return fail(KHR_ESTATE, "no successful khr_places_graph before khr_places_graph_box");
+  c->pl.boxOut(origin, dims);
   return KHR_OK;
 }
 
@@ -5403,9 +5328,9 @@ int khr_places_graph_into(khr_ctx* c, int on_device, int32_t* place, int32_t* ce
                           uint32_t* n_cells, int64_t* sum, uint32_t* degree, uint32_t* component, uint32_t* edge_a, uint32_t* edge_b,
                           int32_t* edge_clearance_d2, uint32_t* edge_n_contacts) {
   if (!c) return fail(KHR_EINVAL, "null ctx");
-  if (!c->pl_valid) return fail(KHR_ESTATE, "no successful khr_places_graph before khr_places_graph_into");
+  if (!c->pl.valid) return fail(KHR_ESTATE, "no successful khr_places_graph before khr_places_graph_into");
   HIP_TRY(hipSetDevice(c->device));
-  const size_t n = c->pl_cells, p = static_cast<size_t>(c->pl_stats.n_places), e = static_cast<size_t>(c->pl_stats.n_edges);
+  const size_t n = c->pl.cells, p = static_cast<size_t>(c->pl_stats.n_places), e = static_cast<size_t>(c->pl_stats.n_edges);
   const PlDense D = plDense(n);
   const PlOut L = plOut(p, e);
   const uint8_t* const db = c->d_pl_dense;
@@ -5415,32 +5340,11 @@ int khr_places_graph_into(khr_ctx* c, int on_device, int32_t* place, int32_t* ce
   const void* const src[K] = {db + D.place, ob + L.centre, ob + L.centre_d2, ob + L.radius, ob + L.basis, ob + L.site, ob + L.n_cells, ob + L.sum, ob + L.degree,
                               ob + L.component, ob + L.edge_a, ob + L.edge_b, ob + L.edge_clear, ob + L.edge_contacts};
   const size_t bytes[K] = {4 * n, 12 * p, 4 * p, 4 * p, p, 12 * p, 4 * p, 24 * p, 4 * p, 4 * p, 4 * e, 4 * e, 4 * e, 4 * e};
-  if (on_device) {
-    for (int k = 0; k < K; ++k)
-      if (dst[k] && bytes[k]) HIP_TRY(hipMemcpyAsync(dst[k], src[k], bytes[k], hipMemcpyDeviceToDevice, c->stream));
-    return KHR_OK;
-  }
-  // the host form: through the page-locked staging, one wait
-  size_t off[K], stage_bytes = 0;
-  for (int k = 0; k < K; ++k) {
-    off[k] = stage_bytes;
-    if (dst[k]) stage_bytes += vorAlign(bytes[k]);
-  }
-  if (stage_bytes == 0) return KHR_OK;
-  if (c->h_pl_stage.count() < stage_bytes) {
-    HIP_TRY(hipStreamSynchronize(c->stream));  // (a copy of khr_places_graph_from may still read the old block)
-    if (c->h_pl_stage.reserve(stage_bytes)) return fail(KHR_ENOMEM, "khr_places_graph_into: %zu bytes of page-locked staging", stage_bytes);
-  }
-  for (int k = 0; k < K; ++k)
-    if (dst[k] && bytes[k]) HIP_TRY(hipMemcpyAsync(c->h_pl_stage + off[k], src[k], bytes[k], hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  for (int k = 0; k < K; ++k)
-    if (dst[k] && bytes[k]) std::memcpy(dst[k], c->h_pl_stage + off[k], bytes[k]);
-  return KHR_OK;
+  return copyOut(c, c->h_pl_stage, on_device, dst, src, bytes, "khr_places_graph_into");
 }
 
 // ---- clearance-bounded travel cost and paths in a box of cells (khr_travel_field / khr_travel_field_from / khr_travel_paths;
-// ASSUMPTIONS.md A.22, device side: khr_kernels_travel.h) ----------------------------------------------------------------------
+// ASSUMPTIONS.md A.22, device side: khr_kernels_travel.h; the layouts of its buffers: tfIn, tfDense and tfStarts of khr_box_host.h)
 namespace {
 
 static_assert(kTfRoundsPerWait == KHR_TF_ROUNDS_PER_WAIT && kTfEdge == KHR_TF_TILE_EDGE && kTfUnreached == KHR_TF_UNREACHED, "khr_kernels_travel.h and khronos_amd.h");
@@ -5451,30 +5355,6 @@ inline size_t tfTiles(const int32_t dims[3]) {
   size_t t = 1;
   for (int a = 0; a < 3; ++a) t *= static_cast<size_t>((dims[a] + kTfEdge - 1) / kTfEdge);
   return t;
-}
-// the per-cell arrays of n cells in `tiles` tiles: the result first, then the work arrays
-struct TfDense {
-  size_t keys, cost, goal, parent, mask, flags, go_on, bytes;
-};
-TfDense tfDense(size_t n, size_t tiles) {
-  TfDense L{};
-  size_t o = 0;
-  auto carve = [&](size_t bytes) { const size_t at = o; o += vorAlign(bytes); return at; };
-  L.keys = carve(8 * n), L.cost = carve(4 * n), L.goal = carve(4 * n), L.parent = carve(n), L.mask = carve(n), L.flags = carve(2 * tiles), L.go_on = carve(4 * kTfRoundsPerWait);
-  L.bytes = o;
-  return L;
-}
-// the per-start arrays of s starts
-struct TfStarts {
-  size_t offsets, starts, path_cost, path_goal, bytes;
-};
-TfStarts tfStarts(size_t s) {
-  TfStarts L{};
-  size_t o = 0;
-  auto carve = [&](size_t bytes) { const size_t at = o; o += vorAlign(bytes); return at; };
-  L.offsets = carve(8 * (s + 1)), L.starts = carve(12 * s), L.path_cost = carve(4 * s), L.path_goal = carve(4 * s);
-  L.bytes = o;
-  return L;
 }
 
 // the request checks both calls share (KHR_EINVAL / KHR_ESTATE: nothing is done)
@@ -5538,9 +5418,8 @@ int tfRun(khr_ctx* c, const khr_travel_request* rq, const int32_t origin[3], con
     }
     HIP_TRY(hipGetLastError());
     queued += kTfRoundsPerWait;
-    HIP_TRY(hipMemcpyAsync(h_go, f.go_on, 4 * kTfRoundsPerWait, hipMemcpyDeviceToHost, st));
     if (queued == kTfRoundsPerWait) HIP_TRY(hipMemcpyAsync(h, c->d_tf_ctr, sizeof(unsigned long long) * TFC_COUNT, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    KHR_TRY(readWords(c, f.go_on, h_go, 4 * kTfRoundsPerWait));
     ++s.n_waits;
     if (queued == kTfRoundsPerWait && h[TFC_GOALS_USED] == 0) carry = false;  // (no usable goal: no tile ran)
     // rounds in which a tile ran: the batch's first if the batch before said so, round j + 1 if round j raised a flag
@@ -5552,24 +5431,14 @@ int tfRun(khr_ctx* c, const khr_travel_request* rq, const int32_t origin[3], con
   else if (rq->connectivity == 18) tfLaunchFinish<18>(f, n, st);
   else tfLaunchFinish<26>(f, n, st);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h, c->d_tf_ctr, sizeof(unsigned long long) * TFC_COUNT, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  KHR_TRY(readWords(c, c->d_tf_ctr, h, sizeof(unsigned long long) * TFC_COUNT));
   s.n_traversable = h[TFC_TRAVERSABLE], s.n_goals_used = h[TFC_GOALS_USED], s.n_reached = h[TFC_REACHED], s.max_cost = h[TFC_MAX_COST];
   if (s.n_traversable > n || s.n_reached > s.n_traversable || s.n_goals_used > n_goals)
     return fail(KHR_EDEVICE, "khr_travel_field: inconsistent counts (%llu reached of %llu traversable of %zu cells)", static_cast<unsigned long long>(s.n_reached),
                 static_cast<unsigned long long>(s.n_traversable), n);
   c->tf_stats = s;
-  c->tf_cells = n;
-  for (int a = 0; a < 3; ++a) c->tf_origin[a] = origin[a], c->tf_dims[a] = dims[a];
-  c->tf_valid = true;
+  c->tf.set(origin, dims, n);
   if (stats) *stats = s;
-  return KHR_OK;
-}
-
-// host goals through the page-locked staging into the device copy, at byte `at` of both
-int tfStageGoals(khr_ctx* c, const int32_t* goals, uint64_t n_goals, size_t at) {
-  std::memcpy(c->h_tf_stage + at, goals, 12 * static_cast<size_t>(n_goals));
-  HIP_TRY(hipMemcpyAsync(c->d_tf_in + at, c->h_tf_stage + at, 12 * static_cast<size_t>(n_goals), hipMemcpyHostToDevice, c->stream));
   return KHR_OK;
 }
 
@@ -5579,19 +5448,20 @@ int khr_travel_field(khr_ctx* c, const khr_travel_request* rq, const int32_t* go
   if (stats) *stats = khr_travel_stats{};
   if (!c || !rq || !goals) return fail(KHR_EINVAL, "khr_travel_field: null argument");
   KHR_TRY(tfCheckRequest(c, rq, n_goals, "khr_travel_field"));
-  if (!c->vor_valid) return fail(KHR_ESTATE, "no successful khr_voronoi_field before khr_travel_field");
+  if (!c->vor.valid) return fail(KHR_ESTATE, "no successful khr_voronoi_field before khr_travel_field");
   // from here on a failure discards the earlier result
-  c->tf_valid = c->tfp_valid = false;
+  c->tf.valid = c->tfp_valid = false;
   c->tf_stats = khr_travel_stats{};
   HIP_TRY(hipSetDevice(c->device));
-  const size_t n = c->vor_cells;
-  const TfDense D = tfDense(n, tfTiles(c->vor_dims));
-  KHR_TRY(tfReserve(c, goals_on_device ? 0 : vorAlign(12 * static_cast<size_t>(n_goals)), D));
-  if (!goals_on_device) KHR_TRY(tfStageGoals(c, goals, n_goals, 0));
+  const size_t n = c->vor.cells;
+  const TfDense D = tfDense(n, tfTiles(c->vor.dims));
+  const size_t goal_bytes = 12 * static_cast<size_t>(n_goals);
+  KHR_TRY(tfReserve(c, goals_on_device ? 0 : Arena::align(goal_bytes), D));
+  if (!goals_on_device) KHR_TRY(copyIn(c, c->d_tf_in, c->h_tf_stage, goals, goal_bytes));
   const VorDense V = vorDense(n);
   const uint8_t* const vb = c->d_vor_dense;
   c->tf_from_voronoi = true;
-  return tfRun(c, rq, c->vor_origin, c->vor_dims, reinterpret_cast<const float*>(vb + V.distance), vb + V.status,
+  return tfRun(c, rq, c->vor.origin, c->vor.dims, reinterpret_cast<const float*>(vb + V.distance), vb + V.status,
                goals_on_device ? goals : reinterpret_cast<const int32_t*>(c->d_tf_in.get()), n_goals, D, stats);
 }
 
@@ -5600,19 +5470,12 @@ int khr_travel_field_from(khr_ctx* c, const khr_travel_request* rq, const int32_
   if (stats) *stats = khr_travel_stats{};
   if (!c || !rq || !origin || !dims || !distance || !status || !goals) return fail(KHR_EINVAL, "khr_travel_field_from: null argument");
   KHR_TRY(tfCheckRequest(c, rq, n_goals, "khr_travel_field_from"));
-  uint64_t cells = 1;
-  for (int a = 0; a < 3; ++a) {
-    if (dims[a] < 1 || dims[a] > KHR_DF_MAX_DIM) return fail(KHR_EINVAL, "khr_travel_field_from: dims[%d] = %d: 1 .. %d", a, dims[a], KHR_DF_MAX_DIM);
-    cells *= static_cast<uint64_t>(dims[a]);
-    const int64_t lo = origin[a], hi = static_cast<int64_t>(origin[a]) + dims[a] - 1;
-    if (lo <= -(int64_t(1) << 30) || hi >= (int64_t(1) << 30)) return fail(KHR_EINVAL, "khr_travel_field_from: the box leaves the cell index range on axis %d", a);
-  }
-  if (cells > (uint64_t(1) << 24)) return fail(KHR_EINVAL, "khr_travel_field_from: %llu cells: at most 2^24", static_cast<unsigned long long>(cells));
+  size_t n = 0;
+  KHR_TRY(checkBox("khr_travel_field_from", origin, dims, 1, &n));
   // from here on a failure discards the earlier result
-  c->tf_valid = c->tfp_valid = false;
+  c->tf.valid = c->tfp_valid = false;
   c->tf_stats = khr_travel_stats{};
   HIP_TRY(hipSetDevice(c->device));
-  const size_t n = static_cast<size_t>(cells);
   const TfDense D = tfDense(n, tfTiles(dims));
   c->tf_from_voronoi = false;
   if (on_device) {
@@ -5620,77 +5483,41 @@ int khr_travel_field_from(khr_ctx* c, const khr_travel_request* rq, const int32_
     return tfRun(c, rq, origin, dims, distance, status, goals, n_goals, D, stats);
   }
   // a host field and host goals: through the page-locked staging into a device copy
-  const size_t at[3] = {0, vorAlign(4 * n), vorAlign(4 * n) + vorAlign(n)};
-  const size_t in_bytes = at[2] + vorAlign(12 * static_cast<size_t>(n_goals));
-  KHR_TRY(tfReserve(c, in_bytes, D));
-  const void* const src[2] = {distance, status};
-  const size_t bytes[2] = {4 * n, n};
-  for (int k = 0; k < 2; ++k) {
-    std::memcpy(c->h_tf_stage + at[k], src[k], bytes[k]);
-    HIP_TRY(hipMemcpyAsync(c->d_tf_in + at[k], c->h_tf_stage + at[k], bytes[k], hipMemcpyHostToDevice, c->stream));
-  }
-  KHR_TRY(tfStageGoals(c, goals, n_goals, at[2]));
+  const TfIn I = tfIn(n, static_cast<size_t>(n_goals));
+  KHR_TRY(tfReserve(c, I.bytes, D));
+  const void* const src[3] = {distance, status, goals};
+  const size_t bytes[3] = {4 * n, n, 12 * static_cast<size_t>(n_goals)};
+  const size_t at[3] = {I.distance, I.status, I.goals};
+  KHR_TRY(copyIn(c, c->d_tf_in, c->h_tf_stage, src, bytes, at));
   const uint8_t* const ib = c->d_tf_in;
-  return tfRun(c, rq, origin, dims, reinterpret_cast<const float*>(ib + at[0]), ib + at[1], reinterpret_cast<const int32_t*>(ib + at[2]), n_goals, D, stats);
+  return tfRun(c, rq, origin, dims, reinterpret_cast<const float*>(ib + I.distance), ib + I.status, reinterpret_cast<const int32_t*>(ib + I.goals), n_goals, D, stats);
 }
 
 int khr_travel_field_box(khr_ctx* c, int32_t* origin, int32_t* dims) {
   if (!c) return fail(KHR_EINVAL, "null ctx");
-  if (!c->tf_valid) return fail(KHR_ESTATE, "no successful khr_travel_field before khr_travel_field_box");
-  for (int a = 0; a < 3; ++a) {
-    if (origin) origin[a] = c->tf_origin[a];
-    if (dims) dims[a] = c->tf_dims[a];
-  }
+  if (!c->tf.valid) return fail(KHR_ESTATE, "no successful khr_travel_field before khr_travel_field_box");
+  c->tf.boxOut(origin, dims);
   return KHR_OK;
 }
-
-namespace {
-
-// K result arrays out of ctx's buffers into the caller's: device-to-device in stream order, or through the page-locked staging with one wait
-int tfCopyOut(khr_ctx* c, int on_device, int K, void* const* dst, const void* const* src, const size_t* bytes, const char* who) {
-  if (on_device) {
-    for (int k = 0; k < K; ++k)
-      if (dst[k] && bytes[k]) HIP_TRY(hipMemcpyAsync(dst[k], src[k], bytes[k], hipMemcpyDeviceToDevice, c->stream));
-    return KHR_OK;
-  }
-  size_t off[4], stage_bytes = 0;
-  for (int k = 0; k < K; ++k) {
-    off[k] = stage_bytes;
-    if (dst[k]) stage_bytes += vorAlign(bytes[k]);
-  }
-  if (stage_bytes == 0) return KHR_OK;
-  if (c->h_tf_stage.count() < stage_bytes) {
-    HIP_TRY(hipStreamSynchronize(c->stream));  // (a copy of khr_travel_field_from may still read the old block)
-    if (c->h_tf_stage.reserve(stage_bytes)) return fail(KHR_ENOMEM, "%s: %zu bytes of page-locked staging", who, stage_bytes);
-  }
-  for (int k = 0; k < K; ++k)
-    if (dst[k] && bytes[k]) HIP_TRY(hipMemcpyAsync(c->h_tf_stage + off[k], src[k], bytes[k], hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  for (int k = 0; k < K; ++k)
-    if (dst[k] && bytes[k]) std::memcpy(dst[k], c->h_tf_stage + off[k], bytes[k]);
-  return KHR_OK;
-}
-
-}  // namespace
 
 int khr_travel_field_into(khr_ctx* c, int on_device, uint32_t* cost, int32_t* goal, uint8_t* parent) {
   if (!c) return fail(KHR_EINVAL, "null ctx");
-  if (!c->tf_valid) return fail(KHR_ESTATE, "no successful khr_travel_field before khr_travel_field_into");
+  if (!c->tf.valid) return fail(KHR_ESTATE, "no successful khr_travel_field before khr_travel_field_into");
   HIP_TRY(hipSetDevice(c->device));
-  const size_t n = c->tf_cells;
-  const TfDense D = tfDense(n, tfTiles(c->tf_dims));
+  const size_t n = c->tf.cells;
+  const TfDense D = tfDense(n, tfTiles(c->tf.dims));
   const uint8_t* const db = c->d_tf_dense;
   void* const dst[3] = {cost, goal, parent};
   const void* const src[3] = {db + D.cost, db + D.goal, db + D.parent};
   const size_t bytes[3] = {4 * n, 4 * n, n};
-  return tfCopyOut(c, on_device, 3, dst, src, bytes, "khr_travel_field_into");
+  return copyOut(c, c->h_tf_stage, on_device, dst, src, bytes, "khr_travel_field_into");
 }
 
 int khr_travel_paths(khr_ctx* c, uint64_t n_starts, const int32_t* starts, int on_device, uint64_t* n_cells_total) {
   if (n_cells_total) *n_cells_total = 0;
   if (!c || !starts) return fail(KHR_EINVAL, "khr_travel_paths: null argument");
   if (n_starts < 1 || n_starts > kTfMaxStarts) return fail(KHR_EINVAL, "khr_travel_paths: %llu starts: 1 .. %u", static_cast<unsigned long long>(n_starts), kTfMaxStarts);
-  if (!c->tf_valid) return fail(KHR_ESTATE, "no successful khr_travel_field before khr_travel_paths");
+  if (!c->tf.valid) return fail(KHR_ESTATE, "no successful khr_travel_field before khr_travel_paths");
   // from here on a failure discards the earlier paths (the travel field stays)
   c->tfp_valid = false;
   HIP_TRY(hipSetDevice(c->device));
@@ -5707,17 +5534,13 @@ int khr_travel_paths(khr_ctx* c, uint64_t n_starts, const int32_t* starts, int o
       return fail(KHR_ENOMEM, "khr_travel_paths: work arrays of %zu starts (%zu bytes)", s, L.bytes + cub_bytes);
   }
   uint8_t* const pb = c->d_tf_path;
-  if (on_device) {
-    HIP_TRY(hipMemcpyAsync(pb + L.starts, starts, 12 * s, hipMemcpyDeviceToDevice, st));
-  } else {
-    std::memcpy(c->h_tf_stage.get(), starts, 12 * s);
-    HIP_TRY(hipMemcpyAsync(pb + L.starts, c->h_tf_stage.get(), 12 * s, hipMemcpyHostToDevice, st));
-  }
-  const TfDense D = tfDense(c->tf_cells, tfTiles(c->tf_dims));
+  if (on_device) HIP_TRY(hipMemcpyAsync(pb + L.starts, starts, 12 * s, hipMemcpyDeviceToDevice, st));
+  else KHR_TRY(copyIn(c, pb + L.starts, c->h_tf_stage, starts, 12 * s));
+  const TfDense D = tfDense(c->tf.cells, tfTiles(c->tf.dims));
   const uint8_t* const db = c->d_tf_dense;
   TfPaths p{};
-  p.ox = c->tf_origin[0], p.oy = c->tf_origin[1], p.oz = c->tf_origin[2];
-  p.nx = c->tf_dims[0], p.ny = c->tf_dims[1], p.nz = c->tf_dims[2];
+  p.ox = c->tf.origin[0], p.oy = c->tf.origin[1], p.oz = c->tf.origin[2];
+  p.nx = c->tf.dims[0], p.ny = c->tf.dims[1], p.nz = c->tf.dims[2];
   p.cost = reinterpret_cast<const uint32_t*>(db + D.cost), p.goal = reinterpret_cast<const int32_t*>(db + D.goal), p.parent = db + D.parent;
   p.starts = reinterpret_cast<const int32_t*>(pb + L.starts), p.n_starts = static_cast<uint32_t>(s);
   p.offsets = reinterpret_cast<long long*>(pb + L.offsets);
@@ -5728,8 +5551,7 @@ int khr_travel_paths(khr_ctx* c, uint64_t n_starts, const int32_t* starts, int o
   HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->d_tf_cub.get(), tb, p.offsets, p.offsets, static_cast<int>(s + 1), st));
   // the one host wait: the total sizes the list
   unsigned long long* const h_total = c->h_tf + TFC_COUNT + kTfRoundsPerWait;
-  HIP_TRY(hipMemcpyAsync(h_total, p.offsets + s, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  KHR_TRY(readWords(c, p.offsets + s, h_total, 8));
   const uint64_t total = *h_total;
   if (total > kTfMaxPathCells)
     return fail(KHR_ENOMEM, "khr_travel_paths: the paths hold %llu cells: at most 2^26 in one call", static_cast<unsigned long long>(total));
@@ -5748,7 +5570,7 @@ int khr_travel_paths(khr_ctx* c, uint64_t n_starts, const int32_t* starts, int o
 
 int khr_travel_paths_into(khr_ctx* c, int on_device, int64_t* offsets, int32_t* cells, uint32_t* path_cost, int32_t* path_goal) {
   if (!c) return fail(KHR_EINVAL, "null ctx");
-  if (!c->tf_valid || !c->tfp_valid) return fail(KHR_ESTATE, "no successful khr_travel_paths before khr_travel_paths_into");
+  if (!c->tf.valid || !c->tfp_valid) return fail(KHR_ESTATE, "no successful khr_travel_paths before khr_travel_paths_into");
   HIP_TRY(hipSetDevice(c->device));
   const size_t s = c->tfp_starts, total = c->tfp_total;
   const TfStarts L = tfStarts(s);
@@ -5756,7 +5578,7 @@ int khr_travel_paths_into(khr_ctx* c, int on_device, int64_t* offsets, int32_t* 
   void* const dst[4] = {offsets, cells, path_cost, path_goal};
   const void* const src[4] = {pb + L.offsets, c->d_tf_cells.get(), pb + L.path_cost, pb + L.path_goal};
   const size_t bytes[4] = {8 * (s + 1), 12 * total, 4 * s, 4 * s};
-  return tfCopyOut(c, on_device, 4, dst, src, bytes, "khr_travel_paths_into");
+  return copyOut(c, c->h_tf_stage, on_device, dst, src, bytes, "khr_travel_paths_into");
 }
 
 // ---- the live map as a registration target (khr_align_linearize / khr_align_frame; ASSUMPTIONS.md A.14, device side:
@@ -6279,9 +6101,9 @@ int khr_checkpoint_load(khr_ctx* c, const void* buffer, uint64_t n_bytes, int64_
   c->weld_valid = false;  // (khr_weld_mesh: the welded mesh belongs to the map before the load)
   c->diff_valid = false;  // (khr_diff_map: so does the diff)
   c->seg_valid = false;   // (khr_segment_map: and the segmentation)
-  c->vor_valid = false;   // (khr_voronoi_field: and the Voronoi field)
-  c->pl_valid = false;    // (khr_places_graph: and the places graph)
-  c->tf_valid = c->tfp_valid = false;  // (khr_travel_field: and the travel field with its paths)
+  c->vor.valid = false;   // (khr_voronoi_field: and the Voronoi field)
+  c->pl.valid = false;    // (khr_places_graph: and the places graph)
+  c->tf.valid = c->tfp_valid = false;  // (khr_travel_field: and the travel field with its paths)
   khr_checkpoint_header h;
   int rc = khr_checkpoint_inspect(buffer, n_bytes, &h);
   if (rc) return rc;
@@ -6995,17 +6817,14 @@ int khr_weld_mesh(khr_ctx* c, float resolution, khr_weld_stats* stats) {
   uint32_t tsize = 4;
   while (tsize < 2u * n_cap) tsize <<= 1;
   // the three areas; a growth waits for whatever still reads the old block (a device-to-device copy of the last result)
-  auto al = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
-  size_t o = 0;
-  auto carve = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
-  const size_t w_cnt = carve(4ull * (cap + 1)), w_base = carve(4ull * (cap + 1)), w_off = carve(4ull * cap), w_src = carve(4ull * n_cap),
-               w_hs = carve(4ull * n_cap), w_rep = carve(4ull * (n_cap + 1)), w_widx = carve(4ull * (n_cap + 1)), w_keep = carve(4ull * (nf_cap + 1)),
-               w_fidx = carve(4ull * (nf_cap + 1)), w_keys = carve(8ull * tsize), w_vals = carve(4ull * tsize), w_head = carve(4ull * kWeldHeadWords);
-  const size_t work_bytes = o;
-  o = 0;
-  const size_t o_p = carve(12ull * n_cap), o_c = carve(4ull * n_cap), o_l = carve(4ull * n_cap), o_s = carve(8ull * n_cap),
-               o_f = carve(12ull * (nf_cap + 1)), o_v = carve(4ull * n_cap);
-  const size_t out_bytes = o;
+  Arena wa, oa;
+  const size_t w_cnt = wa.take(4ull * (cap + 1)), w_base = wa.take(4ull * (cap + 1)), w_off = wa.take(4ull * cap), w_src = wa.take(4ull * n_cap),
+               w_hs = wa.take(4ull * n_cap), w_rep = wa.take(4ull * (n_cap + 1)), w_widx = wa.take(4ull * (n_cap + 1)), w_keep = wa.take(4ull * (nf_cap + 1)),
+               w_fidx = wa.take(4ull * (nf_cap + 1)), w_keys = wa.take(8ull * tsize), w_vals = wa.take(4ull * tsize), w_head = wa.take(4ull * kWeldHeadWords);
+  const size_t work_bytes = wa.bytes();
+  const size_t o_p = oa.take(12ull * n_cap), o_c = oa.take(4ull * n_cap), o_l = oa.take(4ull * n_cap), o_s = oa.take(8ull * n_cap),
+               o_f = oa.take(12ull * (nf_cap + 1)), o_v = oa.take(4ull * n_cap);
+  const size_t out_bytes = oa.bytes();
   const int scan_len = static_cast<int>(std::max(n_cap, cap) + 1u);
   size_t cub_bytes = 0;
   HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, static_cast<uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), scan_len, c->stream));
@@ -7345,11 +7164,9 @@ int khr_diff_map(khr_ctx* c, khr_ctx* ref, const khr_diff_request* rq, khr_diff_
   const uint32_t m = h[DC_CHANGED], n = static_cast<uint32_t>(n64);
   if (m > 0) {
     // the work area and the result; nothing is queued on the stream here (the wait above), so a growth frees nothing in use
-    auto al = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
-    size_t o = 0;
-    auto carve = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
-    const size_t w_key = carve(8ull * m), w_cand = carve(4ull * m), w_cnt = carve(4ull * (m + 1ull)), w_first = carve(4ull * (m + 1ull));
-    const size_t work_bytes = o, out_bytes = diffLayout(n, m).bytes;
+    Arena wa;
+    const size_t w_key = wa.take(8ull * m), w_cand = wa.take(4ull * m), w_cnt = wa.take(4ull * (m + 1ull)), w_first = wa.take(4ull * (m + 1ull));
+    const size_t work_bytes = wa.bytes(), out_bytes = diffLayout(n, m).bytes;
     size_t sort_bytes = 0, scan_bytes = 0;
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, static_cast<const uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr),
                                                static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), static_cast<int>(m), 0, 63, st));
@@ -7461,12 +7278,10 @@ int khr_segment_map(khr_ctx* c, const khr_segment_request* rq, khr_segment_stats
   const size_t nv = static_cast<size_t>(c->p.nvox), cap = c->m.capacity;
   const size_t bound = std::max<size_t>(1, c->host_index_valid ? std::min(cap, c->host_index.size()) : cap);
   const size_t nodes = bound * nv;
-  auto al = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
-  size_t o = 0;
-  auto carve = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
-  const size_t w_ctr = carve(8 * SC_COUNT), w_ros = carve(4 * cap), w_sor = carve(4 * bound), w_par = carve(4 * nodes), w_cnt = carve(4 * nodes),
-               w_num = carve(4 * (nodes + 1));
-  const size_t work_bytes = o;
+  Arena wa;
+  const size_t w_ctr = wa.take(8 * SC_COUNT), w_ros = wa.take(4 * cap), w_sor = wa.take(4 * bound), w_par = wa.take(4 * nodes), w_cnt = wa.take(4 * nodes),
+               w_num = wa.take(4 * (nodes + 1));
+  const size_t work_bytes = wa.bytes();
   if (nodes + 1 > static_cast<size_t>(INT32_MAX))  // (the scan counts in int; node ids then fit 32 bits with room for kSegNone)
     return fail(KHR_ENOMEM, "khr_segment_map: %zu blocks of %zu voxels to number, at most 2^31 - 2 voxels (%zu bytes of scratch)", bound, nv, work_bytes);
   size_t cub_bytes = 0;
@@ -7531,7 +7346,7 @@ int khr_segment_map(khr_ctx* c, const khr_segment_request* rq, khr_segment_stats
     if (n > (1ull << 30)) return fail(KHR_ENOMEM, "khr_segment_map: a voxel list of %llu entries, at most 2^30 (%llu bytes)", static_cast<unsigned long long>(n),
                                        static_cast<unsigned long long>(48 * n));
     // the result and the sort's work area; nothing is queued on the stream here (the wait above), so a growth frees nothing in use
-    const size_t out_bytes = segLayout(m, n).bytes, sort_bytes = 2 * al(8 * n);
+    const size_t out_bytes = segLayout(m, n).bytes, sort_bytes = 2 * Arena::align(8 * n);
     size_t scan64_bytes = 0, radix_bytes = 0;
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan64_bytes, static_cast<uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr), static_cast<int>(m), st));
     if (n) HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, radix_bytes, static_cast<const uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr), static_cast<int>(n), 0, 64, st));
@@ -7542,7 +7357,7 @@ int khr_segment_map(khr_ctx* c, const khr_segment_request* rq, khr_segment_stats
     uint8_t* const out = c->d_seg_out;
     const SegLayout L = segLayout(m, n);
     uint64_t* const keys_in = n ? reinterpret_cast<uint64_t*>(c->d_seg_sort.get()) : nullptr;
-    uint64_t* const keys_out = n ? reinterpret_cast<uint64_t*>(c->d_seg_sort.get() + al(8 * n)) : nullptr;
+    uint64_t* const keys_out = n ? reinterpret_cast<uint64_t*>(c->d_seg_sort.get() + Arena::align(8 * n)) : nullptr;
     const dim3 live_grid(static_cast<uint32_t>(std::min<size_t>(std::max<size_t>(1, gridFor(static_cast<size_t>(n_blocks) * nv)), 8192)));
     rc = dispatchVps(c, [&](auto vps) {
       constexpr int V = decltype(vps)::value;
